@@ -17,6 +17,10 @@ one RCCL all_gather of {frames, seconds} per rank, on the device.  Rank 0 prints
   memread      : the spatial-memory read region (all its launches): algorithmic bytes / HIP-event time vs the HBM peak
   fp32, config3: (N = 1 only) the parity mode on the same workload, and BASELINE config 3 (512x512, 50 frames, growing bank)
   cpu_baseline : (N = 1 only) the CPU oracle (a port of the reference algorithm, oracle/) on this box's host cores
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step returned to its caller as DIR/<name>.npy
+(dump_outputs below).  Weights, frames and ground truth are seeded, so the same arguments give the same inputs in every run and
+two builds can be compared file by file.
 """
 import argparse
 import json
@@ -65,6 +69,8 @@ def parse_args(argv=None):
     ap.add_argument("--train-batch", type=int, default=4)
     ap.add_argument("--schedule", default="", help="comma list of schedule switches to turn OFF: batch_encode, defer_head2, "
                                                    "grouped_decoder (debugging / A-B runs; default = the shipped schedule)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32; at most 64 MB, a seeded sample beyond that)")
     return ap.parse_args(argv)
 
 
@@ -131,10 +137,42 @@ def time_sequences(model, seqs, steps, warmup, world=1):
     if world > 1:
         dist.barrier()
     sync()
-    frames, seconds, _ = run_sequences(model, [seqs[i % len(seqs)] for i in range(steps)], sync=sync)
+    frames, seconds, last = run_sequences(model, [seqs[i % len(seqs)] for i in range(steps)], sync=sync)
     if world > 1:
         dist.barrier()
-    return frames, seconds
+    return frames, seconds, last
+
+
+DUMP_LIMIT = 60 * 10 ** 6       # bytes of array data per --dump-outputs directory (64 MB with the .npy headers and a margin)
+
+
+def forward_arrays(outputs):
+    """(preds, preds_all) of Spann3R.forward -> {name: tensor}: frameNN_<key> is preds[N]; pairNN_view2_<key> is the second view of
+    step N (preds_all[N][1]; its first view IS preds[N])"""
+    preds, preds_all = outputs[:2]
+    arrays = {"frame%02d_%s" % (i, k): v for i, p in enumerate(preds) for k, v in p.items()}
+    arrays.update({"pair%02d_view2_%s" % (i, k): v for i, (_, r2) in enumerate(preds_all) for k, v in r2.items()})
+    return arrays
+
+
+def dump_outputs(dirname, arrays):
+    """{name: tensor or number} -> dirname/<name>.npy, float32 (float64 stays float64), whole arrays in their own shape while the sum
+    stays within DUMP_LIMIT.  Beyond it every array keeps the same share of its elements, flattened, at sorted positions drawn from a
+    fixed seed: the same arguments select the same positions in every run and on every build."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, v in arrays.items():
+        t = torch.as_tensor(v).detach().cpu()
+        host[name] = (t if t.dtype == torch.float64 else t.float()).numpy()
+    total = sum(a.nbytes for a in host.values())
+    rng = np.random.default_rng(0)
+    for name, a in host.items():
+        if total > DUMP_LIMIT:
+            keep = max(1, a.size * DUMP_LIMIT // total)
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, keep, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def instance_key(key):
@@ -592,6 +630,9 @@ def _main(args, real_stdout):
         stats = gather_stats(args.train_batch * 5 * args.steps, tr["seconds_per_step"] * args.steps, extra=[float(tr["hip_graph"])], device=dev)
         fps, _, max_seconds = aggregate(stats)
         tr["hip_graph_per_rank"] = [bool(x) for x in stats[:, 2].tolist()]       # every rank reports its own execution mode
+        if args.dump_outputs and rank == 0:
+            # what TrainStep.run handed back in the last timed step (the step's other product is the updated model)
+            dump_outputs(args.dump_outputs, {k: torch.tensor(tr[k], dtype=torch.float64) for k in ("loss", "grad_norm") if tr[k] is not None})
         if rank == 0:
             print(file=real_stdout, flush=True, *[json.dumps({"metric": "training frames/sec (batch %d x %d ranks, 5-frame 224px sequences, ConfLoss backward, AdamW)" % (args.train_batch, world),
                               "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -608,7 +649,10 @@ def _main(args, real_stdout):
     n_distinct = 4
     my_ids = shard(n_distinct * world, rank, world)
     seqs = [make_sequence(s, args.frames, args.size, args.size, device=dev) for s in my_ids]
-    frames, seconds = time_sequences(model, seqs, args.steps, args.warmup, world)
+    frames, seconds, last = time_sequences(model, seqs, args.steps, args.warmup, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, forward_arrays(last))            # before anything else runs: the outputs live in the runner's buffers
+    del last
     stats = gather_stats(frames, seconds, device=dev)           # RCCL all_gather on the device when world > 1
     fps, tot_frames, max_seconds = aggregate(stats)
 
@@ -649,26 +693,26 @@ def _main(args, real_stdout):
     if world == 1 and not args.no_extras and (args.size, args.frames, args.precision, args.train_policy) == (224, 10, "bf16", False):
         print("bench.py: extras: fp32 mode", file=sys.stderr, flush=True)
         model.set_precision("fp32")
-        f32_frames, f32_s = time_sequences(model, seqs, 6, 3)
+        f32_frames, f32_s, _ = time_sequences(model, seqs, 6, 3)
         out["fp32"] = {"value": f32_frames / f32_s, "unit": "frames/s", "what": "same workload in the fp32 MFMA parity mode "
                        "(<=1e-3 vs the reference, tests/test_model_gpu.py)", "steps": 6,
                        "frac_of_mfma_peak": fl * 6 / f32_s / 1e12 / PEAK_TFLOPS["fp32"]}
         model.set_precision("f32x3")
-        x3_frames, x3_s = time_sequences(model, seqs, 6, 3)
+        x3_frames, x3_s, _ = time_sequences(model, seqs, 6, 3)
         out["f32x3"] = {"value": x3_frames / x3_s, "unit": "frames/s", "steps": 6, "parity_mode": False,
                         "what": "same workload, fp32 operands with every GEMM product through three bf16 MFMAs of a (hi, lo) split (16 "
                                 "mantissa bits per product, fp32 accumulate).  NOT a parity mode: it FAILS the 1e-3 bar on the trained-like "
                                 "stress fixture (1.4e-3 pointmaps / 2.0e-3 mem_attn; <= 4e-4 on the reference-initialised fixtures); "
                                 "kept as a throughput data point only -- the parity-carrying modes are fp32, f32x6 and f16x3"}
         model.set_precision("f32x6")
-        x6_frames, x6_s = time_sequences(model, seqs, 6, 3)
+        x6_frames, x6_s, _ = time_sequences(model, seqs, 6, 3)
         out["f32x6"] = {"value": x6_frames / x6_s, "unit": "frames/s", "steps": 6,
                         "what": "same workload, fp32 operands, every GEMM product through SIX bf16 MFMAs of a three-way (h, m, l) split: 24 operand "
                                 "bits, fp32-grade products, fp32 accumulate; exact-fp32 attention.  The fast parity mode that also holds 1e-3 on "
                                 "trained-like weight statistics (stress fixture), where f32x3 measures 1.4e-3"}
         print("bench.py: extras: f16x3 mode", file=sys.stderr, flush=True)
         model.set_precision("f16x3")
-        h3_frames, h3_s = time_sequences(model, seqs, 6, 3)
+        h3_frames, h3_s, _ = time_sequences(model, seqs, 6, 3)
         out["f16x3"] = {"value": h3_frames / h3_s, "unit": "frames/s", "steps": 6,
                         "what": "same workload, fp32 operands, every GEMM and attention product through THREE fp16 MFMAs of a two-way split "
                                 "x = h + l * 2^-11 (22 operand bits, fp32 accumulate): the fast fp32-grade mode -- pointmaps within 5e-6 of the reference on "
@@ -690,7 +734,7 @@ def _main(args, real_stdout):
         # NOT the headline configuration (BASELINE config 2 is batch 1): reported next to it.
         print("bench.py: extras: batch 4", file=sys.stderr, flush=True)
         seqs_b4 = [make_sequence(200, args.frames, args.size, args.size, batch=4, device=dev)]
-        b4_frames, b4_s = time_sequences(model, seqs_b4, 6, 3)
+        b4_frames, b4_s, _ = time_sequences(model, seqs_b4, 6, 3)
         out["batch4"] = {"value": 4 * b4_frames / b4_s, "unit": "frames/s", "steps": 6,
                          "what": "same model and sequence length, 4 independent sequences per forward call (batch 4): "
                                  "every launch carries 4x the rows; not the BASELINE configuration"}
@@ -699,7 +743,7 @@ def _main(args, real_stdout):
         print("bench.py: extras: config 3 (512x512, 50 frames)", file=sys.stderr, flush=True)
         m3, _ = build_model("bf16", dev, train_policy=True)
         seq3 = [make_sequence(100, 50, 512, 512, device=dev)]
-        c3_frames, c3_s = time_sequences(m3, seq3, 3, 3)
+        c3_frames, c3_s, _ = time_sequences(m3, seq3, 3, 3)
         fl3 = flops_per_sequence(50, 512)
         c3 = {"workload": "Spann3R.forward, 50-frame 512x512 sequence, batch 1, growing bank (train memory policy, dropout off), bf16",
               "value": c3_frames / c3_s, "unit": "frames/s", "steps": 3, "ms_per_sequence": 1e3 * c3_s / 3,

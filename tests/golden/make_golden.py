@@ -715,6 +715,47 @@ def make_lrsched():
     print("lr_schedule.npz: %d arrays" % len(out))
 
 
+def make_memread():
+    """the train-mode read of the UNMODIFIED SpatialMemory (spann3r/model.py memory_read(res=True), attn_thresh = 0, no dropout) after
+    two add_mem calls, on the seeded inputs of tests/test_train.py::test_oracle_matches_reference_memory_read"""
+    from spann3r.model import SpatialMemory
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from test_train import _inputs, MEMREAD_REF_CASE
+    B, P, T, C, seed = MEMREAD_REF_CASE
+    leaves, _, _ = _inputs(B, P, T, C, seed=seed)
+    leaves = {k: v.detach() for k, v in leaves.items()}
+    norms = [torch.nn.LayerNorm(C, eps=1e-5) for _ in range(3)]
+    for m, n in zip(norms, "qkv"):
+        m.weight.data.copy_(leaves["g" + n])
+        m.bias.data.copy_(leaves["b" + n])
+    sp = SpatialMemory(*norms, mem_dropout=None, attn_thresh=0)
+    sp.add_mem(leaves["mem_k"][:, :P], leaves["mem_v"][:, :P])
+    sp.add_mem(leaves["mem_k"][:, P:], leaves["mem_v"][:, P:])
+    with torch.no_grad():
+        out = sp.memory_read(leaves["feat"], res=True)
+    np.savez_compressed(os.path.join(HERE, "memory_read_train.npz"), out=out.numpy(), feat=leaves["feat"].numpy())
+    print("memory_read_train.npz: out %s" % (tuple(out.shape),))
+
+
+def make_rope():
+    """the reference's own curope CPU routine (curope.cpp:11-69, compiled in place by oracle/build_ref.py) on the seeded case of
+    tests/test_rope_cref.py, forward and backward rotation: what the GPU test compares sp3_rope_2d with where the routine is not built"""
+    sys.path.insert(0, os.path.join(REPO, "oracle"))
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import build_ref
+    from test_rope_cref import _case
+    build_ref.build()
+    mod = build_ref.load_ref()
+    tok, pos = _case()
+    out = {}
+    for name, fwd in (("fwd", 1.0), ("bwd", -1.0)):
+        a = tok.transpose(1, 2).contiguous()
+        mod.rope_2d(a, pos, 100.0, fwd)
+        out[name] = a.numpy()
+    np.savez_compressed(os.path.join(HERE, "rope2d_reference.npz"), tok=tok.numpy(), **out)
+    print("rope2d_reference.npz: %s" % (tuple(out["fwd"].shape),))
+
+
 def make_crop():
     """f3 pin: the crop / resize plan of the reference's own functions.  `cropping.py` imports cv2 (used only for the depth map,
     cropping.py:73-75) and `dust3r.utils.image` imports torchvision (ImgNorm); neither is installed here and neither touches the
@@ -855,6 +896,10 @@ if __name__ == "__main__":
         make_trainloop()
     if "lrsched" in what:
         make_lrsched()
+    if "memread" in what:
+        make_memread()
+    if "rope" in what:
+        make_rope()
     if "postprocess" in what:
         make_postprocess()
     if "loss" in what:

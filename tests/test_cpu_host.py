@@ -176,6 +176,36 @@ def test_bench_flop_model():
     assert abs(bench.flops_per_sequence(50, 512) / 1e9 - 1.061e5) / 1.061e5 < 0.01
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: names follow the forward's (preds, preds_all); arrays within the byte limit are written whole as
+    float32 (float64 stays), beyond it as the same seeded positions in every call"""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    res = lambda base, key: {key: torch.arange(base, base + 24.0).reshape(1, 2, 4, 3), "conf": torch.full((1, 2, 4), base).bfloat16()}
+    r1, r2, r3 = res(0.0, "pts3d"), res(100.0, "pts3d_in_other_view"), res(200.0, "pts3d_in_other_view")
+    arrays = bench.forward_arrays(([r1, r2, r3], [(r1, r2), (r2, r3)]))
+    assert sorted(arrays) == ["frame00_conf", "frame00_pts3d", "frame01_conf", "frame01_pts3d_in_other_view", "frame02_conf",
+                              "frame02_pts3d_in_other_view", "pair00_view2_conf", "pair00_view2_pts3d_in_other_view", "pair01_view2_conf",
+                              "pair01_view2_pts3d_in_other_view"]
+    arrays["loss"] = torch.tensor(0.1, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    assert sorted(os.listdir(tmp_path / "whole")) == sorted(k + ".npy" for k in arrays)
+    for k, v in arrays.items():
+        a = np.load(tmp_path / "whole" / (k + ".npy"))
+        assert a.dtype == (np.float64 if k == "loss" else np.float32) and a.shape == tuple(v.shape)
+        assert np.array_equal(a, v.double().numpy())
+    big = {"a": torch.arange(40000.0), "b": torch.arange(10000.0).reshape(100, 100)}
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 20000)
+    for d in ("s0", "s1"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    a, b = np.load(tmp_path / "s0" / "a.npy"), np.load(tmp_path / "s0" / "b.npy")
+    assert a.dtype == b.dtype == np.float32 and a.nbytes + b.nbytes <= 20000 and a.size == 4 * b.size == 4000
+    for x, n in ((a, 40000), (b, 10000)):                   # the values ARE the flat positions: distinct, sorted, spread over the array
+        assert np.all(np.diff(x) > 0) and 0 <= x[0] and x[-1] < n and x[-1] - x[0] > n / 2
+    assert np.array_equal(a, np.load(tmp_path / "s1" / "a.npy")) and np.array_equal(b, np.load(tmp_path / "s1" / "b.npy"))
+
+
 # ----------------------------------------------------------------------------- multi-process sharding (gloo, world 2)
 WORKER = r'''
 import os, sys

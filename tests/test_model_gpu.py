@@ -1014,6 +1014,33 @@ def test_bench_self_spawn_one_rank_through_rccl(capsys):
     assert bench.spawn_ranks(torch.cuda.device_count() + 1, _bench_argv(torch.cuda.device_count() + 1)) != 0     # never a smaller job
 
 
+def test_bench_dump_outputs_repeats_across_processes(tmp_path):
+    """`bench.py --dump-outputs DIR` in two fresh processes: same arguments -> same seeded inputs -> the same files, also when the
+    profiling pass runs after the timed steps in one of them (the outputs are taken before the runner's buffers are reused); the
+    record's ms_per_step is the timed window over --steps"""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    recs = []
+    for d, argv in (("a", _bench_argv(1)), ("b", [a for a in _bench_argv(1) if a != "--no-profile"])):
+        p = subprocess.run([sys.executable, os.path.join(repo, "bench.py")] + argv + ["--dump-outputs", str(tmp_path / d)],
+                           capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        recs.append(json.loads(p.stdout))
+    for r in recs:
+        assert r["steps"] == 2 and abs(r["ms_per_step"] - 1e3 * max(r["per_rank_seconds"]) / 2) < 1e-3 * r["ms_per_step"]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "frame00_pts3d.npy" in names and "pair01_view2_conf.npy" in names
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 * 10 ** 6
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and np.isfinite(a).all() and a.shape[:3] == (1, 64, 64), n
+        assert np.array_equal(a, b), n
+
+
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs (the driver's 8-GPU node)")
 def test_bench_two_ranks_over_rccl(capsys):
     """two ranks, one per GPU: sequences sharded, stats all_gather over RCCL / xGMI, whole-job frames/s from the slower rank"""

@@ -7,7 +7,7 @@ import subprocess
 import pytest
 import torch
 
-from conftest import REPO, rel_err
+from conftest import REPO, load_golden, rel_err
 from oracle import spann3r_oracle as O
 
 
@@ -64,18 +64,25 @@ def test_real_reference_routine_pins_the_oracle(fwd):
     B, N, H, D = b.shape
     _cref().rope2d_ref(b.data_ptr(), pos.contiguous().data_ptr(), B, N, H, D, 100.0, fwd)
     assert torch.equal(a, b)                                    # same arithmetic, same libm: bit-exact
+    assert torch.equal(a, _stored_reference(tok, fwd))          # the stored output (tests/golden/make_golden.py rope) is this routine's
     assert rel_err(a.transpose(1, 2), O.rope2d(tok, pos, 100.0, fwd)) < 2e-6
     with pytest.raises(RuntimeError):                           # the TORCH_CHECK convention our binding mirrors
         ref_mod.rope_2d(a, pos[:1], 100.0, fwd)
 
 
+def _stored_reference(tok, fwd):
+    """tests/golden/rope2d_reference.npz: the real reference routine's output [B,N,H,D] on _case(), pinned to the live routine by
+    test_real_reference_routine_pins_the_oracle wherever that is built"""
+    g = load_golden("rope2d_reference.npz")
+    assert torch.equal(torch.from_numpy(g["tok"]), tok)         # made from these inputs
+    return torch.from_numpy(g["fwd" if fwd > 0 else "bwd"])
+
+
 @pytest.mark.gpu
 def test_hip_rope_equals_real_reference():
     from spann3r_amd import ops
-    ref_mod = _real_reference()
     tok, pos = _case()
-    a = tok.transpose(1, 2).contiguous()
-    ref_mod.rope_2d(a, pos, 100.0, 1.0)
+    a = _stored_reference(tok, 1.0)
     t = tok.clone().cuda()
     ops.rope_2d(t.transpose(1, 2), pos.cuda(), 100.0, 1.0)
     assert rel_err(t.cpu(), a.transpose(1, 2)) < 1e-5

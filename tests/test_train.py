@@ -33,24 +33,18 @@ def _run(fn, leaves, mask, dout):
     return out.detach(), {k: v.grad for k, v in leaves.items()}
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/spann3r"), reason="needs the reference checkout (build container only)")
+MEMREAD_REF_CASE = (2, 24, 72, 64, 3)        # B, P, T, C, seed of the stored reference read (tests/golden/make_golden.py memread)
+
+
 def test_oracle_matches_reference_memory_read():
-    import sys
-    sys.dont_write_bytecode = True
-    sys.path.insert(0, "/root/reference")
-    try:
-        from spann3r.model import SpatialMemory
-    finally:
-        sys.path.remove("/root/reference")
-    B, P, T, C = 2, 24, 72, 64
-    leaves, _, dout = _inputs(B, P, T, C, seed=3)
-    norms = [torch.nn.LayerNorm(C, eps=1e-5) for _ in range(3)]
-    for m, n in zip(norms, "qkv"):
-        m.weight.data.copy_(leaves["g" + n].detach()); m.bias.data.copy_(leaves["b" + n].detach())
-    sp = SpatialMemory(*norms, mem_dropout=None, attn_thresh=0)
-    sp.add_mem(leaves["mem_k"].detach()[:, :P], leaves["mem_v"].detach()[:, :P])
-    sp.add_mem(leaves["mem_k"].detach()[:, P:], leaves["mem_v"].detach()[:, P:])
-    ref = sp.memory_read(leaves["feat"].detach(), res=True)
+    """the oracle's train-mode read against the output of the unmodified reference module on the same seeded inputs
+    (tests/golden/memory_read_train.npz: SpatialMemory.memory_read(res=True) after two add_mem calls, attn_thresh = 0, no dropout)"""
+    from conftest import load_golden
+    B, P, T, C, seed = MEMREAD_REF_CASE
+    leaves, _, _ = _inputs(B, P, T, C, seed=seed)
+    g = load_golden("memory_read_train.npz")
+    assert np.array_equal(g["feat"], leaves["feat"].detach().numpy())             # the fixture was made from these inputs
+    ref = torch.from_numpy(g["out"])
     got = TO.memory_read_train(leaves["feat"], leaves["mem_k"], leaves["mem_v"], (leaves["gq"], leaves["bq"]), (leaves["gk"], leaves["bk"]),
                                (leaves["gv"], leaves["bv"]), None)
     assert rel_err(got.detach(), ref.detach()) < 1e-6

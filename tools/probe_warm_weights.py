@@ -34,7 +34,7 @@ for mode in a.alias.split(","):
                 w[k] = w["val0." + k.split(".", 1)[1]]
                 n += 1
     model._runners = {}                  # drop graphs captured with the old pointers
-    fr, s = bench.time_sequences(model, seqs, 12, 4)
+    fr, s, _ = bench.time_sequences(model, seqs, 12, 4)
     print("alias=%-8s (%3d tensors re-pointed): %.1f frames/s  %.3f ms per 10-frame sequence" % (mode, n, fr / s, 1e3 * s / 12), flush=True)
     del model
     torch.cuda.empty_cache()
