@@ -159,6 +159,12 @@ typedef struct sp3_gemm_desc {
    *   dyn_n[0] % 4 == 0), so ONE captured hipGraph serves every bank length up to it.  Lean instances only: the general tiles
    *   refuse a descriptor with dyn_n set. */
   const int32_t* dyn_n;
+  /* --- res2 as a HALF-resolution map (lean small-map convolutions, tiles 40 / 41, bf16 maps only): res2_up_H > 0 says res2 is the NHWC map
+   *   [B, res2_up_H, res2_up_W, N] and the residual added is its bilinear x2 (align_corners, the arithmetic of sp3_upsample2x), cropped to
+   *   conv_OH x conv_OW (<= 2 res2_up_H x 2 res2_up_W) and rounded to the map dtype as the stored upsampled map would have been:
+   *   FeatureFusionBlock's interpolate -> next block's `output + res` (croco/models/dpt_block.py:205-218) without the upsampled map in
+   *   memory.  sp3_gemm_plan answers -1 for any other kernel family. */
+  int32_t res2_up_H, res2_up_W;
 } sp3_gemm_desc;
 int sp3_gemm(const sp3_gemm_desc* desc_host, void* stream);
 /* Two differently shaped groups of problems in ONE launch (grid.y = a.batch + b.batch), e.g. a decoder layer's self-attention
@@ -166,6 +172,11 @@ int sp3_gemm(const sp3_gemm_desc* desc_host, void* stream);
  * (dust3r/model.py:196-198, croco/models/blocks.py:187-189), so the second launch boundary buys nothing.  Both descriptors
  * must resolve to the same kernel instance (dtypes, loader, tile; b.tile < 0 takes a's); no split-K. */
 int sp3_gemm2(const sp3_gemm_desc* a, const sp3_gemm_desc* b, void* stream);
+/* A level launch: n (1..4) independent problems, e.g. the convolutions of one dependency level of a DPT head, in ONE launch.
+ * sp3_gemm2 is its n = 2 case.  Either every descriptor resolves to the same general kernel instance (the rules of sp3_gemm2; grid.y =
+ * sum of the batches), or every one is a small-map convolution (tiles 40 / 41, which may be mixed: one 1-D grid, problem i owns a
+ * contiguous range of workgroups, the one with the longest contraction first). */
+int sp3_gemm_n(const sp3_gemm_desc* const* descs, int n, void* stream);
 /* The tile sp3_gemm runs `desc` on when desc->tile < 0 (desc->tile itself is ignored), or < 0 for an invalid descriptor.  Tiles
  * 30.. are the LEAN small-M instances (csrc/gemm_sm.hip): the per-frame step's 196-row weight-streaming Linears
  * (croco/models/blocks.py:73-79,94-112,149-169 at batch 1) on bf16 fragment-order operands, with shape, tile and epilogue fixed at

@@ -96,6 +96,33 @@ __device__ __forceinline__ void st_out(bf16x8* p, bf16x8 v) {
 template <typename T> __device__ __forceinline__ void st_out(T* p, T v) { *p = v; }
 #endif
 
+// Bilinear x2 (align_corners=True) read of a half-resolution NHWC map at output pixel (oy, ox): the index clamps, scale factors and
+// association of sp3_upsample2x (csrc/dpt.hip), for epilogues that take the upsampled map as a residual without it existing in
+// memory.  p00..p11: pixel offsets (y * W + x) of the four taps in the H x W source.
+struct Up2xTaps {
+  int p00, p01, p10, p11;
+  float hy, ly, hx, lx;
+};
+__device__ __forceinline__ Up2xTaps up2x_taps(int H, int W, int oy, int ox) {
+  const int OH = 2 * H, OW = 2 * W;
+  const float sh = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
+  const float sw = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
+  int y0 = (int)__fmul_rn(sh, (float)oy), x0 = (int)__fmul_rn(sw, (float)ox);
+  y0 = y0 < H - 1 ? y0 : H - 1;
+  x0 = x0 < W - 1 ? x0 : W - 1;
+  const int y1 = y0 < H - 1 ? y0 + 1 : y0, x1 = x0 < W - 1 ? x0 + 1 : x0;
+  Up2xTaps t;
+  // the contraction the compiler chose for sp3_upsample2x's kernels, spelled out (a different one differs in the last bit)
+  t.ly = __fmaf_rn(sh, (float)oy, -(float)y0); t.lx = __fmaf_rn(sw, (float)ox, -(float)x0);
+  t.hy = 1.f - t.ly; t.hx = 1.f - t.lx;
+  t.p00 = y0 * W + x0; t.p01 = y0 * W + x1; t.p10 = y1 * W + x0; t.p11 = y1 * W + x1;
+  return t;
+}
+__device__ __forceinline__ float up2x_mix(const Up2xTaps& t, float v00, float v01, float v10, float v11) {
+  const float top = __fmaf_rn(t.hx, v00, __fmul_rn(t.lx, v01)), bot = __fmaf_rn(t.hx, v10, __fmul_rn(t.lx, v11));
+  return __fmaf_rn(t.hy, top, __fmul_rn(t.ly, bot));
+}
+
 // Fragment-order ("packed") operand layout shared by sp3_gemm's a_packed / w_packed and every producer's
 // out_packed option: [ceil(rows/16)][ceil(K/KB)][2 halves h][4 lane groups g][16 rows r][CH/2], KB/CH = 64/16 (bf16),
 // 32/8 (fp32): lane 16g + r of a wave owns k = kb*KB + g*CH + [0, CH) of row r, and its first and second 16 bytes live in

@@ -31,11 +31,11 @@
 
 namespace {
 
-// d2 / nb1: sp3_gemm2 -- a second, differently shaped group of problems in the same launch: blockIdx.y >= nb1 works on d2
+// dn / nb: sp3_gemm_n -- up to 4 differently shaped groups of problems in the same launch: group g owns blockIdx.y in
+// [nb[g], nb[g + 1]) (nb[0] = 0; unused groups start at INT_MAX)
 struct GemmArgs {
-  sp3_gemm_desc d;
-  sp3_gemm_desc d2;
-  int nb1;
+  sp3_gemm_desc dn[4];
+  int nb[4];
   int xcd_slices;        // split-K slices mapped to XCDs (see the tile map)
 };
 
@@ -486,8 +486,10 @@ template <typename TA, typename TW, int LOADER, int MF, int NF, int WM, int WN, 
 __global__ __launch_bounds__(64 * (WM * WN * WK + (LOOP >= 2 ? LOOP : 0)), (gemm_min_waves<TA, LOADER, MF, NF, WK>()))
 void gemm_kernel(const GemmArgs args) {
   // local copy: grouped launches shift the per-problem pointers below (kernarg segment, wave-uniform select)
-  const bool second = args.nb1 > 0 && (int)blockIdx.y >= args.nb1;
-  sp3_gemm_desc d = second ? args.d2 : args.d;
+  int grp = 0;
+#pragma unroll
+  for (int i = 1; i < 4; ++i) grp = (int)blockIdx.y >= args.nb[i] ? i : grp;
+  sp3_gemm_desc d = args.dn[grp];
   using M_ = MM<TA, TW>;
   constexpr bool LDSK = LOOP != 0;
   constexpr int NCW = WM * WN * WK;          // consumer (MFMA) waves
@@ -524,7 +526,7 @@ void gemm_kernel(const GemmArgs args) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wk = wave % WK, wn = (wave / WK) % WN, wm = wave / (WK * WN);
   const int g = lane >> 4;
-  const int bz = second ? (int)blockIdx.y - args.nb1 : (int)blockIdx.y;
+  const int bz = (int)blockIdx.y - args.nb[grp];
   if (d.batch > 1) {                         // grouped launch: problem bz (wave-uniform pointer arithmetic)
     auto shift = [&](auto*& p, int64_t bytes) {
       using P = std::remove_reference_t<decltype(p)>;
@@ -540,7 +542,7 @@ void gemm_kernel(const GemmArgs args) {
   const TW* W = reinterpret_cast<const TW*>(d.W) + (int64_t)bz * d.strideW;
 
   const int m0 = tile_m * BM, n0 = tile_n * BN;
-  int64_t* tr0 = ((LOOP == 0 || LOOP == -1) && args.d.trace && blockIdx.x < 8 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) ? args.d.trace + blockIdx.x * 64 : nullptr;
+  int64_t* tr0 = ((LOOP == 0 || LOOP == -1) && d.trace && blockIdx.x < 8 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) ? d.trace + blockIdx.x * 64 : nullptr;
   if (tr0) { tr0[0] = clock64(); tr0[3] = wall_clock64(); }
   ARows<TA, LOADER, MF> arows;
   arows.init(d, A, m0 + wm * MF * 16, lane, M_::KB, M_::CH);
@@ -1654,8 +1656,9 @@ void gemm_kernel(const GemmArgs args) {
   if (tr0) { tr0[2] = clock64(); tr0[4] = wall_clock64(); }
 }
 
-// sp3_gemm2: the second group of problems of the launch being dispatched (same kernel instance), or null
-thread_local const sp3_gemm_desc* g_pair = nullptr;
+// sp3_gemm_n: the further groups of problems of the launch being dispatched (same kernel instance)
+thread_local const sp3_gemm_desc* g_more[3] = {nullptr, nullptr, nullptr};
+thread_local int g_nmore = 0;
 
 template <typename TA, typename TW, int LOADER, int MF, int NF, int WM, int WN, int WK, int STAGES, int LOOP = 0, int XM = 0>
 int launch(const sp3_gemm_desc& d, hipStream_t stream) {
@@ -1681,17 +1684,20 @@ int launch(const sp3_gemm_desc& d, hipStream_t stream) {
     }
   }
   GemmArgs a;
-  a.d = d;
-  a.nb1 = 0;
+  a.dn[0] = d;
+  a.nb[0] = 0;
   int gy = d.batch;
-  if (g_pair) {                      // workgroups past a group's own tile count exit at once
-    a.d2 = *g_pair;
-    a.nb1 = d.batch;
-    gy += g_pair->batch;
-    const int b2 = grid_x(*g_pair);
-    blocks = blocks > b2 ? blocks : b2;
-  } else {
-    a.d2 = d;
+  for (int i = 1; i < 4; ++i) {
+    if (i <= g_nmore) {              // workgroups past a group's own tile count exit at once
+      a.dn[i] = *g_more[i - 1];
+      a.nb[i] = gy;
+      gy += g_more[i - 1]->batch;
+      const int b2 = grid_x(*g_more[i - 1]);
+      blocks = blocks > b2 ? blocks : b2;
+    } else {
+      a.dn[i] = d;
+      a.nb[i] = 0x7fffffff;
+    }
   }
   a.xcd_slices = (gy == 1 && d.splitk >= 8 && d.splitk % 8 == 0 && blocks % 8 == 0) ? 1 : 0;
   hipLaunchKernelGGL(kern, dim3(blocks, gy, d.splitk), dim3(NT), lds, stream, a);
@@ -1954,6 +1960,7 @@ extern "C" int sp3_gemm(const sp3_gemm_desc* dp, void* stream_) {
   if (d.tile >= 30 || (d.tile < 0 && sp3_gemm_sm_tile(d) >= 0)) return sp3_gemm_sm_launch(d, nullptr, reinterpret_cast<hipStream_t>(stream_));
   SP3_CHECK(!(d.a_packed && d.A2), "sp3_gemm: a fragment-order A split along K runs on the lean instances only (no instance for M=%d N=%d K=%d)", d.M, d.N, d.K);
   SP3_CHECK(!(d.res_bf16 && (d.res1 || d.res2)), "sp3_gemm: bf16 residual maps are read by the lean small-map convolutions only (res_bf16 = out_bf16 = a_bf16; M=%d N=%d K=%d)", d.M, d.N, d.K);
+  SP3_CHECK(!d.res2_up_H, "sp3_gemm: a half-resolution res2 is read by the lean small-map convolutions only (tiles 40 / 41; M=%d N=%d K=%d)", d.M, d.N, d.K);
   SP3_CHECK(!d.dyn_n, "sp3_gemm: a device-side extent (dyn_n) is served by the lean memory-read instances only (tiles 43 / 44; M=%d N=%d K=%d)", d.M, d.N, d.K);
   return gemm_dispatch(d, tile, reinterpret_cast<hipStream_t>(stream_));
 }
@@ -1970,33 +1977,55 @@ extern "C" int sp3_gemm_plan(const sp3_gemm_desc* dp) {
   return lean >= 0 ? lean : tile;
 }
 
-extern "C" int sp3_gemm2(const sp3_gemm_desc* ap, const sp3_gemm_desc* bp, void* stream_) {
-  SP3_CHECK(ap != nullptr && bp != nullptr, "sp3_gemm2: null descriptor");
-  sp3_gemm_desc a = *ap, b = *bp;
-  int ta = -1, tb = -1;
+extern "C" int sp3_gemm_n(const sp3_gemm_desc* const* dp, int n, void* stream_) {
+  SP3_CHECK(dp != nullptr && n >= 1 && n <= 4, "sp3_gemm_n: 1..4 descriptors (n=%d)", n);
+  for (int i = 0; i < n; ++i) SP3_CHECK(dp[i] != nullptr, "sp3_gemm_n: null descriptor");
+  if (n == 1) return sp3_gemm(dp[0], stream_);
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  sp3_gemm_desc d[4];
+  int t[4] = {-1, -1, -1, -1};
   {
-    // both groups on one lean instance (gemm_sm.hip): decided before the legacy tiles are consulted
-    sp3_gemm_desc a0 = a, b0 = b;
-    int t0 = -1, t1 = -1;
-    const int want = a0.tile;
-    a0.tile = b0.tile = -1;
-    if (gemm_prepare(a0, t0) == 0 && gemm_prepare(b0, t1) == 0) {
-      const int la = sp3_gemm_sm_tile(a0), lb = sp3_gemm_sm_tile(b0);
+    // every group on the lean instances (gemm_sm.hip): decided before the legacy tiles are consulted
+    sp3_gemm_desc d0[4];
+    const int want = dp[0]->tile;
+    bool ok = true;
+    for (int i = 0; i < n; ++i) {
+      d0[i] = *dp[i];
+      const int keep = d0[i].tile;
+      d0[i].tile = -1;
+      int ti = -1;
+      ok = ok && gemm_prepare(d0[i], ti) == 0;
+      if (d0[i].loader == SP3_LOAD_CONV3X3) d0[i].tile = keep;    // (a level of small-map convolutions may name its tiles 40 / 41)
+    }
+    if (ok && sp3_gemm_sm_conv_level(d0, n)) return sp3_gemm_sm_conv_level_launch(d0, n, stream);
+    if (ok && n == 2) {
+      d0[0].tile = d0[1].tile = -1;
+      const int la = sp3_gemm_sm_tile(d0[0]), lb = sp3_gemm_sm_tile(d0[1]);
       // (only the q/k/v projections' ROPE instances take a second group; two STREAM / PACKED problems that share an instance
       //  pair on the general tiles below, as they did before the lean families existed)
-      if (la >= 30 && la == lb && sp3_gemm_sm_pairs(a0) && (want < 0 || want == la)) return sp3_gemm_sm_launch(a0, &b0, reinterpret_cast<hipStream_t>(stream_));
+      if (la >= 30 && la == lb && sp3_gemm_sm_pairs(d0[0]) && (want < 0 || want == la)) return sp3_gemm_sm_launch(d0[0], &d0[1], stream);
     }
-    SP3_CHECK(want < 30, "sp3_gemm2: tile %d asks for a lean instance that does not take this pair", want);
+    SP3_CHECK(want < 30, "sp3_gemm_n: tile %d asks for a lean instance that does not take these %d groups", want, n);
   }
-  if (int rc = gemm_prepare(a, ta)) return rc;
-  if (b.tile < 0) b.tile = ta;                   // the second group runs on the first one's kernel instance
-  if (int rc = gemm_prepare(b, tb)) return rc;
-  SP3_CHECK(!(a.res_bf16 && (a.res1 || a.res2)) && !(b.res_bf16 && (b.res1 || b.res2)), "sp3_gemm2: bf16 residual maps are read by the lean small-map convolutions only");
-  SP3_CHECK(ta == tb && a.wdtype == b.wdtype && a.a_bf16 == b.a_bf16 && a.loader == b.loader && a.loader != SP3_LOAD_SOFTMAX,
-            "sp3_gemm2: both groups must use one kernel instance (tile %d / %d, same dtypes and loader)", ta, tb);
-  SP3_CHECK(a.splitk == 1 && b.splitk == 1 && !a.trace && !b.trace && !a.dyn_n && !b.dyn_n, "sp3_gemm2: no split-K, no trace, no device-side extent");
-  g_pair = &b;
-  const int rc = gemm_dispatch(a, ta, reinterpret_cast<hipStream_t>(stream_));
-  g_pair = nullptr;
+  for (int i = 0; i < n; ++i) {
+    d[i] = *dp[i];
+    if (i > 0 && d[i].tile < 0) d[i].tile = t[0];                 // the further groups run on the first one's kernel instance
+    if (int rc = gemm_prepare(d[i], t[i])) return rc;
+    SP3_CHECK(!(d[i].res_bf16 && (d[i].res1 || d[i].res2)) && !d[i].res2_up_H, "sp3_gemm_n: bf16 and half-resolution residual maps are read by the lean small-map convolutions only");
+    SP3_CHECK(t[i] == t[0] && d[i].wdtype == d[0].wdtype && d[i].a_bf16 == d[0].a_bf16 && d[i].loader == d[0].loader && d[i].loader != SP3_LOAD_SOFTMAX &&
+              d[i].f32x3 == d[0].f32x3 && (d[i].w_packed == 2) == (d[0].w_packed == 2),
+              "sp3_gemm_n: every group must use one kernel instance (tile %d / %d, same dtypes and loader)", t[0], t[i]);
+    SP3_CHECK(d[i].splitk == 1 && !d[i].trace && !d[i].dyn_n, "sp3_gemm_n: no split-K, no trace, no device-side extent");
+  }
+  for (int i = 1; i < n; ++i) g_more[i - 1] = &d[i];
+  g_nmore = n - 1;
+  const int rc = gemm_dispatch(d[0], t[0], stream);
+  g_nmore = 0;
   return rc;
+}
+
+extern "C" int sp3_gemm2(const sp3_gemm_desc* ap, const sp3_gemm_desc* bp, void* stream_) {
+  SP3_CHECK(ap != nullptr && bp != nullptr, "sp3_gemm2: null descriptor");
+  const sp3_gemm_desc* two[2] = {ap, bp};
+  return sp3_gemm_n(two, 2, stream_);
 }

@@ -1271,6 +1271,16 @@ struct ConvSmArgs {
   const float* bias; const void* res1; const void* res2;
   int M, N, H, Wd, Cin, OH, OW, stride, nkb, relu_in, act;
   unsigned cin_magic, per_magic, ow_magic;        // floor(2^32 / d) + 1: n / d by one multiply-high (n < 65536)
+  int up_H, up_W;                                 // > 0: res2 is a HALF-resolution map [B, up_H, up_W, N], read through the bilinear x2 of
+                                                  // sp3_upsample2x (cropped to OH x OW) and rounded to TM as the stored map was
+};
+
+// a level launch (sp3_gemm_n): up to 4 independent convolutions, tiles 40 and 41 mixed, in one 1-D grid.  Problem i owns the
+// workgroups [start[i], start[i + 1]) (multiples of 8: its XCD map is that of its own launch)
+struct ConvLevelArgs {
+  ConvSmArgs p[4];
+  int start[5];
+  int tile[4];
 };
 
 typedef __attribute__((ext_vector_type(4))) unsigned int csm_u32x4;
@@ -1320,6 +1330,7 @@ __device__ __forceinline__ float4 csm_load4(const __bf16* p) {
   const bf16x4 t = *reinterpret_cast<const bf16x4*>(p);
   return make_float4((float)t[0], (float)t[1], (float)t[2], (float)t[3]);
 }
+template <typename TM> __device__ __forceinline__ float csm_round(float v) { return (float)(TM)v; }      // a value as the map stores it
 __device__ __forceinline__ void csm_store4(float* p, const float (&v)[4]) { st_out(reinterpret_cast<float4*>(p), make_float4(v[0], v[1], v[2], v[3])); }
 __device__ __forceinline__ void csm_store4(__bf16* p, const float (&v)[4]) {
   bf16x4 t;
@@ -1327,14 +1338,13 @@ __device__ __forceinline__ void csm_store4(__bf16* p, const float (&v)[4]) {
   st_out(reinterpret_cast<bf16x4*>(p), t);
 }
 
+// one workgroup's output tile (tile_m, tile_n).  Waves past WK (a level launch sized for a wider member) leave before the barrier.
 template <typename TM, int MF, int NF, int WK, int R>
-__global__ __launch_bounds__(64 * WK) void conv_sm_kernel(const ConvSmArgs a) {
+__device__ __forceinline__ void conv_sm_body(const ConvSmArgs& a, const int tile_m, const int tile_n, float* smem) {
   constexpr int BM = MF * 16, BN = NF * 16, NT = 64 * WK, LD = BN + 4, CG = BN / 4;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wk = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int tile_m = blockIdx.y, tile_n = blockIdx.z * 8 + blockIdx.x;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
-  if (n0 >= a.N) return;
+  if (n0 >= a.N || wk >= WK) return;
   const int g = lane >> 4, r16 = lane & 15;
   const TM* X = reinterpret_cast<const TM*>(a.x);
 
@@ -1346,7 +1356,7 @@ __global__ __launch_bounds__(64 * WK) void conv_sm_kernel(const ConvSmArgs a) {
     const long o = (long)(m0 + erow) * a.N + n0 + ec4;
     if (a.bias) b4 = *reinterpret_cast<const float4*>(a.bias + n0 + ec4);
     if (a.res1) r1 = csm_load4(reinterpret_cast<const TM*>(a.res1) + o);
-    if (a.res2) r2 = csm_load4(reinterpret_cast<const TM*>(a.res2) + o);
+    if (a.res2 && !a.up_H) r2 = csm_load4(reinterpret_cast<const TM*>(a.res2) + o);
   }
 
   // this lane's output pixels (one per row block)
@@ -1440,8 +1450,46 @@ __global__ __launch_bounds__(64 * WK) void conv_sm_kernel(const ConvSmArgs a) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
     }
+    if (a.up_H) {
+      // half-resolution res2: its four taps are read HERE, not next to the other epilogue operands -- held across the K loop they cost
+      // the 32x32 instance its third wave per SIMD (168 -> 188 registers); the source is 4x smaller than the map it stands for and L2-hot
+      const int row = m0 + erow;
+      const int b = (int)__umulhi((unsigned)row, a.per_magic), rem = row - b * a.OH * a.OW;
+      const int oy = (int)__umulhi((unsigned)rem, a.ow_magic), ox = rem - oy * a.OW;
+      const Up2xTaps up = up2x_taps(a.up_H, a.up_W, oy, ox);
+      const TM* src = reinterpret_cast<const TM*>(a.res2) + (long)b * a.up_H * a.up_W * a.N + n0 + ec4;
+      const float4 u00 = csm_load4(src + (long)up.p00 * a.N), u01 = csm_load4(src + (long)up.p01 * a.N);
+      const float4 u10 = csm_load4(src + (long)up.p10 * a.N), u11 = csm_load4(src + (long)up.p11 * a.N);
+      r2.x = csm_round<TM>(up2x_mix(up, u00.x, u01.x, u10.x, u11.x)); r2.y = csm_round<TM>(up2x_mix(up, u00.y, u01.y, u10.y, u11.y));
+      r2.z = csm_round<TM>(up2x_mix(up, u00.z, u01.z, u10.z, u11.z)); r2.w = csm_round<TM>(up2x_mix(up, u00.w, u01.w, u10.w, u11.w));
+    }
     v[0] += r1.x + r2.x; v[1] += r1.y + r2.y; v[2] += r1.z + r2.z; v[3] += r1.w + r2.w;
     csm_store4(reinterpret_cast<TM*>(a.out) + (long)(m0 + erow) * a.N + n0 + ec4, v);
+  }
+}
+
+template <typename TM, int MF, int NF, int WK, int R>
+__global__ __launch_bounds__(64 * WK) void conv_sm_kernel(const ConvSmArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  conv_sm_body<TM, MF, NF, WK, R>(a, blockIdx.y, blockIdx.z * 8 + blockIdx.x, smem);
+}
+
+// workgroup w of a level launch -> (problem, tile_m, tile_n): within a problem the order of its own grid (8, mt, ntz), x fastest
+template <typename TM>
+__global__ __launch_bounds__(64 * 12) void conv_level_kernel(const ConvLevelArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int w = blockIdx.x;
+  int p = 0;
+#pragma unroll
+  for (int i = 1; i < 4; ++i) p = w >= a.start[i] ? i : p;
+  const ConvSmArgs q = a.p[p];
+  const int local = w - a.start[p], j = local >> 3;
+  if (a.tile[p] == 40) {
+    const int mt = (q.M + 15) / 16;
+    conv_sm_body<TM, 1, 1, 12, 3>(q, j % mt, (j / mt) * 8 + (local & 7), smem);
+  } else if constexpr (sizeof(TM) == 2) {       // (fp32 maps: the 32x32 body needs 240 registers, 12 waves leave 168 -- it stays in launches of its own)
+    const int mt = (q.M + 31) / 32;
+    conv_sm_body<TM, 2, 2, 8, 3>(q, j % mt, (j / mt) * 8 + (local & 7), smem);
   }
 }
 
@@ -1469,11 +1517,15 @@ int conv_sm_tile(const sp3_gemm_desc& d) {
   if ((d.res1 || d.res2) && (d.res_bf16 != 0) != (d.out_bf16 != 0)) return -1;
   // the kernel divides by conv_C, OH * OW and OW with floor(2^32 / d) + 1 multiply-highs: d = 1 overflows the 32-bit magic
   if (d.conv_OW < 2 || d.conv_OH * d.conv_OW < 2 || d.conv_C < 2) return -1;
+  // a half-resolution res2 (bilinear x2 in the epilogue): the output is the 2 up_H x 2 up_W map or a crop of it
+  // (bf16 maps only: the fp32 upsample kernel's contraction is not the one up2x_mix spells out)
+  if ((d.res2_up_H != 0) != (d.res2_up_W != 0) || d.res2_up_H < 0 || (d.res2_up_H && !d.out_bf16) ||
+      (d.res2 && d.res2_up_H && (d.conv_OH > 2 * d.res2_up_H || d.conv_OW > 2 * d.res2_up_W))) return -1;
   if (d.M <= 256) return d.N % 16 == 0 ? 40 : -1;
   return d.N % 32 == 0 ? 41 : -1;
 }
 
-int conv_sm_dispatch(const sp3_gemm_desc& d, int tile, hipStream_t stream) {
+ConvSmArgs conv_sm_args(const sp3_gemm_desc& d) {
   ConvSmArgs a;
   a.x = d.A; a.W = reinterpret_cast<const char*>(d.W); a.out = d.C;
   a.bias = d.bias; a.res1 = d.res1; a.res2 = d.res2;
@@ -1481,12 +1533,51 @@ int conv_sm_dispatch(const sp3_gemm_desc& d, int tile, hipStream_t stream) {
   a.stride = d.conv_stride; a.nkb = d.K / 64; a.relu_in = d.relu_in; a.act = d.act;
   auto magic = [](int v) { return (unsigned)((1ull << 32) / (unsigned)v + 1); };
   a.cin_magic = magic(d.conv_C); a.per_magic = magic(d.conv_OH * d.conv_OW); a.ow_magic = magic(d.conv_OW);
+  a.up_H = d.res2 ? d.res2_up_H : 0; a.up_W = d.res2 ? d.res2_up_W : 0;
+  return a;
+}
+
+int conv_sm_dispatch(const sp3_gemm_desc& d, int tile, hipStream_t stream) {
+  const ConvSmArgs a = conv_sm_args(d);
   if (d.a_bf16) {
     if (tile == 40) return conv_sm_launch<__bf16, 1, 1, 12, 3>(a, stream);
     return conv_sm_launch<__bf16, 2, 2, 8, 3>(a, stream);
   }
   if (tile == 40) return conv_sm_launch<float, 1, 1, 12, 3>(a, stream);
   return conv_sm_launch<float, 2, 2, 8, 3>(a, stream);
+}
+
+// Level launch: problems sorted by the k-blocks a wave walks (longest first: its workgroups are dispatched first); block size and
+// dynamic LDS are those of the widest member.
+int conv_level_dispatch(const sp3_gemm_desc* ds, int n, hipStream_t stream) {
+  ConvLevelArgs a = {};
+  int order[4], cost[4];
+  for (int i = 0; i < n; ++i) {
+    order[i] = i;
+    cost[i] = conv_sm_tile(ds[i]) == 40 ? ds[i].K / 64 * 2 : ds[i].K / 64 * 3;     // k-blocks per wave x 24: K over 12 / 8 waves
+  }
+  for (int i = 1; i < n; ++i)
+    for (int j = i; j > 0 && cost[order[j]] > cost[order[j - 1]]; --j) { const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
+  size_t lds = 0;
+  int threads = 0;
+  for (int i = 0; i < n; ++i) {
+    const sp3_gemm_desc& d = ds[order[i]];
+    const int tile = conv_sm_tile(d);
+    const int bm = tile == 40 ? 16 : 32, wk = tile == 40 ? 12 : 8;
+    a.p[i] = conv_sm_args(d);
+    a.tile[i] = tile;
+    a.start[i + 1] = a.start[i] + 8 * ((d.M + bm - 1) / bm) * ((d.N / bm + 7) / 8);
+    const size_t l = (size_t)wk * bm * (bm + 4) * sizeof(float);
+    lds = l > lds ? l : lds;
+    threads = 64 * wk > threads ? 64 * wk : threads;
+  }
+  for (int i = n; i < 4; ++i) { a.p[i] = a.p[0]; a.tile[i] = a.tile[0]; a.start[i + 1] = 0x7fffffff; }
+  const int blocks = a.start[n];
+  if (n < 4) a.start[n] = 0x7fffffff;
+  if (ds[0].a_bf16) hipLaunchKernelGGL(conv_level_kernel<__bf16>, dim3(blocks), dim3(threads), lds, stream, a);
+  else              hipLaunchKernelGGL(conv_level_kernel<float>, dim3(blocks), dim3(threads), lds, stream, a);
+  SP3_LAUNCH_CHECK("sp3_gemm_n (lean conv3x3 level)");
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -1664,6 +1755,17 @@ bool sp3_gemm_sm_pairs(const sp3_gemm_desc& d) {
   const SmInst* s = sm_find(d);
   return s && s->epi == SM_ROPE;
 }
+
+bool sp3_gemm_sm_conv_level(const sp3_gemm_desc* ds, int n) {
+  if (!sm_enabled() || n < 2 || n > 4) return false;
+  for (int i = 0; i < n; ++i) {
+    const int t = conv_sm_tile(ds[i]);
+    if (t < 0 || (ds[i].tile >= 0 && ds[i].tile != t) || (ds[i].a_bf16 != 0) != (ds[0].a_bf16 != 0) || (t == 41 && !ds[i].a_bf16)) return false;
+  }
+  return true;
+}
+
+int sp3_gemm_sm_conv_level_launch(const sp3_gemm_desc* ds, int n, hipStream_t stream) { return conv_level_dispatch(ds, n, stream); }
 
 int sp3_gemm_sm_launch(const sp3_gemm_desc& d, const sp3_gemm_desc* pair, hipStream_t stream) {
   if (d.loader == SP3_LOAD_SOFTMAX && sm_enabled() && pvs_ok(d) && !pair && (d.tile < 30 || d.tile == 46)) return pvs_dispatch(d, stream);

@@ -692,33 +692,47 @@ class Engine:
         sized for the largest map that is ever split: 8 partial copies of <= 256 x 768 or 2 of 1024 x 256 outputs per image"""
         return self.ws("conv_splitk_ws" + str(head), (1 << 23,))
 
-    def _rcu(self, x, pre, B, H, W_, out, extra_res=None, tag=""):
-        """ResidualConvUnit_custom (croco/models/dpt_block.py:120-142): conv2(relu(conv1(relu(x)))) + x [+ extra]."""
+    def _rcu_c1(self, x, pre, B, H, W_, tag=""):
+        """first half of a ResidualConvUnit: relu(conv1(relu(x))) into the unit's scratch map (reads x only: the head issues it with
+        the level x belongs to, ahead of the rest of its refinenet)"""
         w, F = self.w, self.cfg.dpt_feat
         t = self.ws("rcu_tmp" + tag, (B * H * W_, F), self.mdt)
-        sk = self._conv_ws(tag[:1])
         ops.conv3x3(x, w[pre + "c1.w"], t, B=B, H=H, W_=W_, Cin=F, Cout=F, bias=w[pre + "c1.b"], relu_in=True, act=ACT_RELU,
-                    splitk_ws=sk)
+                    splitk_ws=self._conv_ws(tag[:1]))
+        return t
+
+    def _rcu(self, x, pre, B, H, W_, out, extra_res=None, tag="", c1_done=False, extra_up=None):
+        """ResidualConvUnit_custom (croco/models/dpt_block.py:120-142): conv2(relu(conv1(relu(x)))) + x [+ extra].
+        extra_up=(h, w): extra_res is the half-resolution map whose bilinear x2 is the residual (ops.conv3x3 res2_up)."""
+        w, F = self.w, self.cfg.dpt_feat
+        t = self.ws("rcu_tmp" + tag, (B * H * W_, F), self.mdt)
+        if not c1_done:
+            self._rcu_c1(x, pre, B, H, W_, tag)
         ops.conv3x3(t, w[pre + "c2.w"], out, B=B, H=H, W_=W_, Cin=F, Cout=F, bias=w[pre + "c2.b"], res1=x, res2=extra_res,
-                    splitk_ws=sk)
+                    splitk_ws=self._conv_ws(tag[:1]), res2_up=extra_up)
         return out
 
-    def _fusion(self, pre, B, H, W_, x0, x1, tag, crop=None):
+    def _fusion(self, pre, B, H, W_, x0, x1, tag, crop=None, c1_done=False, x0_up=None, fold_up=False):
         """FeatureFusionBlock_custom (croco/models/dpt_block.py:190-218).  The 1x1 out_conv is applied BEFORE the
         bilinear x2 (both are linear and the interpolation weights sum to 1, so the two commute exactly in real
-        arithmetic): 4x fewer FLOPs in out_conv.  x0/x1 NHWC [B,H,W,256]; returns ([B,2H,2W,256] or cropped, OH, OW)."""
+        arithmetic): 4x fewer FLOPs in out_conv.  x0/x1 NHWC [B,H,W,256]; returns ([B,2H,2W,256] or cropped, OH, OW).
+        c1_done: the block's first convolution (u1.c1, or u2.c1 without x1) was issued already.  x0_up=(h, w): x0 is the previous
+        block's out_conv result at half resolution.  fold_up: return that result (oc, OH, OW) instead of its upsampled map -- the next
+        block's u1.c2 takes the x2 in its epilogue."""
         w, F = self.w, self.cfg.dpt_feat
         M = B * H * W_
         cur = x0
         if x1 is not None:
             s = self.ws("fus_sum_" + tag, (M, F), self.mdt)
-            self._rcu(x1, pre + "u1", B, H, W_, s, extra_res=x0, tag=tag)
+            self._rcu(x1, pre + "u1", B, H, W_, s, extra_res=x0, tag=tag, c1_done=c1_done, extra_up=x0_up)
             cur = s
         r = self.ws("fus_rcu2_" + tag, (M, F), self.mdt)
-        self._rcu(cur, pre + "u2", B, H, W_, r, tag=tag)
+        self._rcu(cur, pre + "u2", B, H, W_, r, tag=tag, c1_done=c1_done and x1 is None)
         oc = self.ws("fus_oc_" + tag, (M, F), self.mdt)
         ops.gemm(r, w[pre + "out.w"], oc, M=M, N=F, K=F, lda=F, ldc=F, bias=w[pre + "out.b"])
         OH, OW = (2 * H, 2 * W_) if crop is None else crop
+        if fold_up:
+            return oc, OH, OW
         up = self.ws("fus_up_" + tag, (B * OH * OW, F), self.mdt)
         ops.upsample2x(oc, up, B=B, H=H, W_=W_, C_=F, outH=OH, outW=OW)
         return up, OH, OW
@@ -737,13 +751,16 @@ class Engine:
         mdt = self.mdt
         t = [self.ws("dpt%d_pp%d" % (num, i), (R, ld[i]), mdt) for i in range(4)]
         pairable = len({dec[hk[i]].dtype for i in range(4)}) == 1          # one kernel instance per pair (same operand dtypes)
-        # the four hooks are independent: two launches of two differently shaped problems each (sp3_gemm2)
+        # the four hooks are independent: one launch of four differently shaped problems (sp3_gemm_n), or two of two each (sp3_gemm2)
         import contextlib
+        lv = ops.HEAD_LEVELS
+        level = ops.level if lv else contextlib.nullcontext
         pair = ops.pair if pairable else contextlib.nullcontext
-        for i0 in (0, 2):
-            with pair():
-                for i in (i0, i0 + 1):
-                    ops.gemm(dec[hk[i]], w[pre + "pp%d.w" % i], t[i], M=R, N=ld[i], K=dims[i], lda=dims[i], ldc=ld[i], bias=w[pre + "pp%d.b" % i])
+        with (level if pairable else contextlib.nullcontext)():
+            for i0 in (0, 2):
+                with (contextlib.nullcontext if lv else pair)():
+                    for i in (i0, i0 + 1):
+                        ops.gemm(dec[hk[i]], w[pre + "pp%d.w" % i], t[i], M=R, N=ld[i], K=dims[i], lda=dims[i], ldc=ld[i], bias=w[pre + "pp%d.b" % i])
         # act_postprocess tails (croco/models/dpt_block.py:356-410)
         c0 = 128 if self.wdt == torch.bfloat16 else ld[0]         # (bf16 mode: 32 zero channels ride along, see _pack)
         l0 = self.ws("dpt%d_l0" % num, (B * 16 * nh * nw, c0), mdt)
@@ -755,21 +772,47 @@ class Engine:
         h3, w3 = (nh - 1) // 2 + 1, (nw - 1) // 2 + 1
         l3 = self.ws("dpt%d_l3" % num, (B * h3 * w3, ld[3]), mdt)
         sk = self._conv_ws(num)
-        ops.conv3x3(t[3], w[pre + "pp3c.w"], l3, B=B, H=nh, W_=nw, Cin=ld[3], Cout=ld[3], stride=2, bias=w[pre + "pp3c.b"],
-                    splitk_ws=sk)
         # scratch.layer_rn (3x3, no bias) -> 256 channels
         geo = ((4 * nh, 4 * nw), (2 * nh, 2 * nw), (nh, nw), (h3, w3))
-        rn = []
-        for i, src in enumerate((l0, l1, l2, l3)):
-            Hh, Ww = geo[i]
-            o = self.ws("dpt%d_rn%d" % (num, i), (B * Hh * Ww, F), mdt)
-            ops.conv3x3(src, w[pre + "rn%d.w" % i], o, B=B, H=Hh, W_=Ww, Cin=(c0 if i == 0 else ld[i]), Cout=F, splitk_ws=sk)
-            rn.append(o)
-        # refinenets; path_4 is cropped to layer 3's size (dust3r/heads/dpt_head.py:57)
-        p4, H4, W4 = self._fusion(pre + "ref4.", B, h3, w3, rn[3], None, "%d_4" % num, crop=(nh, nw))
-        p3, H3, W3 = self._fusion(pre + "ref3.", B, H4, W4, p4, rn[2], "%d_3" % num)
-        p2, H2, W2 = self._fusion(pre + "ref2.", B, H3, W3, p3, rn[1], "%d_2" % num)
-        p1, H1, W1 = self._fusion(pre + "ref1.", B, H2, W2, p2, rn[0], "%d_1" % num)
+        srcs = (l0, l1, l2, l3)
+        rn = [self.ws("dpt%d_rn%d" % (num, i), (B * geo[i][0] * geo[i][1], F), mdt) for i in range(4)]
+
+        def layer_rn(i):
+            ops.conv3x3(srcs[i], w[pre + "rn%d.w" % i], rn[i], B=B, H=geo[i][0], W_=geo[i][1], Cin=(c0 if i == 0 else ld[i]), Cout=F, splitk_ws=sk)
+
+        def pp3c():
+            ops.conv3x3(t[3], w[pre + "pp3c.w"], l3, B=B, H=nh, W_=nw, Cin=ld[3], Cout=ld[3], stride=2, bias=w[pre + "pp3c.b"], splitk_ws=sk)
+
+        refs = [(pre + "ref%d." % (4 - j), "%d_%d" % (num, 4 - j)) for j in range(4)]       # ref4 .. ref1 work on rn[3] .. rn[0]
+        if lv:
+            # launches by dependency level: what reads only the hooks' maps goes with the act_postprocess tails, and the first
+            # convolution of each refinenet (it reads rn[i] only) right after the layer_rn level
+            with level():
+                pp3c()
+                layer_rn(2)
+            with level():
+                layer_rn(0)
+                layer_rn(1)
+                layer_rn(3)
+                self._rcu_c1(rn[2], refs[1][0] + "u1", B, geo[2][0], geo[2][1], refs[1][1])
+            with level():
+                self._rcu_c1(rn[3], refs[0][0] + "u2", B, geo[3][0], geo[3][1], refs[0][1])
+                self._rcu_c1(rn[1], refs[2][0] + "u1", B, geo[1][0], geo[1][1], refs[2][1])
+                self._rcu_c1(rn[0], refs[3][0] + "u1", B, geo[0][0], geo[0][1], refs[3][1])
+        else:
+            pp3c()
+            for i in range(4):
+                layer_rn(i)
+        # refinenets; path_4 is cropped to layer 3's size (dust3r/heads/dpt_head.py:57).  The bilinear x2 between two refinenets is
+        # taken by the consumer's epilogue where its kernel can (small maps); the last one feeds a convolution's input and stays a launch
+        path, up, Hc, Wc = rn[3], None, h3, w3
+        for j in range(4):
+            Hn, Wn = geo[3 - j]
+            fold = lv and j < 3 and ops.conv3x3_takes_res2_up(w[refs[j + 1][0] + "u1c2.w"], mdt, B, *geo[2 - j])
+            nxt, OH_, OW_ = self._fusion(refs[j][0], B, Hn, Wn, path, rn[3 - j] if j else None, refs[j][1], crop=(nh, nw) if j == 0 else None,
+                                         c1_done=lv, x0_up=up, fold_up=fold)
+            path, up = nxt, ((Hn, Wn) if fold else None)
+        p1, H1, W1 = path, OH_, OW_
         # head: conv3x3(256->128) -> x2 -> conv3x3(128->128) + ReLU -> 1x1(128->4) + postprocess
         a = self.ws("dpt%d_h0" % num, (B * H1 * W1, Lc), mdt)
         ops.conv3x3(p1, w[pre + "h0.w"], a, B=B, H=H1, W_=W1, Cin=F, Cout=Lc, bias=w[pre + "h0.b"])

@@ -43,6 +43,7 @@ class GemmDesc(C.Structure):
         ("trace", C.c_void_p),
         ("sm_stats_out", C.c_void_p), ("sm_stats", C.c_void_p), ("sm_nt", C.c_int32), ("sm_thresh", C.c_float), ("sm_zout", C.c_void_p),
         ("f32x3", C.c_int32), ("res_bf16", C.c_int32), ("dyn_n", C.c_void_p),
+        ("res2_up_H", C.c_int32), ("res2_up_W", C.c_int32),
     ]
 
 
@@ -106,6 +107,7 @@ _lib = None
 _PROTOS = {
     "sp3_gemm": [C.POINTER(GemmDesc), C.c_void_p],
     "sp3_gemm2": [C.POINTER(GemmDesc), C.POINTER(GemmDesc), C.c_void_p],
+    "sp3_gemm_n": [C.POINTER(C.POINTER(GemmDesc)), C.c_int, C.c_void_p],
     "sp3_gemm_plan": [C.POINTER(GemmDesc)],
     "sp3_layernorm": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_int,
                       C.c_int, C.c_int, C.c_void_p],

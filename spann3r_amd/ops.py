@@ -155,7 +155,96 @@ PROF_SHAPES = _os.environ.get("SP3_PROF_SHAPES", "0")[:1] == "1"
 LEAN = _os.environ.get("SP3_LEAN_GEMM", "1")[:1] != "0"          # mirrors sm_enabled() in csrc/gemm_sm.hip: with the lean instances off the
                                                                   # engine must not pick the layouts only they serve (packed split-A, bf16 DPT maps)
 
+HEAD_LEVELS = _os.environ.get("SP3_HEAD_LEVELS", "1")[:1] != "0"  # DPT heads: one launch per dependency level, bilinear x2 folded into the
+                                                                  # consuming convolution (0: the launch-per-op schedule, for A/B runs)
 _pair = None
+
+
+def level_block_map(problems):
+    """Mirror of conv_level_kernel's workgroup map (csrc/gemm_sm.hip): problems = [(tile, M, N), ..] in launch order; returns
+    (total workgroups, f) with f(w) = (problem, tile_m, tile_n) -- tile_n may lie past the problem's last N-tile (padding of the
+    8-wide XCD groups: those workgroups exit)."""
+    start = [0]
+    for tile, M, N in problems:
+        bm = 16 if tile == 40 else 32
+        start.append(start[-1] + 8 * ((M + bm - 1) // bm) * ((N // bm + 7) // 8))
+
+    def f(w):
+        p = max(i for i in range(len(problems)) if w >= start[i])
+        tile, M, N = problems[p]
+        bm = 16 if tile == 40 else 32
+        mt = (M + bm - 1) // bm
+        local = w - start[p]
+        j = local >> 3
+        return p, j % mt, (j // mt) * 8 + (local & 7)
+    return start[-1], f
+
+
+def level_order(problems):
+    """launch order of a level's small-map convolutions (conv_level_dispatch): most k-blocks per wave first, stable"""
+    cost = [(K // 64) * (2 if tile == 40 else 3) for tile, K in problems]
+    return sorted(range(len(problems)), key=lambda i: -cost[i])
+
+
+class level:
+    """`with ops.level():` -- the independent launches issued inside (one dependency level, up to 4) go out as ONE launch where the
+    library has a kernel for the group (sp3_gemm_n): small-map convolutions on the lean tiles 40 / 41 (mixed, bf16 maps; fp32 maps: tile
+    40 only), or GEMMs of one general kernel instance.  What does not fit a group is launched on its own, after the group."""
+
+    def __enter__(self):
+        global _pair
+        assert _pair is None
+        _pair = []
+        return self
+
+    def __exit__(self, et, ev, tb):
+        global _pair
+        descs, _pair = _pair, None
+        if et is not None:
+            return False
+        lean = [x for x in descs if x[0].loader == L.LOAD_CONV3X3]                  # (only the lean small-map convolutions are held back)
+        conv = [x for x in lean if x[0].a_bf16 or x[0].tile == 40]
+        rest = [x for x in descs if x[0].loader != L.LOAD_CONV3X3]
+        if lean and rest:
+            raise RuntimeError("ops.level(): small-map convolutions and other GEMMs do not share a launch")
+        for x in lean:
+            if not any(x is y for y in conv):
+                self._send([x], True)
+        for group in (conv, rest):
+            for i in range(0, len(group), 4):
+                self._send(group[i:i + 4], group is conv)
+        return False
+
+    @staticmethod
+    def _send(group, is_conv):
+        if len(group) == 1:
+            _gemm_launch(group[0][0], "sp3_gemm", group[0][1])
+            return
+        ds = [g[0] for g in group]
+        if not is_conv:
+            # the general tiles: launches that ops.pair() would send two by two, each pair on its first member's tile (the K split of a
+            # tile is part of the arithmetic) -- one launch if the pairs agree on the tile, else pair by pair
+            for i in range(0, len(ds), 2):
+                if ds[i].tile < 0:
+                    _pick_general(ds[i])
+                for d in ds[i + 1:i + 2]:
+                    if d.tile < 0:
+                        d.tile = ds[i].tile
+            if len(ds) > 2 and len({d.tile for d in ds}) > 1:
+                for i in range(0, len(group), 2):
+                    level._send(group[i:i + 2], False)
+                return
+        arr = (C.POINTER(GemmDesc) * len(ds))(*[C.pointer(d) for d in ds])
+        e0 = _prof.begin() if _prof is not None else None
+        L.check(L.load().sp3_gemm_n(arr, len(ds), L.stream_ptr()), "sp3_gemm_n")
+        if _prof is not None:
+            fl, by = 0.0, 0.0
+            for d in ds:
+                f, n = _gemm_cost(d)
+                fl, by = fl + f, by + n
+            a = ds[0]
+            _prof.end("gemm_n<A%s,W%s,%s,%s x%d>" % ("bf16" if a.a_bf16 else "f32", "f32" if a.wdtype == F32 else "bf16", group[0][1],
+                                                     "+".join(sorted({_TILE_NAMES[d.tile] for d in ds})), len(ds)), e0, fl, by)
 
 
 class pair:
@@ -526,15 +615,19 @@ def reduce_ln(partial, splits, rows, C_, *, bias=None, res=None, ldres=0, x_out=
 
 
 def conv3x3(x, Wp, out, *, B, H, W_, Cin, Cout, stride=1, bias=None, res1=None, res2=None, act=ACT_NONE,
-            relu_in=False, tile=-1, force_tile_kernel=False, splitk_ws=None, tile_px=None):
+            relu_in=False, tile=-1, force_tile_kernel=False, splitk_ws=None, tile_px=None, res2_up=None):
     """3x3 Conv2d, padding 1, on an NHWC fp32 map [B,H,W,Cin] -> [B,OH,OW,Cout] (implicit GEMM).
     Wp is the weight packed as [Cout, 9*Cin] with k = (ky*3+kx)*Cin + ci.
+    res2_up=(h, w): res2 is the half-resolution map [B,h,w,Cout]; its bilinear x2 (upsample2x, cropped to the output) is what is added
+    (lean small-map kernels only; conv3x3_takes_res2_up tells).
     tile_px (LDS-tiled kernel only; tests and tools/bench_conv_tile.py): None = the library's size rule, "8x8" | "8x16" | "8x16n32" = that
     workgroup tile of sp3_conv3x3_tile (pixels, n32 = 32 instead of 64 output channels)."""
     OH, OW = (H - 1) // stride + 1, (W_ - 1) // stride + 1
     if (tile < 0 and stride == 1 and isinstance(Wp, PackedWeight) and Wp.dtype == torch.bfloat16
             and Cin % 64 == 0 and Cout % 64 == 0 and Cin <= 768 and (force_tile_kernel or B * H * W_ >= 2048)):
         # bf16 weights, stride 1: the LDS-tiled kernel (input halo tile staged once, 9 taps read it from LDS)
+        if res2_up is not None:
+            raise ValueError("conv3x3: a half-resolution res2 is read by the lean small-map kernels only (B*H*W=%d)" % (B * H * W_))
         _act(x, "x")
         rbf = [t.dtype == torch.bfloat16 for t in (res1, res2) if t is not None]
         if rbf and (any(rbf) != all(rbf) or (any(rbf) and out.dtype != torch.bfloat16)):
@@ -568,11 +661,15 @@ def conv3x3(x, Wp, out, *, B, H, W_, Cin, Cout, stride=1, bias=None, res1=None, 
         if rbf and any(rbf) != all(rbf):
             raise TypeError("conv3x3: residual maps must share one dtype")
         p.res_bf16 = int(any(rbf))                  # the lean instances read the residuals in the map dtype: the plan refuses a mismatch
+        if res2_up is not None:
+            p.res2_up_H, p.res2_up_W = res2_up
         lean = L.load().sp3_gemm_plan(C.byref(p))
         if lean >= 30:
             p.tile = lean
             _gemm_launch(p, "sp3_gemm(conv3x3)", "conv3x3")
             return out
+    if res2_up is not None:
+        raise ValueError("conv3x3: a half-resolution res2 is read by the lean small-map kernels only (B*H*W=%d)" % (B * H * W_))
     if any(t is not None and t.dtype == torch.bfloat16 for t in (res1, res2)):
         raise TypeError("conv3x3: bf16 residual maps are served by the lean small-map and the LDS-tiled kernels only "
                         "(B*H*W=%d, Cin=%d, Cout=%d, stride %d)" % (B * H * W_, Cin, Cout, stride))
@@ -588,11 +685,22 @@ def conv3x3(x, Wp, out, *, B, H, W_, Cin, Cout, stride=1, bias=None, res1=None, 
     d.loader, d.epi, d.tile = L.LOAD_CONV3X3, (L.EPI_PLAIN if S == 1 else L.EPI_PARTIAL), (tile if S == 1 else 0)
     d.splitk = S if S > 1 else 0
     d.conv_H, d.conv_W, d.conv_C, d.conv_OH, d.conv_OW, d.conv_stride = H, W_, Cin, OH, OW, stride
-    _gemm_launch(d, "sp3_gemm(conv3x3)", "conv3x3")
+    global _pair
+    held, _pair = _pair, None                       # (a split-K launch is followed by its reduce: never held back by a level)
+    try:
+        _gemm_launch(d, "sp3_gemm(conv3x3)", "conv3x3")
+    finally:
+        _pair = held
     if S > 1:
         # few output tiles, long K (small maps): K split over S workgroups per tile, finished by one reduce launch
         reduce_ln(splitk_ws, S, M, Cout, bias=bias, res=res1, ldres=Cout, x_out=out, ldx=Cout, act=act, res2=res2, ldres2=Cout)
     return out
+
+
+def conv3x3_takes_res2_up(Wp, map_dtype, B, H, W_):
+    """whether conv3x3 on this stride-1 map runs on a kernel that reads a half-resolution res2 (the lean small-map tiles: bf16 weights
+    and maps, fewer than 2048 pixels) -- the engine keeps the upsample2x launch in front of any other"""
+    return LEAN and isinstance(Wp, PackedWeight) and Wp.dtype == torch.bfloat16 and map_dtype == torch.bfloat16 and B * H * W_ < 2048
 
 
 def conv_splitk(M, N, K, wdtype):
