@@ -117,7 +117,8 @@ typedef struct sp3_gemm_desc {
                              64/16 (bf16) or 32/8 (fp32); lane = 16*g + r holds row 16*nb + r, k = kb*KB + g*CH + e: e < CH/2 in the first 1 KB
                              half of the 2 KB block, the rest in the second (every wave access is one contiguous KB).
                              2 (fp32 W, product mode f16x3 only): same blocks, but a lane's 32 bytes hold the fp16 planes of its 8 k --
-                             first half h = fp16(w), second half l = fp16((w - h) * 2^11), the split the kernel would take per use */
+                             first half h = fp16(w), second half l = fp16((w - h) * 2^11), the split the kernel would take per use.  Accepted only with
+                             wdtype fp32, f32x3 == 4, not the softmax loader and a resolved tile 0..2: anything else is an error (sp3_gemm_plan: -1) */
   /* --- grouped launches (batch > 1, grid.y): `batch` independent problems of one shape in one launch, e.g. the two
    *   sides of a DUSt3R decoder layer (different weights, dust3r/model.py:196-198).  A / W / C advance by strideA /
    *   strideW / strideC ELEMENTS per batch index (C in its own dtype, any epilogue, also the packed layouts), res1 /
@@ -167,16 +168,24 @@ typedef struct sp3_gemm_desc {
   int32_t res2_up_H, res2_up_W;
 } sp3_gemm_desc;
 int sp3_gemm(const sp3_gemm_desc* desc_host, void* stream);
-/* Two differently shaped groups of problems in ONE launch (grid.y = a.batch + b.batch), e.g. a decoder layer's self-attention
- * q/k/v projection (N = 2304) and its cross-attention k/v projection (N = 1536): both read the previous layer's tokens
- * (dust3r/model.py:196-198, croco/models/blocks.py:187-189), so the second launch boundary buys nothing.  Both descriptors
- * must resolve to the same kernel instance (dtypes, loader, tile; b.tile < 0 takes a's); no split-K. */
-int sp3_gemm2(const sp3_gemm_desc* a, const sp3_gemm_desc* b, void* stream);
-/* A level launch: n (1..4) independent problems, e.g. the convolutions of one dependency level of a DPT head, in ONE launch.
- * sp3_gemm2 is its n = 2 case.  Either every descriptor resolves to the same general kernel instance (the rules of sp3_gemm2; grid.y =
- * sum of the batches), or every one is a small-map convolution (tiles 40 / 41, which may be mixed: one 1-D grid, problem i owns a
- * contiguous range of workgroups, the one with the longest contraction first). */
+/* Launch planning.  Which kernel instance a descriptor runs on is decided in the library only (csrc/gemm.hip gemm_plan): hosts pass
+ * tile < 0 and ask sp3_gemm_plan / sp3_gemm_plan_n when they need the answer (a profile label, an operand layout to prepare).
+ *
+ * sp3_gemm_n: n (1..4) independent problems that depend on the same inputs, in ONE launch where the library has a kernel for the
+ * group; sp3_gemm is its n = 1 case.
+ *  - every descriptor a small-map convolution (tiles 40 / 41, which may be mixed): one level launch -- a 1-D grid in which problem i
+ *    owns a contiguous range of workgroups, the one with the longest contraction first.  (The level kernel holds tile 41 for bf16
+ *    maps only: an fp32 map on tile 41 goes out on its own, before the level.)
+ *  - n = 2, both on one lean q/k/v instance (ROPE_VT, tiles 30 / 31 / 50..): one launch of that instance, e.g. a decoder layer's
+ *    self-attention q/k/v projection (N = 2304) and its cross-attention k/v projection (N = 1536), which both read the previous
+ *    layer's tokens (dust3r/model.py:196-198, croco/models/blocks.py:187-189).
+ *  - otherwise differently shaped groups of ONE general kernel instance (grid.y = sum of the batches; same dtypes, loader and product
+ *    mode; no split-K, no softmax loader).  A pair's second descriptor with tile < 0 runs on the first one's tile.  With more than
+ *    two, every descriptor must resolve to the first one's tile by itself -- grouping never moves a member of a level to another
+ *    instance -- and a group that disagrees is refused.
+ * sp3_gemm_plan_n: tiles[i] = the tile sp3_gemm_n(descs, n) runs descs[i] on; nonzero for a group it refuses. */
 int sp3_gemm_n(const sp3_gemm_desc* const* descs, int n, void* stream);
+int sp3_gemm_plan_n(const sp3_gemm_desc* const* descs, int n, int* tiles);
 /* The tile sp3_gemm runs `desc` on when desc->tile < 0 (desc->tile itself is ignored), or < 0 for an invalid descriptor.  Tiles
  * 30.. are the LEAN small-M instances (csrc/gemm_sm.hip): the per-frame step's 196-row weight-streaming Linears
  * (croco/models/blocks.py:73-79,94-112,149-169 at batch 1) on bf16 fragment-order operands, with shape, tile and epilogue fixed at

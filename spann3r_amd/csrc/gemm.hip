@@ -1656,12 +1656,14 @@ void gemm_kernel(const GemmArgs args) {
   if (tr0) { tr0[2] = clock64(); tr0[4] = wall_clock64(); }
 }
 
-// sp3_gemm_n: the further groups of problems of the launch being dispatched (same kernel instance)
-thread_local const sp3_gemm_desc* g_more[3] = {nullptr, nullptr, nullptr};
-thread_local int g_nmore = 0;
+// sp3_gemm_n: the further groups of problems of a launch (they run on the first group's kernel instance)
+struct MoreGroups {
+  const sp3_gemm_desc* d[3] = {nullptr, nullptr, nullptr};
+  int n = 0;
+};
 
 template <typename TA, typename TW, int LOADER, int MF, int NF, int WM, int WN, int WK, int STAGES, int LOOP = 0, int XM = 0>
-int launch(const sp3_gemm_desc& d, hipStream_t stream) {
+int launch(const sp3_gemm_desc& d, const MoreGroups& more, hipStream_t stream) {
   constexpr bool LDSK = LOOP != 0;
   constexpr int BM = MF * 16 * WM, BN = NF * 16 * WN, NT = 64 * (WM * WN * WK + (LOOP >= 2 ? LOOP : 0));
   auto grid_x = [](const sp3_gemm_desc& q) {
@@ -1688,11 +1690,11 @@ int launch(const sp3_gemm_desc& d, hipStream_t stream) {
   a.nb[0] = 0;
   int gy = d.batch;
   for (int i = 1; i < 4; ++i) {
-    if (i <= g_nmore) {              // workgroups past a group's own tile count exit at once
-      a.dn[i] = *g_more[i - 1];
+    if (i <= more.n) {               // workgroups past a group's own tile count exit at once
+      a.dn[i] = *more.d[i - 1];
       a.nb[i] = gy;
-      gy += g_more[i - 1]->batch;
-      const int b2 = grid_x(*g_more[i - 1]);
+      gy += more.d[i - 1]->batch;
+      const int b2 = grid_x(*more.d[i - 1]);
       blocks = blocks > b2 ? blocks : b2;
     } else {
       a.dn[i] = d;
@@ -1706,16 +1708,16 @@ int launch(const sp3_gemm_desc& d, hipStream_t stream) {
 }
 
 template <typename TA, typename TW, int LOADER>
-int dispatch_tile(const sp3_gemm_desc& d, int tile, hipStream_t stream) {
+int dispatch_tile(const sp3_gemm_desc& d, const MoreGroups& more, int tile, hipStream_t stream) {
   if constexpr (sizeof(TA) == 4 && sizeof(TW) == 4) {
     // fp32 operands on the register-ring tiles 0-2: the product mode (sp3_gemm_desc.f32x3) selects the kernel instance
     const int xm = d.f32x3;
     if (xm >= 1 && xm <= 4 && tile >= 0 && tile <= 2) {
 #define SP3_XM_TILES(XM_)                                                                         \
       switch (tile) {                                                                             \
-        case 0: return launch<TA, TW, LOADER, 2, 2, 1, 1, 4, 3, 0, XM_>(d, stream);               \
-        case 1: return launch<TA, TW, LOADER, 2, 2, 2, 2, 1, 2, 0, XM_>(d, stream);               \
-        default: return launch<TA, TW, LOADER, 2, 4, 2, 2, 1, 2, 0, XM_>(d, stream);              \
+        case 0: return launch<TA, TW, LOADER, 2, 2, 1, 1, 4, 3, 0, XM_>(d, more, stream);               \
+        case 1: return launch<TA, TW, LOADER, 2, 2, 2, 2, 1, 2, 0, XM_>(d, more, stream);               \
+        default: return launch<TA, TW, LOADER, 2, 4, 2, 2, 1, 2, 0, XM_>(d, more, stream);              \
       }
       if (xm == 1) { SP3_XM_TILES(1) }
       if (xm == 2) { SP3_XM_TILES(2) }
@@ -1726,14 +1728,14 @@ int dispatch_tile(const sp3_gemm_desc& d, int tile, hipStream_t stream) {
     }
   }
   switch (tile) {
-    case 0: return launch<TA, TW, LOADER, 2, 2, 1, 1, 4, 3>(d, stream);   // 32x32, K over 4 waves
-    case 1: return launch<TA, TW, LOADER, 2, 2, 2, 2, 1, 2>(d, stream);   // 64x64, wave tile 32x32
-    case 2: return launch<TA, TW, LOADER, 2, 4, 2, 2, 1, 2>(d, stream);   // 64x128, wave tile 32x64
-    case 3: return launch<TA, TW, LOADER, 4, 4, 1, 1, 4, 3>(d, stream);   // 64x64, K over 4 waves
+    case 0: return launch<TA, TW, LOADER, 2, 2, 1, 1, 4, 3>(d, more, stream);   // 32x32, K over 4 waves
+    case 1: return launch<TA, TW, LOADER, 2, 2, 2, 2, 1, 2>(d, more, stream);   // 64x64, wave tile 32x32
+    case 2: return launch<TA, TW, LOADER, 2, 4, 2, 2, 1, 2>(d, more, stream);   // 64x128, wave tile 32x64
+    case 3: return launch<TA, TW, LOADER, 4, 4, 1, 1, 4, 3>(d, more, stream);   // 64x64, K over 4 waves
     case 4: case 18:                                                       // 32x64 / 16x64, K over 4 waves (bf16 operands)
       if constexpr (sizeof(TA) == 2 && LOADER == SP3_LOAD_PLAIN) {
-        if (tile == 4) return launch<TA, TW, LOADER, 2, 4, 1, 1, 4, 3>(d, stream);
-        return launch<TA, TW, LOADER, 1, 4, 1, 1, 4, 3>(d, stream);
+        if (tile == 4) return launch<TA, TW, LOADER, 2, 4, 1, 1, 4, 3>(d, more, stream);
+        return launch<TA, TW, LOADER, 1, 4, 1, 1, 4, 3>(d, more, stream);
       }
       sp3_set_error("sp3_gemm: tile %d needs bf16 A and the plain loader", tile);
       return 1;
@@ -1741,12 +1743,12 @@ int dispatch_tile(const sp3_gemm_desc& d, int tile, hipStream_t stream) {
       if constexpr (sizeof(TA) == sizeof(TW) && LOADER == SP3_LOAD_PLAIN) {
         if (d.a_packed && d.w_packed && !d.A2 && d.K % MM<TA, TW>::KB == 0) {
           switch (tile) {
-            case 20: return launch<TA, TW, LOADER, 4, 4, 4, 2, 1, 3, -1>(d, stream);   // 256x128, 4x2 waves of 64x64, 3 slots
-            case 21: return launch<TA, TW, LOADER, 4, 4, 2, 2, 2, 4, -1>(d, stream);   // 128x128, 2x2 waves of 64x64 x 2 K halves, 4 slots
-            case 22: return launch<TA, TW, LOADER, 4, 4, 2, 1, 2, 3, -1>(d, stream);   // 128x64,  2x1 waves of 64x64 x 2 K halves
-            case 24: return launch<TA, TW, LOADER, 4, 2, 1, 1, 2, 4, -1>(d, stream);   // 64x32,   1 wave pair, 4 slots (score GEMM of the read)
-            case 25: return launch<TA, TW, LOADER, 2, 2, 1, 1, 2, 4, -1>(d, stream);   // 32x32,   1 wave pair, 4 slots
-            default: return launch<TA, TW, LOADER, 4, 4, 1, 1, 2, 4, -1>(d, stream);   // 64x64,   1 wave pair (2 K halves), 4 slots
+            case 20: return launch<TA, TW, LOADER, 4, 4, 4, 2, 1, 3, -1>(d, more, stream);   // 256x128, 4x2 waves of 64x64, 3 slots
+            case 21: return launch<TA, TW, LOADER, 4, 4, 2, 2, 2, 4, -1>(d, more, stream);   // 128x128, 2x2 waves of 64x64 x 2 K halves, 4 slots
+            case 22: return launch<TA, TW, LOADER, 4, 4, 2, 1, 2, 3, -1>(d, more, stream);   // 128x64,  2x1 waves of 64x64 x 2 K halves
+            case 24: return launch<TA, TW, LOADER, 4, 2, 1, 1, 2, 4, -1>(d, more, stream);   // 64x32,   1 wave pair, 4 slots (score GEMM of the read)
+            case 25: return launch<TA, TW, LOADER, 2, 2, 1, 1, 2, 4, -1>(d, more, stream);   // 32x32,   1 wave pair, 4 slots
+            default: return launch<TA, TW, LOADER, 4, 4, 1, 1, 2, 4, -1>(d, more, stream);   // 64x64,   1 wave pair (2 K halves), 4 slots
           }
         }
       }
@@ -1756,14 +1758,14 @@ int dispatch_tile(const sp3_gemm_desc& d, int tile, hipStream_t stream) {
       if constexpr (sizeof(TA) == sizeof(TW) && LOADER == SP3_LOAD_PLAIN) {
         if (d.a_packed && d.w_packed && !d.A2 && d.K % MM<TA, TW>::KB == 0) {
           switch (tile) {
-            case 5: return launch<TA, TW, LOADER, 4, 4, 2, 2, 1, 2, 1>(d, stream);    // 128x128, 2x2 waves of 64x64
-            case 6: return launch<TA, TW, LOADER, 4, 2, 2, 2, 1, 2, 1>(d, stream);    // 128x64,  2x2 waves of 64x32
-            case 7: return launch<TA, TW, LOADER, 7, 1, 1, 4, 1, 4, 1>(d, stream);    // 112x64,  4 waves of 112x16, 4 slots
-            case 8: return launch<TA, TW, LOADER, 13, 1, 1, 4, 1, 3, 1>(d, stream);   // 208x64,  4 waves of 208x16, 3 slots
-            case 9: return launch<TA, TW, LOADER, 7, 1, 1, 2, 1, 4, 1>(d, stream);    // 112x32,  2 waves of 112x16, 4 slots
-            case 10: return launch<TA, TW, LOADER, 7, 2, 1, 2, 1, 4, 1>(d, stream);   // 112x64,  2 waves of 112x32, 4 slots
-            case 11: return launch<TA, TW, LOADER, 7, 1, 1, 4, 2, 4, 1>(d, stream);   // 112x64,  4x2 waves (K halves), 4 slots
-            case 12: return launch<TA, TW, LOADER, 13, 1, 1, 4, 2, 3, 1>(d, stream);  // 208x64,  4x2 waves (K halves), 3 slots
+            case 5: return launch<TA, TW, LOADER, 4, 4, 2, 2, 1, 2, 1>(d, more, stream);    // 128x128, 2x2 waves of 64x64
+            case 6: return launch<TA, TW, LOADER, 4, 2, 2, 2, 1, 2, 1>(d, more, stream);    // 128x64,  2x2 waves of 64x32
+            case 7: return launch<TA, TW, LOADER, 7, 1, 1, 4, 1, 4, 1>(d, more, stream);    // 112x64,  4 waves of 112x16, 4 slots
+            case 8: return launch<TA, TW, LOADER, 13, 1, 1, 4, 1, 3, 1>(d, more, stream);   // 208x64,  4 waves of 208x16, 3 slots
+            case 9: return launch<TA, TW, LOADER, 7, 1, 1, 2, 1, 4, 1>(d, more, stream);    // 112x32,  2 waves of 112x16, 4 slots
+            case 10: return launch<TA, TW, LOADER, 7, 2, 1, 2, 1, 4, 1>(d, more, stream);   // 112x64,  2 waves of 112x32, 4 slots
+            case 11: return launch<TA, TW, LOADER, 7, 1, 1, 4, 2, 4, 1>(d, more, stream);   // 112x64,  4x2 waves (K halves), 4 slots
+            case 12: return launch<TA, TW, LOADER, 13, 1, 1, 4, 2, 3, 1>(d, more, stream);  // 208x64,  4x2 waves (K halves), 3 slots
             // weight streaming with roles: consumers keep their weights in a register ring, 2 loader waves DMA the activations
             default: break;
           }
@@ -1777,11 +1779,11 @@ int dispatch_tile(const sp3_gemm_desc& d, int tile, hipStream_t stream) {
             return 1;
           }
           if constexpr (sizeof(TA) == 2) switch (tile) {      // bf16 only (the fp32 mode is MFMA-bound, not weight-bound)
-            case 13: return launch<TA, TW, LOADER, 7, 1, 1, 4, 2, 4, 2>(d, stream);   // 112x64,  4x2 consumer waves + 2 loaders
-            case 14: return launch<TA, TW, LOADER, 7, 1, 1, 4, 1, 4, 2>(d, stream);   // 112x64,  4 consumer waves + 2 loaders
-            case 15: return launch<TA, TW, LOADER, 13, 1, 1, 4, 2, 3, 2>(d, stream);  // 208x64,  4x2 consumer waves + 2 loaders
-            case 16: return launch<TA, TW, LOADER, 7, 1, 1, 4, 1, 4, 6>(d, stream);   // 112x64,  4 consumer waves + 6 loaders
-            case 17: return launch<TA, TW, LOADER, 7, 1, 1, 4, 2, 4, 4>(d, stream);   // 112x64,  4x2 consumer waves + 4 loaders
+            case 13: return launch<TA, TW, LOADER, 7, 1, 1, 4, 2, 4, 2>(d, more, stream);   // 112x64,  4x2 consumer waves + 2 loaders
+            case 14: return launch<TA, TW, LOADER, 7, 1, 1, 4, 1, 4, 2>(d, more, stream);   // 112x64,  4 consumer waves + 2 loaders
+            case 15: return launch<TA, TW, LOADER, 13, 1, 1, 4, 2, 3, 2>(d, more, stream);  // 208x64,  4x2 consumer waves + 2 loaders
+            case 16: return launch<TA, TW, LOADER, 7, 1, 1, 4, 1, 4, 6>(d, more, stream);   // 112x64,  4 consumer waves + 6 loaders
+            case 17: return launch<TA, TW, LOADER, 7, 1, 1, 4, 2, 4, 4>(d, more, stream);   // 112x64,  4x2 consumer waves + 4 loaders
           }
         }
       }
@@ -1902,10 +1904,6 @@ static int gemm_prepare(sp3_gemm_desc& d, int& tile_out) {
       tile = 0;
     } else if (d.loader != SP3_LOAD_CONV3X3 && d.M >= 1024) {
       tile = 1;                                           // many rows, narrow N (also split-K partials): 64x64 register tiles
-      // fp32 operands (the fp32 / f32x6 / f16x3 modes' whole-sequence encoder): the register-ring tiles are bound by L2 -> CU bytes,
-      // the 64 x 128 tile moves a quarter fewer per product -- wide N only (f16x3 at 1960 rows: q/k/v 85.5 -> 72.4 us, fc1 113.5 ->
-      // 86.4; N = 1024 leaves 248 workgroups and loses: 102.8 -> 122.4 us; profiles/r06_f16x3_manyrow_tiles.txt)
-      if (d.wdtype == SP3_F32 && !d.a_bf16 && sk == 1 && d.epi != SP3_EPI_PARTIAL && d.N % 128 == 0 && t128 >= 512) tile = 2;
     } else if (lds_ok && d.M <= 224 && d.M > 112 && d.epi == SP3_EPI_PLAIN && d.N >= 3072 && d.K <= 1024 &&
                (!d.ln_stats || d.ln_nt <= 32)) {
       // the widest 196-row GEMMs (fc1 of the decoder pair and of the value encoder): 112x64 role tile -- consumers keep
@@ -1923,109 +1921,135 @@ static int gemm_prepare(sp3_gemm_desc& d, int& tile_out) {
     }
   }
   SP3_CHECK(!d.sm_stats_out || tile <= 3 || tile >= 20, "sp3_gemm: sm_stats_out needs a register-ring tile (0-3) or a pipelined one (20-25)");
+  // (only dispatch_tile's f16x3 instances of the register-ring tiles read the planes; anything else would take them for fp32 values)
+  SP3_CHECK(d.w_packed != 2 || (d.wdtype == SP3_F32 && d.f32x3 == 4 && d.loader != SP3_LOAD_SOFTMAX && tile >= 0 && tile <= 2),
+            "sp3_gemm: w_packed = 2 (fp16 planes) needs fp32 weights, the f16x3 product mode, not the softmax loader, and tile 0..2 (tile %d)", tile);
   tile_out = tile;
   return 0;
 }
 
-static int gemm_dispatch(const sp3_gemm_desc& d, int tile, hipStream_t stream) {
+static int gemm_dispatch(const sp3_gemm_desc& d, const MoreGroups& more, int tile, hipStream_t stream) {
   if (d.loader == SP3_LOAD_SOFTMAX) {
     // 16 x 64 tile, K over the 4 waves: the probabilities of a row are rebuilt by every column tile, so few wide ones
     // (32 x 32: 16.6 us at 196 x 1764, half of it exponentials)
     if (d.tile == 1) {
-      if (d.wdtype == SP3_BF16) return launch<float, __bf16, SP3_LOAD_SOFTMAX, 2, 2, 1, 1, 4, 3>(d, stream);
-      return launch<float, float, SP3_LOAD_SOFTMAX, 2, 2, 1, 1, 4, 3>(d, stream);
+      if (d.wdtype == SP3_BF16) return launch<float, __bf16, SP3_LOAD_SOFTMAX, 2, 2, 1, 1, 4, 3>(d, more, stream);
+      return launch<float, float, SP3_LOAD_SOFTMAX, 2, 2, 1, 1, 4, 3>(d, more, stream);
     }
-    if (d.wdtype == SP3_BF16) return launch<float, __bf16, SP3_LOAD_SOFTMAX, 1, 4, 1, 1, 4, 3>(d, stream);
-    return launch<float, float, SP3_LOAD_SOFTMAX, 1, 4, 1, 1, 4, 3>(d, stream);
+    if (d.wdtype == SP3_BF16) return launch<float, __bf16, SP3_LOAD_SOFTMAX, 1, 4, 1, 1, 4, 3>(d, more, stream);
+    return launch<float, float, SP3_LOAD_SOFTMAX, 1, 4, 1, 1, 4, 3>(d, more, stream);
   }
   if (d.wdtype == SP3_BF16) {
     if (d.a_bf16) {
-      if (d.loader == SP3_LOAD_PLAIN) return dispatch_tile<__bf16, __bf16, SP3_LOAD_PLAIN>(d, tile, stream);
-      return dispatch_tile<__bf16, __bf16, SP3_LOAD_CONV3X3>(d, tile, stream);
+      if (d.loader == SP3_LOAD_PLAIN) return dispatch_tile<__bf16, __bf16, SP3_LOAD_PLAIN>(d, more, tile, stream);
+      return dispatch_tile<__bf16, __bf16, SP3_LOAD_CONV3X3>(d, more, tile, stream);
     }
-    if (d.loader == SP3_LOAD_PLAIN) return dispatch_tile<float, __bf16, SP3_LOAD_PLAIN>(d, tile, stream);
-    return dispatch_tile<float, __bf16, SP3_LOAD_CONV3X3>(d, tile, stream);
+    if (d.loader == SP3_LOAD_PLAIN) return dispatch_tile<float, __bf16, SP3_LOAD_PLAIN>(d, more, tile, stream);
+    return dispatch_tile<float, __bf16, SP3_LOAD_CONV3X3>(d, more, tile, stream);
   } else {
-    if (d.loader == SP3_LOAD_PLAIN) return dispatch_tile<float, float, SP3_LOAD_PLAIN>(d, tile, stream);
-    return dispatch_tile<float, float, SP3_LOAD_CONV3X3>(d, tile, stream);
+    if (d.loader == SP3_LOAD_PLAIN) return dispatch_tile<float, float, SP3_LOAD_PLAIN>(d, more, tile, stream);
+    return dispatch_tile<float, float, SP3_LOAD_CONV3X3>(d, more, tile, stream);
   }
 }
 
-extern "C" int sp3_gemm(const sp3_gemm_desc* dp, void* stream_) {
-  SP3_CHECK(dp != nullptr, "sp3_gemm: null descriptor");
-  sp3_gemm_desc d = *dp;
-  int tile = -1;
-  if (int rc = gemm_prepare(d, tile)) return rc;
-  // the 196-row weight-streaming shapes of the per-frame step: lean shape-specialised instances (gemm_sm.hip, tiles 30..)
-  if (d.tile >= 30 || (d.tile < 0 && sp3_gemm_sm_tile(d) >= 0)) return sp3_gemm_sm_launch(d, nullptr, reinterpret_cast<hipStream_t>(stream_));
-  SP3_CHECK(!(d.a_packed && d.A2), "sp3_gemm: a fragment-order A split along K runs on the lean instances only (no instance for M=%d N=%d K=%d)", d.M, d.N, d.K);
-  SP3_CHECK(!(d.res_bf16 && (d.res1 || d.res2)), "sp3_gemm: bf16 residual maps are read by the lean small-map convolutions only (res_bf16 = out_bf16 = a_bf16; M=%d N=%d K=%d)", d.M, d.N, d.K);
-  SP3_CHECK(!d.res2_up_H, "sp3_gemm: a half-resolution res2 is read by the lean small-map convolutions only (tiles 40 / 41; M=%d N=%d K=%d)", d.M, d.N, d.K);
-  SP3_CHECK(!d.dyn_n, "sp3_gemm: a device-side extent (dyn_n) is served by the lean memory-read instances only (tiles 43 / 44; M=%d N=%d K=%d)", d.M, d.N, d.K);
-  return gemm_dispatch(d, tile, reinterpret_cast<hipStream_t>(stream_));
+// How one call goes out: the prepared descriptors, the tile each one runs on and the kernel family that takes them.  sp3_gemm
+// (n = 1) and sp3_gemm_n launch what gemm_plan decides, sp3_gemm_plan / sp3_gemm_plan_n report it: the rules exist once, here.
+struct GroupPlan {
+  sp3_gemm_desc d[4];
+  int tile[4] = {-1, -1, -1, -1};
+  enum { GENERAL, LEAN, CONV_LEVEL } kind = GENERAL;
+};
+
+static int gemm_plan(const sp3_gemm_desc* const* dp, int n, GroupPlan& p) {
+  SP3_CHECK(dp != nullptr && n >= 1 && n <= 4, "sp3_gemm_n: 1..4 descriptors (n=%d)", n);
+  int lean[4];
+  for (int i = 0; i < n; ++i) {
+    SP3_CHECK(dp[i] != nullptr, "sp3_gemm_n: null descriptor");
+    p.d[i] = *dp[i];
+    if (int rc = gemm_prepare(p.d[i], p.tile[i])) return rc;
+    lean[i] = sp3_gemm_sm_tile(p.d[i]);
+  }
+  // the lean shape-specialised instances (gemm_sm.hip, tiles 30..) are decided before the general tiles are consulted
+  const int want = p.d[0].tile;
+  if (n == 1) {
+    if (want >= 30 || (want < 0 && lean[0] >= 0)) {
+      p.kind = GroupPlan::LEAN;
+      p.tile[0] = want >= 30 ? want : lean[0];
+    }
+    return 0;
+  }
+  if (sp3_gemm_sm_conv_level(p.d, n)) {
+    p.kind = GroupPlan::CONV_LEVEL;
+    for (int i = 0; i < n; ++i) p.tile[i] = lean[i];
+    return 0;
+  }
+  // (only the q/k/v projections' ROPE instances take a second group; two STREAM / PACKED problems that share an instance
+  //  pair on the general tiles below, as they did before the lean families existed)
+  if (n == 2 && lean[0] >= 30 && lean[0] == lean[1] && sp3_gemm_sm_pairs(p.d[0]) && (want < 0 || want == lean[0])) {
+    p.kind = GroupPlan::LEAN;
+    p.tile[0] = p.tile[1] = lean[0];
+    return 0;
+  }
+  SP3_CHECK(want < 30, "sp3_gemm_n: tile %d asks for a lean instance that does not take these %d groups", want, n);
+  for (int i = 1; i < n; ++i) {
+    sp3_gemm_desc& d = p.d[i];
+    // a pair's second group runs on the first one's tile (the K split of a tile is part of the arithmetic: the rule the decoder's
+    // q/k/v + cross k/v launch was measured with).  With more groups every member must choose that tile itself, so that no member
+    // of a level changes its kernel instance by being grouped: a level that disagrees is refused.
+    if (n == 2 && d.tile < 0) {
+      d.tile = p.tile[0];
+      if (int rc = gemm_prepare(d, p.tile[i])) return rc;
+    }
+    SP3_CHECK(p.tile[i] == p.tile[0] && d.wdtype == p.d[0].wdtype && d.a_bf16 == p.d[0].a_bf16 && d.loader == p.d[0].loader &&
+              d.f32x3 == p.d[0].f32x3 && (d.w_packed == 2) == (p.d[0].w_packed == 2),
+              "sp3_gemm_n: every group must use one kernel instance (tile %d / %d, same dtypes and loader)", p.tile[0], p.tile[i]);
+  }
+  for (int i = 0; i < n; ++i)
+    SP3_CHECK(p.d[i].loader != SP3_LOAD_SOFTMAX && p.d[i].splitk == 1 && !p.d[i].trace && !p.d[i].dyn_n,
+              "sp3_gemm_n: no softmax loader, no split-K, no trace, no device-side extent");
+  return 0;
+}
+
+static int gemm_run(const GroupPlan& p, int n, hipStream_t stream) {
+  if (p.kind == GroupPlan::CONV_LEVEL) return sp3_gemm_sm_conv_level_launch(p.d, n, stream);
+  if (p.kind == GroupPlan::LEAN) return sp3_gemm_sm_launch(p.d[0], n == 2 ? &p.d[1] : nullptr, stream);
+  MoreGroups more;
+  for (int i = 0; i < n; ++i) {
+    const sp3_gemm_desc& d = p.d[i];
+    SP3_CHECK(!(d.a_packed && d.A2), "sp3_gemm: a fragment-order A split along K runs on the lean instances only (no instance for M=%d N=%d K=%d)", d.M, d.N, d.K);
+    SP3_CHECK(!(d.res_bf16 && (d.res1 || d.res2)), "sp3_gemm: bf16 residual maps are read by the lean small-map convolutions only (res_bf16 = out_bf16 = a_bf16; M=%d N=%d K=%d)", d.M, d.N, d.K);
+    SP3_CHECK(!d.res2_up_H, "sp3_gemm: a half-resolution res2 is read by the lean small-map convolutions only (tiles 40 / 41; M=%d N=%d K=%d)", d.M, d.N, d.K);
+    SP3_CHECK(!d.dyn_n, "sp3_gemm: a device-side extent (dyn_n) is served by the lean memory-read instances only (tiles 43 / 44; M=%d N=%d K=%d)", d.M, d.N, d.K);
+    if (i > 0) more.d[more.n++] = &d;
+  }
+  return gemm_dispatch(p.d[0], more, p.tile[0], stream);
+}
+
+extern "C" int sp3_gemm_n(const sp3_gemm_desc* const* dp, int n, void* stream_) {
+  GroupPlan p;
+  if (int rc = gemm_plan(dp, n, p)) return rc;
+  return gemm_run(p, n, reinterpret_cast<hipStream_t>(stream_));
+}
+
+extern "C" int sp3_gemm(const sp3_gemm_desc* dp, void* stream_) { return sp3_gemm_n(&dp, 1, stream_); }
+
+// The tile sp3_gemm_n(descs, n) runs each descriptor on (tiles[0..n)); nonzero (sp3_last_error) for a group it refuses.  Hosts
+// label profiles with it.
+extern "C" int sp3_gemm_plan_n(const sp3_gemm_desc* const* dp, int n, int* tiles) {
+  GroupPlan p;
+  SP3_CHECK(tiles != nullptr, "sp3_gemm_plan_n: null tiles");
+  if (int rc = gemm_plan(dp, n, p)) return rc;
+  for (int i = 0; i < n; ++i) tiles[i] = p.tile[i];
+  return 0;
 }
 
 // The tile sp3_gemm would run this descriptor on when desc.tile < 0 (the lean instances 30.. included); < 0: invalid descriptor
-// (sp3_last_error).  Hosts use it to label profiles and to decide whether two launches can be paired.
+// (sp3_last_error).  Hosts use it to decide which operand layout to prepare.
 extern "C" int sp3_gemm_plan(const sp3_gemm_desc* dp) {
   if (!dp) return -1;
   sp3_gemm_desc d = *dp;
   d.tile = -1;
-  int tile = -1;
-  if (gemm_prepare(d, tile)) return -1;
-  const int lean = sp3_gemm_sm_tile(d);
-  return lean >= 0 ? lean : tile;
-}
-
-extern "C" int sp3_gemm_n(const sp3_gemm_desc* const* dp, int n, void* stream_) {
-  SP3_CHECK(dp != nullptr && n >= 1 && n <= 4, "sp3_gemm_n: 1..4 descriptors (n=%d)", n);
-  for (int i = 0; i < n; ++i) SP3_CHECK(dp[i] != nullptr, "sp3_gemm_n: null descriptor");
-  if (n == 1) return sp3_gemm(dp[0], stream_);
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  sp3_gemm_desc d[4];
-  int t[4] = {-1, -1, -1, -1};
-  {
-    // every group on the lean instances (gemm_sm.hip): decided before the legacy tiles are consulted
-    sp3_gemm_desc d0[4];
-    const int want = dp[0]->tile;
-    bool ok = true;
-    for (int i = 0; i < n; ++i) {
-      d0[i] = *dp[i];
-      const int keep = d0[i].tile;
-      d0[i].tile = -1;
-      int ti = -1;
-      ok = ok && gemm_prepare(d0[i], ti) == 0;
-      if (d0[i].loader == SP3_LOAD_CONV3X3) d0[i].tile = keep;    // (a level of small-map convolutions may name its tiles 40 / 41)
-    }
-    if (ok && sp3_gemm_sm_conv_level(d0, n)) return sp3_gemm_sm_conv_level_launch(d0, n, stream);
-    if (ok && n == 2) {
-      d0[0].tile = d0[1].tile = -1;
-      const int la = sp3_gemm_sm_tile(d0[0]), lb = sp3_gemm_sm_tile(d0[1]);
-      // (only the q/k/v projections' ROPE instances take a second group; two STREAM / PACKED problems that share an instance
-      //  pair on the general tiles below, as they did before the lean families existed)
-      if (la >= 30 && la == lb && sp3_gemm_sm_pairs(d0[0]) && (want < 0 || want == la)) return sp3_gemm_sm_launch(d0[0], &d0[1], stream);
-    }
-    SP3_CHECK(want < 30, "sp3_gemm_n: tile %d asks for a lean instance that does not take these %d groups", want, n);
-  }
-  for (int i = 0; i < n; ++i) {
-    d[i] = *dp[i];
-    if (i > 0 && d[i].tile < 0) d[i].tile = t[0];                 // the further groups run on the first one's kernel instance
-    if (int rc = gemm_prepare(d[i], t[i])) return rc;
-    SP3_CHECK(!(d[i].res_bf16 && (d[i].res1 || d[i].res2)) && !d[i].res2_up_H, "sp3_gemm_n: bf16 and half-resolution residual maps are read by the lean small-map convolutions only");
-    SP3_CHECK(t[i] == t[0] && d[i].wdtype == d[0].wdtype && d[i].a_bf16 == d[0].a_bf16 && d[i].loader == d[0].loader && d[i].loader != SP3_LOAD_SOFTMAX &&
-              d[i].f32x3 == d[0].f32x3 && (d[i].w_packed == 2) == (d[0].w_packed == 2),
-              "sp3_gemm_n: every group must use one kernel instance (tile %d / %d, same dtypes and loader)", t[0], t[i]);
-    SP3_CHECK(d[i].splitk == 1 && !d[i].trace && !d[i].dyn_n, "sp3_gemm_n: no split-K, no trace, no device-side extent");
-  }
-  for (int i = 1; i < n; ++i) g_more[i - 1] = &d[i];
-  g_nmore = n - 1;
-  const int rc = gemm_dispatch(d[0], t[0], stream);
-  g_nmore = 0;
-  return rc;
-}
-
-extern "C" int sp3_gemm2(const sp3_gemm_desc* ap, const sp3_gemm_desc* bp, void* stream_) {
-  SP3_CHECK(ap != nullptr && bp != nullptr, "sp3_gemm2: null descriptor");
-  const sp3_gemm_desc* two[2] = {ap, bp};
-  return sp3_gemm_n(two, 2, stream_);
+  const sp3_gemm_desc* one = &d;
+  GroupPlan p;
+  return gemm_plan(&one, 1, p) ? -1 : p.tile[0];
 }

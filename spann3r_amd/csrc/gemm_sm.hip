@@ -1760,12 +1760,25 @@ bool sp3_gemm_sm_conv_level(const sp3_gemm_desc* ds, int n) {
   if (!sm_enabled() || n < 2 || n > 4) return false;
   for (int i = 0; i < n; ++i) {
     const int t = conv_sm_tile(ds[i]);
-    if (t < 0 || (ds[i].tile >= 0 && ds[i].tile != t) || (ds[i].a_bf16 != 0) != (ds[0].a_bf16 != 0) || (t == 41 && !ds[i].a_bf16)) return false;
+    if (t < 0 || (ds[i].tile >= 0 && ds[i].tile != t) || (ds[i].a_bf16 != 0) != (ds[0].a_bf16 != 0)) return false;
   }
   return true;
 }
 
-int sp3_gemm_sm_conv_level_launch(const sp3_gemm_desc* ds, int n, hipStream_t stream) { return conv_level_dispatch(ds, n, stream); }
+int sp3_gemm_sm_conv_level_launch(const sp3_gemm_desc* ds, int n, hipStream_t stream) {
+  // the level kernel holds tile 41 for bf16 maps only: an fp32 map on it goes out on its own, before the level
+  sp3_gemm_desc lv[4];
+  int m = 0;
+  for (int i = 0; i < n; ++i) {
+    if (conv_sm_tile(ds[i]) == 41 && !ds[i].a_bf16) {
+      if (int rc = conv_sm_dispatch(ds[i], 41, stream)) return rc;
+    } else {
+      lv[m++] = ds[i];
+    }
+  }
+  if (m == 1) return conv_sm_dispatch(lv[0], conv_sm_tile(lv[0]), stream);
+  return m ? conv_level_dispatch(lv, m, stream) : 0;
+}
 
 int sp3_gemm_sm_launch(const sp3_gemm_desc& d, const sp3_gemm_desc* pair, hipStream_t stream) {
   if (d.loader == SP3_LOAD_SOFTMAX && sm_enabled() && pvs_ok(d) && !pair && (d.tile < 30 || d.tile == 46)) return pvs_dispatch(d, stream);
@@ -1799,7 +1812,7 @@ int sp3_gemm_sm_launch(const sp3_gemm_desc& d, const sp3_gemm_desc* pair, hipStr
     const SmInst* s2 = sm_find(*pair);
     if (s2 != s || pair->M != d.M || pair->tokens != d.tokens || pair->heads != d.heads || pair->vt_ld != d.vt_ld || pair->pos != d.pos ||
         pair->rope_cos != d.rope_cos || pair->rope_sin != d.rope_sin || pair->ln_eps != d.ln_eps || s->epi != SM_ROPE) {
-      sp3_set_error("sp3_gemm2: the two groups do not share a lean instance");
+      sp3_set_error("sp3_gemm_n: the two groups do not share a lean instance");
       return 1;
     }
     sm_fill(a.op[1], *pair, *s);

@@ -645,7 +645,7 @@ class Engine:
         packed = None
         if feat1p is not None and feat2p is not None and self.adt == torch.bfloat16 and ops.LEAN:
             # a packed split A runs on lean instances only (tiles 42 / 66 / 67; no general tile): ask the library whether it has one
-            # for THIS descriptor (SP3_LEAN_BIG=0 with R > 256, or a batch the families do not take, answer no) before taking the layout
+            # for THIS descriptor (a row count or batch the families do not take answers no) before taking the layout
             np_ = self.wspg("decg_normed_packed", R, D)
             dFp = feat2p.data_ptr() - feat1p.data_ptr()
             assert dFp % 16 == 0
@@ -750,22 +750,21 @@ class Engine:
         ld = (96, 192, 384, 768)
         mdt = self.mdt
         t = [self.ws("dpt%d_pp%d" % (num, i), (R, ld[i]), mdt) for i in range(4)]
-        pairable = len({dec[hk[i]].dtype for i in range(4)}) == 1          # one kernel instance per pair (same operand dtypes)
-        # the four hooks are independent: one launch of four differently shaped problems (sp3_gemm_n), or two of two each (sp3_gemm2)
         import contextlib
         lv = ops.HEAD_LEVELS
-        level = ops.level if lv else contextlib.nullcontext
-        pair = ops.pair if pairable else contextlib.nullcontext
-        with (level if pairable else contextlib.nullcontext)():
+        # one kernel instance per grouped launch: same operand dtypes
+        group = ops.level if len({dec[hk[i]].dtype for i in range(4)}) == 1 else contextlib.nullcontext
+        # the four hooks are independent: one launch of four differently shaped problems, or two of two each
+        with (group if lv else contextlib.nullcontext)():
             for i0 in (0, 2):
-                with (contextlib.nullcontext if lv else pair)():
+                with (contextlib.nullcontext if lv else group)():
                     for i in (i0, i0 + 1):
                         ops.gemm(dec[hk[i]], w[pre + "pp%d.w" % i], t[i], M=R, N=ld[i], K=dims[i], lda=dims[i], ldc=ld[i], bias=w[pre + "pp%d.b" % i])
         # act_postprocess tails (croco/models/dpt_block.py:356-410)
         c0 = 128 if self.wdt == torch.bfloat16 else ld[0]         # (bf16 mode: 32 zero channels ride along, see _pack)
         l0 = self.ws("dpt%d_l0" % num, (B * 16 * nh * nw, c0), mdt)
         l1 = self.ws("dpt%d_l1" % num, (B * 4 * nh * nw, ld[1]), mdt)
-        with pair():
+        with group():
             ops.conv_transpose_ks(t[0], w[pre + "pp0t.w"], l0, B=B, H=nh, W_=nw, Cin=ld[0], Cout=c0, ks=4, bias=w[pre + "pp0t.b"])
             ops.conv_transpose_ks(t[1], w[pre + "pp1t.w"], l1, B=B, H=nh, W_=nw, Cin=ld[1], Cout=ld[1], ks=2, bias=w[pre + "pp1t.b"])
         l2 = t[2]
@@ -787,15 +786,15 @@ class Engine:
         if lv:
             # launches by dependency level: what reads only the hooks' maps goes with the act_postprocess tails, and the first
             # convolution of each refinenet (it reads rn[i] only) right after the layer_rn level
-            with level():
+            with ops.level():
                 pp3c()
                 layer_rn(2)
-            with level():
+            with ops.level():
                 layer_rn(0)
                 layer_rn(1)
                 layer_rn(3)
                 self._rcu_c1(rn[2], refs[1][0] + "u1", B, geo[2][0], geo[2][1], refs[1][1])
-            with level():
+            with ops.level():
                 self._rcu_c1(rn[3], refs[0][0] + "u2", B, geo[3][0], geo[3][1], refs[0][1])
                 self._rcu_c1(rn[1], refs[2][0] + "u1", B, geo[1][0], geo[1][1], refs[2][1])
                 self._rcu_c1(rn[0], refs[3][0] + "u1", B, geo[0][0], geo[0][1], refs[3][1])

@@ -106,8 +106,8 @@ _lib = None
 
 _PROTOS = {
     "sp3_gemm": [C.POINTER(GemmDesc), C.c_void_p],
-    "sp3_gemm2": [C.POINTER(GemmDesc), C.POINTER(GemmDesc), C.c_void_p],
     "sp3_gemm_n": [C.POINTER(C.POINTER(GemmDesc)), C.c_int, C.c_void_p],
+    "sp3_gemm_plan_n": [C.POINTER(C.POINTER(GemmDesc)), C.c_int, C.POINTER(C.c_int)],
     "sp3_gemm_plan": [C.POINTER(GemmDesc)],
     "sp3_layernorm": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_int,
                       C.c_int, C.c_int, C.c_void_p],

@@ -118,46 +118,15 @@ _TILE_NAMES = {0: "32x32xk4", 1: "64x64", 2: "64x128", 3: "64x64xk4", 4: "32x64x
                61: "lean-stream-k1024-256x128", 62: "lean-stream-k4096-256x128", 63: "lean-rope-k768-256x128", 64: "lean-packed-k768-256x128", 65: "lean-rope-k768-128x64", 66: "lean-packed-splitA-k1792-128x128", 67: "lean-packed-splitA-k1792-256x128"}
 
 
-def pick_tile(M, N, batch=1, splitk=1, conv=False, K=0, packed_bf16=False, plain=False, ln_nt=0, pipe_ok=False, rope=False):
-    """Mirror of the auto heuristic in csrc/gemm.hip (kept in sync so profiles can be keyed by instantiation)."""
-    t64 = ((M + 63) // 64) * ((N + 63) // 64) * batch * splitk
-    t128 = ((M + 63) // 64) * ((N + 127) // 128) * batch
-    lds_ok = not conv and splitk == 1 and packed_bf16 and K % 64 == 0
-    wide_legacy = lds_ok and M >= 1024 and N >= 2304 and N % 128 == 0 and N < 16384
-    if pipe_ok and PIPE_TILES and M >= 512 and not rope and not wide_legacy:
-        mt256, mt128, nt128 = (M + 255) // 256, (M + 127) // 128, (N + 127) // 128
-        if mt256 * nt128 * batch * splitk >= 144:
-            return 20
-        if mt128 * nt128 * batch * splitk >= 200:
-            return 21
-        if mt128 * ((N + 63) // 64) * batch * splitk <= 192:
-            return 24
-        return 22
-    if lds_ok and M >= 1024 and N >= 2304 and N % 128 == 0:
-        return 5 if (N % 4096 == 0 or ((M + 127) // 128) * (N // 128) * batch >= 1024) else 6
-    if not conv and M >= 1024:
-        return 1
-    if lds_ok and 112 < M <= 224 and plain and N >= 3072 and K <= 1024 and ln_nt <= 32:
-        return 13
-    if conv or M > 2048:
-        if t128 >= 1024 and N % 128 == 0:
-            return 2
-        if t64 >= 512:
-            return 1
-        return 0
-    return 0
-
-
 import os as _os
 import threading as _threading
-PIPE_TILES = True                                               # (the pipelined LDS tiles 20-23 of csrc/gemm.hip: always on since round 6)
 PROF_SHAPES = _os.environ.get("SP3_PROF_SHAPES", "0")[:1] == "1"
 LEAN = _os.environ.get("SP3_LEAN_GEMM", "1")[:1] != "0"          # mirrors sm_enabled() in csrc/gemm_sm.hip: with the lean instances off the
                                                                   # engine must not pick the layouts only they serve (packed split-A, bf16 DPT maps)
 
 HEAD_LEVELS = _os.environ.get("SP3_HEAD_LEVELS", "1")[:1] != "0"  # DPT heads: one launch per dependency level, bilinear x2 folded into the
                                                                   # consuming convolution (0: the launch-per-op schedule, for A/B runs)
-_pair = None
+_held = None     # descriptors held back by an open ops.level()
 
 
 def level_block_map(problems):
@@ -187,32 +156,27 @@ def level_order(problems):
 
 
 class level:
-    """`with ops.level():` -- the independent launches issued inside (one dependency level, up to 4) go out as ONE launch where the
-    library has a kernel for the group (sp3_gemm_n): small-map convolutions on the lean tiles 40 / 41 (mixed, bf16 maps; fp32 maps: tile
-    40 only), or GEMMs of one general kernel instance.  What does not fit a group is launched on its own, after the group."""
+    """`with ops.level():` -- the independent GEMM / convolution launches issued inside (one dependency level) are held back and go
+    out at exit through sp3_gemm_n, up to 4 per call, with tile < 0: the library decides what the group runs on (include/
+    spann3r_hip.h "launch planning": a level of small-map convolutions, a lean q/k/v pair, or groups of one general kernel instance)
+    and refuses a group it has no single kernel for."""
 
     def __enter__(self):
-        global _pair
-        assert _pair is None
-        _pair = []
+        global _held
+        assert _held is None
+        _held = []
         return self
 
     def __exit__(self, et, ev, tb):
-        global _pair
-        descs, _pair = _pair, None
+        global _held
+        held, _held = _held, None
         if et is not None:
             return False
-        lean = [x for x in descs if x[0].loader == L.LOAD_CONV3X3]                  # (only the lean small-map convolutions are held back)
-        conv = [x for x in lean if x[0].a_bf16 or x[0].tile == 40]
-        rest = [x for x in descs if x[0].loader != L.LOAD_CONV3X3]
-        if lean and rest:
+        conv = [x[0].loader == L.LOAD_CONV3X3 for x in held]
+        if any(conv) and not all(conv):
             raise RuntimeError("ops.level(): small-map convolutions and other GEMMs do not share a launch")
-        for x in lean:
-            if not any(x is y for y in conv):
-                self._send([x], True)
-        for group in (conv, rest):
-            for i in range(0, len(group), 4):
-                self._send(group[i:i + 4], group is conv)
+        for i in range(0, len(held), 4):
+            self._send(held[i:i + 4], any(conv))
         return False
 
     @staticmethod
@@ -221,89 +185,24 @@ class level:
             _gemm_launch(group[0][0], "sp3_gemm", group[0][1])
             return
         ds = [g[0] for g in group]
-        if not is_conv:
-            # the general tiles: launches that ops.pair() would send two by two, each pair on its first member's tile (the K split of a
-            # tile is part of the arithmetic) -- one launch if the pairs agree on the tile, else pair by pair
-            for i in range(0, len(ds), 2):
-                if ds[i].tile < 0:
-                    _pick_general(ds[i])
-                for d in ds[i + 1:i + 2]:
-                    if d.tile < 0:
-                        d.tile = ds[i].tile
-            if len(ds) > 2 and len({d.tile for d in ds}) > 1:
-                for i in range(0, len(group), 2):
-                    level._send(group[i:i + 2], False)
-                return
         arr = (C.POINTER(GemmDesc) * len(ds))(*[C.pointer(d) for d in ds])
         e0 = _prof.begin() if _prof is not None else None
         L.check(L.load().sp3_gemm_n(arr, len(ds), L.stream_ptr()), "sp3_gemm_n")
         if _prof is not None:
-            fl, by = 0.0, 0.0
-            for d in ds:
-                f, n = _gemm_cost(d)
-                fl, by = fl + f, by + n
+            tiles = (C.c_int * len(ds))()
+            L.check(L.load().sp3_gemm_plan_n(arr, len(ds), tiles), "sp3_gemm_plan_n")
+            cost = [_gemm_cost(d) for d in ds]
             a = ds[0]
-            _prof.end("gemm_n<A%s,W%s,%s,%s x%d>" % ("bf16" if a.a_bf16 else "f32", "f32" if a.wdtype == F32 else "bf16", group[0][1],
-                                                     "+".join(sorted({_TILE_NAMES[d.tile] for d in ds})), len(ds)), e0, fl, by)
+            head = "<A%s,W%s,%s," % ("bf16" if a.a_bf16 else "f32", "f32" if a.wdtype == F32 else "bf16", group[0][1])
+            # (bench.py books a pair with the single launches of its instance: gemm2<..> names one tile; a level names every tile it mixes)
+            if len(ds) == 2 and not is_conv:
+                key = "gemm2" + head + _TILE_NAMES[tiles[0]] + ">"
+            else:
+                key = "gemm_n" + head + "+".join(sorted({_TILE_NAMES[t] for t in tiles})) + " x%d>" % len(ds)
+            _prof.end(key, e0, sum(c[0] for c in cost), sum(c[1] for c in cost))
 
 
-class pair:
-    """`with ops.pair():` -- the two GEMM launches issued inside go out as ONE launch (sp3_gemm2: two differently shaped
-    groups of problems that depend on the same inputs; same dtypes / loader; the second runs on the first one's tile)."""
-
-    def __enter__(self):
-        global _pair
-        assert _pair is None
-        _pair = []
-        return self
-
-    def __exit__(self, et, ev, tb):
-        global _pair
-        descs, _pair = _pair, None
-        if et is not None:
-            return False
-        if len(descs) != 2:
-            raise RuntimeError("ops.pair(): expected exactly two GEMM launches, got %d" % len(descs))
-        (a, na), (b, _) = descs
-        if a.tile < 0 and b.tile < 0:
-            ta, tb = L.load().sp3_gemm_plan(C.byref(a)), L.load().sp3_gemm_plan(C.byref(b))
-            if ta >= 30 and ta == tb and a.epi == L.EPI_ROPE_VT and b.epi == L.EPI_ROPE_VT:   # both groups on one lean q/k/v instance (the only
-                a.tile = b.tile = ta                # family that takes a second group; others pair on the general tiles)
-        if a.tile < 0:
-            _pick_general(a)                        # (a lean instance for one group only: both take the general tiles)
-        if b.tile < 0:
-            b.tile = a.tile
-        if _prof is None:
-            L.check(L.load().sp3_gemm2(C.byref(a), C.byref(b), L.stream_ptr()), "sp3_gemm2")
-            return False
-        e0 = _prof.begin()
-        L.check(L.load().sp3_gemm2(C.byref(a), C.byref(b), L.stream_ptr()), "sp3_gemm2")
-        fl, by = 0.0, 0.0
-        for d in (a, b):
-            f, n = _gemm_cost(d)
-            fl, by = fl + f, by + n
-        _prof.end("gemm2<A%s,W%s,%s,%s>" % ("bf16" if a.a_bf16 else "f32", "f32" if a.wdtype == F32 else "bf16", na, _TILE_NAMES[a.tile]), e0, fl, by)
-        return False
-
-
-def _pipe_ok(d):
-    return bool(d.loader == L.LOAD_PLAIN and d.a_packed and d.w_packed and d.a_bf16 and not d.A2 and not d.sm_stats_out and d.K % 64 == 0
-                and (max(d.splitk, 1) == 1 or d.epi == L.EPI_PARTIAL))
-
-
-def _pick_general(d):
-    d.tile = pick_tile(d.M, d.N, max(d.batch, 1), max(d.splitk, 1), d.loader == L.LOAD_CONV3X3, d.K,
-                       bool(d.a_packed and d.w_packed and d.a_bf16 and not d.A2 and d.epi != L.EPI_PARTIAL
-                            and not d.sm_stats_out),
-                       d.epi == L.EPI_PLAIN, d.ln_nt if d.ln_stats else 0, _pipe_ok(d), d.epi == L.EPI_ROPE_VT)
-
-
-def _pick(d):
-    t = L.load().sp3_gemm_plan(C.byref(d))          # the lean small-M instances (tiles 30..) are chosen by the library
-    if t >= 30:
-        d.tile = t
-        return
-    _pick_general(d)
+pair = level     # the two-launch use (a decoder layer's q/k/v + cross k/v projections) keeps its name
 
 
 def _gemm_cost(d):
@@ -315,33 +214,21 @@ def _gemm_cost(d):
 
 
 def _gemm_launch(d, what, loader_name):
-    if _pair is not None:
-        _pair.append((d, loader_name))
+    if _held is not None:
+        _held.append((d, loader_name))
         return
-    if d.loader == L.LOAD_SOFTMAX:
-        if d.tile < 0:
-            t = L.load().sp3_gemm_plan(C.byref(d))          # 44: the lean P.V instance of the memory read
-            d.tile = t if t >= 30 else 0
-        elif d.tile < 30:
-            d.tile = 1 if d.tile == 1 else 0
-    if d.tile < 0:
-        _pick(d)
     if _prof is None:
         L.check(L.load().sp3_gemm(C.byref(d), L.stream_ptr()), what)
         return
     e0 = _prof.begin()
     L.check(L.load().sp3_gemm(C.byref(d), L.stream_ptr()), what)
-    b = max(d.batch, 1)
-    wsz = 4 if d.wdtype == F32 else 2
-    flops = 2.0 * d.M * d.N * d.K * b
-    asz, csz = (2 if d.a_bf16 else 4), (2 if d.out_bf16 else 4)
-    a_elems = d.M * d.K if d.loader != L.LOAD_CONV3X3 else d.M * d.conv_stride * d.conv_stride * d.conv_C   # conv: the map, once
-    nbytes = b * (asz * a_elems + wsz * d.N * d.K + csz * d.M * d.N)      # algorithmic: every operand once
-    adt = "bf16" if d.a_bf16 else "f32"
-    tname = ("16x64xk4" if d.tile == 0 else "32x32xk4") if (d.loader == L.LOAD_SOFTMAX and d.tile < 30) else _TILE_NAMES[d.tile]
-    key = "gemm<A%s,W%s,%s,%s>" % (adt, "f32" if d.wdtype == F32 else "bf16", loader_name, tname)
+    flops, nbytes = _gemm_cost(d)
+    tile = d.tile if d.tile >= 0 else L.load().sp3_gemm_plan(C.byref(d))
+    # (the softmax loader's general instances are tiles of their own: 16x64 unless tile 1 is asked for)
+    tname = ("32x32xk4" if tile == 1 else "16x64xk4") if (d.loader == L.LOAD_SOFTMAX and tile < 30) else _TILE_NAMES[tile]
+    key = "gemm<A%s,W%s,%s,%s>" % ("bf16" if d.a_bf16 else "f32", "f32" if d.wdtype == F32 else "bf16", loader_name, tname)
     if PROF_SHAPES:                                 # (tools: one profile line per GEMM shape)
-        key += " %dx%dx%d x%d%s" % (d.M, d.N, d.K, b, " splitA" if d.A2 else "")
+        key += " %dx%dx%d x%d%s" % (d.M, d.N, d.K, max(d.batch, 1), " splitA" if d.A2 else "")
     _prof.end(key, e0, flops, nbytes)
 
 
@@ -665,7 +552,6 @@ def conv3x3(x, Wp, out, *, B, H, W_, Cin, Cout, stride=1, bias=None, res1=None, 
             p.res2_up_H, p.res2_up_W = res2_up
         lean = L.load().sp3_gemm_plan(C.byref(p))
         if lean >= 30:
-            p.tile = lean
             _gemm_launch(p, "sp3_gemm(conv3x3)", "conv3x3")
             return out
     if res2_up is not None:
@@ -685,12 +571,12 @@ def conv3x3(x, Wp, out, *, B, H, W_, Cin, Cout, stride=1, bias=None, res1=None, 
     d.loader, d.epi, d.tile = L.LOAD_CONV3X3, (L.EPI_PLAIN if S == 1 else L.EPI_PARTIAL), (tile if S == 1 else 0)
     d.splitk = S if S > 1 else 0
     d.conv_H, d.conv_W, d.conv_C, d.conv_OH, d.conv_OW, d.conv_stride = H, W_, Cin, OH, OW, stride
-    global _pair
-    held, _pair = _pair, None                       # (a split-K launch is followed by its reduce: never held back by a level)
+    global _held
+    held, _held = _held, None                       # (a split-K launch is followed by its reduce: never held back by a level)
     try:
         _gemm_launch(d, "sp3_gemm(conv3x3)", "conv3x3")
     finally:
-        _pair = held
+        _held = held
     if S > 1:
         # few output tiles, long K (small maps): K split over S workgroups per tile, finished by one reduce launch
         reduce_ln(splitk_ws, S, M, Cout, bias=bias, res=res1, ldres=Cout, x_out=out, ldx=Cout, act=act, res2=res2, ldres2=Cout)

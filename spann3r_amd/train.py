@@ -1227,7 +1227,7 @@ class TrainStep:
         self.crit = ConfLoss_t(Regr3D_t(L21, norm_mode="avg_dis", fix_first=False), alpha=0.4)      # training.py:37
         self.clip_grad = clip_grad
         # multi-rank too: the bucket all-reduces (RCCL through torch.distributed's NCCL backend is capturable) are part of the
-        # captured step; SP3_TRAIN_GRAPH=0 forces the eager step
+        # captured step (graph=False gives the eager step)
         import os
         self.graph = bool(graph)
         self._g = self._static = self._out = None

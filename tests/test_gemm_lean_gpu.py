@@ -219,7 +219,7 @@ def test_lean_rope_vt(B, nh, nw, C, heads, kind):
 
 @pytest.mark.parametrize("M,npad,grid", [(196, 256, 14), (1024, 1024, 32)])
 def test_lean_pair_equals_two_launches(M, npad, grid):
-    """sp3_gemm2 on a lean instance (a decoder layer's q/k/v + cross k/v projections, both sides): bit-identical to the two launches"""
+    """sp3_gemm_n (n = 2) on a lean instance (a decoder layer's q/k/v + cross k/v projections, both sides): bit-identical to the two launches"""
     from spann3r_amd.engine import _rope_tables
     ops = _ops()
     K, heads, P, B = 768, 12, M, 1

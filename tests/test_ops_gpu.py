@@ -821,7 +821,7 @@ def test_two_launch_memory_read(wdt, rows, M, thresh):
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32])
 def test_paired_launch_equals_two_launches(dt):
-    """sp3_gemm2: two differently shaped groups of problems in one launch == the two launches, bit for bit"""
+    """sp3_gemm_n, n = 2: two differently shaped groups of problems in one launch == the two launches, bit for bit"""
     ops = _ops()
     M, K = 196, 768
     A = ops.PackedAct.group(2, M, K, dt, DEV)
@@ -847,9 +847,11 @@ def test_paired_launch_equals_two_launches(dt):
         outs[mode] = res
     for a, b in zip(outs["two"], outs["pair"]):
         assert torch.equal(a, b) and float(a.abs().max()) > 0
-    with pytest.raises(RuntimeError):
+    a32, ws = rnd(M, K, seed=2).to(DEV), [(rnd(64, K, seed=3) * 0.05).to(DEV).to(wdt) for wdt in (torch.float32, torch.bfloat16)]
+    with pytest.raises(RuntimeError, match="one kernel instance"):      # (weight dtypes differ: the library refuses the group, nothing is launched)
         with ops.pair():
-            pass
+            for w in ws:
+                ops.gemm(a32, w, torch.zeros(M, 64, device=DEV), M=M, N=64, K=K, lda=K, ldc=64, tile=0)
 
 
 def test_attention_f32x3():

@@ -31,7 +31,7 @@ def lean_key(row):
         tile = (SM if m.group(1) == "sm" else BM).get(ints)
         if tile is None:
             return None
-        # sp3_gemm2 (q/k/v + cross k/v projections of a decoder layer in one launch): the only paired lean launch of the 224x224 step
+        # a pair of sp3_gemm_n (q/k/v + cross k/v projections of a decoder layer in one launch): the only paired lean launch of the 224x224 step
         pair = tile == 31 and row["grid"][2] == 30
         return ("gemm2" if pair else "gemm") + "<Abf16,Wbf16,plain,%s>" % _TILE_NAMES[tile]
     if "conv3x3_tile_kernel" in n or "conv3x3_wide_kernel" in n:        # both pixel tiles of sp3_conv3x3_tile (bench.py times them as one op)
@@ -62,7 +62,7 @@ def key_of(row):
     name = NAMES.get(tuple(ints[:7]))
     if name is None:
         return None
-    # sp3_gemm2 (two differently shaped groups in one launch): grid.y = 4 in the per-frame step (2 + 2 problems)
+    # a pair of sp3_gemm_n (two differently shaped groups in one launch): grid.y = 4 in the per-frame step (2 + 2 problems)
     return ("gemm2" if row["grid"][1] == 4 else "gemm") + "<Abf16,Wbf16,plain,%s>" % name
 
 
@@ -86,7 +86,7 @@ def main():
                     "64 B, MI355X_MICROARCH.md) + WRITE * 1024",
            "note": "memory-side (fabric) requests of the 8 per-XCD L2s, Infinity-Cache hits included (MI355X_MICROARCH.md): every XCD fetches its "
                    "own copy of the activation panel, so a 196-row launch counts W + 8 x A + C; launches of one kernel are split by grid "
-                   "(tools/rocpd_pmc_grid.py) so sp3_gemm2 pairs are separate",
+                   "(tools/rocpd_pmc_grid.py) so paired launches (sp3_gemm_n, n = 2) are separate",
            "kernels": {}}
     for k, (f, n) in fetch.items():
         if k not in write:

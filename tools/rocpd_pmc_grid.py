@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Per-(kernel, grid) average of one PMC counter from a rocprofv3 rocpd database: pmc_events joined to the kernel
-dispatches by dispatch_id, so launches of one kernel with different grids (e.g. sp3_gemm vs sp3_gemm2: grid.y 2 vs 4)
+dispatches by dispatch_id, so launches of one kernel with different grids (e.g. a single launch vs a pair of sp3_gemm_n: grid.y 2 vs 4)
 are reported apart.  Usage: python tools/rocpd_pmc_grid.py results.db [--json out.json]"""
 import collections, json, sqlite3, sys
 db = sys.argv[1]
