@@ -179,6 +179,9 @@ int sp3_gemm(const sp3_gemm_desc* desc_host, void* stream);
  *  - n = 2, both on one lean q/k/v instance (ROPE_VT, tiles 30 / 31 / 50..): one launch of that instance, e.g. a decoder layer's
  *    self-attention q/k/v projection (N = 2304) and its cross-attention k/v projection (N = 1536), which both read the previous
  *    layer's tokens (dust3r/model.py:196-198, croco/models/blocks.py:187-189).
+ *    The two descriptors describe the same tokens: equal M, tokens, heads, vt_ld and ln_eps, and the SAME pos / rope_cos / rope_sin
+ *    pointers (the launch carries one set).  Planning reads no pointer values, so sp3_gemm_plan_n answers the pair's tile whatever
+ *    the pointers are; sp3_gemm_n refuses a pair that breaks this rule before anything is launched.
  *  - otherwise differently shaped groups of ONE general kernel instance (grid.y = sum of the batches; same dtypes, loader and product
  *    mode; no split-K, no softmax loader).  A pair's second descriptor with tile < 0 runs on the first one's tile.  With more than
  *    two, every descriptor must resolve to the first one's tile by itself -- grouping never moves a member of a level to another

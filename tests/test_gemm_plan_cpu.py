@@ -84,6 +84,19 @@ def test_group_plan_rules():
     assert l.sp3_gemm_n(arr, 3, None) != 0 and b"one kernel instance" in l.sp3_last_error()       # (refused before anything is launched)
     # ... and one whose members agree is planned on that tile
     assert _plan(lib, [wide, wide, wide, wide]) == [tw] * 4
+    # a lean q/k/v pair shares positions and RoPE tables (header, sp3_gemm_n): planning reads no pointer values and answers the pair's
+    # tile, the launch refuses two descriptors with different pos pointers -- before anything is launched
+    rope = dict(epi=lib.EPI_ROPE_VT, heads=12, tokens=196, vt_ld=256, qkv_packed=1, pos=1, rope_cos=1, rope_sin=1, vt=1, ln_stats=1, ln_s=1,
+                ln_nt=24, ln_C=768, batch=2)
+    qkv, ckv = _packed_bf16(lib, 196, 2304, 768, rope_cols=1536, **rope), _packed_bf16(lib, 196, 1536, 768, rope_cols=768, **rope)
+    if _plan(lib, [qkv])[0] >= 30:                      # (lean instances on)
+        assert _plan(lib, [qkv, ckv]) == [31, 31]
+        ds = [_desc(lib, f) for f in (qkv, ckv)]
+        ds[1].pos = 8192
+        arr = (C.POINTER(lib.GemmDesc) * 2)(*[C.pointer(d) for d in ds])
+        tiles = (C.c_int * 2)()
+        assert l.sp3_gemm_plan_n(arr, 2, tiles) == 0 and list(tiles) == [31, 31]
+        assert l.sp3_gemm_n(arr, 2, None) != 0 and b"do not share a lean instance" in l.sp3_last_error()
     # different operand dtypes never share a launch
     f32 = dict(A=1, W=1, C=1, M=196, N=768, K=768, lda=768, ldc=768, alpha=1.0)
     assert _plan(lib, [f32, dict(f32, wdtype=lib.BF16)]) == [-1, -1]
