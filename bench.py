@@ -11,7 +11,9 @@ batch 1, bf16 MFMA (BASELINE.json configs[1]).  value = whole-job frames/s with 
       the launcher's RANK / LOCAL_RANK / WORLD_SIZE are used as they are.
 
 One process per GPU; independent sequences are sharded across ranks (no data-path collective); the only collective is
-one RCCL all_gather of {frames, seconds} per rank, on the device.  Rank 0 prints ONE JSON line with the extra objects
+one RCCL all_gather of {frames, seconds} per rank, on the device.  Rank 0 prints ONE JSON line.  A plain run does only what that
+line's value needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  --full runs, after the timed steps, the measurements
+that take runs of their own (each has its --no-... switch) and adds them to the line as the extra objects
   roofline     : dominant kernel (by GPU time): algorithmic bytes / FLOPs per launch over its average launch duration,
                  measured live with HIP events on the launch stream (event cost calibrated against a spin kernel)
   memread      : the spatial-memory read region (all its launches): algorithmic bytes / HIP-event time vs the HBM peak
@@ -58,9 +60,11 @@ def parse_args(argv=None):
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "f32x3", "f32x6", "f16x3"])
     ap.add_argument("--frames", type=int, default=10)
     ap.add_argument("--size", type=int, default=224)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the fp32 and config-3 secondary measurements")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the per-kernel profile, the secondary measurements "
+                                                        "(other precisions, sizes and configurations, the training step) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the per-kernel HIP-event profile (roofline, memread)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the fp32, config-3 and training-step secondary measurements")
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--train-policy", action="store_true", help="growing bank (train-mode memory policy, dropout off)")
     ap.add_argument("--train", action="store_true", help="time the training step (BASELINE config 5 per rank: batch 4, 5 frames of 224x224, "
@@ -678,8 +682,9 @@ def _main(args, real_stdout):
                          "achieved_tflops_per_gpu": fl * args.steps / max_seconds / 1e12,
                          "frac_of_mfma_peak": fl * args.steps / max_seconds / 1e12 / PEAK_TFLOPS[args.precision]}
 
+    # ---- everything below is --full: measurements next to the headline that take runs of their own
     # ---- per-kernel HIP-event timing over one more sequence (eager launches, same kernels, same stream)
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         roof, breakdown, total_ms, memread = kernel_profile(model, seqs[0], args.precision)
         out["roofline"], out["kernel_breakdown"], out["profiled_sequence_kernel_ms"] = roof, breakdown, total_ms
         if memread:
@@ -690,7 +695,7 @@ def _main(args, real_stdout):
                 out["memread"]["graph_replay"] = rep
 
     # ---- secondary measurements on this GPU (N = 1 only): the fp32 parity mode, and BASELINE config 3
-    if world == 1 and not args.no_extras and (args.size, args.frames, args.precision, args.train_policy) == (224, 10, "bf16", False):
+    if args.full and world == 1 and not args.no_extras and (args.size, args.frames, args.precision, args.train_policy) == (224, 10, "bf16", False):
         print("bench.py: extras: fp32 mode", file=sys.stderr, flush=True)
         model.set_precision("fp32")
         f32_frames, f32_s, _ = time_sequences(model, seqs, 6, 3)
@@ -766,7 +771,7 @@ def _main(args, real_stdout):
         torch.cuda.empty_cache()
 
     # ---- the training step (BASELINE config 5, one rank's share): bf16 products, flat buckets, device-side clip
-    if world == 1 and not args.no_extras and args.precision == "bf16":
+    if args.full and world == 1 and not args.no_extras and args.precision == "bf16":
         try:
             del model
         except NameError:
@@ -796,7 +801,7 @@ def _main(args, real_stdout):
             out["train"]["rccl_world1"] = {"error": repr(e)[:300]}
 
     # ---- CPU baseline: the oracle (port of the reference algorithm) on this box's host cores, bounded sample
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         print("bench.py: cpu baseline", file=sys.stderr, flush=True)
         out["cpu_baseline"] = cpu_baseline(sd, args.size, args.train_policy)
     print(json.dumps(out), file=real_stdout, flush=True)

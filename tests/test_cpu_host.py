@@ -176,6 +176,15 @@ def test_bench_flop_model():
     assert abs(bench.flops_per_sequence(50, 512) / 1e9 - 1.061e5) / 1.061e5 < 0.01
 
 
+def test_bench_full_is_opt_in():
+    """a plain `bench.py --gpus 1 --steps N --warmup W` is the headline alone; what runs next to it waits for --full"""
+    sys.path.insert(0, REPO)
+    import bench
+    assert bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"]).full is False
+    a = bench.parse_args(["--full", "--no-extras"])
+    assert a.full and a.no_extras and not a.no_profile and not a.no_cpu_baseline
+
+
 def test_bench_dump_outputs(tmp_path, monkeypatch):
     """bench.py --dump-outputs: names follow the forward's (preds, preds_all); arrays within the byte limit are written whole as
     float32 (float64 stays), beyond it as the same seeded positions in every call"""

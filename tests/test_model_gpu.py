@@ -988,7 +988,7 @@ def test_forward_is_deterministic_run_to_run(tiny_model):
 
 
 def _bench_argv(n):
-    return ["--gpus", str(n), "--steps", "2", "--warmup", "1", "--frames", "3", "--size", "64", "--no-extras", "--no-cpu-baseline", "--no-profile"]
+    return ["--gpus", str(n), "--steps", "2", "--warmup", "1", "--frames", "3", "--size", "64"]
 
 
 def test_bench_self_spawn_one_rank_through_rccl(capsys):
@@ -1015,8 +1015,8 @@ def test_bench_self_spawn_one_rank_through_rccl(capsys):
 
 def test_bench_dump_outputs_repeats_across_processes(tmp_path):
     """`bench.py --dump-outputs DIR` in two fresh processes: same arguments -> same seeded inputs -> the same files, also when the
-    profiling pass runs after the timed steps in one of them (the outputs are taken before the runner's buffers are reused); the
-    record's ms_per_step is the timed window over --steps"""
+    profiling pass of --full runs after the timed steps in one of them (the outputs are taken before the runner's buffers are reused;
+    a plain run has no such pass); the record's ms_per_step is the timed window over --steps"""
     import json
     import os
     import subprocess
@@ -1024,11 +1024,12 @@ def test_bench_dump_outputs_repeats_across_processes(tmp_path):
     import numpy as np
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     recs = []
-    for d, argv in (("a", _bench_argv(1)), ("b", [a for a in _bench_argv(1) if a != "--no-profile"])):
+    for d, argv in (("a", _bench_argv(1)), ("b", _bench_argv(1) + ["--full", "--no-extras", "--no-cpu-baseline"])):
         p = subprocess.run([sys.executable, os.path.join(repo, "bench.py")] + argv + ["--dump-outputs", str(tmp_path / d)],
                            capture_output=True, text=True, timeout=600)
         assert p.returncode == 0, p.stderr[-2000:]
         recs.append(json.loads(p.stdout))
+    assert "roofline" not in recs[0] and "kernel_breakdown" not in recs[0] and recs[1]["roofline"]["launches"] > 0
     for r in recs:
         assert r["steps"] == 2 and abs(r["ms_per_step"] - 1e3 * max(r["per_rank_seconds"]) / 2) < 1e-3 * r["ms_per_step"]
     names = sorted(os.listdir(tmp_path / "a"))

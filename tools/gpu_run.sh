@@ -4,7 +4,7 @@
 # Every stage writes under gpurun_out/<tag>/ (merged back by gpurun).  Stages:
 #   optests   kernel-level parity tests (tests/test_ops_gpu.py)          gemmsweep  tile sweep of the many-row GEMMs
 #   modeltests tests/test_model_gpu.py                                    alltests   the whole -m gpu suite
-#   bench     python bench.py (default line)                              benchfast  bench.py without extras / CPU baseline
+#   bench     python bench.py --full (every object of the line)           benchfast  bench.py --full without extras / CPU baseline
 #   cold      tools/cold_start.py (first call / later calls / eager)      prof       rocprofv3 --kernel-trace --stats of benchfast
 #   train     tools/train_step_time.py (bf16, fp32; trainbf: bf16 only)   memread    tools/bench_memread.py
 #   trainprof rocprofv3 --kernel-trace --stats of the training step       traintests tests/test_train.py + test_loss.py
@@ -39,10 +39,10 @@ for stage in "$@"; do
                 for C in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE" "FETCH_SIZE" "WRITE_SIZE"; do
                   n=$(echo $C | cut -d" " -f1); (cd /tmp && timeout 300 rocprofv3 --pmc $C -d "$OLDPWD/$OUT/pmcr_$n" -o run --output-format csv -- python "$OLDPWD/tools/bench_manyrow.py" --rows 16384,8192 > "$OLDPWD/$OUT/pmcr_$n.log" 2>&1); F=$(find "$OUT/pmcr_$n" -name "*counter_collection.csv" | head -1); python tools/pmc_csv.py "$F" bm_kernel > "$OUT/pmcmanyrow_$n.txt" 2>&1; rm -rf "$OUT/pmcr_$n"; cat "$OUT/pmcmanyrow_$n.txt" | cut -c1-160 | head -60; done ;;
     tracegemm)  for t in 20 22; do for a in gelu noact; do timeout 120 python tools/trace_gemm.py $t $a >> "$OUT/tracegemm.txt" 2>&1; done; done; cat "$OUT/tracegemm.txt" ;;
-    bench)      timeout 900 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; head -c 1500 "$OUT/bench.json"; tail -3 "$OUT/bench.err" ;;
-    benchfast)  timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras > "$OUT/benchfast.json" 2> "$OUT/benchfast.err"; head -c 1200 "$OUT/benchfast.json"; tail -3 "$OUT/benchfast.err" ;;
+    bench)      timeout 900 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; head -c 1500 "$OUT/bench.json"; tail -3 "$OUT/bench.err" ;;
+    benchfast)  timeout 600 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-extras > "$OUT/benchfast.json" 2> "$OUT/benchfast.err"; head -c 1200 "$OUT/benchfast.json"; tail -3 "$OUT/benchfast.err" ;;
     cold)       timeout 400 python tools/cold_start.py > "$OUT/cold.txt" 2>&1; tail -12 "$OUT/cold.txt"; timeout 400 python tools/cold_start.py --size 512 --frames 50 --train-policy --calls 4 > "$OUT/cold512.txt" 2>&1; tail -9 "$OUT/cold512.txt" ;;
-    bench3)     timeout 600 python bench.py --size 512 --frames 50 --train-policy --steps 3 --warmup 2 --no-cpu-baseline --no-extras > "$OUT/bench3.json" 2> "$OUT/bench3.err"; head -c 1500 "$OUT/bench3.json"; tail -3 "$OUT/bench3.err" ;;
+    bench3)     timeout 600 python bench.py --size 512 --frames 50 --train-policy --steps 3 --warmup 2 --full --no-cpu-baseline --no-extras > "$OUT/bench3.json" 2> "$OUT/bench3.err"; head -c 1500 "$OUT/bench3.json"; tail -3 "$OUT/bench3.err" ;;
     prof)       (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d "$OLDPWD/$OUT/prof" -o run -- python "$OLDPWD/bench.py" --steps 6 --warmup 3 --no-cpu-baseline --no-profile --no-extras > "$OLDPWD/$OUT/prof.log" 2>&1); DB=$(find "$OUT/prof" -name "*results.db" | head -1); python tools/rocpd_stats.py "$DB" > "$OUT/prof_stats.md" 2>&1; python tools/rocpd_lastseq.py "$DB" > "$OUT/prof_lastseq.txt" 2>&1; rm -rf "$OUT/prof"; head -40 "$OUT/prof_stats.md" ;;
     pmcbench)   for C in FETCH_SIZE WRITE_SIZE; do (cd /tmp && timeout 600 rocprofv3 --pmc $C -d "$OLDPWD/$OUT/pmcb_$C" -o run -- python "$OLDPWD/bench.py" --steps 3 --warmup 2 --no-cpu-baseline --no-profile --no-extras --no-graphs > "$OLDPWD/$OUT/pmcb_$C.log" 2>&1); DB=$(find "$OUT/pmcb_$C" -name "*results.db" | head -1); python tools/rocpd_pmc_grid.py "$DB" --json "$OUT/pmc_$C.json" > "$OUT/pmc_${C}_by_grid.md" 2>&1; rm -rf "$OUT/pmcb_$C"; head -12 "$OUT/pmc_${C}_by_grid.md" | cut -c1-200; done ;;
     proff16)    # rocprofv3 kernel stats of the f16x3 parity mode on the headline workload
@@ -58,7 +58,7 @@ for stage in "$@"; do
     memread)    timeout 600 python tools/bench_memread.py > "$OUT/memread.txt" 2>&1; tail -30 "$OUT/memread.txt" ;;
     memreadlong) timeout 600 python tools/bench_memread.py --tokens 50176 --rows 1024 --copies 3 > "$OUT/memread_long.txt" 2>&1; tail -30 "$OUT/memread_long.txt" ;;
     f16x3)      timeout 900 python -m pytest tests/test_ops_gpu.py tests/test_model_gpu.py -x -q -m gpu -s -k "f16x3 or stress or precision or f32x3" > "$OUT/f16x3_tests.txt" 2>&1; grep -v "^$" "$OUT/f16x3_tests.txt" | tail -25
-                timeout 600 python bench.py --precision f16x3 --steps 10 --warmup 3 --no-cpu-baseline --no-extras > "$OUT/bench_f16x3.json" 2> "$OUT/bench_f16x3.err"; head -c 1200 "$OUT/bench_f16x3.json"; tail -3 "$OUT/bench_f16x3.err" ;;
+                timeout 600 python bench.py --precision f16x3 --steps 10 --warmup 3 --full --no-cpu-baseline --no-extras > "$OUT/bench_f16x3.json" 2> "$OUT/bench_f16x3.err"; head -c 1200 "$OUT/bench_f16x3.json"; tail -3 "$OUT/bench_f16x3.err" ;;
     *)          echo "unknown stage $stage" ;;
   esac
 done
