@@ -112,7 +112,7 @@ class SpatialMemory:
         """device_state (round 6; the static hipGraph runner in bf16 mode): the fill level (M, wm) also lives in a device int32 block
         that the step's kernels read -- score GEMM N, P.V GEMM K, the row a frame is written to, the working-memory window of the
         similarity gate -- so the captured step does not depend on it: one graph per step KIND (and grid bucket)
-        instead of one per bank length.  The host still owns the policy and pushes the values after every change (_push_state)."""
+        instead of one per bank length.  The host still owns the policy and pushes the values at the end of every policy call (_push_state)."""
         self.eng = engine
         self.B, self.P, self.C = batch, num_patches, engine.cfg.enc_dim
         self.attn_thresh = attn_thresh
@@ -132,7 +132,7 @@ class SpatialMemory:
         self.lm = 0
         self.events = []
         self._score = torch.zeros(batch, max(work_mem_size, 1), device=dev)
-        self._score_host, self._score_event, self._score_pending = None, None, False
+        self._score_host, self._score_pending = None, False
         self._cos_scratch = torch.empty(max(work_mem_size, 1) * num_patches, device=dev)
         self._sel = torch.zeros(batch, max(long_mem_size, 1), dtype=torch.int32, device=dev)
         w = engine.w
@@ -182,17 +182,17 @@ class SpatialMemory:
         return min(self.cap, (self.M + step - 1) // step * step)
 
     def graph_key(self):
-        """what a captured step depends on: (M, wm) when the launches carry them as arguments; the grid bucket of the two-launch read
-        in device-state mode (long banks: their launch list still depends on M)"""
+        """what a captured step depends on, next to the active arena half: (M, wm) when the launches carry them as arguments; the grid
+        bucket of the two-launch read in device-state mode (long banks: their launch list still depends on M)"""
         if self.state is None:
-            return (self.M, self.wm)
+            return (self.M, self.wm, self._cur)
         if self.M == 0:
-            return ("s", 0)
+            return ("s", 0, self._cur)
         if self.read_dyn and self._read_plan()[1]:
-            return ("s", self._bucket())
+            return ("s", self._bucket(), self._cur)
         if self._prob_read():
-            return ("p", self._bucket(self.PROB_BUCKET))
-        return ("l", self.M)
+            return ("p", self._bucket(self.PROB_BUCKET), self._cur)
+        return ("l", self.M, self._cur)
 
     PROB_BUCKET = 8192                # device-state mode, long banks: grid bucket of the score-matrix-free read (<= 64 idle N-tiles)
 
@@ -394,14 +394,13 @@ class SpatialMemory:
 
     def add_mem(self, feat_k, feat_v):
         self.stage_write(feat_k, feat_v)
-        self.commit()
-        self._push_state()
+        self.commit_staged()
 
     # ------------------------------------------------------------------ similarity gate (:97-118)
     def sim_scores(self, feat_k, to_host=False):
         """[B, wm] mean cosine similarity of feat_k against each of the last `wm` stored frames.
-        to_host (single-graph step, device-resident bank state): the reduction kernel stores the scores STRAIGHT into the pinned host
-        buffer the host polls (pinned memory is mapped into the device's address space) -- no copy node between the step's halves."""
+        to_host (the runner's step, device-resident bank state): the reduction kernel stores the scores STRAIGHT into the pinned host
+        buffer the host polls (pinned memory is mapped into the device's address space) -- no copy between the step's halves."""
         B, P, C = self.B, self.P, self.C
         n = self.wm * P
         for b in range(B):
@@ -424,31 +423,26 @@ class SpatialMemory:
     def _host_scores(self):
         if self._score_host is None:
             self._score_host = torch.empty(self._score.shape, dtype=torch.float32).pin_memory()
-            self._score_event = torch.cuda.Event()
         return self._score_host
 
-    def fetch_scores_async(self):
-        """queue the device->host copy of the scores behind the kernels launched so far; sim_verdict() waits for it only"""
-        self._host_scores().copy_(self._score, non_blocking=True)
-        self._score_event.record()
-        self._score_pending = True
-
-    def copy_scores_in_graph(self):
-        """The same copy as a node INSIDE the step's hipGraph (single-graph step): no event can be recorded in the middle of a
-        replay, so the host learns that the copy has landed from the data itself -- arm_score_poll() fills the pinned buffer with
-        a sentinel no cosine can take (2.0; a NaN sentinel could not tell "not landed" from a genuinely NaN score of degenerate
-        features) before the launch, sim_verdict() spins until the wm scores have replaced it."""
+    def copy_scores_to_host(self):
+        """The device->host copy of the scores between the step's halves (bank state in launch arguments: the reduction kernel left
+        them in the device buffer) -- a node INSIDE the step's hipGraph when the step is captured.  No event can be recorded in the
+        middle of a replay, so the host learns that the scores have landed from the data itself: arm_score_poll() fills the pinned
+        buffer with a sentinel no cosine can take (2.0; a NaN sentinel could not tell "not landed" from a genuinely NaN score of
+        degenerate features) before the launch, sim_verdict() spins until the wm scores have replaced it."""
         self._host_scores().copy_(self._score, non_blocking=True)
 
     _SENTINEL = 2.0                       # outside [-1, 1]: never a mean cosine (NaN scores pass through: a NaN maximum compares False below)
 
     def arm_score_poll(self):
         self._host_scores().fill_(self._SENTINEL)
-        self._score_pending = "poll"
+        self._score_pending = True
 
     def sim_verdict(self):
-        """Host side of check_sim: reads the scores the cos_sim kernels left in self._score (host sync, as :114)."""
-        if self._score_pending == "poll":
+        """Host side of check_sim: reads the scores the cos_sim kernels left in self._score (host sync, as :114) -- after
+        arm_score_poll(), the ones the step hands over through the pinned buffer."""
+        if self._score_pending:
             import time
             self._score_pending = False
             view = self._score_host[:, :self.wm]
@@ -456,14 +450,10 @@ class SpatialMemory:
             while bool((view == self._SENTINEL).any()):
                 if time.perf_counter() - t0 > 0.25:          # (never observed: fall back to a stream sync)
                     torch.cuda.current_stream().synchronize()
-                    if bool((view == self._SENTINEL).any()):  # (the copy-node form: the scores are in the device buffer)
+                    if bool((view == self._SENTINEL).any()):  # (the copy form: the scores are in the device buffer)
                         view = self._score[:, :self.wm].cpu()
                     break
             mx = float(view.max())                 # (torch's max propagates NaN, as the reference's mean_corr.max() does: never 'similar')
-        elif self._score_pending:
-            self._score_event.synchronize()
-            self._score_pending = False
-            mx = float(self._score_host[:, :self.wm].max())
         else:
             mx = float(self._score[:, :self.wm].max())
         if mx > self.sim_thresh:
@@ -482,13 +472,17 @@ class SpatialMemory:
         if self.check_sim(feat_k):
             self.events.append("skip")
             return
-        self.add_mem(feat_k, feat_v)
-        self._after_write()
+        self.stage_write(feat_k, feat_v)
+        self.finish_staged(False)
+
+    def commit_staged(self):
+        """Second half of add_mem (the growing-bank policy, :80-95) when the write was already launched (the runner's step)."""
+        self.commit()
         self._push_state()
 
     def finish_staged(self, similar):
         """Second half of add_mem_check when the similarity kernel and the speculative write were already launched
-        (hipGraph path): commit or drop the staged frame, then the working/long-term bookkeeping and prune."""
+        (the runner's step): commit or drop the staged frame, then the working/long-term bookkeeping and prune."""
         if similar:
             self.events.append("skip")
             self._flush_attn()
@@ -514,24 +508,27 @@ class SpatialMemory:
         P tokens leave.  P is not a multiple of the 16-row fragment blocks, so the fragment-order copies are re-gathered like a
         prune with the selection [P, M) (same kernels, other arena half)."""
         self._flush_attn()
-        B, C, M, P = self.B, self.C, self.M, self.P
-        k = M - P
-        src = self.bank
-        if self._banks[1 - self._cur] is None:
-            self._banks[1 - self._cur] = self._alloc(self.eng.device, self.eng.wdt)
-        dst = self._banks[1 - self._cur]
+        M, P = self.M, self.P
         sel = self._window_sel.get((P, M))
         if sel is None:
             sel = self._window_sel[(P, M)] = torch.arange(P, M, dtype=torch.int32, device=self.eng.device)
-        for b in range(B):
-            ops.gather_rows(src["k_raw"][b], dst["k_raw"][b], sel, k, C)
-            ops.gather_rows(src["v_raw"][b], dst["v_raw"][b], sel, k, C)
-            ops.gather_packed_rows(src["k_hat"][b], dst["k_hat"][b], sel, k, C)
-            ops.gather_packed_cols(src["v_hat_t"][b], dst["v_hat_t"][b], sel, k, self.cap, C, self.cap)
+        self._regather(sel.expand(self.B, -1), M - P)
+        print("Memory pruned:", torch.Size((self.B, M - P, self.C)))     # (spann3r/model.py:137 prints mem_k.shape)
+        self.events.append("window %d->%d" % (M, M - P))
+
+    def _regather(self, sel, k):
+        """rows sel[b, :k] of the bank -> rows [0, k) of the other arena half (allocated at its first use), which becomes the bank"""
+        C, src = self.C, self.bank
+        if self._banks[1 - self._cur] is None:
+            self._banks[1 - self._cur] = self._alloc(self.eng.device, self.eng.wdt)
+        dst = self._banks[1 - self._cur]
+        for b in range(self.B):
+            ops.gather_rows(src["k_raw"][b], dst["k_raw"][b], sel[b], k, C)
+            ops.gather_rows(src["v_raw"][b], dst["v_raw"][b], sel[b], k, C)
+            ops.gather_packed_rows(src["k_hat"][b], dst["k_hat"][b], sel[b], k, C)
+            ops.gather_packed_cols(src["v_hat_t"][b], dst["v_hat_t"][b], sel[b], k, self.cap, C, self.cap)
             for name in ("s_bank", "b_bank", "attn", "count"):
-                ops.gather_1d(src[name][b], dst[name][b], sel, k)
-        print("Memory pruned:", torch.Size((B, k, C)))              # (spann3r/model.py:137 prints mem_k.shape)
-        self.events.append("window %d->%d" % (M, k))
+                ops.gather_1d(src[name][b], dst[name][b], sel[b], k)
         self._cur = 1 - self._cur
         self.M = k
 
@@ -541,24 +538,12 @@ class SpatialMemory:
         The kept tokens are stored sorted by weight descending, ties by index ascending (the reference's torch.topk
         leaves the tie order implementation-defined, SURVEY.md §7 quirk i)."""
         self._flush_attn()
-        B, C, M, k = self.B, self.C, self.M, self.top_k
-        src = self.bank
-        if self._banks[1 - self._cur] is None:
-            self._banks[1 - self._cur] = self._alloc(self.eng.device, self.eng.wdt)
-        dst = self._banks[1 - self._cur]
-        for b in range(B):
+        M, k, src = self.M, self.top_k, self.bank
+        for b in range(self.B):
             ops.prune_select(src["attn"][b], src["count"][b], M, self.work_mem_size + 5, k, self._sel[b])
-            sel = self._sel[b]
-            ops.gather_rows(src["k_raw"][b], dst["k_raw"][b], sel, k, C)
-            ops.gather_rows(src["v_raw"][b], dst["v_raw"][b], sel, k, C)
-            ops.gather_packed_rows(src["k_hat"][b], dst["k_hat"][b], sel, k, C)
-            ops.gather_packed_cols(src["v_hat_t"][b], dst["v_hat_t"][b], sel, k, self.cap, C, self.cap)
-            for name in ("s_bank", "b_bank", "attn", "count"):
-                ops.gather_1d(src[name][b], dst[name][b], sel, k)
+        self._regather(self._sel, k)
         print("Memory pruned:", M, "->", k)
         self.events.append("prune %d->%d" % (M, k))
-        self._cur = 1 - self._cur
-        self.M = k
 
 
 class MemorySnapshot:
@@ -567,14 +552,122 @@ class MemorySnapshot:
     wm = lm = M = 0
 
 
+class _GraphCache:
+    """The hipGraphs of one runner, by key: a key runs eagerly the first time it is seen (that run also creates every workspace
+    buffer), is captured + replayed the second time, and replayed afterwards.
+    The captured graphs are an LRU bounded in count and in the device bytes their captures allocated (all captures of a
+    runner share one memory pool); an evicted key is simply captured again when it comes back.
+    len(), iteration and `in` are over the keys that hold a graph."""
+
+    MAX_GRAPHS = 16                      # per geometry.  bf16: the bank's fill level is device state, a 50-frame growing-bank sequence holds
+                                         # ~15 (encoder / head chunks, one step graph per grid bucket); round 5 held ~100 (one per bank length)
+    MAX_GRAPH_BYTES = 1 << 30            # device memory the captures of one geometry may pin in their pool
+
+    def __init__(self):
+        self.live = collections.OrderedDict()        # key -> (hipGraph, device bytes its capture allocated), least recently used first
+        self.seen = set()
+        self.pool = self.capture_stream = None
+        self.clear()
+
+    def __len__(self):
+        return len(self.live)
+
+    def __iter__(self):
+        return iter(self.live)
+
+    def __contains__(self, key):
+        return key in self.live
+
+    def clear(self):
+        """every key is new again (the buffers its launches baked in are gone)"""
+        self.live.clear()
+        self.seen.clear()
+        self.graph_bytes = 0
+        self.length_keys, self.length_keys_eager = set(), False    # keys that carry the bank length; True: they run eagerly (see run)
+
+    def drop(self, pred):
+        """the keys pred(key) holds for are new again"""
+        for k in [k for k in self.live if pred(k)]:
+            self.graph_bytes -= self.live.pop(k)[1]
+        self.seen = {k for k in self.seen if not pred(k)}
+
+    def run(self, key, fn, use_graphs, per_length=0):
+        """fn() -- called (use_graphs False, or the key's first sight), or captured / replayed as the key's graph.
+        per_length: the key carries the bank length (the fp32-operand modes, whose launches take it as an argument); the value is
+        how many such keys the running sequence brings where that is known before its first step, else 1.  Such steps are
+        captured only if ALL of a sequence's fit next to the runner's other graphs: a long sequence would otherwise evict and
+        re-capture one graph per step, which costs more than launching eagerly (these modes are GPU-bound: eager launches keep up).
+        The decision is per runner, never per step (`length_keys_eager`): one sequence is either replayed or launched eagerly
+        throughout."""
+        if per_length and not self.length_keys_eager and (
+                per_length > self.MAX_GRAPHS - 4 or
+                (use_graphs and key not in self.live and key in self.seen and len(self.live) >= self.MAX_GRAPHS - 2)):
+            # no room for this sequence's per-length steps (four slots stay free for the encoder / deferred-head graphs when the
+            # count is known up front, two when the cache fills up under way): from here on they all run eagerly, and the ones
+            # captured so far go
+            self.length_keys_eager = True
+            self.drop(lambda k: k in self.length_keys)
+        if per_length:
+            self.length_keys.add(key)
+        if not use_graphs or (per_length and self.length_keys_eager):
+            fn()
+        elif key in self.live:
+            self.live.move_to_end(key)
+            self.live[key][0].replay()
+        elif key in self.seen:
+            if self.pool is None or not self.live:
+                # a pool whose last graph is gone is retired by the allocator (its blocks are freed at the next empty_cache / OOM
+                # retry) and must not be captured into again: a runner that dropped all of its graphs starts a new pool
+                self.pool = torch.cuda.graph_pool_handle()
+            if self.capture_stream is None:
+                self.capture_stream = torch.cuda.Stream()
+            before = torch.cuda.memory_allocated()
+            g = torch.cuda.CUDAGraph()
+            # capture_begin / capture_end directly instead of the torch.cuda.graph context manager, which opens with a device
+            # synchronise and torch.cuda.empty_cache(): a capture records launches, it does not need an idle GPU -- the eager step
+            # queued before it keeps running while the host records this one (a first forward call captures its step graph between
+            # two steps), and the allocator keeps the blocks the next call's outputs will want.
+            # (no cyclic garbage collection during the capture: finalising another runner's hipGraph is not permitted while a
+            # stream captures)
+            import gc
+            gc_was = gc.isenabled()
+            gc.disable()
+            main = torch.cuda.current_stream()
+            cap = self.capture_stream
+            cap.wait_stream(main)
+            try:
+                with torch.cuda.stream(cap):
+                    g.capture_begin(self.pool, capture_error_mode="thread_local")
+                    try:
+                        fn()
+                    finally:
+                        g.capture_end()
+            finally:
+                if gc_was:
+                    gc.enable()
+            main.wait_stream(cap)
+            nbytes = max(0, torch.cuda.memory_allocated() - before)
+            self.live[key] = (g, nbytes)
+            self.graph_bytes += nbytes
+            while len(self.live) > self.MAX_GRAPHS or (self.graph_bytes > self.MAX_GRAPH_BYTES and len(self.live) > 1):
+                _, (old, ob) = self.live.popitem(last=False)
+                self.graph_bytes -= ob
+                del old
+            g.replay()
+        else:
+            self.seen.add(key)
+            fn()
+
+
 class _SequenceRunner:
     """Static-buffer, hipGraph-captured execution of Spann3R.forward for one (batch, H, W, policy) geometry.
 
     Every per-frame step is a fixed kernel sequence over persistent buffers; the only things that vary between steps
-    of a sequence are the memory fill M, the working-memory count wm and the active bank, so graphs are cached by
-    (M, wm, bank).  A key runs eagerly the first time it is seen (that run also creates every workspace buffer), is
-    captured + replayed the second time, and replayed afterwards.  The host only touches the device between steps to
-    read the similarity score (the reference's own host sync, spann3r/model.py:114) and to clone the outputs.
+    of a sequence are the memory fill M, the working-memory count wm and the active bank.  A step is ONE function (`run`)
+    that the graph cache captures and replays or, without graphs, calls; its graphs are cached by step kind,
+    SpatialMemory.graph_key() (the grid bucket of the read where the fill level is device state, else (M, wm); the bank) and the
+    schedule attributes.  The host only touches the device between steps to read the similarity score (the reference's own host
+    sync, spann3r/model.py:114) and to clone the outputs.
     """
 
     def __init__(self, model, eng, B, H, W, training, true_hw=None):
@@ -610,12 +703,8 @@ class _SequenceRunner:
         self.v = torch.empty(B, self.P, self.E, device=dev)
         self.mem = None
         self.k2_aux = (None, None)
-        self.graphs = collections.OrderedDict()        # key -> (hipGraph, device bytes its capture allocated), least recently used first
-        self.graph_bytes = 0
-        self.seen = set()
-        self.length_keys, self.length_keys_eager = set(), False    # keys that carry the bank length; True: they run eagerly (see _graphed)
+        self.graphs = _GraphCache()
         self.out = None
-        self._scores_to_host = False  # set around _part1 by the single-graph step (SpatialMemory.sim_scores)
         self.batched = False          # True: the frames of the sequence were encoded up front (encode_sequence)
         self.img_all = self.feats = None
         self.defer2 = False           # True: the view-2 DPT head runs once for all steps after the loop (finish_head2)
@@ -635,9 +724,6 @@ class _SequenceRunner:
         if self.mem is None or self.mem.cap < need:
             self.mem = SpatialMemory(self.eng, self.B, self.P, capacity=need, attn_thresh=0.0 if self.training else 5e-4, device_state=True)
             self.graphs.clear()
-            self.graph_bytes = 0
-            self.seen.clear()
-            self.length_keys, self.length_keys_eager = set(), False
         self.mem.reset()
         return self.mem
 
@@ -655,8 +741,7 @@ class _SequenceRunner:
             self.feats = torch.empty(n * B, self.P, self.E, device=self.eng.device)
             self.feats_p = ops.PackedAct.group(n, B * self.P, self.E, torch.bfloat16, self.eng.device) if self.packed_feats else None
             # every graph that baked in the old buffers dies with them: the encoder's AND the deferred head's (reads feats)
-            self._drop_graphs(lambda k: k[0] in ("enc", "head2"))
-            self.seen = {k for k in self.seen if k[0] not in ("enc", "head2")}
+            self.graphs.drop(lambda k: k[0] in ("enc", "head2"))
         slots = [(f["img"], self.img_all[i * B:(i + 1) * B]) for i, f in enumerate(frames)]
         fast = [p for p in slots if p[0].is_cuda and p[0].dtype == torch.float32 and p[0].is_contiguous() and p[0].shape == p[1].shape]
         for c0 in range(0, len(fast), 8):                      # 8 frames per launch instead of one copy each
@@ -669,8 +754,8 @@ class _SequenceRunner:
             c1 = min(n, c0 + per)
             img, out = self.img_all[c0 * B:c1 * B], self.feats[c0 * B:c1 * B]
             outp = self.feats_p.at(c0) if self.feats_p is not None else None          # frame f -> group f of the packed copy
-            self._graphed(("enc", c0, c1), lambda: self.eng.encode_image(img, out=out, tag="_seq", out_packed=outp, group_rows=B * self.P),
-                          use_graphs)
+            self.graphs.run(("enc", c0, c1), lambda: self.eng.encode_image(img, out=out, tag="_seq", out_packed=outp, group_rows=B * self.P),
+                            use_graphs)
         self.batched = True
 
     # ---- deferred view-2 head --------------------------------------------------------------------------------
@@ -684,8 +769,7 @@ class _SequenceRunner:
         D = self.model.cfg.dec_dim
         if self.seq_dec2 is None or self.seq_dec2[0].shape[0] < rows:
             self.seq_dec2 = [torch.empty(rows, D, device=self.eng.device) for _ in range(3)]
-            self._drop_graphs(lambda k: k[0] == "head2")
-            self.seen = {k for k in self.seen if k[0] != "head2"}
+            self.graphs.drop(lambda k: k[0] == "head2")
         self.defer2 = True
 
     def dec2_copies(self, i):
@@ -711,7 +795,7 @@ class _SequenceRunner:
             def fn(dec=dec, key=key, nb=(c1 - c0) * B):
                 pts, conf, _ = self.eng.dpt_head(dec, nb, self.hh, self.hw, 2)
                 self.head2_out[key] = (pts, conf)
-            self._graphed(key, fn, use_graphs)
+            self.graphs.run(key, fn, use_graphs)
             pts, conf = self.head2_out[key]
             pts, conf = pts.clone(), conf.clone()
             for j in range(c1 - c0):
@@ -723,13 +807,6 @@ class _SequenceRunner:
         call), not four torch.empty per step: the caller still owns fresh tensors, the caching allocator is out
         of the step loop."""
         self._out_slabs, self._out_steps, self._out_i = None, n_steps, 0
-        # step graphs that carry the bank length (fp32-operand modes): decided for the WHOLE sequence before its first step -- if one
-        # graph (or two, two-graph steps) per step does not fit next to the encoder / head graphs, every step launches eagerly
-        if self.mem is not None and self.mem.state is None and not self.length_keys_eager:
-            per_step = 1 if self.model.single_graph_step else 2
-            if n_steps * per_step > self.MAX_GRAPHS - 4:
-                self.length_keys_eager = True
-                self._drop_graphs(lambda k: k in self.length_keys)
 
     def _step_outputs(self, srcs):
         if getattr(self, "_out_steps", 0) <= 0 or self._out_i >= self._out_steps:
@@ -752,85 +829,12 @@ class _SequenceRunner:
     def load_pair(self, i):
         ops.copy_multi(self.pair_copies(i))
 
-    def _drop_graphs(self, pred):
-        for k in [k for k in self.graphs if pred(k)]:
-            self.graph_bytes -= self.graphs.pop(k)[1]
-
-    MAX_GRAPHS = 16                      # per geometry.  bf16: the bank's fill level is device state, a 50-frame growing-bank sequence holds
-                                         # ~15 (encoder / head chunks, one step graph per grid bucket); round 5 held ~100 (one per bank length)
-    MAX_GRAPH_BYTES = 1 << 30            # device memory the captures of one geometry may pin in their pool
-
-    def _graphed(self, key, fn, use_graphs, per_length=False):
-        """eager the first time a key is seen (creates the workspaces), captured the second time, replayed afterwards.
-        The captured graphs are an LRU bounded in count and in the device bytes their captures allocated (all captures of a
-        runner share one memory pool); an evicted key is simply captured again when it comes back.
-        per_length: the key carries the bank length (the fp32-operand modes, whose launches take it as an argument).  Such steps are
-        captured only if ALL of a sequence's fit next to the runner's other graphs: a long sequence would otherwise evict and
-        re-capture one graph per step, which costs more than launching eagerly (these modes are GPU-bound: eager launches keep up).
-        The decision is per runner, never per step (`length_keys_eager`): one sequence is either replayed or launched eagerly
-        throughout."""
-        if per_length and use_graphs and not self.length_keys_eager and key not in self.graphs and key in self.seen \
-                and len(self.graphs) >= self.MAX_GRAPHS - 2:
-            # no room for this sequence's per-length steps (two slots stay free for the encoder / deferred-head graphs): from
-            # here on they all run eagerly, and the ones captured so far go
-            self.length_keys_eager = True
-            self._drop_graphs(lambda k: k in self.length_keys)
-        if per_length:
-            self.length_keys.add(key)
-        if not use_graphs or (per_length and self.length_keys_eager):
-            fn()
-        elif key in self.graphs:
-            self.graphs.move_to_end(key)
-            self.graphs[key][0].replay()
-        elif key in self.seen:
-            if getattr(self, "_pool", None) is None or not self.graphs:
-                # a pool whose last graph is gone is retired by the allocator (its blocks are freed at the next empty_cache / OOM
-                # retry) and must not be captured into again: a runner that dropped all of its graphs starts a new pool
-                self._pool = torch.cuda.graph_pool_handle()
-            if getattr(self, "_capture_stream", None) is None:
-                self._capture_stream = torch.cuda.Stream()
-            before = torch.cuda.memory_allocated()
-            g = torch.cuda.CUDAGraph()
-            # capture_begin / capture_end directly instead of the torch.cuda.graph context manager, which opens with a device
-            # synchronise and torch.cuda.empty_cache(): a capture records launches, it does not need an idle GPU -- the eager step
-            # queued before it keeps running while the host records this one (a first forward call captures its step graph between
-            # two steps), and the allocator keeps the blocks the next call's outputs will want.
-            # (no cyclic garbage collection during the capture: finalising another runner's hipGraph is not permitted while a
-            # stream captures)
-            import gc
-            gc_was = gc.isenabled()
-            gc.disable()
-            main = torch.cuda.current_stream()
-            cap = self._capture_stream
-            cap.wait_stream(main)
-            try:
-                with torch.cuda.stream(cap):
-                    g.capture_begin(self._pool, capture_error_mode="thread_local")
-                    try:
-                        fn()
-                    finally:
-                        g.capture_end()
-            finally:
-                if gc_was:
-                    gc.enable()
-            main.wait_stream(cap)
-            nbytes = max(0, torch.cuda.memory_allocated() - before)
-            self.graphs[key] = (g, nbytes)
-            self.graph_bytes += nbytes
-            while len(self.graphs) > self.MAX_GRAPHS or (self.graph_bytes > self.MAX_GRAPH_BYTES and len(self.graphs) > 1):
-                _, (old, ob) = self.graphs.popitem(last=False)
-                self.graph_bytes -= ob
-                del old
-            g.replay()
-        else:
-            self.seen.add(key)
-            fn()
-
     # ---- the kernel sequences (spann3r/model.py:485-531) ----------------------------------------------------
-    def _part1(self, first, has_next):
+    def _part1(self, first, has_next, scores_to_host):
         """Everything up to the similarity scores: (memory read) + decoder + key MLPs + check_sim's cosine scores.
         The two decoder sides run on two streams (or as grouped launches); a third stream encodes the NEXT frame in
-        the frame-by-frame mode (each frame is encoded exactly once, spann3r/model.py:293-295)."""
+        the frame-by-frame mode (each frame is encoded exactly once, spann3r/model.py:293-295).
+        scores_to_host: the scores go straight to the buffer the host polls, where the kernel can do that (SpatialMemory.sim_scores)."""
         eng, mem, B, P, E = self.eng, self.mem, self.B, self.P, self.E
         main = torch.cuda.current_stream()
         st = eng.side_streams()
@@ -862,20 +866,14 @@ class _SequenceRunner:
             self.k2_aux = eng.encode_feat_keys_grouped(self.feat1, self.feat2, dec1[-1], dec2[-1], B * P, self.k1, self.k2,
                                                        feat1p=p1, feat2p=p2)
         else:
-            if self.model.decoder_streams:
-                dec1, dec2 = eng.decoder(f1, self.feat2, B, self.nh, self.nw, self.nh, self.nw, streams=st)   # joined on return
-                st[2].wait_stream(main)
-                with torch.cuda.stream(st[2]):
-                    self.k2_aux = eng.encode_feat_key(self.feat2, dec2[-1], B * P, 2, self.k2, aux=True)
-                eng.encode_feat_key(self.feat1, dec1[-1], B * P, 1, self.k1)
-                main.wait_stream(st[2])
-            else:
-                # one stream, side after side: a graph fork/join pair costs more than the overlap of two 196-row launches buys
-                dec1, dec2 = eng.decoder(f1, self.feat2, B, self.nh, self.nw, self.nh, self.nw, streams=None)
+            dec1, dec2 = eng.decoder(f1, self.feat2, B, self.nh, self.nw, self.nh, self.nw, streams=st)   # joined on return
+            st[2].wait_stream(main)
+            with torch.cuda.stream(st[2]):
                 self.k2_aux = eng.encode_feat_key(self.feat2, dec2[-1], B * P, 2, self.k2, aux=True)
-                eng.encode_feat_key(self.feat1, dec1[-1], B * P, 1, self.k1)
+            eng.encode_feat_key(self.feat1, dec1[-1], B * P, 1, self.k1)
+            main.wait_stream(st[2])
         if not self.training and mem.sim_needed():
-            mem.sim_scores(self.k1, to_host=self._scores_to_host and mem.state is not None)
+            mem.sim_scores(self.k1, to_host=scores_to_host and mem.state is not None)
         if has_next:
             main.wait_stream(st[3])
         self.dec = (dec1, dec2)
@@ -906,44 +904,32 @@ class _SequenceRunner:
         self.out = (pts1, conf1, pts2, conf2)
 
     def run(self, first, has_next, use_graphs, post_copies=()):
-        """post_copies: (src, dst) pairs issued with the step's own result copies in ONE launch after the second graph
+        """One step: ONE function -- _part1, the hand-off of the similarity scores to the host, _part2 -- captured and replayed
+        as one hipGraph, or called (use_graphs False, a profiler, or a sequence whose per-length steps launch eagerly).  The host
+        polls the pinned score buffer and takes the memory decision while the second half (head, value encoder) still runs -> the
+        next step's launches are queued before the GPU runs dry.  The reference syncs at the same point of the data flow (:114).
+        post_copies: (src, dst) pairs issued with the step's own result copies in ONE launch after the step
         (decoder hooks -> sequence slots, the next pair of encoder features): six eager launches per frame became one"""
         mem = self.mem
         has_next = has_next and not self.batched                # nothing to prefetch: the sequence is already encoded
         gk = mem.graph_key()
-        per_length = gk[0] not in ("s", "p")               # (the bank length itself is in the key: see _graphed)
-        key = gk + (mem._cur, has_next, self.batched, self.defer2, self.model.grouped_decoder, self.model.packed_features)
+        # the bank length itself is in the key (see _GraphCache.run): a long bank's steps, EVERY step where the fill level is a launch argument
+        per_length = 0 if gk[0] in ("s", "p") else self._out_steps if mem.state is None else 1
         if not use_graphs and ops._prof is not None:
             ops._prof.step_begin()
-        # two graphs per step: the host fetches the similarity scores (async copy + event) as soon as the first one is
-        # done and takes the memory decision while the second one (head, value encoder) still runs -> the next step's
-        # launches are queued before the GPU runs dry.  The reference syncs at the same point of the data flow (:114).
         need_sim = not self.training and mem.sim_needed()
-        if self.model.single_graph_step and use_graphs and ops._prof is None:
-            # ONE graph per step: the score copy is a memcpy node between the two halves and the host polls the pinned buffer for
-            # it while the second half runs (two graph launches per step left ~15 us of launch gaps around the copy)
-            if need_sim:
-                mem.arm_score_poll()
+        if need_sim:
+            mem.arm_score_poll()
 
-            def whole():
-                self._scores_to_host = need_sim                 # (device-resident bank state: cos_mean stores into the pinned buffer itself)
-                try:
-                    self._part1(first, has_next)
-                finally:
-                    self._scores_to_host = False
-                if need_sim and mem.state is None:
-                    mem.copy_scores_in_graph()
-                self._part2()
-            self._graphed(("whole", first, need_sim) + key, whole, use_graphs, per_length)
-            if not first:
-                mem.note_deferred_read()        # (a replayed graph ran no Python)
-        else:
-            self._graphed(("first" if first else "step",) + key, lambda: self._part1(first, has_next), use_graphs, per_length)
-            if not first:
-                mem.note_deferred_read()        # (a replayed graph ran no Python)
-            if need_sim:
-                mem.fetch_scores_async()
-            self._graphed(("tail",) + key, self._part2, use_graphs, per_length)
+        def whole():
+            self._part1(first, has_next, need_sim)
+            if need_sim and mem.state is None:              # (device-resident bank state: cos_mean stored into the pinned buffer itself)
+                mem.copy_scores_to_host()
+            self._part2()
+        key = ("whole", first, need_sim) + gk + (has_next, self.batched, self.defer2, self.model.grouped_decoder, self.model.packed_features)
+        self.graphs.run(key, whole, use_graphs and ops._prof is None, per_length)
+        if not first:
+            mem.note_deferred_read()            # (a replayed graph ran no Python)
         pts1, conf1, pts2, conf2 = self.out
         srcs = (pts1, conf1) + (() if pts2 is None else (pts2, conf2))
         outs = self._step_outputs(srcs)
@@ -958,8 +944,7 @@ class _SequenceRunner:
             res2 = {k: v.swapaxes(1, 2) for k, v in res2.items()}
         # memory policy (:518-521): the frame was staged inside the step; commit or drop it here
         if self.training:
-            mem.commit()
-            mem._push_state()
+            mem.commit_staged()
         else:
             mem.finish_staged(mem.sim_verdict() if need_sim else False)
         return res1, res2
@@ -1026,9 +1011,7 @@ class Spann3R(nn.Module):
         self.batch_encode = True     # forward(): encode all frames of the sequence together (False: frame by frame)
         self.defer_head2 = True      # with batch_encode: run the view-2 DPT head once for all steps after the loop
         self.grouped_decoder = True  # bf16: the two decoder sides as grouped launches on one stream (False: two streams)
-        self.single_graph_step = True   # one hipGraph per step, the similarity scores polled from pinned memory (False: two graphs + an event)
         self.packed_features = True  # bf16 + batch_encode + grouped_decoder: decoder_embed / key MLPs read fragment-order bf16 copies of the features (lean instances)
-        self.decoder_streams = True  # ungrouped decoder (the fp32-operand modes): two streams with a fork/join per layer (False: one stream, side after side)
         self.force_general = False   # True: always take the reference-shaped eager loop (_forward_general; tests)
         self.max_runners = 4         # geometries (batch, H, W, policy, true_shape) kept with their buffers and graphs
 
@@ -1361,7 +1344,7 @@ class Spann3R(nn.Module):
 
     def _forward_static(self, eng, frames, return_memory, true_hw):
         """Same-shape sequences with one true_shape (what demo / eval / app / training batches are): static buffers,
-        whole-sequence encoder, two hipGraphs per step."""
+        whole-sequence encoder, one hipGraph per step."""
         img0 = frames[0]["img"]
         B, _, H, W = img0.shape
         key = (B, H, W, bool(self.training), true_hw)

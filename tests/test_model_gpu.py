@@ -205,7 +205,7 @@ def test_graph_replay_equals_eager(tiny_model):
     frames = to_dev(synth_frames(5, 48, 64, seed=5))
     outs = [m(frames, return_memory=True) for _ in range(3)]
     run = [r for k, r in m._runners.items() if k[:3] == (1, 48, 64)][0]
-    assert sum(k[0] in ("first", "step", "whole") for k in run.graphs) == 4      # one per step of the 5-frame sequence
+    assert sum(k[0] == "whole" for k in run.graphs) == 4                         # one per step of the 5-frame sequence
     assert ("enc", 0, 5) in run.graphs                                   # + the whole-sequence encoder
     m.use_graphs = False
     try:
@@ -241,7 +241,7 @@ def test_one_step_graph_serves_a_growing_bank(tiny_sd, policy):
     first = m(frames, return_memory=True)                 # call 1: step graphs are captured INSIDE it (second sight of their key)
     run = [r for k, r in m._runners.items() if k[:3] == (1, 48, 64)][0]
     assert run.mem.state is not None
-    steps = [k for k in run.graphs if k[0] in ("first", "step", "whole")]
+    steps = [k for k in run.graphs if k[0] == "whole"]
     assert 1 <= len(steps) <= 3, steps                    # (eval: the similarity gate switches on once -> a second step kind)
     again = m(frames, return_memory=True)                 # call 2: every key replays or is captured now
     n_graphs = len(run.graphs)
@@ -268,7 +268,7 @@ def test_one_step_graph_serves_a_growing_bank(tiny_sd, policy):
             assert torch.equal(a[k], b[k]), k
     assert torch.equal(eager_long[2].mem_attn, got_long[2].mem_attn)
     run = [r for k, r in m._runners.items() if k[:3] == (1, 48, 64)][0]
-    assert sum(k[0] in ("first", "step", "whole") for k in run.graphs) <= 3
+    assert sum(k[0] == "whole" for k in run.graphs) <= 3
 
 
 def test_two_models_of_different_precision_in_one_process(tiny_sd):
@@ -604,7 +604,7 @@ def test_true_shape_takes_graph_path_and_matches_reference(tiny_model, tag):
             assert rel_err(r2["conf"].cpu(), g["%s_step%d_conf2" % (tag, i)]) < TOL_FP32
         assert rel_err(mem.mem_attn.cpu(), g["%s_mem_attn" % tag]) < TOL_FP32
     run = m._runners[(int(g["meta_batch"]), H, W, False, ts)]
-    assert any(k[0] == "whole" for k in run.graphs) or (any(k[0] == "step" for k in run.graphs) and any(k[0] == "tail" for k in run.graphs))
+    assert any(k[0] == "whole" for k in run.graphs)
     # a device-resident true_shape and the key-less form give the same thing (landscape only for the latter)
     p_dev, _ = m(_with_true_shape(frames, ts, DEV))
     assert all(torch.equal(a[k], b[k]) for a, b in zip(preds, p_dev) for k in a)
@@ -773,8 +773,7 @@ def test_cfg2_224x10_vs_reference(full_sd, precision, tol):
 
 
 @pytest.mark.parametrize("switch,precision", [("batch_encode", "bf16"), ("defer_head2", "bf16"), ("grouped_decoder", "bf16"),
-                                              ("single_graph_step", "bf16"), ("packed_features", "bf16"), ("use_graphs", "bf16"),
-                                              ("decoder_streams", "fp32"), ("batch_encode", "fp32"), ("single_graph_step", "fp32")])
+                                              ("packed_features", "bf16"), ("use_graphs", "bf16"), ("batch_encode", "fp32")])
 def test_cfg2_schedule_switches_vs_reference(full_sd, switch, precision):
     """Every scheduling attribute the model keeps, with its NON-default value, on the config-2 reference dump (each switch
     is a path of its own; the defaults alone were pinned to the BASELINE fixtures).  The measured call is the third of its geometry,

@@ -77,7 +77,7 @@ def main():
         rows.append((i + 1, h, t))
         print("call %d: host %.2f ms, wall %.2f ms -> %.1f frames/s" % (i + 1, 1e3 * h, 1e3 * t, a.frames / t))
     run = list(m._runners.values())[0]
-    print("graphs held: %d, keys seen: %d" % (len(run.graphs), len(run.seen)))
+    print("graphs held: %d, keys seen: %d" % (len(run.graphs), len(run.graphs.seen)))
     m.use_graphs = False
     for i in range(3):
         h, t = timed(m, seqs[i])

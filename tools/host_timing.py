@@ -20,13 +20,13 @@ def wrap(obj, name, label=None):
         t = time.perf_counter(); r = f(*a, **k); acc[label or name] += time.perf_counter() - t; return r
     setattr(obj, name, g)
 run = list(m._runners.values())[0]
-orig_graphed = run._graphed
-def graphed(key, fn, ug):
-    t = time.perf_counter(); orig_graphed(key, fn, ug); acc["replay:" + key[0]] += time.perf_counter() - t
-run._graphed = graphed
-for nm in ("save_dec2", "load_pair", "finish_head2", "encode_sequence"):
+orig_graphed = run.graphs.run
+def graphed(key, fn, ug, per_length=0):
+    t = time.perf_counter(); orig_graphed(key, fn, ug, per_length); acc["replay:" + key[0]] += time.perf_counter() - t
+run.graphs.run = graphed
+for nm in ("load_pair", "finish_head2", "encode_sequence"):
     wrap(run, nm)
-wrap(run.mem, "sim_verdict"); wrap(run.mem, "finish_staged"); wrap(run.mem, "fetch_scores_async")
+wrap(run.mem, "sim_verdict"); wrap(run.mem, "finish_staged")
 wrap(run, "run", "run(total)")
 N = 10
 t0 = time.perf_counter()
