@@ -88,9 +88,12 @@ typedef struct sp3_gemm_desc {
   int32_t heads;
   int64_t vt_ld;
   int32_t ps_k, ps_H, ps_W, ps_C;
-  int32_t tile;           /* -1 auto (sp3_gemm_plan tells which); 30..: lean small-M instances (sp3_gemm_plan); 0: 32x32 (K over 4 waves); 1: 64x64; 2: 64x128; 3: 64x64 (K over 4 waves);
-                             5 / 6: 128x128 / 128x64 with both operands staged through LDS (bf16 fragment-order A and W,
-                             K % 64 == 0) */
+  int32_t tile;           /* -1 auto (sp3_gemm_plan tells which); 30..: lean small-M instances (sp3_gemm_plan); the general tiles, all there are:
+                             0: 32x32 (K over 4 waves); 1: 64x64; 2: 64x128; 3: 64x64 (K over 4 waves) -- operands from a register ring;
+                             5 / 6: 128x128 / 128x64 with both operands staged through LDS (fragment-order A and W in the MFMA
+                             dtype, whole k-blocks); 13: 112x64, weights in a register ring, loader waves stage A (bf16 only);
+                             20 / 21 / 22 / 24 / 25: 256x128 / 128x128 / 128x64 / 64x32 / 32x32 with the LDS ring pipelined (operands
+                             as for 5 / 6).  Any other number below 30 is an error. */
   int32_t a_bf16;
   int32_t splitk;         /* >= 1; > 1 only with SP3_EPI_PARTIAL */
   int32_t a_packed;       /* A is in MFMA-fragment order [ceil(M/16)][ceil(K/KB)][2 halves][64 lanes][CH/2] (see w_packed); written
@@ -126,7 +129,7 @@ typedef struct sp3_gemm_desc {
    *   cross-attention k/v projection of side z reads the tokens and statistics of side 1-z).  rope tables / pos are
    *   shared. */
   int64_t sb_A2, sb_bias, sb_ln_stats, sb_ln_s, sb_stats_out, sb_c2, sb_vt;
-  /* --- diagnostics: if non-null, the first 8 workgroups of a role-loop launch (tiles 13-15) store shader-clock stamps of
+  /* --- diagnostics: if non-null, the first 8 workgroups of a role-loop launch (tile 13) store shader-clock stamps of
    *   their own timeline: trace[wg*64 + 0] = entry, [1] = loop done, [2] = epilogue done, [8 + i/4] = loader passed the
    *   barrier of k-block i (i % 4 == 0), [32 + i/4] = consumer wave 0 finished k-block i.  tools/trace_gemm.py prints it. */
   int64_t* trace;
@@ -134,7 +137,7 @@ typedef struct sp3_gemm_desc {
    *   attn_thresh dropped, renormalised, times V):
    *   launch 1, the score GEMM (plain loader/epilogue): sm_stats_out[M][ceil(N/32)][2] receives, per row and 32-column
    *     group of the finished C, (max, sum exp(x - max)) -- the softmax statistics leave with the scores.
-   *   launch 2, loader SP3_LOAD_SOFTMAX (32x32 tile): A is the fp32 score matrix [M, lda] (K = bank tokens, any multiple
+   *   launch 2, loader SP3_LOAD_SOFTMAX (16x64 tile, K over 4 waves): A is the fp32 score matrix [M, lda] (K = bank tokens, any multiple
    *     of 4); each lane merges sm_stats[M][sm_nt][2] of its rows to (m, Z) and turns the scores it loads into
    *     p = exp(a - m) / Z, p < sm_thresh -> 0, on their way into the MFMA; C = (p . W^T) / sum(kept p) (+ bias, res);
    *     sm_zout[M][4] receives (sum(kept p), m, 1/Z, -) per row.  No probability matrix exists in memory.

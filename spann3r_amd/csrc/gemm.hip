@@ -116,8 +116,6 @@ template <> struct MM<float, __bf16> {
       }
     }
   }
-  template <int MF, int NF>
-  static __device__ __forceinline__ void mma_half(f32x4 (&)[MF][NF], const AReg (&)[MF], const WReg (&)[NF]) {}
 };
 
 template <> struct MM<__bf16, __bf16> {
@@ -145,7 +143,7 @@ template <> struct MM<__bf16, __bf16> {
         acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[m].v[1], w[n].v[1], acc[m][n], 0, 0, 0);
       }
   }
-  // one 16-byte half of the k-block (v[0] only): the LDS-staged loop with the contraction split over a wave pair
+  // one 16-byte half of the k-block (v[0] only): the role loop, whose wave pairs split every k-block
   template <int MF, int NF>
   static __device__ __forceinline__ void mma_half(f32x4 (&acc)[MF][NF], const AReg (&a)[MF], const WReg (&w)[NF]) {
 #pragma unroll
@@ -316,18 +314,6 @@ template <> struct MM<float, float> {
       for (int n = 0; n < NF; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wh[n], acc[m][n], 0, 0, 0);
     }
   }
-  template <int MF, int NF>
-  static __device__ __forceinline__ void mma_half(f32x4 (&acc)[MF][NF], const AReg (&a)[MF], const WReg (&w)[NF]) {
-#pragma unroll
-    for (int m = 0; m < MF; ++m)
-#pragma unroll
-      for (int n = 0; n < NF; ++n) {
-        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m].v[0].x, w[n].v[0].x, acc[m][n], 0, 0, 0);
-        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m].v[0].y, w[n].v[0].y, acc[m][n], 0, 0, 0);
-        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m].v[0].z, w[n].v[0].z, acc[m][n], 0, 0, 0);
-        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m].v[0].w, w[n].v[0].w, acc[m][n], 0, 0, 0);
-      }
-  }
   static __device__ __forceinline__ void mma16(f32x4& acc, const float4& a, const float4& w) {
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w.x, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w.y, acc, 0, 0, 0);
@@ -449,18 +435,16 @@ __device__ __forceinline__ void glds16(const char* gsrc, char* lds) {
 
 // LDSK = true selects the LDS-staged K loop (fragment-order A and W in the MFMA dtype, STAGES = 2..4 ring slots, one
 // barrier per k-block): both operand tiles arrive once per workgroup by global_load_lds and every wave reads its fragments
-// from LDS.  Two uses: (a) tiles too wide for the per-wave register ring (128 x 128: the many-row GEMMs of the
-// whole-sequence encoder; 2 slots measured best there, three workgroups per CU beat a deeper ring); (b) the 196-row
-// weight-streaming GEMMs of the per-frame step: 112- or 208-row tiles read each weight panel once or twice instead of
-// seven times (32-row tiles), which is what bounds those launches (L2 -> CU bytes), with a 3-4 slot ring because only
-// one workgroup fits a CU.  The epilogues are shared.
+// from LDS.  Its use: tiles too wide for the per-wave register ring (128 x 128 and 128 x 64: the many-row GEMMs of the
+// whole-sequence encoder; 2 slots measured best there, three workgroups per CU beat a deeper ring).  (The 112- and 208-row
+// weight-streaming tiles that also ran this loop gave way to the role loop below.)  The epilogues are shared.
 // The hot 32x32 bf16 tile sits at the edge of 3 waves per SIMD (512 / 3 = 170 registers); small edits used to tip it
 // over to 2, which costs 10-25 % on the wide-N launches (tools/bench_block.py), so its register budget is pinned.
 template <typename TA, int LOADER, int MF, int NF, int WK>
 constexpr int gemm_min_waves() { return (sizeof(TA) == 2 && LOADER == SP3_LOAD_PLAIN && MF == 2 && NF == 2 && WK == 4) ? 3 : 1; }
 
-// LOOP: 0 = register ring, 1 = both operands through LDS (above), >= 2 = weight streaming with roles (below) and
-// LOOP loader waves.
+// LOOP: 0 = register ring, 1 = both operands through LDS (above), -1 = the same ring pipelined (tiles 20-22, 24, 25), >= 2 = weight
+// streaming with roles (below) and LOOP loader waves.
 // LOOP >= 2 (the per-frame step's 196-row GEMMs with HBM-cold weights).  Measured on MI355X (tools/ubench/stream.hip, tools/
 // bench_gemm2.py): a CU pulls 40-50 B/clk of L2-hot data but every cold weight byte is ~3000 clk away, so a loop that
 // keeps its weights and activations in ONE in-order vmcnt queue runs at latency / ring depth per k-block.  Here the
@@ -602,9 +586,9 @@ void gemm_kernel(const GemmArgs args) {
   // behind the GEMM instead of sitting between two barriers.
   // threads per tile row: the largest power of two (lane-aligned groups) with TPR * BM <= NT; spare threads idle here
   constexpr int TPR = NT >= 8 * BM ? 8 : NT >= 4 * BM ? 4 : NT >= 2 * BM ? 2 : 1;
-  // partials requested up front per thread: 4 where registers are short (the register-ring tiles, the 128-row LDS tiles
-  // that live on three workgroups per CU); the weight-streaming LDS tiles take all of a 1024-wide row (32 groups)
-  constexpr int NPRE = (LDSK && LOOP != -1 && STAGES >= 3) ? 32 / TPR : 4;
+  // partials requested up front per thread: registers are short (the register-ring tiles, the 128-row LDS tiles that live on
+  // three workgroups per CU)
+  constexpr int NPRE = 4;
   const int srow = tid / TPR, sj = tid % TPR;
   float2 sp[NPRE];
 #pragma unroll
@@ -701,7 +685,8 @@ void gemm_kernel(const GemmArgs args) {
 
   if constexpr (LOOP >= 2) {
     constexpr int kLoaderWaves = LOOP;
-    static_assert(sizeof(TA) == sizeof(TW) && WK <= 2 && NF == 1 && WM == 1, "role loop: fragment-order operands, one column block per wave");
+    static_assert(sizeof(TA) == sizeof(TW) && WK == 2 && NF == 1 && WM == 1,
+                  "role loop: fragment-order operands, one column block per wave pair, which splits every k-block by its halves");
     constexpr int MBLK = BM / 16, STAGE_BYTES = MBLK * 2048, NINSTR = 2 * MBLK;
     constexpr int PER = (NINSTR + kLoaderWaves - 1) / kLoaderWaves, NST = STAGES;
     static_assert(NST >= 2 && NST <= 4 && PER * (NST - 1) < 64, "activation ring: 2..4 slots");
@@ -790,14 +775,12 @@ void gemm_kernel(const GemmArgs args) {
       int nb = (n0 >> 4) + wn;
       const int nb_max = (d.N + 15) / 16 - 1;
       nb = nb < nb_max ? nb : nb_max;
-      // WK = 2: the pair splits every k-block by its two 1 KB halves
-      const int hoff = WK == 2 ? wk * 1024 : 0;
+      // the wave pair splits every k-block by its two 1 KB halves
+      const int hoff = wk * 1024;
       const char* wsrc = reinterpret_cast<const char*>(W + (int64_t)nb * nkb_w * (2048 / sizeof(TW))) + lane * 16;
-      W16 wr[kWRing][WK == 2 ? 1 : 2];
+      W16 wr[kWRing];
       auto loadw = [&](int slot, int kb) {                // kb clamped by the caller
-        const char* q = wsrc + (int64_t)kb * 2048;
-        wr[slot][0] = *reinterpret_cast<const W16*>(q + hoff);
-        if constexpr (WK == 1) wr[slot][1] = *reinterpret_cast<const W16*>(q + 1024);
+        wr[slot] = *reinterpret_cast<const W16*>(wsrc + (int64_t)kb * 2048 + hoff);
       };
       const int kb_last = kb_hi - 1;
       // the first kWHead k-blocks of weights go out at once; the rest of the ring waits until the loaders have queued their
@@ -819,10 +802,7 @@ void gemm_kernel(const GemmArgs args) {
       auto read_a = [&](int buf, int stage) {
         const char* st = lds_b + (stage % NST) * STAGE_BYTES + lane * 16;
 #pragma unroll
-        for (int m = 0; m < MF; ++m) {
-          af[buf][m].v[0] = *reinterpret_cast<const V16*>(st + m * 2048 + hoff);
-          if constexpr (WK == 1) af[buf][m].v[1] = *reinterpret_cast<const V16*>(st + m * 2048 + 1024);
-        }
+        for (int m = 0; m < MF; ++m) af[buf][m].v[0] = *reinterpret_cast<const V16*>(st + m * 2048 + hoff);
       };
       asm volatile("s_barrier" ::: "memory");             // stage 0 landed
       read_a(0, 0);
@@ -834,9 +814,8 @@ void gemm_kernel(const GemmArgs args) {
           read_a((i + 1) & 1, i + 1);
         }
         typename M_::WReg wf[1];
-        wf[0].v[0] = wr[i % kWRing][0];
-        if constexpr (WK == 1) { wf[0].v[1] = wr[i % kWRing][1]; M_::template mma<MF, 1>(acc, af[i & 1], wf); }
-        else M_::template mma_half<MF, 1>(acc, af[i & 1], wf);
+        wf[0].v[0] = wr[i % kWRing];
+        M_::template mma_half<MF, 1>(acc, af[i & 1], wf);
         if (i + kWRing < kMaxKb) {                        // refill this register slot kWRing k-blocks ahead: unconditional
           const int kn = kb_lo + i + kWRing;              // (clamped) -- a predicated load would drain the queue
           loadw(i % kWRing, kn < kb_last ? kn : kb_last);
@@ -1006,6 +985,7 @@ void gemm_kernel(const GemmArgs args) {
     // the surplus slots repeat the last piece (same bytes to the same place), so every wave issues exactly PER
     // instructions per stage and the hand-counted vmcnt below is the same constant for all of them.
     static_assert(sizeof(TA) == sizeof(TW), "LDS-staged loop: A and W in the MFMA dtype (fragment order)");
+    static_assert(WK == 1, "LDS-staged loop: every wave multiplies whole k-blocks (no K split inside the workgroup)");
     constexpr int NW = NT / 64;
     constexpr int NBLK = BM / 16 + BN / 16, STAGE_BYTES = NBLK * 2048, NINSTR = 2 * NBLK, PER = (NINSTR + NW - 1) / NW;
     constexpr int NST = STAGES;
@@ -1061,30 +1041,19 @@ void gemm_kernel(const GemmArgs args) {
       using V16 = std::remove_reference_t<decltype(af[0].v[0])>;
       using W16 = std::remove_reference_t<decltype(wf[0].v[0])>;
       static_assert(sizeof(V16) == 16 && sizeof(W16) == 16, "fragment halves are 16 bytes");
-      if constexpr (WK == 1) {
 #pragma unroll
-        for (int m = 0; m < MF; ++m) {
-          const char* q = st + (wm * MF + m) * 2048;
-          af[m].v[0] = *reinterpret_cast<const V16*>(q);
-          af[m].v[1] = *reinterpret_cast<const V16*>(q + 1024);
-        }
-#pragma unroll
-        for (int n = 0; n < NF; ++n) {
-          const char* q = st + (BM / 16 + wn * NF + n) * 2048;
-          wf[n].v[0] = *reinterpret_cast<const W16*>(q);
-          wf[n].v[1] = *reinterpret_cast<const W16*>(q + 1024);
-        }
-        M_::template mma<MF, NF>(acc, af, wf);
-      } else {
-        // WK = 2: the two waves of a pair split the contraction inside the k-block (one 1 KB half each)
-        static_assert(WK <= 2, "LDS-staged loop: K over at most 2 waves");
-        const int hoff = wk * 1024;
-#pragma unroll
-        for (int m = 0; m < MF; ++m) af[m].v[0] = *reinterpret_cast<const V16*>(st + (wm * MF + m) * 2048 + hoff);
-#pragma unroll
-        for (int n = 0; n < NF; ++n) wf[n].v[0] = *reinterpret_cast<const W16*>(st + (BM / 16 + wn * NF + n) * 2048 + hoff);
-        M_::template mma_half<MF, NF>(acc, af, wf);
+      for (int m = 0; m < MF; ++m) {
+        const char* q = st + (wm * MF + m) * 2048;
+        af[m].v[0] = *reinterpret_cast<const V16*>(q);
+        af[m].v[1] = *reinterpret_cast<const V16*>(q + 1024);
       }
+#pragma unroll
+      for (int n = 0; n < NF; ++n) {
+        const char* q = st + (BM / 16 + wn * NF + n) * 2048;
+        wf[n].v[0] = *reinterpret_cast<const W16*>(q);
+        wf[n].v[1] = *reinterpret_cast<const W16*>(q + 1024);
+      }
+      M_::template mma<MF, NF>(acc, af, wf);
       slot = slot + 1 == NST ? 0 : slot + 1;
       fill = fill + 1 == NST ? 0 : fill + 1;
     }
@@ -1732,14 +1701,7 @@ int dispatch_tile(const sp3_gemm_desc& d, const MoreGroups& more, int tile, hipS
     case 1: return launch<TA, TW, LOADER, 2, 2, 2, 2, 1, 2>(d, more, stream);   // 64x64, wave tile 32x32
     case 2: return launch<TA, TW, LOADER, 2, 4, 2, 2, 1, 2>(d, more, stream);   // 64x128, wave tile 32x64
     case 3: return launch<TA, TW, LOADER, 4, 4, 1, 1, 4, 3>(d, more, stream);   // 64x64, K over 4 waves
-    case 4: case 18:                                                       // 32x64 / 16x64, K over 4 waves (bf16 operands)
-      if constexpr (sizeof(TA) == 2 && LOADER == SP3_LOAD_PLAIN) {
-        if (tile == 4) return launch<TA, TW, LOADER, 2, 4, 1, 1, 4, 3>(d, more, stream);
-        return launch<TA, TW, LOADER, 1, 4, 1, 1, 4, 3>(d, more, stream);
-      }
-      sp3_set_error("sp3_gemm: tile %d needs bf16 A and the plain loader", tile);
-      return 1;
-    case 20: case 21: case 22: case 23: case 24: case 25:   // pipelined LDS-staged operands (many-row GEMMs; 24 / 25: the memory read)
+    case 20: case 21: case 22: case 24: case 25:   // pipelined LDS-staged operands (many-row GEMMs; 24 / 25: the memory read)
       if constexpr (sizeof(TA) == sizeof(TW) && LOADER == SP3_LOAD_PLAIN) {
         if (d.a_packed && d.w_packed && !d.A2 && d.K % MM<TA, TW>::KB == 0) {
           switch (tile) {
@@ -1748,27 +1710,17 @@ int dispatch_tile(const sp3_gemm_desc& d, const MoreGroups& more, int tile, hipS
             case 22: return launch<TA, TW, LOADER, 4, 4, 2, 1, 2, 3, -1>(d, more, stream);   // 128x64,  2x1 waves of 64x64 x 2 K halves
             case 24: return launch<TA, TW, LOADER, 4, 2, 1, 1, 2, 4, -1>(d, more, stream);   // 64x32,   1 wave pair, 4 slots (score GEMM of the read)
             case 25: return launch<TA, TW, LOADER, 2, 2, 1, 1, 2, 4, -1>(d, more, stream);   // 32x32,   1 wave pair, 4 slots
-            default: return launch<TA, TW, LOADER, 4, 4, 1, 1, 2, 4, -1>(d, more, stream);   // 64x64,   1 wave pair (2 K halves), 4 slots
           }
         }
       }
       sp3_set_error("sp3_gemm: tile %d (pipelined LDS) needs fragment-order A and W in the MFMA dtype, whole k-blocks, no split A", tile);
       return 1;
-    case 5: case 6: case 7: case 8: case 9: case 10: case 11: case 12: case 13: case 14: case 15: case 16: case 17:     // LDS-staged operands
+    case 5: case 6: case 13:     // LDS-staged operands
       if constexpr (sizeof(TA) == sizeof(TW) && LOADER == SP3_LOAD_PLAIN) {
         if (d.a_packed && d.w_packed && !d.A2 && d.K % MM<TA, TW>::KB == 0) {
-          switch (tile) {
-            case 5: return launch<TA, TW, LOADER, 4, 4, 2, 2, 1, 2, 1>(d, more, stream);    // 128x128, 2x2 waves of 64x64
-            case 6: return launch<TA, TW, LOADER, 4, 2, 2, 2, 1, 2, 1>(d, more, stream);    // 128x64,  2x2 waves of 64x32
-            case 7: return launch<TA, TW, LOADER, 7, 1, 1, 4, 1, 4, 1>(d, more, stream);    // 112x64,  4 waves of 112x16, 4 slots
-            case 8: return launch<TA, TW, LOADER, 13, 1, 1, 4, 1, 3, 1>(d, more, stream);   // 208x64,  4 waves of 208x16, 3 slots
-            case 9: return launch<TA, TW, LOADER, 7, 1, 1, 2, 1, 4, 1>(d, more, stream);    // 112x32,  2 waves of 112x16, 4 slots
-            case 10: return launch<TA, TW, LOADER, 7, 2, 1, 2, 1, 4, 1>(d, more, stream);   // 112x64,  2 waves of 112x32, 4 slots
-            case 11: return launch<TA, TW, LOADER, 7, 1, 1, 4, 2, 4, 1>(d, more, stream);   // 112x64,  4x2 waves (K halves), 4 slots
-            case 12: return launch<TA, TW, LOADER, 13, 1, 1, 4, 2, 3, 1>(d, more, stream);  // 208x64,  4x2 waves (K halves), 3 slots
-            // weight streaming with roles: consumers keep their weights in a register ring, 2 loader waves DMA the activations
-            default: break;
-          }
+          if (tile == 5) return launch<TA, TW, LOADER, 4, 4, 2, 2, 1, 2, 1>(d, more, stream);    // 128x128, 2x2 waves of 64x64
+          if (tile == 6) return launch<TA, TW, LOADER, 4, 2, 2, 2, 1, 2, 1>(d, more, stream);    // 128x64,  2x2 waves of 64x32
+          // tile 13, weight streaming with roles: consumers keep their weights in a register ring, 2 loader waves DMA the activations
           const int nkb_slice = ((d.K / MM<TA, TW>::KB) + d.splitk - 1) / d.splitk;
           if (d.ln_stats && d.ln_nt > 32) {
             sp3_set_error("sp3_gemm: tile %d folds a LayerNorm over at most 1024 columns (ln_C=%d)", tile, d.ln_C);
@@ -1778,13 +1730,8 @@ int dispatch_tile(const sp3_gemm_desc& d, const MoreGroups& more, int tile, hipS
             sp3_set_error("sp3_gemm: tile %d streams at most %d k-blocks per K slice (K=%d, splitk=%d)", tile, kMaxKb, d.K, d.splitk);
             return 1;
           }
-          if constexpr (sizeof(TA) == 2) switch (tile) {      // bf16 only (the fp32 mode is MFMA-bound, not weight-bound)
-            case 13: return launch<TA, TW, LOADER, 7, 1, 1, 4, 2, 4, 2>(d, more, stream);   // 112x64,  4x2 consumer waves + 2 loaders
-            case 14: return launch<TA, TW, LOADER, 7, 1, 1, 4, 1, 4, 2>(d, more, stream);   // 112x64,  4 consumer waves + 2 loaders
-            case 15: return launch<TA, TW, LOADER, 13, 1, 1, 4, 2, 3, 2>(d, more, stream);  // 208x64,  4x2 consumer waves + 2 loaders
-            case 16: return launch<TA, TW, LOADER, 7, 1, 1, 4, 1, 4, 6>(d, more, stream);   // 112x64,  4 consumer waves + 6 loaders
-            case 17: return launch<TA, TW, LOADER, 7, 1, 1, 4, 2, 4, 4>(d, more, stream);   // 112x64,  4x2 consumer waves + 4 loaders
-          }
+          if constexpr (sizeof(TA) == 2)      // bf16 only (the fp32 mode is MFMA-bound, not weight-bound)
+            return launch<TA, TW, LOADER, 7, 1, 1, 4, 2, 4, 2>(d, more, stream);   // 112x64,  4x2 consumer waves + 2 loaders
         }
       }
       sp3_set_error("sp3_gemm: tile %d (LDS-staged) needs fragment-order A and W in the MFMA dtype, whole k-blocks, no split A", tile);
@@ -1846,7 +1793,7 @@ static int gemm_prepare(sp3_gemm_desc& d, int& tile_out) {
     SP3_CHECK(d.sm_stats && d.sm_nt == (d.K + 31) / 32 && d.lda % 4 == 0 && d.lda >= (d.K + 15) / 16 * 16 && d.K % 4 == 0,
               "sp3_gemm: softmax loader needs sm_stats[M][ceil(K/32)][2], K %% 4 == 0 and score rows padded to 16 (lda=%lld K=%d)",
               (long long)d.lda, d.K);
-    SP3_CHECK(d.tile <= 1 || d.tile == 44, "sp3_gemm: the softmax loader runs on the 16x64 tile (tile <= 0), the 32x32 one (tile 1) or the lean instance (44)");
+    SP3_CHECK(d.tile <= 0 || d.tile == 44, "sp3_gemm: the softmax loader runs on the 16x64 tile (tile <= 0) or the lean instance (44)");
   } else if (d.loader == SP3_LOAD_CONV3X3) {
     SP3_CHECK(d.conv_C % 16 == 0, "sp3_gemm: conv Cin=%d must be a multiple of 16", d.conv_C);
     SP3_CHECK(d.K == 9 * d.conv_C, "sp3_gemm: conv K=%d != 9*Cin", d.K);
@@ -1876,7 +1823,6 @@ static int gemm_prepare(sp3_gemm_desc& d, int& tile_out) {
     const long t128 = (long)((d.M + 63) / 64) * ((d.N + 127) / 128) * d.batch;
     const bool lds_ok = d.loader == SP3_LOAD_PLAIN && !d.sm_stats_out && sk == 1 && d.a_packed && d.w_packed && d.a_bf16 && !d.A2 &&
                         d.epi != SP3_EPI_PARTIAL && d.K % 64 == 0;
-    constexpr bool pipe_on = true;
     // (split-K partials too: the PARTIAL epilogue is tile-agnostic; every K slice must hold whole k-blocks)
     const bool pipe_ok = d.loader == SP3_LOAD_PLAIN && !d.sm_stats_out && d.a_packed && d.w_packed && d.a_bf16 && !d.A2 && d.K % 64 == 0 &&
                          (sk == 1 || d.epi == SP3_EPI_PARTIAL);
@@ -1886,7 +1832,7 @@ static int gemm_prepare(sp3_gemm_desc& d, int& tile_out) {
     // many rows (N < 2304: proj, fc2, key MLPs, decoder side GEMMs; split-K partials; very wide score GEMMs of the long-bank
     // read) goes to the pipelined tiles.
     const bool wide_legacy = lds_ok && d.M >= 1024 && d.N >= 2304 && d.N % 128 == 0 && d.N < 16384;
-    if (pipe_ok && pipe_on && d.M >= 512 && d.epi != SP3_EPI_ROPE_VT && !wide_legacy) {
+    if (pipe_ok && d.M >= 512 && d.epi != SP3_EPI_ROPE_VT && !wide_legacy) {
       // the largest pipelined tile that still gives most CUs a workgroup (tools/bench_gemm2.py --big on MI355X,
       // profiles/r03_gemm_manyrow_tile_sweep.txt)
       const long mt256 = (d.M + 255) / 256, mt128 = (d.M + 127) / 128, nt128 = (d.N + 127) / 128, nt64 = (d.N + 63) / 64;
@@ -1917,10 +1863,9 @@ static int gemm_prepare(sp3_gemm_desc& d, int& tile_out) {
       // weight-streaming shapes (M ~ 196): measured on MI355X (tools/bench_gemm.py, packed operands) the 32x32 tile
       // with K split over the 4 waves wins on every hot-path shape: ~3 us fixed cost vs ~5 us for the 64x64 tile
       tile = 0;
-      (void)t64;
     }
   }
-  SP3_CHECK(!d.sm_stats_out || tile <= 3 || tile >= 20, "sp3_gemm: sm_stats_out needs a register-ring tile (0-3) or a pipelined one (20-25)");
+  SP3_CHECK(!d.sm_stats_out || tile <= 3 || tile >= 20, "sp3_gemm: sm_stats_out needs a register-ring tile (0-3) or a pipelined one (20-22, 24, 25)");
   // (only dispatch_tile's f16x3 instances of the register-ring tiles read the planes; anything else would take them for fp32 values)
   SP3_CHECK(d.w_packed != 2 || (d.wdtype == SP3_F32 && d.f32x3 == 4 && d.loader != SP3_LOAD_SOFTMAX && tile >= 0 && tile <= 2),
             "sp3_gemm: w_packed = 2 (fp16 planes) needs fp32 weights, the f16x3 product mode, not the softmax loader, and tile 0..2 (tile %d)", tile);
@@ -1931,11 +1876,7 @@ static int gemm_prepare(sp3_gemm_desc& d, int& tile_out) {
 static int gemm_dispatch(const sp3_gemm_desc& d, const MoreGroups& more, int tile, hipStream_t stream) {
   if (d.loader == SP3_LOAD_SOFTMAX) {
     // 16 x 64 tile, K over the 4 waves: the probabilities of a row are rebuilt by every column tile, so few wide ones
-    // (32 x 32: 16.6 us at 196 x 1764, half of it exponentials)
-    if (d.tile == 1) {
-      if (d.wdtype == SP3_BF16) return launch<float, __bf16, SP3_LOAD_SOFTMAX, 2, 2, 1, 1, 4, 3>(d, more, stream);
-      return launch<float, float, SP3_LOAD_SOFTMAX, 2, 2, 1, 1, 4, 3>(d, more, stream);
-    }
+    // (a 32 x 32 tile took 16.6 us at 196 x 1764, half of it exponentials)
     if (d.wdtype == SP3_BF16) return launch<float, __bf16, SP3_LOAD_SOFTMAX, 1, 4, 1, 1, 4, 3>(d, more, stream);
     return launch<float, float, SP3_LOAD_SOFTMAX, 1, 4, 1, 1, 4, 3>(d, more, stream);
   }

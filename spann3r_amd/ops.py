@@ -101,10 +101,8 @@ def set_profiler(p):
     _prof = p
 
 
-_TILE_NAMES = {0: "32x32xk4", 1: "64x64", 2: "64x128", 3: "64x64xk4", 4: "32x64xk4", 18: "16x64xk4", 5: "128x128lds", 6: "128x64lds", 7: "112x64lds",
-               8: "208x64lds", 9: "112x32lds", 10: "112x64lds2w", 11: "112x64lds8w", 12: "208x64lds8w", 13: "112x64wreg8",
-               14: "112x64wreg4", 15: "208x64wreg8", 16: "112x64wreg4l6", 17: "112x64wreg8l4",
-               20: "256x128pipe", 21: "128x128pipe", 22: "128x64pipe", 23: "64x64pipe", 24: "64x32pipe", 25: "32x32pipe",
+_TILE_NAMES = {0: "32x32xk4", 1: "64x64", 2: "64x128", 3: "64x64xk4", 5: "128x128lds", 6: "128x64lds", 13: "112x64wreg8",
+               20: "256x128pipe", 21: "128x128pipe", 22: "128x64pipe", 24: "64x32pipe", 25: "32x32pipe",
                # lean small-M instances (csrc/gemm_sm.hip): epilogue, K, tile, waves over K
                30: "lean-rope-k1024-48x64xk8", 31: "lean-rope-k768-32x32xk4", 32: "lean-packed-k1024-64x64xk8", 33: "lean-packed-k768-32x32xk4",
                34: "lean-stream-k1024-32x32xk8", 35: "lean-stream-k4096-32x32xk8r4", 36: "lean-stream-k768-48x32xk6",
@@ -224,8 +222,8 @@ def _gemm_launch(d, what, loader_name):
     L.check(L.load().sp3_gemm(C.byref(d), L.stream_ptr()), what)
     flops, nbytes = _gemm_cost(d)
     tile = d.tile if d.tile >= 0 else L.load().sp3_gemm_plan(C.byref(d))
-    # (the softmax loader's general instances are tiles of their own: 16x64 unless tile 1 is asked for)
-    tname = ("32x32xk4" if tile == 1 else "16x64xk4") if (d.loader == L.LOAD_SOFTMAX and tile < 30) else _TILE_NAMES[tile]
+    # (the softmax loader's general instance is a tile of its own: 16x64)
+    tname = "16x64xk4" if (d.loader == L.LOAD_SOFTMAX and tile < 30) else _TILE_NAMES[tile]
     key = "gemm<A%s,W%s,%s,%s>" % ("bf16" if d.a_bf16 else "f32", "f32" if d.wdtype == F32 else "bf16", loader_name, tname)
     if PROF_SHAPES:                                 # (tools: one profile line per GEMM shape)
         key += " %dx%dx%d x%d%s" % (d.M, d.N, d.K, max(d.batch, 1), " splitA" if d.A2 else "")

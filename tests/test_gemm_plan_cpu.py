@@ -7,6 +7,7 @@ operands, the whole-sequence encoder, the training step in bf16 and fp32, with t
 the launch ran on at that commit.  Pointers are kept as set / not set, strides and byte offsets are dropped (no rule reads them).
 A rule change shows up as a diff of this table."""
 import ctypes as C
+import itertools
 import json
 import os
 import subprocess
@@ -115,3 +116,46 @@ def test_fp16_plane_weights_are_checked():
     d = _desc(lib, ok)
     d.tile = 3
     assert l.sp3_gemm(C.byref(d), None) != 0 and b"w_packed = 2" in l.sp3_last_error()
+
+
+GENERAL_TILES = {0, 1, 2, 3, 5, 6, 13, 20, 21, 22, 24, 25}       # csrc/gemm.hip dispatch_tile: every general tile there is
+PLANNED_TILES = {0, 1, 2, 5, 6, 13, 20, 21, 22, 24}              # ... and the ones gemm_prepare can answer (3 and 25: by number only)
+REMOVED_TILES = (4, 18, 7, 8, 9, 10, 11, 12, 14, 15, 16, 17, 23)
+
+
+def test_removed_tile_numbers_are_refused():
+    """a tile number without a kernel instance answers like any unknown one, before anything is launched (null stream, no GPU)"""
+    from spann3r_amd import lib
+    l = lib.load()
+    for fields in (dict(A=1, W=1, C=1, M=196, N=768, K=768, lda=768, ldc=768, alpha=1.0), _packed_bf16(lib, 1024, 768, 768)):
+        for n in REMOVED_TILES + (19, 26, 29):
+            d = _desc(lib, fields)
+            d.tile = n
+            assert l.sp3_gemm(C.byref(d), None) != 0, n
+            assert b"bad tile %d" % n in l.sp3_last_error(), (n, l.sp3_last_error())
+
+
+def test_planner_answers_existing_tiles_only():
+    """gemm_prepare cannot choose a tile that dispatch_tile does not have: every census row and a grid of synthetic descriptors
+    (fp32 and bf16, packed and row-major operands, plain and conv loader, split-K 1 and 8)"""
+    from spann3r_amd import lib
+    assert PLANNED_TILES <= GENERAL_TILES and not GENERAL_TILES & set(REMOVED_TILES)
+    answers = []
+    for r in map(json.loads, open(TABLE)):
+        answers += [_plan(lib, [f])[0] for f in r["descs"]]
+    assert len(answers) >= 605 and min(answers) >= 0
+    for M, N, K in itertools.product((7, 196, 784, 1960, 4096, 16384), (96, 768, 2304, 4096, 16384), (64, 768, 4096)):
+        for bf16, packed, conv, sk in itertools.product((0, 1), (0, 1), (0, 1), (1, 8)):
+            f = dict(A=1, W=1, C=1, bias=1, M=M, N=N, K=K, lda=K, ldc=N, alpha=1.0, splitk=sk)
+            if bf16:
+                f.update(wdtype=lib.BF16, a_bf16=1)
+            if packed:
+                f.update(a_packed=1, w_packed=1)
+            if sk > 1:
+                f.update(epi=lib.EPI_PARTIAL)
+            if conv:                                    # K = 9 Cin, M = one OH x OW map per 49 rows (invalid combinations answer -1)
+                f.update(loader=lib.LOAD_CONV3X3, conv_C=K // 9, conv_H=7, conv_W=7, conv_OH=7, conv_OW=7, conv_stride=1)
+            answers.append(_plan(lib, [f])[0])
+    got = {t for t in answers if 0 <= t < 30}
+    assert sum(1 for t in answers if t >= 0) > 700 and got <= PLANNED_TILES, sorted(got - PLANNED_TILES)
+    assert got >= {0, 1, 2, 5, 6, 20, 22, 24}, sorted(got)       # (the sweep does reach the rules' arms)

@@ -57,16 +57,16 @@ def test_gemm_plain(wdt, M, N, K, tile, packed):
     assert rel_err(out.cpu(), ref) < TOL[wdt], (M, N, K, tile)
 
 
-LDS_TILES = [5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 20, 21, 22, 23]    # 13-15: bf16 only, at most 64 k-blocks per K slice; 20-23: pipelined
+LDS_TILES = [5, 6, 13, 20, 21, 22, 24, 25]    # 13: bf16 only, at most 64 k-blocks per K slice; 20-25: pipelined
 
 
 @pytest.mark.parametrize("wdt", [torch.bfloat16, torch.float32])
 @pytest.mark.parametrize("M,N,K", [(1960, 3072, 1024), (300, 256, 192), (129, 384, 64), (1100, 1024, 4096), (196, 768, 768),
                                    (196, 2304, 768), (196, 1024, 4096), (98, 96, 128)])
 def test_gemm_lds_staged_tile(M, N, K, wdt):
-    """tiles 5-12: both operands staged through LDS by global_load_lds (fragment-order A and W in the MFMA dtype): the
-    128-row tiles of the whole-sequence encoder and the 112- / 208-row weight-streaming tiles (2-4 ring slots, pieces dealt
-    unevenly over the waves, K halves over wave pairs); ragged M / N tiles, K down to one k-block; epilogues: bias + GELU
+    """tiles 5 / 6, 13 and 20-25: both operands staged through LDS by global_load_lds (fragment-order A and W in the MFMA dtype):
+    the 128-row tiles of the whole-sequence encoder, the 112-row weight-streaming role tile and the pipelined tiles (2-4 ring
+    slots, K halves over wave pairs); ragged M / N tiles, K down to one k-block; epilogues: bias + GELU
     -> packed, residual + row statistics + packed copy, folded LayerNorm, split-K partials."""
     ops = _ops()
     KB = 64 if wdt == torch.bfloat16 else 32
@@ -92,13 +92,13 @@ def test_gemm_lds_staged_tile(M, N, K, wdt):
         # the same launch must agree with the register-ring tiles to fp32 summation order
         assert rel_err(out.cpu(), out1.cpu()) < 1e-5, tile
     nkb = K // KB
-    for tile, S in ((7, 2), (8, 3), (11, 4), (13, 2), (14, 3), (20, 2), (21, 3), (22, 5), (23, 4)):
-        if nkb >= S and tile in tiles:                                                     # split-K partials of the streaming tiles
+    for tile, S in ((5, 2), (6, 3), (13, 2), (20, 2), (21, 3), (22, 5), (24, 4), (25, 3)):
+        if nkb >= S and tile in tiles:                                                     # split-K partials
             part = torch.full((S, M, N), float("nan"), device=DEV)
             ops.gemm(Ap, Wp, part, M=M, N=N, K=K, lda=K, ldc=N, splitk=S, tile=tile)
             assert rel_err(part.sum(0).cpu(), ref) < tol, (tile, S)
     if N % 32 == 0:
-        for tile in (5, 7, 8, 11, 13, 14, 20, 21, 22, 23):
+        for tile in (5, 6, 13, 20, 21, 22, 24, 25):
             if tile not in tiles:
                 continue
             # producer epilogue: bias + residual, row statistics, packed copy
@@ -126,7 +126,7 @@ def test_gemm_lds_staged_tile(M, N, K, wdt):
                 assert rel_err(h.to_dense().float().cpu(), F.gelu(y)) < (8e-3 if wdt == torch.bfloat16 else 1e-4), tile
 
 
-@pytest.mark.parametrize("tile", [20, 21, 22, 23])
+@pytest.mark.parametrize("tile", [20, 21, 22, 24, 25])
 def test_gemm_pipelined_tiles_long_k_and_groups(tile):
     """the pipelined LDS tiles on what the model throws at them: a long contraction with an odd number of k-blocks (ring
     wrap-around, both unroll parities), a grouped launch (two problems, per-problem bias) and the automatic tile choice;
@@ -199,7 +199,7 @@ def test_gemm_bf16_activations(M, N, K, tile):
     assert rel_err(out32.cpu(), Ab.double() @ bf(W).double().T) < TOL[torch.bfloat16]
 
 
-@pytest.mark.parametrize("M,N,K,S,tile", [(300, 384, 8 * 192, 8, -1), (520, 512, 16 * 256, 16, -1), (520, 512, 16 * 256, 16, 23), (130, 640, 16 * 128, 16, 20)])
+@pytest.mark.parametrize("M,N,K,S,tile", [(300, 384, 8 * 192, 8, -1), (520, 512, 16 * 256, 16, -1), (520, 512, 16 * 256, 16, 24), (130, 640, 16 * 128, 16, 20)])
 def test_splitk_slices_on_xcds(M, N, K, S, tile):
     """Split-K over a multiple of 8 slices: the launch hands whole K slices to the XCDs (gemm_kernel's tile map).  Every partial is
     checked against ITS slice of the product, so a slice that lands in the wrong partial (or is computed twice) shows."""

@@ -61,13 +61,13 @@ if args.big:
     shapes += [("enc16 qkv", 16384, 3072, 1024, 1), ("enc16 fc2", 16384, 1024, 4096, 1), ("read S", 1024, 50176, 1024, 1),
                ("read PV", 1024, 1024, 50176, 1), ("train fc1", 784, 4096, 1024, 1), ("train dec", 784, 768, 3072, 2),
                ("sq4k", 4096, 4096, 4096, 1), ("sq8k", 8192, 4096, 4096, 1), ("enc16 fc1", 16384, 4096, 1024, 1)]
-    tiles = [1, 5, 6, 20, 21, 22, 23]
+    tiles = [1, 5, 6, 20, 21, 22, 24]
 else:
     M = args.M
     shapes = [("dec qkv", M, 2304, 768, 2), ("dec proj", M, 768, 768, 2), ("dec ckv", M, 1536, 768, 2), ("dec fc1", M, 3072, 768, 2),
               ("dec fc2", M, 768, 3072, 2), ("val qkv", M, 3072, 1024, 1), ("val proj", M, 1024, 1024, 1), ("val fc1", M, 4096, 1024, 1),
               ("val fc2", M, 1024, 4096, 1), ("key 0", M, 1792, 1792, 2), ("key 2", M, 1024, 1792, 2)]
-    tiles = [0, 13, 14, 16, 17]
+    tiles = [0, 13]
 
 if args.train:
     shapes = []
@@ -75,7 +75,7 @@ if args.train:
         for nm, N, K in (("proj", C, C), ("qkv", 3 * C, C), ("fc1", Hd, C), ("fc2", C, Hd)):
             shapes.append(("%s %s" % (tag, nm), 784, N, K, 1))            # forward; dX is the same launch with N and K swapped
             shapes.append(("%s %s dW" % (tag, nm), N, K, 832, 1))         # dW = dY^T . X, contraction over the 784 rows (padded to 64)
-    tiles = [0, 1, 21, 22, 23, 24, 25]
+    tiles = [0, 1, 21, 22, 24, 25]
 if args.ksweep:
     shapes = [("k%d" % K, 1960, 4096, K, 1) for K in (128, 512, 1024, 2048, 4096)] + [("n1k k%d" % K, 1960, 1024, K, 1) for K in (128, 1024, 4096)]
     tiles = [5, 20, 21, 22]
@@ -102,8 +102,8 @@ for name, M, N, K, G in shapes:
     ACT = ops.ACT_GELU if (("fc1" in name or name == "key 0") and not args.train) else ops.ACT_NONE
     part = torch.empty(8 * G * M * N, device=dev)
     for tile in tiles:
-        BN = {0: 32, 9: 32, 5: 128, 20: 128, 21: 128, 2: 128, 24: 32, 25: 32}.get(tile, 64)
-        BM = {0: 32, 4: 32, 18: 16, 20: 256, 21: 128, 22: 128, 23: 64, 24: 64, 25: 32, 8: 208, 12: 208, 15: 208, 5: 128, 6: 128, 1: 64, 2: 64}.get(tile, 112)
+        BN = {0: 32, 5: 128, 20: 128, 21: 128, 2: 128, 24: 32, 25: 32}.get(tile, 64)
+        BM = {0: 32, 20: 256, 21: 128, 22: 128, 24: 64, 25: 32, 5: 128, 6: 128, 1: 64, 2: 64}.get(tile, 112)
         wgs = ((M + BM - 1) // BM) * ((N + BN - 1) // BN) * G
         sks = [0]
         if not args.big and tile != 0 and G == 1:

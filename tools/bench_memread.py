@@ -42,8 +42,8 @@ def main():
     steps = {
         "S gemm": lambda b: ops.gemm(qp, ops.PackedWeight.wrap(b[0].data, M, C), S, M=P, N=M, K=C, lda=C, ldc=cap, alpha=1 / 32., bias=b_bank, ln=ln),
         "S gemm + stats": lambda b: ops.gemm(qp, ops.PackedWeight.wrap(b[0].data, M, C), S, M=P, N=M, K=C, lda=C, ldc=cap, alpha=1 / 32., bias=b_bank, ln=ln, sm_stats_out=st),
-        **{"S gemm + stats, tile %d" % t: (lambda b, t=t: ops.gemm(qp, ops.PackedWeight.wrap(b[0].data, M, C), S, M=P, N=M, K=C, lda=C, ldc=cap, alpha=1 / 32., bias=b_bank, ln=ln, sm_stats_out=st, tile=t)) for t in (22, 23, 24, 25)},
-        **{"PV gemm (packed P), tile %d" % t: (lambda b, t=t: ops.gemm(ops.PackedAct(P, Kp, wdt, dev, data=pk), ops.PackedWeight.wrap(b[1].data, C, cap), out, M=P, N=C, K=Kp, lda=Kp, ldc=C, ldw=cap, res1=q, ldr1=C, tile=t)) for t in (23, 24, 25)},
+        **{"S gemm + stats, tile %d" % t: (lambda b, t=t: ops.gemm(qp, ops.PackedWeight.wrap(b[0].data, M, C), S, M=P, N=M, K=C, lda=C, ldc=cap, alpha=1 / 32., bias=b_bank, ln=ln, sm_stats_out=st, tile=t)) for t in (22, 24, 25)},
+        **{"PV gemm (packed P), tile %d" % t: (lambda b, t=t: ops.gemm(ops.PackedAct(P, Kp, wdt, dev, data=pk), ops.PackedWeight.wrap(b[1].data, C, cap), out, M=P, N=C, K=Kp, lda=Kp, ldc=C, ldw=cap, res1=q, ldr1=C, tile=t)) for t in (24, 25)},
         "softmax_pack (2 launches)": lambda b: ops.softmax_pack(S, pk, rowstat, ld=cap, rows=P, M=M, thresh=5e-4, batch=1, strideS=P * cap, stride_packed=pk.numel()),
         "softmax_thresh": lambda b: ops.softmax_thresh(S, None, ld=cap, rows=P, M=M, Mpad=M, thresh=5e-4, batch=1, strideS=P * cap, packed=pk, stride_packed=pk.numel()),
         "PV gemm (packed P)": lambda b: ops.gemm(ops.PackedAct(P, Kp, wdt, dev, data=pk), ops.PackedWeight.wrap(b[1].data, C, cap), out, M=P, N=C, K=Kp, lda=Kp, ldc=C, ldw=cap, res1=q, ldr1=C),
@@ -51,7 +51,6 @@ def main():
         "PV gemm (packed P, split-K 16 partials)": lambda b: ops.gemm(ops.PackedAct(P, Kp, wdt, dev, data=pk), ops.PackedWeight.wrap(b[1].data, C, cap), part, M=P, N=C, K=Kp, lda=Kp, ldc=C, ldw=cap, splitk=16),
         "reduce (16 partials + q)": lambda b: ops.reduce_ln(part, 16, P, C, res=q, ldres=C, x_out=out, ldx=C),
         "PV gemm (softmax loader)": lambda b: ops.gemm(S, ops.PackedWeight.wrap(b[1].data, C, cap), out, M=P, N=C, K=M, lda=cap, ldc=C, ldw=cap, res1=q, ldr1=C, softmax=(st, 5e-4, zk)),
-        "PV gemm (softmax loader, 32x32)": lambda b: ops.gemm(S, ops.PackedWeight.wrap(b[1].data, C, cap), out, M=P, N=C, K=M, lda=cap, ldc=C, ldw=cap, res1=q, ldr1=C, softmax=(st, 5e-4, zk), tile=1),
         "colsum_softmax": lambda b: ops.colsum_softmax(S, cap, P, M, zk, 5e-4, attn),
     }
     if P > 256:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Timeline of the first workgroups of a role-loop GEMM launch (tiles 13-15; sp3_gemm_desc.trace): shader-clock stamps at
+"""Timeline of the first workgroups of a role-loop GEMM launch (tile 13; sp3_gemm_desc.trace): shader-clock stamps at
 entry, per 4 k-blocks for the loader and for consumer wave 0, loop end, epilogue end.  Weights are HBM-cold (a different
 copy per launch).   python tools/trace_gemm.py [tile]"""
 import os
