@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256) void conv3x3_tile_kernel(const ConvArgs a) {
 namespace wide {
 constexpr int TH = 8, TW = 16, HW = TW + 2, HP = (TH + 2) * HW;   // 180 halo pixels
 constexpr int CH = 128, PS = CH * 2 + 16;                          // channels per staged chunk, halo pixel stride (bytes)
-constexpr int MF = 8, DEPTH = 3;
+constexpr int MF = 8;
 constexpr int HALO_BYTES = HP * PS;
 template <int NF> constexpr int lds_bytes() {                     // halo chunk, re-used by the 4 partial tiles of one 64-pixel pass
   return HALO_BYTES > 4 * 64 * (16 * NF + 4) * 4 ? HALO_BYTES : 4 * 64 * (16 * NF + 4) * 4;
@@ -261,6 +261,11 @@ template <int NF> constexpr int lds_bytes() {                     // halo chunk,
 template <typename TIN, int NF = 4, int ABL = 0>
 __global__ __launch_bounds__(256, 2) void conv3x3_wide_kernel(const ConvArgs a) {
   constexpr int BN = 16 * NF, SLAB_LD = BN + 4;
+  // W units in flight per wave.  NF = 2 has the registers for a whole chunk (9 units x 2 fragments x 4): the queue slot is the tap, and
+  // the refill behind tap t requests tap t of the NEXT chunk, which then flies under this chunk's MFMAs, the barrier pair and the next
+  // halo batch -- a workgroup meets cold weights once, in the prologue, not once per three taps.  NF = 4 (256 registers as it is) keeps 3.
+  constexpr int DEPTH = NF == 2 ? 9 : 3;
+  static_assert(9 % DEPTH == 0, "the queue slot of a tap must not depend on the chunk");
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, r = lane & 15;
   const int Cin = a.Cin;
@@ -282,13 +287,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wide_kernel(const ConvArgs a) 
       const_cast<char*>(reinterpret_cast<const char*>(a.w)) + (int64_t)(n0 >> 4) * panel_bytes, 0, (int)(NF * panel_bytes), 0x00020000);
   const uint32_t wlane = (uint32_t)lane * 16 + (uint32_t)(wave & 1) * 1024;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);         // (uniform by construction; lets the unit offset live in SGPRs)
-  auto w_off = [&](int seq) -> uint32_t {                          // byte offset of a unit inside a panel
-    seq = seq < total ? seq : total - 1;                           // the tail re-loads the last unit instead of branching
-    const int c = seq / 9, tap = seq - 9 * c;
+  auto w_off = [&](int c, int tap) -> uint32_t {                   // byte offset of a unit inside a panel
     return (uint32_t)((tap * upt + 4 * c + wave_u) >> 1) * 2048;
   };
-  auto w_load = [&](int seq, bf16x8* dst) {
-    const uint32_t o = w_off(seq);
+  auto w_off_seq = [&](int seq) -> uint32_t {                      // the 3-deep queue runs on across chunk boundaries:
+    seq = seq < total ? seq : total - 1;                           // its tail re-loads the last unit instead of branching
+    const int c = seq / 9;
+    return w_off(c, seq - 9 * c);
+  };
+  auto w_load = [&](uint32_t o, bf16x8* dst) {
 #pragma unroll
     for (int n = 0; n < NF; ++n) {
       const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wlane, o + n * panel_bytes, 0);
@@ -297,7 +304,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wide_kernel(const ConvArgs a) 
   };
   bf16x8 wq[DEPTH][NF];
 #pragma unroll
-  for (int s = 0; s < DEPTH; ++s) w_load(s, wq[s]);
+  for (int s = 0; s < DEPTH; ++s) w_load(DEPTH == 9 ? w_off(0, s) : w_off_seq(s), wq[s]);
 
   f32x4 acc[MF][NF];
 #pragma unroll
@@ -389,8 +396,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wide_kernel(const ConvArgs a) 
         if constexpr (!(ABL & 2))
           if (tap < 8) af[m] = ld_frag_lds(abase + ((m + nky) * HW + nkx) * PS);
       }
-      // refill this queue slot with the unit DEPTH ahead (9 % DEPTH == 0: the slot of a tap is the same in every chunk)
-      if constexpr (!(ABL & 1)) w_load(9 * c + tap + DEPTH, wq[s]);
+      // refill this queue slot with the unit DEPTH ahead (9 % DEPTH == 0: the slot of a tap is the same in every chunk); the
+      // whole-chunk queue has nothing to fetch behind the last chunk (a wave-uniform branch, not nine clamped re-loads)
+      if constexpr (!(ABL & 1)) {
+        if constexpr (DEPTH == 9) { if (c + 1 < nchunk) w_load(w_off(c + 1, tap), wq[s]); }
+        else w_load(w_off_seq(9 * c + tap + DEPTH), wq[s]);
+      }
     }
   }
 

@@ -1485,8 +1485,11 @@ __global__ __launch_bounds__(64 * 12) void conv_level_kernel(const ConvLevelArgs
   const ConvSmArgs q = a.p[p];
   const int local = w - a.start[p], j = local >> 3;
   if (a.tile[p] == 40) {
+    // ring: the deepest that keeps this kernel at 168 registers without scratch (bf16: 7 spills 20 bytes, fp32: 5 spills 76) -- at
+    // K = 6912 a wave walks 9 k-blocks, i.e. 2 cold round trips (fp32: 3) instead of 3
+    constexpr int R40 = sizeof(TM) == 2 ? 6 : 4;
     const int mt = (q.M + 15) / 16;
-    conv_sm_body<TM, 1, 1, 12, 3>(q, j % mt, (j / mt) * 8 + (local & 7), smem);
+    conv_sm_body<TM, 1, 1, 12, R40>(q, j % mt, (j / mt) * 8 + (local & 7), smem);
   } else if constexpr (sizeof(TM) == 2) {       // (fp32 maps: the 32x32 body needs 240 registers, 12 waves leave 168 -- it stays in launches of its own)
     const int mt = (q.M + 31) / 32;
     conv_sm_body<TM, 2, 2, 8, 3>(q, j % mt, (j / mt) * 8 + (local & 7), smem);
@@ -1541,7 +1544,9 @@ int conv_sm_dispatch(const sp3_gemm_desc& d, int tile, hipStream_t stream) {
   const ConvSmArgs a = conv_sm_args(d);
   if (d.a_bf16) {
     if (tile == 40) return conv_sm_launch<__bf16, 1, 1, 12, 3>(a, stream);
-    return conv_sm_launch<__bf16, 2, 2, 8, 3>(a, stream);
+    // a single 32x32 launch has 8 waves, i.e. 256 registers: a ring of 5 (238, no scratch) holds all the k-blocks a wave walks at
+    // K = 2304 -- one cold round trip instead of two.  (fp32 maps: 5 spills 188 registers, the ring stays at 3)
+    return conv_sm_launch<__bf16, 2, 2, 8, 5>(a, stream);
   }
   if (tile == 40) return conv_sm_launch<float, 1, 1, 12, 3>(a, stream);
   return conv_sm_launch<float, 2, 2, 8, 3>(a, stream);
