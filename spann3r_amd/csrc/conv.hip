@@ -463,26 +463,29 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wide_kernel(const ConvArgs a) 
 }  // namespace
 
 extern "C" int sp3_conv3x3_tile(const void* x, int in_bf16, const void* w_packed, const float* bias, const float* res1,
-                                const float* res2, void* out, int out_bf16, int B, int H, int W, int Cin, int Cout,
-                                int relu_in, int act, void* stream) {
+                                const float* res2, void* out, int out_bf16, int res_bf16, int tile_px, int B, int H, int W,
+                                int Cin, int Cout, int relu_in, int act, void* stream) {
   SP3_CHECK(x && w_packed && out, "sp3_conv3x3_tile: null pointer");
   SP3_CHECK(B > 0 && H > 0 && W > 0, "sp3_conv3x3_tile: bad shape");
   SP3_CHECK(Cin % 64 == 0 && Cin >= 64 && Cout % 64 == 0 && Cout >= 64, "sp3_conv3x3_tile: Cin=%d / Cout=%d must be multiples of 64", Cin, Cout);
   SP3_CHECK(act == SP3_ACT_NONE || act == SP3_ACT_RELU, "sp3_conv3x3_tile: act %d", act);
+  SP3_CHECK(out_bf16 == 0 || out_bf16 == 1, "sp3_conv3x3_tile: out_bf16 %d is not 0 or 1", out_bf16);
+  SP3_CHECK(res_bf16 == 0 || res_bf16 == 1, "sp3_conv3x3_tile: res_bf16 %d is not 0 or 1", res_bf16);
+  SP3_CHECK(tile_px >= 0 && tile_px <= 3, "sp3_conv3x3_tile: tile_px %d is not 0..3", tile_px);
   auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   SP3_CHECK(al16(x) && al16(w_packed) && al16(bias) && al16(res1) && al16(res2) && al16(out), "sp3_conv3x3_tile: 16-byte alignment");
   ConvArgs a;
   a.x = x; a.w = reinterpret_cast<const __bf16*>(w_packed); a.bias = bias; a.res1 = res1; a.res2 = res2; a.out = out;
   a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-  a.relu_in = relu_in; a.act = act; a.out_bf16 = out_bf16 & 3;
+  a.relu_in = relu_in; a.act = act; a.out_bf16 = out_bf16 | (res_bf16 << 1);      // (ConvArgs: bit 0 = bf16 output, bit 1 = bf16 residual maps)
   a.xcd_nb = 0;
   constexpr bool xcd_on = true;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   {
-    // tile choice (out_bf16 bits 2-3: 0 = by size, 1 = 8 x 8 pixels, 2 = 8 x 16 pixels x 64 channels, 3 = 8 x 16 pixels x 32 channels): the
+    // tile choice (tile_px: 0 = by size, 1 = 8 x 8 pixels, 2 = 8 x 16 pixels x 64 channels, 3 = 8 x 16 pixels x 32 channels): the
     // wide tile halves the W stream per flop and wins once its own grid covers most of the 256 CUs (profiles/r04_conv_tile_sweep.txt);
     // when the 64-channel grid is too small for that but the 32-channel one is not, the narrow-N instance takes over
-    const int want = (out_bf16 >> 2) & 3;
+    const int want = tile_px;
     const int wtx = (W + wide::TW - 1) / wide::TW, wty = (H + wide::TH - 1) / wide::TH;
     const int64_t wgs = (int64_t)wtx * wty * B * (Cout / 64);
     const bool can = Cin % wide::CH == 0;

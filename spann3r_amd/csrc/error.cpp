@@ -14,4 +14,4 @@ void sp3_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* sp3_last_error(void) { return g_err; }
-extern "C" int sp3_version(void) { return 1; }
+extern "C" int sp3_version(void) { return 2; }

@@ -499,6 +499,44 @@ def reduce_ln(partial, splits, rows, C_, *, bias=None, res=None, ldres=0, x_out=
            lambda: L.check(L.load().sp3_reduce_ln(C.byref(d), L.stream_ptr()), "sp3_reduce_ln"))
 
 
+_TILE_PX = {None: 0, "8x8": 1, "8x16": 2, "8x16n32": 3}      # sp3_conv3x3_tile's tile_px argument
+
+
+def _conv_desc(Wp, xdt, odt, rdt, *, B, H, W_, Cin, Cout, stride, act, relu_in, res2_up):
+    """The implicit-GEMM fields of a 3x3 convolution (padding 1) on [B,H,W_,Cin] -> [B,OH,OW,Cout], filled here and nowhere else.
+    xdt / odt / rdt: dtypes of the map, the output and the residual maps; the operand pointers (A, C, bias, res1, res2) are the caller's."""
+    bf = torch.bfloat16
+    OH, OW = (H - 1) // stride + 1, (W_ - 1) // stride + 1
+    d = GemmDesc()
+    d.a_bf16, d.out_bf16, d.res_bf16 = int(xdt == bf), int(odt == bf), int(rdt == bf)
+    _w(d, Wp)
+    d.M, d.N, d.K, d.batch = B * OH * OW, Cout, 9 * Cin, 1
+    d.lda, d.ldc, d.ldr1, d.ldr2 = Cin, Cout, Cout, Cout
+    d.alpha, d.act, d.relu_in = 1.0, act, int(relu_in)
+    d.loader, d.epi, d.tile = L.LOAD_CONV3X3, L.EPI_PLAIN, -1
+    d.conv_H, d.conv_W, d.conv_C, d.conv_OH, d.conv_OW, d.conv_stride = H, W_, Cin, OH, OW, stride
+    if res2_up is not None:
+        d.res2_up_H, d.res2_up_W = res2_up
+    return d
+
+
+def _conv_route(d, Wp, tile=-1, force_tile_kernel=False):
+    """The host's one convolution rule: which kernel family serves the descriptor d of _conv_desc.
+    "tile": sp3_conv3x3_tile (bf16 packed weights, stride 1, 64-channel multiples, >= 2048 pixels: input halo tile staged once, the
+    9 taps read it from LDS); "lean": a small-map instance of sp3_gemm (the library's plan answers >= 30: one launch, K split inside
+    the workgroup -- no split-K workspace, no reduce launch); "general": sp3_gemm's general tiles, with or without split-K."""
+    free = tile < 0 and isinstance(Wp, PackedWeight)
+    if (free and Wp.dtype == torch.bfloat16 and d.conv_stride == 1 and d.conv_C % 64 == 0 and d.N % 64 == 0 and d.conv_C <= 768
+            and (force_tile_kernel or d.M >= 2048)):
+        return "tile"
+    if free:
+        p = GemmDesc.from_buffer_copy(d)            # planning reads no pointer values, but refuses a null A or C
+        p.A, p.C = p.A or 4096, p.C or 4096
+        if L.load().sp3_gemm_plan(C.byref(p)) >= 30:
+            return "lean"
+    return "general"
+
+
 def conv3x3(x, Wp, out, *, B, H, W_, Cin, Cout, stride=1, bias=None, res1=None, res2=None, act=ACT_NONE,
             relu_in=False, tile=-1, force_tile_kernel=False, splitk_ws=None, tile_px=None, res2_up=None):
     """3x3 Conv2d, padding 1, on an NHWC fp32 map [B,H,W,Cin] -> [B,OH,OW,Cout] (implicit GEMM).
@@ -507,68 +545,44 @@ def conv3x3(x, Wp, out, *, B, H, W_, Cin, Cout, stride=1, bias=None, res1=None, 
     (lean small-map kernels only; conv3x3_takes_res2_up tells).
     tile_px (LDS-tiled kernel only; tests and tools/bench_conv_tile.py): None = the library's size rule, "8x8" | "8x16" | "8x16n32" = that
     workgroup tile of sp3_conv3x3_tile (pixels, n32 = 32 instead of 64 output channels)."""
-    OH, OW = (H - 1) // stride + 1, (W_ - 1) // stride + 1
-    if (tile < 0 and stride == 1 and isinstance(Wp, PackedWeight) and Wp.dtype == torch.bfloat16
-            and Cin % 64 == 0 and Cout % 64 == 0 and Cin <= 768 and (force_tile_kernel or B * H * W_ >= 2048)):
-        # bf16 weights, stride 1: the LDS-tiled kernel (input halo tile staged once, 9 taps read it from LDS)
+    _act(x, "x")
+    rbf = [t.dtype == torch.bfloat16 for t in (res1, res2) if t is not None]
+    mixed = bool(rbf) and any(rbf) != all(rbf)
+    d = _conv_desc(Wp, x.dtype, out.dtype, torch.bfloat16 if any(rbf) else torch.float32, B=B, H=H, W_=W_, Cin=Cin, Cout=Cout,
+                   stride=stride, act=act, relu_in=relu_in, res2_up=res2_up)
+    d.A, d.C, d.bias, d.res1, d.res2 = x.data_ptr(), out.data_ptr(), L.ptr(bias), L.ptr(res1), L.ptr(res2)
+    M = d.M
+    route = _conv_route(d, Wp, tile, force_tile_kernel)
+    if route == "tile":
         if res2_up is not None:
             raise ValueError("conv3x3: a half-resolution res2 is read by the lean small-map kernels only (B*H*W=%d)" % (B * H * W_))
-        _act(x, "x")
-        rbf = [t.dtype == torch.bfloat16 for t in (res1, res2) if t is not None]
-        if rbf and (any(rbf) != all(rbf) or (any(rbf) and out.dtype != torch.bfloat16)):
+        if mixed or (any(rbf) and out.dtype != torch.bfloat16):
             raise TypeError("conv3x3: residual maps must share one dtype (bf16 only next to a bf16 output)")
-        oflag = int(out.dtype == torch.bfloat16) | (2 if any(rbf) else 0) | ({None: 0, "8x8": 1, "8x16": 2, "8x16n32": 3}[tile_px] << 2)
         _timed("conv3x3_tile", 2.0 * B * H * W_ * Cout * 9 * Cin,
                B * H * W_ * (x.element_size() * Cin + out.element_size() * Cout) + 2.0 * 9 * Cin * Cout,
                lambda: L.check(L.load().sp3_conv3x3_tile(
-                   x.data_ptr(), int(x.dtype == torch.bfloat16), Wp.data_ptr(), L.ptr(bias), L.ptr(res1), L.ptr(res2),
-                   out.data_ptr(), oflag, B, H, W_, Cin, Cout, int(relu_in), act,
+                   x.data_ptr(), d.a_bf16, Wp.data_ptr(), L.ptr(bias), L.ptr(res1), L.ptr(res2),
+                   out.data_ptr(), d.out_bf16, d.res_bf16, _TILE_PX[tile_px], B, H, W_, Cin, Cout, int(relu_in), act,
                    L.stream_ptr()), "sp3_conv3x3_tile"))
         return out
-    d = GemmDesc()
-    d.a_bf16 = _act(x, "x")
-    d.out_bf16 = int(out.dtype == torch.bfloat16)
-    _w(d, Wp)
-    M = B * OH * OW
-    lean = -1
-    if tile < 0 and isinstance(Wp, PackedWeight):
-        # small maps (<= 1024 pixels, bf16 weights): one lean launch, K split inside the workgroup -- no split-K workspace, no reduce launch
-        p = GemmDesc()
-        p.a_bf16, p.out_bf16 = d.a_bf16, d.out_bf16
-        _w(p, Wp)
-        p.A, p.C, p.bias, p.res1, p.res2 = x.data_ptr(), out.data_ptr(), L.ptr(bias), L.ptr(res1), L.ptr(res2)
-        p.M, p.N, p.K, p.batch = M, Cout, 9 * Cin, 1
-        p.lda, p.ldc, p.ldr1, p.ldr2 = Cin, Cout, Cout, Cout
-        p.alpha, p.act, p.relu_in = 1.0, act, int(relu_in)
-        p.loader, p.epi, p.tile = L.LOAD_CONV3X3, L.EPI_PLAIN, -1
-        p.conv_H, p.conv_W, p.conv_C, p.conv_OH, p.conv_OW, p.conv_stride = H, W_, Cin, OH, OW, stride
-        rbf = [t.dtype == torch.bfloat16 for t in (res1, res2) if t is not None]
-        if rbf and any(rbf) != all(rbf):
-            raise TypeError("conv3x3: residual maps must share one dtype")
-        p.res_bf16 = int(any(rbf))                  # the lean instances read the residuals in the map dtype: the plan refuses a mismatch
-        if res2_up is not None:
-            p.res2_up_H, p.res2_up_W = res2_up
-        lean = L.load().sp3_gemm_plan(C.byref(p))
-        if lean >= 30:
-            _gemm_launch(p, "sp3_gemm(conv3x3)", "conv3x3")
-            return out
+    if mixed and tile < 0 and isinstance(Wp, PackedWeight):     # (the lean instances read the residuals in one dtype: d.res_bf16)
+        raise TypeError("conv3x3: residual maps must share one dtype")
+    if route == "lean":
+        _gemm_launch(d, "sp3_gemm(conv3x3)", "conv3x3")
+        return out
     if res2_up is not None:
         raise ValueError("conv3x3: a half-resolution res2 is read by the lean small-map kernels only (B*H*W=%d)" % (B * H * W_))
-    if any(t is not None and t.dtype == torch.bfloat16 for t in (res1, res2)):
+    if any(rbf):
         raise TypeError("conv3x3: bf16 residual maps are served by the lean small-map and the LDS-tiled kernels only "
                         "(B*H*W=%d, Cin=%d, Cout=%d, stride %d)" % (B * H * W_, Cin, Cout, stride))
     S = conv_splitk(M, Cout, 9 * Cin, Wp.dtype) if (splitk_ws is not None and tile < 0 and out.dtype == torch.float32) else 1
     if S > 1 and splitk_ws.numel() < S * M * Cout:
         raise ValueError("conv3x3: splitk_ws holds %d floats, needs %d" % (splitk_ws.numel(), S * M * Cout))
-    d.A, d.C = x.data_ptr(), (splitk_ws if S > 1 else out).data_ptr()
-    if S == 1:
-        d.bias, d.res1, d.res2 = L.ptr(bias), L.ptr(res1), L.ptr(res2)
-    d.M, d.N, d.K, d.batch = M, Cout, 9 * Cin, 1
-    d.lda, d.ldc, d.ldr1, d.ldr2 = Cin, Cout, Cout, Cout
-    d.alpha, d.act, d.relu_in = 1.0, (act if S == 1 else ACT_NONE), int(relu_in)
-    d.loader, d.epi, d.tile = L.LOAD_CONV3X3, (L.EPI_PLAIN if S == 1 else L.EPI_PARTIAL), (tile if S == 1 else 0)
-    d.splitk = S if S > 1 else 0
-    d.conv_H, d.conv_W, d.conv_C, d.conv_OH, d.conv_OW, d.conv_stride = H, W_, Cin, OH, OW, stride
+    d.tile = tile
+    if S > 1:
+        # few output tiles, long K (small maps): K split over S workgroups per tile; bias, residuals and activation wait for the reduce
+        d.C, d.bias, d.res1, d.res2 = splitk_ws.data_ptr(), None, None, None
+        d.act, d.epi, d.tile, d.splitk = ACT_NONE, L.EPI_PARTIAL, 0, S
     global _held
     held, _held = _held, None                       # (a split-K launch is followed by its reduce: never held back by a level)
     try:
@@ -576,15 +590,17 @@ def conv3x3(x, Wp, out, *, B, H, W_, Cin, Cout, stride=1, bias=None, res1=None, 
     finally:
         _held = held
     if S > 1:
-        # few output tiles, long K (small maps): K split over S workgroups per tile, finished by one reduce launch
         reduce_ln(splitk_ws, S, M, Cout, bias=bias, res=res1, ldres=Cout, x_out=out, ldx=Cout, act=act, res2=res2, ldres2=Cout)
     return out
 
 
 def conv3x3_takes_res2_up(Wp, map_dtype, B, H, W_):
-    """whether conv3x3 on this stride-1 map runs on a kernel that reads a half-resolution res2 (the lean small-map tiles: bf16 weights
-    and maps, fewer than 2048 pixels) -- the engine keeps the upsample2x launch in front of any other"""
-    return LEAN and isinstance(Wp, PackedWeight) and Wp.dtype == torch.bfloat16 and map_dtype == torch.bfloat16 and B * H * W_ < 2048
+    """whether conv3x3 with the PackedWeight Wp on this stride-1 map (map, output and residuals of map_dtype) runs on a kernel that
+    reads a half-resolution res2 (the lean small-map tiles) -- the engine keeps the upsample2x launch in front of any other"""
+    d = _conv_desc(Wp, map_dtype, map_dtype, map_dtype, B=B, H=H, W_=W_, Cin=Wp.K // 9, Cout=Wp.N, stride=1, act=ACT_NONE, relu_in=False,
+                   res2_up=((H + 1) // 2, (W_ + 1) // 2))
+    d.res1 = d.res2 = 4096                          # (set, as the consumer's are; planning reads no pointer values)
+    return _conv_route(d, Wp) == "lean"
 
 
 def conv_splitk(M, N, K, wdtype):
