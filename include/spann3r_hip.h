@@ -634,6 +634,52 @@ int sp3_pnp_gn_accum(const float* pts, int F, int H, int W, float focal, float c
 int sp3_pnp_score(const float* pts, int F, int H, int W, float focal, float cx, float cy, const float* Rt, int n_hyp, float thresh,
                   int cv_mode, int* counts, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Reconstruction metrics (eval.py:189-231, spann3r/tools/eval_recon.py; spann3r_amd/evaluate.py drives these).
+ * Clouds are fp32 [n, 3]; indices are int32 (n < 2^31).  No entry point allocates or synchronises; `ws` is caller-provided
+ * device scratch of the matching sp3_*_ws_bytes(), 16-byte aligned.
+ *
+ * sp3_nn_grid: a uniform cell grid over the reference cloud, chosen by the host: origin = the cloud's minimum corner, cell edge h,
+ *   inv_h = 1 / h, dims nx * ny * nz (<= 2^24 cells); cell of x = clamp(floor((x - ox) * inv_h), 0, nx - 1), id = (cz * ny + cy) * nx + cx.
+ *   slack: an upper bound of the fp32 rounding of cell assignment and wall positions, taken off every stopping bound.
+ * sp3_nn_cell_ids     : ids[n] = cell id of every point (also used for the queries, clamped into the grid).
+ * sp3_nn_pack_records : recs[i] = (x, y, z, bit pattern of s) of point s = order[i] (order null: s = i): 16-byte records.
+ * sp3_nn_query : exact nearest neighbour of q[nq] among the m records sorted by cell id, cell_start[cells + 1] = first record of each
+ *   cell.  q_order (nullable): a permutation of the queries (sorted by home cell) that decides which lanes run together; results are
+ *   written in caller order.  Rings r = 0..max_ring around the home cell; a query is finished when its best distance is within the
+ *   distance to the nearest wall of the visited block that still has cells behind it.  Queries left open go through the brute-force
+ *   kernel.  dist > max_dist (+inf: no gate) gives idx -1, dist +inf.  After the call the first 32 bytes of ws hold
+ *   { int32 fallback queries, 3 x int32 pad, uint64 cells visited, uint64 points visited }.
+ * sp3_nn_brute : the same result by the LDS-tiled brute-force kernel alone, for every query; recs in any order.
+ * sp3_knn_query: k <= 32 nearest neighbours, ascending: dist / idx [nq, k]; missing entries (m < k, or beyond max_dist) are +inf / -1.
+ *   A grid of one cell makes it a brute-force scan.
+ * sp3_knn_normals : per point, the unit eigenvector of the smallest eigenvalue of the covariance (fp64, about the mean) of the
+ *   points nbr[i][0..k) (entries < 0 skipped); fewer than 3 neighbours: (0, 0, 1).  Sign unconstrained.
+ * sp3_transform_points : out = R src + t in fp64, rounded to fp32; Rt12 (HOST) = row-major R (9) | t (3).
+ * sp3_icp_accum : over the pairs (p_i, q = tgt[idx_i]) with idx_i >= 0, in fp64 and a fixed order:
+ *   out17 = { count, sum p (3), sum q (3), sum p q^T (9, row-major), sum |p - q|^2 }.
+ * sp3_sum_count_f32 : out2 = { sum x_i, #(x_i < thresh) } in fp64, fixed order.
+ * sp3_normal_dot : out_i = |na[idx_i] . nb[i]| (gather_a != 0) or |na[i] . nb[idx_i]|; idx_i < 0 gives 0. */
+typedef struct {
+  float ox, oy, oz, h, inv_h, slack;
+  int nx, ny, nz;
+} sp3_nn_grid;
+int sp3_nn_cell_ids(const float* pts, int64_t n, const sp3_nn_grid* g, int* ids, void* stream);
+int sp3_nn_pack_records(const float* pts, const int64_t* order, int64_t n, float* recs, void* stream);
+int64_t sp3_nn_query_ws_bytes(int64_t nq);
+int sp3_nn_query(const float* q, const int64_t* q_order, int64_t nq, const float* recs, const int* cell_start, int64_t m,
+                 const sp3_nn_grid* g, int max_ring, float max_dist, void* ws, float* dist, int* idx, void* stream);
+int sp3_nn_brute(const float* q, int64_t nq, const float* recs, int64_t m, float max_dist, void* ws, float* dist, int* idx, void* stream);
+int sp3_knn_query(const float* q, const int64_t* q_order, int64_t nq, const float* recs, const int* cell_start, int64_t m,
+                  const sp3_nn_grid* g, int k, float max_dist, float* dist, int* idx, void* stream);
+int sp3_knn_normals(const float* pts, const int* nbr, int64_t n, int k, float* normals, void* stream);
+int sp3_transform_points(const float* src, int64_t n, const double* Rt12, float* out, void* stream);
+int64_t sp3_icp_accum_ws_bytes(int64_t n);
+int sp3_icp_accum(const float* p, const float* tgt, const int* idx, int64_t n, void* ws, double* out17, void* stream);
+int64_t sp3_sum_count_ws_bytes(int64_t n);
+int sp3_sum_count_f32(const float* x, int64_t n, float thresh, void* ws, double* out2, void* stream);
+int sp3_normal_dot(const float* na, const float* nb, const int* idx, int64_t n, int gather_a, float* out, void* stream);
+
 /* small utilities */
 /* n (1..8) contiguous device-to-device copies in one launch; every copy 16-byte aligned and a multiple of 16 bytes.
  * (The sequence loop's per-frame bookkeeping -- torch .clone() / slice assignments around spann3r/model.py:523-531.) */

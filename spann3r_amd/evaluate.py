@@ -1,0 +1,334 @@
+"""Reconstruction metrics of eval.py on the device (reference: eval.py:189-231, spann3r/tools/eval_recon.py:4-39).
+
+The reference scores a scene on the CPU: Open3D's point-to-point ICP of the predicted cloud onto the ground truth, Open3D's
+`estimate_normals` of both, then accuracy / completion / normal consistency through scipy's cKDTree.  Everything here rests on one
+primitive, exact nearest-neighbour search between two clouds (csrc/eval.hip: a cell grid over the reference cloud walked ring by
+ring, an LDS-tiled brute-force kernel for the queries the rings do not settle); distances, covariances and sums are HIP, torch
+provides memory, `torch.sort` (cell ids, medians) and `torch.searchsorted` (the cell-start table).
+
+`accuracy`, `completion` and `completion_ratio` are pinned to the reference's own functions (tests/golden/eval_metrics.npz).
+Open3D is not available to the tests: `icp_point_to_point` and `estimate_normals` implement the algorithms Open3D documents
+(registration_icp with TransformationEstimationPointToPoint; k-NN PCA normals) and are pinned to a float64 restatement --
+parity with Open3D itself is unpinned."""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import lib as L
+
+KNN_MAX = 32
+MAX_CELLS = 1 << 22
+OCCUPANCY = 4.0          # mean points per cell the edge length aims for
+RING_BUDGET = 3          # rings walked before a query is handed to the brute-force kernel
+
+
+def _cloud(x, name):
+    """fp32 [N, 3] on the device: numpy arrays are moved there, CPU tensors are refused (as elsewhere in the package)."""
+    if isinstance(x, np.ndarray):
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to("cuda")
+    elif not isinstance(x, torch.Tensor):
+        raise TypeError("%s: expected a CUDA tensor or a numpy array, got %s" % (name, type(x).__name__))
+    elif not x.is_cuda:
+        raise RuntimeError("%s: the metrics run on the GPU (HIP kernels); there is no CPU path -- pass a CUDA tensor or a numpy array" % name)
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise ValueError("%s: expected shape [N, 3], got %s" % (name, tuple(x.shape)))
+    return x.contiguous().float()
+
+
+def choose_grid(lo, hi, n, occupancy=OCCUPANCY, max_cells=MAX_CELLS):
+    """Cell edge and dims for n points in the box [lo, hi] (host, float64) -> (h, (nx, ny, nz)).
+    h aims at `occupancy` points per cell over the axes the cloud really extends along: an axis thinner than h holds one cell and
+    leaves the volume (planar, collinear and single-point clouds), every extent is floored, and h grows until the cell cap holds."""
+    ext = np.maximum(np.asarray(hi, np.float64) - np.asarray(lo, np.float64), 0.0)
+    emax = float(ext.max())
+    if not np.isfinite(emax) or emax <= 0.0:
+        return 1.0, (1, 1, 1)
+    floored = np.maximum(ext, 1e-6 * emax)
+    active = [0, 1, 2]
+    h = emax
+    while active:
+        h = float((np.prod(floored[active]) * occupancy / max(n, 1)) ** (1.0 / len(active)))
+        thin = [a for a in active if floored[a] < h]
+        if not thin:
+            break
+        active = [a for a in active if a not in thin]
+    if not active:
+        h = 2.0 * emax                               # fewer points than `occupancy`: one cell
+    h = max(h, 1e-30, emax * 2.0 ** -20)
+    while True:
+        dims = tuple(int(math.floor(e / h)) + 1 for e in ext)
+        if dims[0] * dims[1] * dims[2] <= max_cells:
+            return h, dims
+        h *= 1.25
+
+
+class CellGrid:
+    """The reference cloud binned for searching: records sorted by cell id, the cell-start table, the grid descriptor."""
+
+    def __init__(self, ref, brute=False):
+        lib = L.load()
+        self.ref = ref
+        self.m = m = ref.shape[0]
+        dev = ref.device
+        self.recs = torch.empty(m, 4, dtype=torch.float32, device=dev)
+        if brute:                                    # one cell, records in caller order: what the brute-force kernels read
+            self.g = L.NnGrid(0.0, 0.0, 0.0, 1.0, 1.0, 0.0, 1, 1, 1)
+            self.cell_start = torch.tensor([0, m], dtype=torch.int32, device=dev)
+            L.check(lib.sp3_nn_pack_records(ref.data_ptr(), 0, m, self.recs.data_ptr(), L.stream_ptr()), "sp3_nn_pack_records")
+            return
+        lo, hi = torch.aminmax(ref, dim=0)
+        box = torch.stack((lo, hi)).double().cpu().numpy()
+        box = np.where(np.isfinite(box), box, 0.0)
+        h, dims = choose_grid(box[0], box[1], m)
+        maxabs = float(np.abs(box).max())
+        slack = 1e-6 * (maxabs + float((box[1] - box[0]).max()) + h)
+        self.g = L.NnGrid(float(box[0, 0]), float(box[0, 1]), float(box[0, 2]), h, 1.0 / h, slack, *dims)
+        ncell = dims[0] * dims[1] * dims[2]
+        ids = torch.empty(m, dtype=torch.int32, device=dev)
+        L.check(lib.sp3_nn_cell_ids(ref.data_ptr(), m, C.byref(self.g), ids.data_ptr(), L.stream_ptr()), "sp3_nn_cell_ids")
+        sorted_ids, order = torch.sort(ids, stable=True)
+        L.check(lib.sp3_nn_pack_records(ref.data_ptr(), order.data_ptr(), m, self.recs.data_ptr(), L.stream_ptr()), "sp3_nn_pack_records")
+        self.cell_start = torch.searchsorted(sorted_ids, torch.arange(ncell + 1, dtype=torch.int32, device=dev)).to(torch.int32)
+
+    def query_order(self, q):
+        """the queries sorted by the cell they fall in (clamped into the grid): the lanes of a wave then walk the same cells"""
+        ids = torch.empty(q.shape[0], dtype=torch.int32, device=q.device)
+        L.check(L.load().sp3_nn_cell_ids(q.data_ptr(), q.shape[0], C.byref(self.g), ids.data_ptr(), L.stream_ptr()), "sp3_nn_cell_ids")
+        return torch.sort(ids, stable=True)[1]
+
+    def nn(self, q, max_dist=math.inf, ring_budget=RING_BUDGET, ws=None):
+        """1-NN of q [N, 3] -> dist fp32 [N], idx int32 [N], ws (its first 32 bytes hold the counters of this call)"""
+        lib = L.load()
+        n = q.shape[0]
+        dist = torch.empty(n, dtype=torch.float32, device=q.device)
+        idx = torch.empty(n, dtype=torch.int32, device=q.device)
+        if ws is None:
+            ws = torch.empty(lib.sp3_nn_query_ws_bytes(n), dtype=torch.uint8, device=q.device)
+        order = self.query_order(q)
+        L.check(lib.sp3_nn_query(q.data_ptr(), order.data_ptr(), n, self.recs.data_ptr(), self.cell_start.data_ptr(), self.m, C.byref(self.g),
+                                 int(ring_budget), float(max_dist), ws.data_ptr(), dist.data_ptr(), idx.data_ptr(), L.stream_ptr()), "sp3_nn_query")
+        return dist, idx, ws
+
+    def nn_brute(self, q, max_dist=math.inf):
+        lib = L.load()
+        n = q.shape[0]
+        dist = torch.empty(n, dtype=torch.float32, device=q.device)
+        idx = torch.empty(n, dtype=torch.int32, device=q.device)
+        ws = torch.empty(lib.sp3_nn_query_ws_bytes(n), dtype=torch.uint8, device=q.device)
+        L.check(lib.sp3_nn_brute(q.data_ptr(), n, self.recs.data_ptr(), self.m, float(max_dist), ws.data_ptr(), dist.data_ptr(), idx.data_ptr(),
+                                 L.stream_ptr()), "sp3_nn_brute")
+        return dist, idx
+
+    def knn(self, q, k, max_dist=math.inf, sort_queries=True):
+        lib = L.load()
+        n = q.shape[0]
+        dist = torch.empty(n, k, dtype=torch.float32, device=q.device)
+        idx = torch.empty(n, k, dtype=torch.int32, device=q.device)
+        order = self.query_order(q) if sort_queries else None
+        L.check(lib.sp3_knn_query(q.data_ptr(), L.ptr(order), n, self.recs.data_ptr(), self.cell_start.data_ptr(), self.m, C.byref(self.g), int(k),
+                                  float(max_dist), dist.data_ptr(), idx.data_ptr(), L.stream_ptr()), "sp3_knn_query")
+        return dist, idx
+
+
+def _read_counters(ws):
+    head = ws[:32].cpu().numpy()
+    return int(head[:4].view(np.int32)[0]), int(head[16:24].view(np.uint64)[0]), int(head[24:32].view(np.uint64)[0])
+
+
+def nearest_neighbors(query, ref, k=1, max_dist=None, method="grid", return_stats=False, ring_budget=RING_BUDGET):
+    """Exact nearest neighbours of every query point among ref -> (dist fp32, idx int32), [N] for k = 1, [N, k] ascending for
+    k > 1 (k <= 32).  max_dist: neighbours farther than it are reported as index -1, distance +inf.
+    method: "grid" (cell grid + brute-force second pass for what `ring_budget` rings leave open) or "brute" (the brute-force
+    kernel for every query; for k > 1 the k-NN kernel over a grid of one cell) -- the in-tree cross-check.
+    return_stats: also a dict with `fallback_queries` (served by the second pass), `cells_visited`, `points_visited`, `grid`, `h`."""
+    if method not in ("grid", "brute"):
+        raise ValueError("nearest_neighbors: method must be 'grid' or 'brute', got %r" % (method,))
+    if not 1 <= int(k) <= KNN_MAX:
+        raise ValueError("nearest_neighbors: k = %r, must be 1..%d" % (k, KNN_MAX))
+    k = int(k)
+    q, r = _cloud(query, "query"), _cloud(ref, "ref")
+    if r.shape[0] == 0:
+        raise ValueError("nearest_neighbors: ref is empty")
+    md = math.inf if max_dist is None else float(max_dist)
+    if md < 0:
+        raise ValueError("nearest_neighbors: max_dist must be non-negative")
+    n = q.shape[0]
+    stats = {"fallback_queries": 0, "cells_visited": 0, "points_visited": 0, "grid": (1, 1, 1), "h": None}
+    if n == 0:
+        shape = (0,) if k == 1 else (0, k)
+        out = torch.empty(shape, dtype=torch.float32, device=q.device), torch.empty(shape, dtype=torch.int32, device=q.device)
+        return out + (stats,) if return_stats else out
+    grid = CellGrid(r, brute=(method == "brute"))
+    if k > 1:
+        dist, idx = grid.knn(q, k, md, sort_queries=(method == "grid"))
+        stats["fallback_queries"] = n if method == "brute" else 0
+    elif method == "brute":
+        dist, idx = grid.nn_brute(q, md)
+        stats["fallback_queries"] = n
+    else:
+        dist, idx, ws = grid.nn(q, md, ring_budget)
+        if return_stats:
+            stats["fallback_queries"], stats["cells_visited"], stats["points_visited"] = _read_counters(ws)
+    if method == "grid":
+        stats["grid"], stats["h"] = (grid.g.nx, grid.g.ny, grid.g.nz), float(grid.g.h)
+    return (dist, idx, stats) if return_stats else (dist, idx)
+
+
+# ------------------------------------------------------------------------------------------------ eval_recon.py:4-39
+def _sum_count(x, thresh):
+    """device double [2] = (sum x, #(x < thresh)), fp64 partial slabs in a fixed order"""
+    lib = L.load()
+    n = x.numel()
+    ws = torch.empty(lib.sp3_sum_count_ws_bytes(n), dtype=torch.uint8, device=x.device)
+    out = torch.empty(2, dtype=torch.float64, device=x.device)
+    L.check(lib.sp3_sum_count_f32(x.data_ptr(), n, float(thresh), ws.data_ptr(), out.data_ptr(), L.stream_ptr()), "sp3_sum_count_f32")
+    return out
+
+
+def _mean_median(x):
+    """(mean, median) of a device fp32 vector as Python floats; numpy's median rule (mean of the two middle values for an even count)"""
+    n = x.numel()
+    s = torch.sort(x)[0]
+    got = torch.cat((_sum_count(x, 0.0)[:1], s[(n - 1) // 2:n // 2 + 1].double())).cpu().numpy()
+    return float(got[0] / n), float((got[1] + got[-1]) / 2.0)
+
+
+def _nn_with_normals(tree_pts, query_pts, na, nb, gather_a, what):
+    tree, q = _cloud(tree_pts, what + ": tree cloud"), _cloud(query_pts, what + ": query cloud")
+    if tree.shape[0] == 0 or q.shape[0] == 0:
+        raise ValueError(what + ": empty cloud")
+    dist, idx, _ = CellGrid(tree).nn(q)
+    out = _mean_median(dist)
+    if na is not None and nb is not None:
+        na, nb = _cloud(na, what + ": gt_normals"), _cloud(nb, what + ": rec_normals")
+        n = q.shape[0]
+        if (na.shape[0], nb.shape[0]) != ((tree.shape[0], n) if gather_a else (n, tree.shape[0])):
+            raise ValueError(what + ": normals do not match their clouds")
+        dots = torch.empty(n, dtype=torch.float32, device=q.device)
+        L.check(L.load().sp3_normal_dot(na.data_ptr(), nb.data_ptr(), idx.data_ptr(), n, int(gather_a), dots.data_ptr(), L.stream_ptr()),
+                "sp3_normal_dot")
+        out = out + _mean_median(dots)
+    return out
+
+
+def accuracy(gt_points, rec_points, gt_normals=None, rec_normals=None):
+    """eval_recon.py:11-24: distances from every reconstructed point to its nearest ground-truth point ->
+    (mean, median) or, with normals, (mean, median, mean |n_gt[idx] . n_rec|, median of the same)."""
+    return _nn_with_normals(gt_points, rec_points, gt_normals, rec_normals, True, "accuracy")
+
+
+def completion(gt_points, rec_points, gt_normals=None, rec_normals=None):
+    """eval_recon.py:27-39: distances from every ground-truth point to its nearest reconstructed point ->
+    (mean, median) or, with normals, (mean, median, mean |n_gt . n_rec[idx]|, median of the same)."""
+    return _nn_with_normals(rec_points, gt_points, gt_normals, rec_normals, False, "completion")
+
+
+def completion_ratio(gt_points, rec_points, dist_th=0.05):
+    """eval_recon.py:4-8: the share of ground-truth points whose nearest reconstructed point is closer than dist_th (a float32
+    mean of 0 / 1 there, so the float32 quotient here)."""
+    rec, gt = _cloud(rec_points, "completion_ratio: rec_points"), _cloud(gt_points, "completion_ratio: gt_points")
+    if rec.shape[0] == 0 or gt.shape[0] == 0:
+        raise ValueError("completion_ratio: empty cloud")
+    dist, _, _ = CellGrid(rec).nn(gt)
+    count = float(_sum_count(dist, dist_th)[1].item())
+    return float(np.float32(count) / np.float32(gt.shape[0]))
+
+
+# ------------------------------------------------------------------------------------------------ eval.py:203-212
+def estimate_normals(points, knn=30):
+    """Unit normals [N, 3] (device fp32) from the PCA of every point's knn nearest neighbours, itself included (what Open3D's
+    `estimate_normals(KDTreeSearchParamKNN(knn))` documents; eval.py:211-212 uses its default, 30).  Sign is unconstrained;
+    fewer than 3 points give (0, 0, 1).  Parity with Open3D itself is unpinned."""
+    if not 1 <= int(knn) <= KNN_MAX:
+        raise ValueError("estimate_normals: knn = %r, must be 1..%d" % (knn, KNN_MAX))
+    pts = _cloud(points, "points")
+    n = pts.shape[0]
+    out = torch.empty(n, 3, dtype=torch.float32, device=pts.device)
+    if n == 0:
+        return out
+    _, idx = CellGrid(pts).knn(pts, int(knn))
+    L.check(L.load().sp3_knn_normals(pts.data_ptr(), idx.data_ptr(), n, int(knn), out.data_ptr(), L.stream_ptr()), "sp3_knn_normals")
+    return out
+
+
+def _transform(pts, T, out=None):
+    out = torch.empty_like(pts) if out is None else out
+    if pts.shape[0]:
+        rt = (C.c_double * 12)(*T[:3, :3].reshape(-1).tolist(), *T[:3, 3].tolist())
+        L.check(L.load().sp3_transform_points(pts.data_ptr(), pts.shape[0], rt, out.data_ptr(), L.stream_ptr()), "sp3_transform_points")
+    return out
+
+
+def kabsch_update(s):
+    """The rigid motion that best maps the matched source points onto their targets, from the 17 sums of sp3_icp_accum
+    (Umeyama without scale, reflection fixed) -> 4x4 float64."""
+    n = s[0]
+    mp, mq = s[1:4] / n, s[4:7] / n
+    cov = (s[7:16].reshape(3, 3) / n - np.outer(mp, mq)).T          # sum (q - mq)(p - mp)^T / n
+    U, _, Vt = np.linalg.svd(cov)
+    S = np.eye(3)
+    if np.linalg.det(U) * np.linalg.det(Vt) < 0:
+        S[2, 2] = -1.0
+    T = np.eye(4)
+    T[:3, :3] = U @ S @ Vt
+    T[:3, 3] = mq - T[:3, :3] @ mp
+    return T
+
+
+def icp_point_to_point(source, target, max_dist, init=None, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6):
+    """Point-to-point ICP as Open3D documents `registration_icp(source, target, max_dist, init,
+    TransformationEstimationPointToPoint())` -> (T [4, 4] float64 numpy, fitness, inlier_rmse, iterations).
+    Every evaluation matches each transformed source point to its nearest target point within max_dist (fitness = matches /
+    source points, rmse = sqrt(sum d^2 / matches)); every iteration applies the Kabsch update of the current matches,
+    T <- update . T, and re-evaluates; it stops when |d fitness| and |d rmse| are both below their criteria.  The loop reads
+    back 17 doubles per evaluation; the 3x3 SVD runs on the host in float64.  Parity with Open3D itself is unpinned."""
+    lib = L.load()
+    src, tgt = _cloud(source, "source"), _cloud(target, "target")
+    T = np.eye(4) if init is None else np.array(init, dtype=np.float64).reshape(4, 4)
+    n = src.shape[0]
+    if n == 0 or tgt.shape[0] == 0:
+        return T, 0.0, 0.0, 0
+    grid = CellGrid(tgt)
+    moved = torch.empty_like(src)
+    ws_nn = torch.empty(lib.sp3_nn_query_ws_bytes(n), dtype=torch.uint8, device=src.device)
+    ws_acc = torch.empty(lib.sp3_icp_accum_ws_bytes(n), dtype=torch.uint8, device=src.device)
+    sums = torch.empty(17, dtype=torch.float64, device=src.device)
+
+    def evaluate(T):
+        _transform(src, T, moved)
+        _, idx, _ = grid.nn(moved, max_dist, ws=ws_nn)
+        L.check(lib.sp3_icp_accum(moved.data_ptr(), tgt.data_ptr(), idx.data_ptr(), n, ws_acc.data_ptr(), sums.data_ptr(), L.stream_ptr()),
+                "sp3_icp_accum")
+        s = sums.cpu().numpy()
+        if s[0] == 0:
+            return s, 0.0, 0.0
+        return s, float(s[0] / n), float(math.sqrt(s[16] / s[0]))
+
+    s, fitness, rmse = evaluate(T)
+    if s[0] == 0:
+        return T, 0.0, 0.0, 0
+    it = 0
+    while it < max_iteration:
+        it += 1
+        T = kabsch_update(s) @ T
+        s, f2, r2 = evaluate(T)
+        stop = (abs(f2 - fitness) < relative_fitness and abs(r2 - rmse) < relative_rmse) or s[0] == 0
+        fitness, rmse = f2, r2
+        if stop:
+            break
+    return T, fitness, rmse, it
+
+
+def evaluate_reconstruction(pred_points, gt_points, threshold=0.1):
+    """eval.py:203-218 on already-masked clouds: ICP of the prediction onto the ground truth from identity, the prediction
+    transformed, normals of both clouds, accuracy and completion with normal consistency."""
+    pred, gt = _cloud(pred_points, "pred_points"), _cloud(gt_points, "gt_points")
+    T, _, _, _ = icp_point_to_point(pred, gt, threshold)
+    pred = _transform(pred, T)
+    pred_n, gt_n = estimate_normals(pred), estimate_normals(gt)
+    acc, acc_med, nc1, nc1_med = accuracy(gt, pred, gt_n, pred_n)
+    comp, comp_med, nc2, nc2_med = completion(gt, pred, gt_n, pred_n)
+    return {"acc": acc, "comp": comp, "nc1": nc1, "nc2": nc2, "acc_med": acc_med, "comp_med": comp_med, "nc1_med": nc1_med,
+            "nc2_med": nc2_med, "transformation": T}

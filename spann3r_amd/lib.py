@@ -102,6 +102,12 @@ class BankWriteDesc(C.Structure):
     ]
 
 
+class NnGrid(C.Structure):
+    """sp3_nn_grid (include/spann3r_hip.h)"""
+    _fields_ = [("ox", C.c_float), ("oy", C.c_float), ("oz", C.c_float), ("h", C.c_float), ("inv_h", C.c_float), ("slack", C.c_float),
+                ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32)]
+
+
 _lib = None
 
 _PROTOS = {
@@ -213,8 +219,21 @@ _PROTOS = {
     "sp3_preprocess_image": [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                              C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                              C.c_void_p, C.c_void_p],
+    "sp3_nn_cell_ids": [C.c_void_p, C.c_int64, C.POINTER(NnGrid), C.c_void_p, C.c_void_p],
+    "sp3_nn_pack_records": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "sp3_nn_query": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(NnGrid), C.c_int, C.c_float, C.c_void_p,
+                     C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_nn_brute": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_knn_query": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(NnGrid), C.c_int, C.c_float,
+                      C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_knn_normals": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p],
+    "sp3_transform_points": [C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_void_p, C.c_void_p],
+    "sp3_icp_accum": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_sum_count_f32": [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_normal_dot": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p],
 }
-EXPORTS = sorted(list(_PROTOS) + ["sp3_last_error", "sp3_version", "sp3_conf_loss_ws_bytes", "sp3_ssi_loss_ws_bytes", "sp3_sumsq_blocks", "sp3_colsum_rows_ws"])
+EXPORTS = sorted(list(_PROTOS) + ["sp3_last_error", "sp3_version", "sp3_conf_loss_ws_bytes", "sp3_ssi_loss_ws_bytes", "sp3_sumsq_blocks", "sp3_colsum_rows_ws",
+                                  "sp3_nn_query_ws_bytes", "sp3_icp_accum_ws_bytes", "sp3_sum_count_ws_bytes"])
 
 
 def load():
@@ -237,6 +256,9 @@ def load():
     lib.sp3_sumsq_blocks.argtypes = [C.c_int64]
     lib.sp3_colsum_rows_ws.restype = C.c_int64
     lib.sp3_colsum_rows_ws.argtypes = [C.c_int, C.c_int]
+    for name in ("sp3_nn_query_ws_bytes", "sp3_icp_accum_ws_bytes", "sp3_sum_count_ws_bytes"):
+        getattr(lib, name).restype = C.c_int64
+        getattr(lib, name).argtypes = [C.c_int64]
     for name, argtypes in _PROTOS.items():
         fn = getattr(lib, name)
         fn.restype = C.c_int
