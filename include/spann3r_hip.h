@@ -31,6 +31,8 @@ extern "C" {
 #endif
 
 enum { SP3_F32 = 0, SP3_BF16 = 1 };
+/* sp3_attention's further operand codes: fp32 operands in memory, every product through three MFMAs of a two-way split */
+enum { SP3_ATTN_F32X3 = 2, SP3_ATTN_F16X3 = 3 };
 enum { SP3_ACT_NONE = 0, SP3_ACT_GELU = 1, SP3_ACT_RELU = 2 };
 enum { SP3_EPI_PLAIN = 0, SP3_EPI_ROPE_VT = 1, SP3_EPI_PIXSHUF = 2, SP3_EPI_PARTIAL = 3 };
 enum { SP3_LOAD_PLAIN = 0, SP3_LOAD_CONV3X3 = 1, SP3_LOAD_SOFTMAX = 2 };
@@ -264,8 +266,11 @@ int sp3_rope_2d(void* tokens, int dtype, int B, int N, int H, int D, int64_t sB,
  * (croco/models/blocks.py:105-109 and 162-166).  q [B,Nq,heads,64] / k [B,Nk,heads,64] with row
  * strides ldq/ldk and batch strides sq/sk (elements, `dtype`), already RoPE'd; vt as written by
  * the ROPE_VT epilogue; out fp32 (or bf16 if out_bf16) [B*Nq, ldo] with head h at columns [64h, 64h+64).
- * dtype: SP3_F32 | SP3_BF16 | 2 = fp32 operands with every product through three bf16 MFMAs of a (hi, lo) split (the
- * "f32x3" precision of the model: 16 mantissa bits per product, fp32 softmax and accumulation).
+ * dtype: SP3_F32 | SP3_BF16 (operands in that type) |
+ *   SP3_ATTN_F32X3 = fp32 operands with every product through three bf16 MFMAs of a (hi, lo) split (the "f32x3" precision of
+ *                    the model: 16 mantissa bits per product, fp32 softmax and accumulation) |
+ *   SP3_ATTN_F16X3 = fp32 operands with every product through three fp16 MFMAs of a split x = h + l * 2^-11 (the "f16x3" precision:
+ *                    22 operand bits, every product exact in fp32; operands must stay below fp16's 65504).
  */
 int sp3_attention(const void* q, int64_t sq, int64_t ldq, const void* k, int64_t sk, int64_t ldk,
                   const void* vt, int64_t vt_ld, void* out, int64_t ldo, int out_bf16,

@@ -1,5 +1,10 @@
-// sp3_attention: softmax(q k^T * scale) v for head_dim 64 on gfx950, flash-style (online softmax),
-// one wave per 16 query rows, all operands streamed straight from global/L2 into MFMA registers.
+// Attention for head_dim 64 on gfx950: softmax(q k^T * scale) v, flash-style (online softmax), all operands streamed straight from
+// global / L2 into MFMA registers.  The file holds
+//   * the operand policies AttnT<..>: how q rows, k rows and V^T tiles become MFMA operands -- bf16 rows; fp32 rows as exact fp32,
+//     through a two-way split and three MFMAs per product (F32X3, F16X3), or rounded to bf16 (BF16X1, training);
+//   * attention_kernel (row-major operands, any policy; with `lse` the training forward), attention_packed_kernel (bf16 fragment-order
+//     operands, optionally with the cross-attention's q projection in front) and the two training backward kernels;
+//   * the host side: one grid rule and one launch function per forward kernel under the exported entry points.
 //
 // Layout trick (DESIGN.md §"Attention"): compute S^T = K.Q^T and O^T = V^T.P^T, i.e. keys / head-dim
 // on the MFMA row axis and the 16 query rows on the MFMA column axis (lane&15).  Then
@@ -21,11 +26,6 @@ template <typename T> struct AttnT;
 template <> struct AttnT<__bf16> {
   using Store = __bf16;
   // ---- S^T block: 16 keys x 16 queries, contraction over d = 64 in two MFMAs
-  struct QReg { bf16x8 v[2]; };
-  static __device__ __forceinline__ void loadQ(QReg& r, const __bf16* row, int g) {
-    r.v[0] = *reinterpret_cast<const bf16x8*>(row + 8 * g);
-    r.v[1] = *reinterpret_cast<const bf16x8*>(row + 32 + 8 * g);
-  }
   // (the operand row is loaded and multiplied in two steps: the kernels issue the loads of a whole 64-row tile before the first MFMA)
   struct KReg { bf16x8 v[2]; };
   static __device__ __forceinline__ KReg loadK(const __bf16* krow, int g) {
@@ -34,13 +34,14 @@ template <> struct AttnT<__bf16> {
     k.v[1] = *reinterpret_cast<const bf16x8*>(krow + 32 + 8 * g);
     return k;
   }
+  using QReg = KReg;                                        // a query row is the same registers
+  static __device__ __forceinline__ void loadQ(QReg& r, const __bf16* row, int g) { r = loadK(row, g); }
   static __device__ __forceinline__ f32x4 qk(const KReg& k, const QReg& q) {
     f32x4 s = {0.f, 0.f, 0.f, 0.f};
     s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k.v[0], q.v[0], s, 0, 0, 0);
     s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k.v[1], q.v[1], s, 0, 0, 0);
     return s;
   }
-  static __device__ __forceinline__ f32x4 qk(const __bf16* krow, int g, const QReg& q) { return qk(loadK(krow, g), q); }
   // ---- O^T += V^T . P^T over the 64 keys of a tile: p[t][r] is key 16t+4g+r of query lane&15
   static __device__ __forceinline__ void pv(f32x4 (&o)[4], const __bf16* vt_head, int64_t vt_ld, int kbase, int g,
                                             int dl, const f32x4 (&p)[4]) {
@@ -63,13 +64,10 @@ template <> struct AttnT<__bf16> {
   }
 };
 
-template <> struct AttnT<float> {
+// fp32 rows in memory: what every policy but bf16 shares.  A key-side row is four float4 per lane (d = 16g .. 16g+15 of the head).  The V^T
+// tile of the 32-keys-per-MFMA policies is (lo, hi) float4 pairs: lane g supplies keys 32u + 4g + (0..3) and 32u + 16 + 4g + (0..3) of d-block db.
+struct F32Rows {
   using Store = float;
-  struct QReg { float4 v[4]; };
-  static __device__ __forceinline__ void loadQ(QReg& r, const float* row, int g) {
-    const float4* p = reinterpret_cast<const float4*>(row + 16 * g);
-    r.v[0] = p[0]; r.v[1] = p[1]; r.v[2] = p[2]; r.v[3] = p[3];
-  }
   struct KReg { float4 v[4]; };
   static __device__ __forceinline__ KReg loadK(const float* krow, int g) {
     const float4* p = reinterpret_cast<const float4*>(krow + 16 * g);
@@ -77,7 +75,23 @@ template <> struct AttnT<float> {
     k.v[0] = p[0]; k.v[1] = p[1]; k.v[2] = p[2]; k.v[3] = p[3];
     return k;
   }
-  static __device__ __forceinline__ f32x4 qk(const float* krow, int g, const QReg& q) { return qk(loadK(krow, g), q); }
+  struct VTile { float4 lo[2][4], hi[2][4]; };
+  static __device__ __forceinline__ void loadV(VTile& v, const float* vt_head, int64_t vt_ld, int kbase, int g, int dl) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u)                         // all 16 loads of the tile first: one round trip, not eight
+#pragma unroll
+      for (int db = 0; db < 4; ++db) {
+        const float* vr = vt_head + (int64_t)(db * 16 + dl) * vt_ld + kbase + 32 * u + 4 * g;
+        v.lo[u][db] = *reinterpret_cast<const float4*>(vr);
+        v.hi[u][db] = *reinterpret_cast<const float4*>(vr + 16);
+      }
+  }
+};
+
+// exact fp32 products (v_mfma_f32_16x16x4_f32): 4 keys per MFMA, so its pv has its own 16-keys-per-step load pattern
+template <> struct AttnT<float> : F32Rows {
+  using QReg = KReg;
+  static __device__ __forceinline__ void loadQ(QReg& r, const float* row, int g) { r = loadK(row, g); }
   static __device__ __forceinline__ f32x4 qk(const KReg& k, const QReg& q) {
     f32x4 s = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -111,184 +125,82 @@ template <> struct AttnT<float> {
   }
 };
 
-// One workgroup = 16 query rows of one head; its 4 waves split the 64-key tiles (tile t goes to wave t & 3), each with its own
-// online softmax; the partial (m, l, O^T) states are merged through LDS (wave w finishes d-block w) -- at N = 196 every wave
-// has ONE tile, so the dependent chain is 1 tile instead of 4 (fp32 mode: 21 -> 8 us per launch).
-// fp32 operands, every product through three bf16 MFMAs of a (hi, lo) split (the model's "f32x3" precision, see gemm.hip)
+// fp32 operands, every product through three MFMAs of a two-way (hi, lo) split of both operands (split_hi_lo, common.h; the vector
+// type picks the split).  A split policy SP names that type and the product c + a b = c + (ah bh + ah bl + al bh):
+//   SplitBF16 (the model's "f32x3" precision, see gemm.hip): bf16 halves, x = hi + lo, the three products into one accumulator;
+//   SplitF16  (the model's "f16x3" precision, see gemm.hip): fp16 halves, x = h + l * 2^-11 (22 operand bits), every product exact in
+//             fp32; the cross terms are summed separately and folded in with 2^-11.
+struct SplitBF16 {
+  using V8 = bf16x8;
+  static __device__ __forceinline__ f32x4 mfma3(const V8& ah, const V8& al, const V8& bh, const V8& bl, f32x4 c) {
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
+  }
+};
+struct SplitF16 {
+  using V8 = f16x8;
+  static __device__ __forceinline__ f32x4 mfma3(const V8& ah, const V8& al, const V8& bh, const V8& bl, f32x4 c) {
+    f32x4 x = {0.f, 0.f, 0.f, 0.f};
+    x = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, x, 0, 0, 0);
+    x = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, x, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, c, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) c[r] = fmaf(x[r], 1.0f / 2048.0f, c[r]);
+    return c;
+  }
+};
+template <typename SP> struct AttnSplit : F32Rows {
+  using V8 = typename SP::V8;
+  struct QReg { V8 h[2], l[2]; };                           // d = 16g .. 16g+15 of the head, split once per workgroup
+  static __device__ __forceinline__ void loadQ(QReg& r, const float* row, int g) {
+    const float4* p = reinterpret_cast<const float4*>(row + 16 * g);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) split_hi_lo(p[2 * u], p[2 * u + 1], r.h[u], r.l[u]);
+  }
+  static __device__ __forceinline__ f32x4 qk(const KReg& k, const QReg& q) {
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      V8 kh, kl;
+      split_hi_lo(k.v[2 * u], k.v[2 * u + 1], kh, kl);
+      s = SP::mfma3(kh, kl, q.h[u], q.l[u], s);
+    }
+    return s;
+  }
+  // O^T += V^T . P^T over the 64 keys of a tile, 32 keys per MFMA
+  static __device__ __forceinline__ void pv(f32x4 (&o)[4], const float* vt_head, int64_t vt_ld, int kbase, int g, int dl,
+                                            const f32x4 (&p)[4]) {
+    VTile v;
+    loadV(v, vt_head, vt_ld, kbase, g, dl);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const float px[8] = {p[2 * u][0], p[2 * u][1], p[2 * u][2], p[2 * u][3], p[2 * u + 1][0], p[2 * u + 1][1], p[2 * u + 1][2], p[2 * u + 1][3]};
+      V8 ph, pl;
+      split_hi_lo(px, ph, pl);
+#pragma unroll
+      for (int db = 0; db < 4; ++db) {
+        V8 vh, vl;
+        split_hi_lo(v.lo[u][db], v.hi[u][db], vh, vl);
+        o[db] = SP::mfma3(vh, vl, ph, pl, o[db]);
+      }
+    }
+  }
+};
 struct F32X3 {};
-__device__ __forceinline__ void split8f(const float (&x)[8], bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const __bf16 h = (__bf16)x[e];
-    hi[e] = h;
-    lo[e] = (__bf16)(x[e] - (float)h);
-  }
-}
-__device__ __forceinline__ f32x4 mfma3(const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl, f32x4 c) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
-}
-template <> struct AttnT<F32X3> {
-  using Store = float;
-  struct QReg { bf16x8 h[2], l[2]; };                       // d = 16g .. 16g+15 of the head, split once per workgroup
-  static __device__ __forceinline__ void loadQ(QReg& r, const float* row, int g) {
-    const float4* p = reinterpret_cast<const float4*>(row + 16 * g);
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const float4 a = p[2 * u], b = p[2 * u + 1];
-      const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-      split8f(x, r.h[u], r.l[u]);
-    }
-  }
-  struct KReg { float4 v[4]; };
-  static __device__ __forceinline__ KReg loadK(const float* krow, int g) {
-    const float4* p = reinterpret_cast<const float4*>(krow + 16 * g);
-    KReg k;
-    k.v[0] = p[0]; k.v[1] = p[1]; k.v[2] = p[2]; k.v[3] = p[3];
-    return k;
-  }
-  static __device__ __forceinline__ f32x4 qk(const float* krow, int g, const QReg& q) { return qk(loadK(krow, g), q); }
-  static __device__ __forceinline__ f32x4 qk(const KReg& k, const QReg& q) {
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const float4 a = k.v[2 * u], b = k.v[2 * u + 1];
-      const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-      bf16x8 kh, kl;
-      split8f(x, kh, kl);
-      s = mfma3(kh, kl, q.h[u], q.l[u], s);
-    }
-    return s;
-  }
-  // O^T += V^T . P^T over the 64 keys of a tile, 32 keys per MFMA: lane g supplies keys 32u + 4g + (0..3) and 32u + 16 + 4g + (0..3)
-  static __device__ __forceinline__ void pv(f32x4 (&o)[4], const float* vt_head, int64_t vt_ld, int kbase, int g, int dl,
-                                            const f32x4 (&p)[4]) {
-    float4 vlo[2][4], vhi[2][4];                       // all 16 loads of the tile first: one round trip, not eight
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int db = 0; db < 4; ++db) {
-        const float* vr = vt_head + (int64_t)(db * 16 + dl) * vt_ld + kbase + 32 * u + 4 * g;
-        vlo[u][db] = *reinterpret_cast<const float4*>(vr);
-        vhi[u][db] = *reinterpret_cast<const float4*>(vr + 16);
-      }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const float px[8] = {p[2 * u][0], p[2 * u][1], p[2 * u][2], p[2 * u][3], p[2 * u + 1][0], p[2 * u + 1][1], p[2 * u + 1][2], p[2 * u + 1][3]};
-      bf16x8 ph, pl;
-      split8f(px, ph, pl);
-#pragma unroll
-      for (int db = 0; db < 4; ++db) {
-        const float4 lo4 = vlo[u][db], hi4 = vhi[u][db];
-        const float vx[8] = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z, hi4.w};
-        bf16x8 vh, vl;
-        split8f(vx, vh, vl);
-        o[db] = mfma3(vh, vl, ph, pl, o[db]);
-      }
-    }
-  }
-};
-
-// fp32 operands, fp16 two-way split x = h + l * 2^-11 (22 operand bits; the model's "f16x3" precision, see gemm.hip): three fp16 MFMAs per
-// product, exact in fp32; the cross terms are summed separately and folded in with 2^-11
 struct F16X3 {};
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-__device__ __forceinline__ void split8h(const float (&x)[8], f16x8& hi, f16x8& lo) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const _Float16 h = (_Float16)x[e];
-    hi[e] = h;
-    lo[e] = (_Float16)((x[e] - (float)h) * 2048.0f);
-  }
-}
-__device__ __forceinline__ f32x4 mfma3h(const f16x8& ah, const f16x8& al, const f16x8& bh, const f16x8& bl, f32x4 c) {
-  f32x4 x = {0.f, 0.f, 0.f, 0.f};
-  x = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, x, 0, 0, 0);
-  x = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, x, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, c, 0, 0, 0);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) c[r] = fmaf(x[r], 1.0f / 2048.0f, c[r]);
-  return c;
-}
-template <> struct AttnT<F16X3> {
-  using Store = float;
-  struct QReg { f16x8 h[2], l[2]; };
-  static __device__ __forceinline__ void loadQ(QReg& r, const float* row, int g) {
-    const float4* p = reinterpret_cast<const float4*>(row + 16 * g);
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const float4 a = p[2 * u], b = p[2 * u + 1];
-      const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-      split8h(x, r.h[u], r.l[u]);
-    }
-  }
-  struct KReg { float4 v[4]; };
-  static __device__ __forceinline__ KReg loadK(const float* krow, int g) {
-    const float4* p = reinterpret_cast<const float4*>(krow + 16 * g);
-    KReg k;
-    k.v[0] = p[0]; k.v[1] = p[1]; k.v[2] = p[2]; k.v[3] = p[3];
-    return k;
-  }
-  static __device__ __forceinline__ f32x4 qk(const float* krow, int g, const QReg& q) { return qk(loadK(krow, g), q); }
-  static __device__ __forceinline__ f32x4 qk(const KReg& k, const QReg& q) {
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const float4 a = k.v[2 * u], b = k.v[2 * u + 1];
-      const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-      f16x8 kh, kl;
-      split8h(x, kh, kl);
-      s = mfma3h(kh, kl, q.h[u], q.l[u], s);
-    }
-    return s;
-  }
-  static __device__ __forceinline__ void pv(f32x4 (&o)[4], const float* vt_head, int64_t vt_ld, int kbase, int g, int dl,
-                                            const f32x4 (&p)[4]) {
-    float4 vlo[2][4], vhi[2][4];                       // all 16 loads of the tile first: one round trip, not eight
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int db = 0; db < 4; ++db) {
-        const float* vr = vt_head + (int64_t)(db * 16 + dl) * vt_ld + kbase + 32 * u + 4 * g;
-        vlo[u][db] = *reinterpret_cast<const float4*>(vr);
-        vhi[u][db] = *reinterpret_cast<const float4*>(vr + 16);
-      }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const float px[8] = {p[2 * u][0], p[2 * u][1], p[2 * u][2], p[2 * u][3], p[2 * u + 1][0], p[2 * u + 1][1], p[2 * u + 1][2], p[2 * u + 1][3]};
-      f16x8 ph, pl;
-      split8h(px, ph, pl);
-#pragma unroll
-      for (int db = 0; db < 4; ++db) {
-        const float4 lo4 = vlo[u][db], hi4 = vhi[u][db];
-        const float vx[8] = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z, hi4.w};
-        f16x8 vh, vl;
-        split8h(vx, vh, vl);
-        o[db] = mfma3h(vh, vl, ph, pl, o[db]);
-      }
-    }
-  }
-};
+template <> struct AttnT<F32X3> : AttnSplit<SplitBF16> {};
+template <> struct AttnT<F16X3> : AttnSplit<SplitF16> {};
 
 // fp32 operands rounded to bf16 on the way into ONE bf16 MFMA per product (training in "bf16" precision: what bf16 autocast computes)
 struct BF16X1 {};
-template <> struct AttnT<BF16X1> {
-  using Store = float;
+template <> struct AttnT<BF16X1> : F32Rows {
   struct QReg { bf16x8 v[2]; };
   static __device__ __forceinline__ void loadQ(QReg& r, const float* row, int g) {
     const float4* p = reinterpret_cast<const float4*>(row + 16 * g);
     r.v[0] = cvt8(p[0], p[1]);
     r.v[1] = cvt8(p[2], p[3]);
   }
-  struct KReg { float4 v[4]; };
-  static __device__ __forceinline__ KReg loadK(const float* krow, int g) {
-    const float4* p = reinterpret_cast<const float4*>(krow + 16 * g);
-    KReg k;
-    k.v[0] = p[0]; k.v[1] = p[1]; k.v[2] = p[2]; k.v[3] = p[3];
-    return k;
-  }
-  static __device__ __forceinline__ f32x4 qk(const float* krow, int g, const QReg& q) { return qk(loadK(krow, g), q); }
   static __device__ __forceinline__ f32x4 qk(const KReg& k, const QReg& q) {
     f32x4 s = {0.f, 0.f, 0.f, 0.f};
     s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cvt8(k.v[0], k.v[1]), q.v[0], s, 0, 0, 0);
@@ -297,22 +209,15 @@ template <> struct AttnT<BF16X1> {
   }
   static __device__ __forceinline__ void pv(f32x4 (&o)[4], const float* vt_head, int64_t vt_ld, int kbase, int g, int dl,
                                             const f32x4 (&p)[4]) {
-    float4 vlo[2][4], vhi[2][4];                       // all 16 loads of the tile first: one round trip, not eight
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int db = 0; db < 4; ++db) {
-        const float* vr = vt_head + (int64_t)(db * 16 + dl) * vt_ld + kbase + 32 * u + 4 * g;
-        vlo[u][db] = *reinterpret_cast<const float4*>(vr);
-        vhi[u][db] = *reinterpret_cast<const float4*>(vr + 16);
-      }
+    VTile v;
+    loadV(v, vt_head, vt_ld, kbase, g, dl);
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       bf16x8 pb;
 #pragma unroll
       for (int j = 0; j < 8; ++j) pb[j] = (__bf16)p[2 * u + (j >> 2)][j & 3];
 #pragma unroll
-      for (int db = 0; db < 4; ++db) o[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cvt8(vlo[u][db], vhi[u][db]), pb, o[db], 0, 0, 0);
+      for (int db = 0; db < 4; ++db) o[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cvt8(v.lo[u][db], v.hi[u][db]), pb, o[db], 0, 0, 0);
     }
   }
 };
@@ -339,6 +244,22 @@ __device__ __forceinline__ bool attn_tile_of(int xcd_map, int heads, int& qt, in
 // grid serves (heads and B are checked against 65535 separately)
 static bool attn_xcd_ok(int heads, int B) { return ((long)heads * B + 7) / 8 * 8 <= 65535; }
 
+// Four consecutive head dimensions [col, col + 4) of output row `row` (the output is [rows][heads * 64]): acc * inv as fp32 or bf16,
+// row-major with stride ldo or in fragment order
+__device__ __forceinline__ void store_o4(void* O, int row, int col, int heads, int64_t ldo, int out_bf16, int out_packed, float4 acc, float inv) {
+  const int64_t off = out_packed ? packed_off(row, col, heads * 64, out_bf16 != 0) : (int64_t)row * ldo + col;
+  if (out_bf16) {
+    bf16x4 ob;
+    ob[0] = (__bf16)(acc.x * inv); ob[1] = (__bf16)(acc.y * inv); ob[2] = (__bf16)(acc.z * inv); ob[3] = (__bf16)(acc.w * inv);
+    st_out(reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(O) + off), ob);
+  } else {
+    st_out(reinterpret_cast<float4*>(reinterpret_cast<float*>(O) + off), make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv));
+  }
+}
+
+// One workgroup = 16 query rows of one head; its 4 waves split the 64-key tiles (tile t goes to wave t & 3), each with its own
+// online softmax; the partial (m, l, O^T) states are merged through LDS (wave w finishes d-block w) -- at N = 196 every wave
+// has ONE tile, so the dependent chain is 1 tile instead of 4 (fp32 mode: 21 -> 8 us per launch).
 template <typename TT>
 __global__ __launch_bounds__(256) void attention_kernel(const typename AttnT<TT>::Store* __restrict__ Q, int64_t sq, int64_t ldq,
                                                        const typename AttnT<TT>::Store* __restrict__ K, int64_t sk, int64_t ldk,
@@ -437,17 +358,9 @@ __global__ __launch_bounds__(256) void attention_kernel(const typename AttnT<TT>
   if (q0 + ql < Nq) {
     const int row = b * Nq + q0 + ql;
     const int col = h * 64 + db * 16 + 4 * g;
-    const int64_t off = out_packed ? packed_off(row, col, heads * 64, out_bf16 != 0) : (int64_t)row * ldo + col;
-    if (out_bf16) {
-      bf16x4 ob;
-      ob[0] = (__bf16)(acc.x * inv); ob[1] = (__bf16)(acc.y * inv); ob[2] = (__bf16)(acc.z * inv); ob[3] = (__bf16)(acc.w * inv);
-      st_out(reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(O) + off), ob);
-    } else {
-      st_out(reinterpret_cast<float4*>(reinterpret_cast<float*>(O) + off), make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv));
-    }
+    store_o4(O, row, col, heads, ldo, out_bf16, out_packed, acc, inv);
   }
 }
-
 
 // ------------------------------------------------------------------ bf16, fragment-order operands, prefetching
 struct KFrag { bf16x8 v[2]; };
@@ -735,18 +648,10 @@ __global__ __launch_bounds__(256, MINW) void attention_packed_kernel(const __bf1
       // (grouped launches keep each problem's packed rows 16-aligned)
       const int row = o_group > 0 ? (b / o_group) * o_group_rows + (b % o_group) * Nq + q : b * Nq + q;
       const int col = h * 64 + db * 16 + 4 * g;
-      const int64_t off = out_packed ? packed_off(row, col, heads * 64, out_bf16 != 0) : (int64_t)row * ldo + col;
-      if (out_bf16) {
-        bf16x4 ob;
-        ob[0] = (__bf16)(acc.x * inv); ob[1] = (__bf16)(acc.y * inv); ob[2] = (__bf16)(acc.z * inv); ob[3] = (__bf16)(acc.w * inv);
-        st_out(reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(O) + off), ob);
-      } else {
-        st_out(reinterpret_cast<float4*>(reinterpret_cast<float*>(O) + off), make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv));
-      }
+      store_o4(O, row, col, heads, ldo, out_bf16, out_packed, acc, inv);
     }
   }
 }
-
 
 // ------------------------------------------------------------------ training: the backward of softmax(q k^T * scale) v
 // Same register layout as the forward (a lane owns one row of the 16-row block its workgroup works on; the other axis is streamed
@@ -928,6 +833,38 @@ __global__ __launch_bounds__(256) void attention_bwd_dkv_kernel(AttnBwdArgs a) {
   }
 }
 
+// ------------------------------------------------------------------ host side: one grid rule, one launch per kernel family
+// the XCD map where its pairs fit grid.y (attn_xcd_ok), the plain (q tiles, heads, B) grid otherwise
+struct AttnGrid { dim3 grid; int xcd_map; };
+AttnGrid attn_grid(int q_tiles, int heads, int B) {
+  if (attn_xcd_ok(heads, B)) return {dim3(q_tiles, (heads * B + 7) / 8 * 8, 1), heads * B};
+  return {dim3(q_tiles, heads, B), 0};
+}
+
+// row-major operands in AttnT<TT>::Store; lse: the training forward's softmax statistics, or null
+template <typename TT>
+void launch_rows(const void* q, int64_t sq, int64_t ldq, const void* k, int64_t sk, int64_t ldk, const void* vt, int64_t vt_ld, void* out,
+                 int64_t ldo, int out_bf16, int out_packed, int B, int heads, int Nq, int Nk, float scale, float* lse, void* stream) {
+  using S = typename AttnT<TT>::Store;
+  const AttnGrid G = attn_grid((Nq + 15) / 16, heads, B);
+  hipLaunchKernelGGL(attention_kernel<TT>, G.grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), static_cast<const S*>(q), sq, ldq,
+                     static_cast<const S*>(k), sk, ldk, static_cast<const S*>(vt), vt_ld, out, ldo, out_bf16, out_packed, heads, Nq, Nk,
+                     scale, lse, G.xcd_map);
+}
+
+// fragment-order bf16 operands, QB query blocks per workgroup; QNKB > 0: q comes from the projection `qa` (qp unused)
+template <int QB, int MINW, int QNKB = 0>
+void launch_packed(const void* qp, int q_cols, int q_col0, int npad_q, const void* kp, int k_cols, int k_col0, int npad_k, const void* vtp,
+                   void* out, int64_t ldo, int out_bf16, int out_packed, int B, int heads, int Nq, int Nk, float scale, int o_group,
+                   int o_group_rows, const QProjArgs& qa, void* stream) {
+  constexpr int lds = (4 * QB * 4 * 64 * 4 + 2 * 4 * QB * 64) * 4;       // the merge scratch: sh_o, sh_m, sh_l of the kernel
+  static_assert(QNKB == 0 || lds >= 4 * 16 * 68 * 4, "the q projection's partial tiles fit the merge scratch");
+  const AttnGrid G = attn_grid((Nq + 16 * QB - 1) / (16 * QB), heads, B);
+  hipLaunchKernelGGL((attention_packed_kernel<QB, MINW, QNKB>), G.grid, dim3(256), lds, reinterpret_cast<hipStream_t>(stream),
+                     static_cast<const __bf16*>(qp), q_cols, q_col0, npad_q, static_cast<const __bf16*>(kp), k_cols, k_col0, npad_k,
+                     static_cast<const __bf16*>(vtp), out, ldo, out_bf16, out_packed, heads, Nq, Nk, scale, o_group, o_group_rows,
+                     G.xcd_map, qa);
+}
 
 }  // namespace
 
@@ -938,27 +875,15 @@ extern "C" int sp3_attention_ex(const void* q, int64_t sq, int64_t ldq, const vo
   SP3_CHECK(B > 0 && heads > 0 && Nq > 0 && Nk > 0, "sp3_attention: bad shape");
   SP3_CHECK(vt_ld >= ((Nk + 63) / 64) * 64 && vt_ld % 8 == 0, "sp3_attention: vt_ld=%lld must be >= Nk padded to 64", (long long)vt_ld);
   SP3_CHECK(ldq % 8 == 0 && ldk % 8 == 0 && (out_packed || ldo % 4 == 0), "sp3_attention: row strides must keep 16-byte alignment");
-  SP3_CHECK(dtype == SP3_F32 || dtype == SP3_BF16 || dtype == 2 || dtype == 3,
+  SP3_CHECK(dtype == SP3_F32 || dtype == SP3_BF16 || dtype == SP3_ATTN_F32X3 || dtype == SP3_ATTN_F16X3,
             "sp3_attention: bad dtype %d (0 fp32, 1 bf16, 2 / 3: fp32 operands with bf16x3 / fp16x3 split products)", dtype);
-  const int xcd_map = attn_xcd_ok(heads, B) ? heads * B : 0;
-  dim3 grid((Nq + 15) / 16, xcd_map ? (heads * B + 7) / 8 * 8 : heads, xcd_map ? 1 : B);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == SP3_BF16)
-    hipLaunchKernelGGL(attention_kernel<__bf16>, grid, dim3(256), 0, st, reinterpret_cast<const __bf16*>(q), sq, ldq,
-                       reinterpret_cast<const __bf16*>(k), sk, ldk, reinterpret_cast<const __bf16*>(vt), vt_ld, out, ldo,
-                       out_bf16, out_packed, heads, Nq, Nk, scale, (float*)nullptr, xcd_map);
-  else if (dtype == 3)
-    hipLaunchKernelGGL(attention_kernel<F16X3>, grid, dim3(256), 0, st, reinterpret_cast<const float*>(q), sq, ldq,
-                       reinterpret_cast<const float*>(k), sk, ldk, reinterpret_cast<const float*>(vt), vt_ld, out, ldo, out_bf16,
-                       out_packed, heads, Nq, Nk, scale, (float*)nullptr, xcd_map);
-  else if (dtype == 2)
-    hipLaunchKernelGGL(attention_kernel<F32X3>, grid, dim3(256), 0, st, reinterpret_cast<const float*>(q), sq, ldq,
-                       reinterpret_cast<const float*>(k), sk, ldk, reinterpret_cast<const float*>(vt), vt_ld, out, ldo, out_bf16,
-                       out_packed, heads, Nq, Nk, scale, (float*)nullptr, xcd_map);
-  else
-    hipLaunchKernelGGL(attention_kernel<float>, grid, dim3(256), 0, st, reinterpret_cast<const float*>(q), sq, ldq,
-                       reinterpret_cast<const float*>(k), sk, ldk, reinterpret_cast<const float*>(vt), vt_ld, out, ldo, out_bf16,
-                       out_packed, heads, Nq, Nk, scale, (float*)nullptr, xcd_map);
+  auto launch = launch_rows<__bf16>;
+  switch (dtype) {
+    case SP3_ATTN_F16X3: launch = launch_rows<F16X3>; break;
+    case SP3_ATTN_F32X3: launch = launch_rows<F32X3>; break;
+    case SP3_F32: launch = launch_rows<float>; break;
+  }
+  launch(q, sq, ldq, k, sk, ldk, vt, vt_ld, out, ldo, out_bf16, out_packed, B, heads, Nq, Nk, scale, nullptr, stream);
   SP3_LAUNCH_CHECK("sp3_attention");
   return 0;
 }
@@ -979,23 +904,10 @@ extern "C" int sp3_attention_packed(const void* qp, int q_cols, int q_col0, int 
   SP3_CHECK(q_cols % 64 == 0 && k_cols % 64 == 0 && q_col0 % 64 == 0 && k_col0 % 64 == 0, "sp3_attention_packed: column geometry");
   SP3_CHECK(out_packed || ldo % 4 == 0, "sp3_attention_packed: ldo");
   SP3_CHECK(o_group == 0 || (o_group > 0 && B % o_group == 0 && o_group_rows >= o_group * Nq), "sp3_attention_packed: output grouping");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int np = heads * B, xcd_map = attn_xcd_ok(heads, B) ? np : 0;
-  const dim3 tail = xcd_map ? dim3((np + 7) / 8 * 8, 1) : dim3(heads, B);
   // two query blocks per workgroup once the grid still fills the chip that way (profiles/r05_attn_long_variants.txt)
-  if (Nq >= 512) {
-    constexpr int QB = 2, lds = (4 * QB * 4 * 64 * 4 + 2 * 4 * QB * 64) * 4;
-    hipLaunchKernelGGL((attention_packed_kernel<QB, 3>), dim3((Nq + 16 * QB - 1) / (16 * QB), tail.x, tail.y), dim3(256), lds, st,
-                       reinterpret_cast<const __bf16*>(qp), q_cols, q_col0, npad_q, reinterpret_cast<const __bf16*>(kp), k_cols, k_col0,
-                       npad_k, reinterpret_cast<const __bf16*>(vtp), out, ldo, out_bf16, out_packed, heads, Nq, Nk, scale, o_group, o_group_rows,
-                       xcd_map, QProjArgs{});
-  } else {
-    constexpr int QB = 1, lds = (4 * QB * 4 * 64 * 4 + 2 * 4 * QB * 64) * 4;
-    hipLaunchKernelGGL((attention_packed_kernel<QB, 4>), dim3((Nq + 15) / 16, tail.x, tail.y), dim3(256), lds, st,
-                       reinterpret_cast<const __bf16*>(qp), q_cols, q_col0, npad_q, reinterpret_cast<const __bf16*>(kp), k_cols, k_col0,
-                       npad_k, reinterpret_cast<const __bf16*>(vtp), out, ldo, out_bf16, out_packed, heads, Nq, Nk, scale, o_group, o_group_rows,
-                       xcd_map, QProjArgs{});
-  }
+  const auto launch = Nq >= 512 ? launch_packed<2, 3> : launch_packed<1, 4>;
+  launch(qp, q_cols, q_col0, npad_q, kp, k_cols, k_col0, npad_k, vtp, out, ldo, out_bf16, out_packed, B, heads, Nq, Nk, scale, o_group,
+         o_group_rows, QProjArgs{}, stream);
   SP3_LAUNCH_CHECK("sp3_attention_packed");
   return 0;
 }
@@ -1021,15 +933,8 @@ extern "C" int sp3_attention_packed_qproj(const sp3_attn_qproj_desc* dp, void* s
   qa.ln_s = d.ln_s; qa.bias = d.bias; qa.v_gs = d.vec_group_stride;
   qa.pos = d.pos; qa.cos = d.rope_cos; qa.sin = d.rope_sin;
   qa.eps = d.ln_eps; qa.group_imgs = d.o_group; qa.img_tokens = d.Nq;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int np = d.heads * d.B, xcd_map = attn_xcd_ok(d.heads, d.B) ? np : 0;
-  const dim3 tail = xcd_map ? dim3((np + 7) / 8 * 8, 1) : dim3(d.heads, d.B);
-  constexpr int QB = 1, lds = (4 * QB * 4 * 64 * 4 + 2 * 4 * QB * 64) * 4;
-  static_assert(lds >= 4 * 16 * 68 * 4, "the q projection's partial tiles fit the merge scratch");
-  hipLaunchKernelGGL((attention_packed_kernel<QB, 2, 12>), dim3((d.Nq + 15) / 16, tail.x, tail.y), dim3(256), lds, st,
-                     (const __bf16*)nullptr, 0, 0, 16, reinterpret_cast<const __bf16*>(d.kp), d.k_cols, d.k_col0, d.npad_k,
-                     reinterpret_cast<const __bf16*>(d.vtp), d.out, d.ldo, d.out_bf16, d.out_packed, d.heads, d.Nq, d.Nk, d.scale, d.o_group,
-                     d.o_group_rows, xcd_map, qa);
+  launch_packed<1, 2, 12>(nullptr, 0, 0, 16, d.kp, d.k_cols, d.k_col0, d.npad_k, d.vtp, d.out, d.ldo, d.out_bf16, d.out_packed, d.B, d.heads,
+                          d.Nq, d.Nk, d.scale, d.o_group, d.o_group_rows, qa, stream);
   SP3_LAUNCH_CHECK("sp3_attention_packed_qproj");
   return 0;
 }
@@ -1041,13 +946,8 @@ extern "C" int sp3_attention_train_fwd(const float* q, int64_t sq, int64_t ldq, 
   SP3_CHECK(B > 0 && heads > 0 && Nq > 0 && Nk > 0 && B <= 65535 && heads <= 65535, "sp3_attention_train_fwd: bad shape");
   SP3_CHECK(vt_ld >= ((Nk + 63) / 64) * 64 && vt_ld % 8 == 0, "sp3_attention_train_fwd: vt_ld=%lld must be >= Nk padded to 64", (long long)vt_ld);
   SP3_CHECK(ldq % 4 == 0 && ldk % 4 == 0 && ldo % 4 == 0 && sq % 4 == 0 && sk % 4 == 0, "sp3_attention_train_fwd: strides must keep 16-byte alignment");
-  const int xcd_map = attn_xcd_ok(heads, B) ? heads * B : 0;
-  dim3 grid((Nq + 15) / 16, xcd_map ? (heads * B + 7) / 8 * 8 : heads, xcd_map ? 1 : B);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (bf16_products)
-    hipLaunchKernelGGL(attention_kernel<BF16X1>, grid, dim3(256), 0, st, q, sq, ldq, k, sk, ldk, vt, vt_ld, (void*)out, ldo, 0, 0, heads, Nq, Nk, scale, lse, xcd_map);
-  else
-    hipLaunchKernelGGL(attention_kernel<float>, grid, dim3(256), 0, st, q, sq, ldq, k, sk, ldk, vt, vt_ld, (void*)out, ldo, 0, 0, heads, Nq, Nk, scale, lse, xcd_map);
+  const auto launch = bf16_products ? launch_rows<BF16X1> : launch_rows<float>;
+  launch(q, sq, ldq, k, sk, ldk, vt, vt_ld, out, ldo, 0, 0, B, heads, Nq, Nk, scale, lse, stream);
   SP3_LAUNCH_CHECK("sp3_attention_train_fwd");
   return 0;
 }

@@ -49,6 +49,35 @@ __device__ __forceinline__ bf16x8 cvt8(const float4 a, const float4 b) {
   return r;
 }
 
+// The two-way operand splits that define the "f32x3" and "f16x3" product modes on fp32 operands: the 8 fp32 values a lane holds of a
+// k-block as (hi, lo) halves for three MFMAs per product (hi.hi + hi.lo + lo.hi; the lo.lo term is dropped).  The GEMM
+// (gemm.hip MM<float, float>::mma_x3 / mma_h3) and the attention (attention.hip AttnSplit) are at parity in those modes because both
+// take the split from here.  The result type selects the arithmetic:
+//   bf16x8: x = hi + lo, hi = bf16(x), lo = bf16(x - hi): 16 operand bits, the dropped term is 2^-16 relative;
+//   f16x8 : x = hi + lo * 2^-11, hi = fp16(x), lo = fp16((x - hi) * 2^11): 22 operand bits, every product exact in fp32; the consumer
+//           scales the cross terms by 2^-11.  Operands must stay below fp16's 65504.
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+__device__ __forceinline__ void split_hi_lo(const float (&x)[8], bf16x8& hi, bf16x8& lo) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const __bf16 h = (__bf16)x[e];
+    hi[e] = h;
+    lo[e] = (__bf16)(x[e] - (float)h);
+  }
+}
+__device__ __forceinline__ void split_hi_lo(const float (&x)[8], f16x8& hi, f16x8& lo) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const _Float16 h = (_Float16)x[e];
+    hi[e] = h;
+    lo[e] = (_Float16)((x[e] - (float)h) * 2048.0f);
+  }
+}
+template <typename V8> __device__ __forceinline__ void split_hi_lo(const float4& x0, const float4& x1, V8& hi, V8& lo) {
+  const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+  split_hi_lo(x, hi, lo);
+}
+
 __device__ __forceinline__ float4 relu4(float4 v) {
   v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
   return v;

@@ -198,24 +198,15 @@ template <> struct MM<float, float> {
   // v_mfma_f32_16x16x32_bf16 (hi.hi + hi.lo + lo.hi; the dropped lo.lo term is 2^-16 relative) instead of eight
   // v_mfma_f32_16x16x4_f32: products carry 16 mantissa bits (TF32, which the reference enables on its own GPUs, carries 10),
   // accumulation stays fp32.  The fp32 MFMA rate, not the bytes, bounds the fp32 GEMMs of the per-frame step.
-  static __device__ __forceinline__ void split8(const float4& x0, const float4& x1, bf16x8& hi, bf16x8& lo) {
-    const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const __bf16 h = (__bf16)x[e];
-      hi[e] = h;
-      lo[e] = (__bf16)(x[e] - (float)h);
-    }
-  }
   template <int MF, int NF>
   static __device__ __forceinline__ void mma_x3(f32x4 (&acc)[MF][NF], const AReg (&a)[MF], const WReg (&w)[NF]) {
     bf16x8 wh[NF], wl[NF];
 #pragma unroll
-    for (int n = 0; n < NF; ++n) split8(w[n].v[0], w[n].v[1], wh[n], wl[n]);
+    for (int n = 0; n < NF; ++n) split_hi_lo(w[n].v[0], w[n].v[1], wh[n], wl[n]);
 #pragma unroll
     for (int m = 0; m < MF; ++m) {
       bf16x8 ah, al;
-      split8(a[m].v[0], a[m].v[1], ah, al);
+      split_hi_lo(a[m].v[0], a[m].v[1], ah, al);
 #pragma unroll
       for (int n = 0; n < NF; ++n) {
         acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, wh[n], acc[m][n], 0, 0, 0);
@@ -263,16 +254,6 @@ template <> struct MM<float, float> {
   // bits (bf16 halves: 16) for the same three MFMAs -- hh into the main accumulator, hl + lh into a second one that is scaled by
   // 2^-11 when the accumulators leave the K loop.  Every product is exact in fp32 (11 x 11 bits), accumulation is fp32.  Operands
   // must stay below fp16's 65504 (activations and weights of this model do; the fp32 / f32x6 modes have no such limit).
-  typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-  static __device__ __forceinline__ void split8h(const float4& x0, const float4& x1, f16x8& h, f16x8& l) {
-    const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const _Float16 hh = (_Float16)x[e];
-      h[e] = hh;
-      l[e] = (_Float16)((x[e] - (float)hh) * 2048.0f);
-    }
-  }
   // WPRE (sp3_gemm_desc.w_packed == 2): the weight already IS its two fp16 planes -- the first 16-byte half of a lane's fragment holds
   // h of its 8 k, the second half l (split once at pack time, ops.PackedWeight(halves=True): the same two conversions, so the same
   // bits) -- and the split of W leaves the K loop (a third of the loop's VALU work on the 32x32 wave tile)
@@ -285,13 +266,13 @@ template <> struct MM<float, float> {
         wh[n] = __builtin_bit_cast(f16x8, w[n].v[0]);
         wl[n] = __builtin_bit_cast(f16x8, w[n].v[1]);
       } else {
-        split8h(w[n].v[0], w[n].v[1], wh[n], wl[n]);
+        split_hi_lo(w[n].v[0], w[n].v[1], wh[n], wl[n]);
       }
     }
 #pragma unroll
     for (int m = 0; m < MF; ++m) {
       f16x8 ah, al;
-      split8h(a[m].v[0], a[m].v[1], ah, al);
+      split_hi_lo(a[m].v[0], a[m].v[1], ah, al);
 #pragma unroll
       for (int n = 0; n < NF; ++n) {
         accx[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, wh[n], accx[m][n], 0, 0, 0);

@@ -476,7 +476,7 @@ class Engine:
                         ops.proj_rope_vt(xp[o][cur], w[pre + "ckv.w"], w[pre + "ckv.b"], kbuf, 0, vt, npk, M=Ro, N=2 * D, K=D,
                                          lda=D, rope_cols=D, pos=pos[o], cos=self.cos, sin=self.sin, tokens=Po, heads=Hh,
                                          qkv_packed=True, ln=lnk)
-                        if P < 512 and D == 768 and ops.LEAN:
+                        if ops.attention_takes_qproj(P, D):
                             # (the q projection inside the attention launch, as in decoder_grouped: one group of B images)
                             ops.attention_packed_qproj(xq, stq, w[pre + "cq.w"], w[pre + "cq.s"], w[pre + "cq.b"], pos[s], self.cos, self.sin,
                                                        kbuf, D, 0, npk, vt, ao, D, B=B, heads=Hh, Nq=P, Nk=Po, scale=64 ** -0.5,
@@ -594,7 +594,7 @@ class Engine:
                                  scale=64 ** -0.5, o_group=B, o_group_rows=Rp)
             upd(ao, D, "proj", xi, stq, xq)
             # cross attention (:188-189): q from this side (norm2); k/v of the OTHER side's previous layer were projected above
-            if P < 512 and D == 768 and ops.LEAN:
+            if ops.attention_takes_qproj(P, D):
                 # the q projection inside the attention launch: one launch less per layer (csrc/attention.hip attn_qproj)
                 ops.attention_packed_qproj(xq, stq, w[g + "cq.w"], w[g + "cq.s"], w[g + "cq.b"], pos, self.cos, self.sin, ckp, D, 0, npad, cvtp,
                                            ao, D, B=2 * B, heads=Hh, Nq=P, Nk=P, scale=64 ** -0.5, o_group=B, o_group_rows=Rp, eps=1e-6,

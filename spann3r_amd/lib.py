@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SP3_LIB_PATH") or os.path.join(_HERE, "libspann3r_hip.so")   # override: kernel-variant experiments
 
 F32, BF16 = 0, 1
+ATTN_F32X3, ATTN_F16X3 = 2, 3        # sp3_attention only: fp32 operands, split products (SP3_ATTN_*)
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
 EPI_PLAIN, EPI_ROPE_VT, EPI_PIXSHUF, EPI_PARTIAL = 0, 1, 2, 3
 LOAD_PLAIN, LOAD_CONV3X3, LOAD_SOFTMAX = 0, 1, 2

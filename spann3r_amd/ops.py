@@ -10,7 +10,7 @@ import ctypes as C
 import torch
 
 from . import lib as L
-from .lib import GemmDesc, F32, BF16, ACT_NONE, ACT_GELU, ACT_RELU  # noqa: F401
+from .lib import GemmDesc, F32, BF16, ATTN_F32X3, ATTN_F16X3, ACT_NONE, ACT_GELU, ACT_RELU  # noqa: F401
 
 
 # ----------------------------------------------------------------------------- optional per-launch profiler
@@ -708,13 +708,20 @@ def rope_2d(tokens, positions, base, fwd):
     return tokens
 
 
+# sp3_attention's code for fp32 operands by product mode: the two split modes have their own kernels, every other mode runs exact fp32
+_ATTN_F32_CODE = {PRODUCT_MODES["f32x3"]: ATTN_F32X3, PRODUCT_MODES["f16x3"]: ATTN_F16X3}
+
+
 def attention(q, sq, ldq, k, sk, ldk, vt, vt_ld, out, ldo, *, B, heads, Nq, Nk, scale):
     es = vt.element_size()
+    code = wdtype_of(vt)
+    if code == F32:
+        code = _ATTN_F32_CODE.get(get_product_mode(), F32)
     _timed("attention<%s>" % ("f32" if es == 4 else "bf16"), 4.0 * B * heads * Nq * Nk * 64,
            B * heads * 64.0 * (es * (Nq + 2 * Nk) + 4 * Nq),
            lambda: L.check(L.load().sp3_attention_ex(q.data_ptr(), sq, ldq, k.data_ptr(), sk, ldk, vt.data_ptr(), vt_ld,
                                                      out.data_ptr(), ldo, int(out.dtype == torch.bfloat16), _is_packed(out),
-                                                     B, heads, Nq, Nk, float(scale), (2 if (get_product_mode() == 1 and es == 4) else 3 if (get_product_mode() == 4 and es == 4) else wdtype_of(vt)),
+                                                     B, heads, Nq, Nk, float(scale), code,
                                                      L.stream_ptr()),
                            "sp3_attention"))
     return out
@@ -730,6 +737,12 @@ def attention_packed(qp, q_cols, q_col0, npad_q, kp, k_cols, k_col0, npad_k, vtp
                                                          float(scale), o_group, o_group_rows, L.stream_ptr()),
                            "sp3_attention_packed"))
     return out
+
+
+def attention_takes_qproj(Nq, D):
+    """whether a cross-attention of Nq query rows at width D takes its q projection inside the launch (attention_packed_qproj) instead
+    of a projection GEMM in front of attention_packed: the shapes sp3_attention_packed_qproj accepts, on the lean path only"""
+    return Nq < 512 and D == 768 and LEAN
 
 
 def attention_packed_qproj(xq, stats, Wq, ln_s, bias, pos, cos, sin, kp, k_cols, k_col0, npad_k, vtp, out, ldo, *, B, heads, Nq, Nk, scale,

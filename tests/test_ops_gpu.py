@@ -518,7 +518,11 @@ def test_proj_rope_vt(wdt):
 
 
 @pytest.mark.parametrize("wdt", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("B,heads,Nq,Nk", [(1, 16, 196, 196), (2, 12, 20, 20), (1, 12, 50, 300), (1, 2, 1024, 1024), (2, 3, 17, 65)])
+@pytest.mark.parametrize("B,heads,Nq,Nk", [(1, 16, 196, 196), (2, 12, 20, 20), (1, 12, 50, 300), (1, 2, 1024, 1024), (2, 3, 17, 65),
+                                           # the plain (query tiles, heads, B) grid, which serves once the (head, batch) pairs, padded to a multiple
+                                           # of 8, no longer fit grid.y: 65530 pairs is the fewest with heads and B each within a grid dimension and
+                                           # ragged 16-row / 64-key tiles left.  Hence the size: the zero-padded V^T alone is 65530 x 64 x 64 (1 GB in fp32)
+                                           (32765, 2, 2, 3)])
 def test_attention(wdt, B, heads, Nq, Nk):
     ops = _ops()
     C = heads * 64
