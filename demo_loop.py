@@ -25,6 +25,12 @@ def main():
                     "estimated focal of the first camera (demo.py:147-151)")
     ap.add_argument("--conf_thresh", type=float, default=1e-3)
     ap.add_argument("--offline", action="store_true", help="demo.py --offline: DUSt3R pair graph + next-best-view order")
+    ap.add_argument("--vis", default=None, metavar="DIR", help="demo.py --vis, headless: write DIR/render_frames/frame_XXX.png (the cloud as "
+                    "it grows, drawn on the device) and the pts/ imgs/ confs/ folders of vis_pred_and_imgs (spann3r_amd.vis)")
+    ap.add_argument("--dynamic", action="store_true", help="demo.py --dynamic: each rendered frame shows its own points alone")
+    ap.add_argument("--vis_camera", default=None, metavar="camera.json", help="render from this Open3D PinholeCameraParameters file "
+                    "(e.g. one picked with the reference's find_render_cam) instead of fitting a camera to the cloud")
+    ap.add_argument("--point_size", type=int, default=1)
     args = ap.parse_args()
     cfg = TINY if args.tiny else FULL
     device = "cuda"
@@ -75,16 +81,32 @@ def main():
         if images_all.shape[1:3] != pts_all.shape[1:3]:
             images_all = images_all.swapaxes(1, 2)                                # portrait frames were rectified to landscape
         points, colours = confident_points(pts_all, conf_all, args.conf_thresh, images_all)
+        import os
+        os.makedirs(os.path.dirname(os.path.abspath(args.save_ply)), exist_ok=True)
         write_ply(args.save_ply, points, colours)
         print("wrote %d of %d points to %s" % (len(points), conf_all.numel(), args.save_ply))
         if focal.item() > 1e-3:                                                 # (seeded random weights give no geometry at all)
             poses_all, inliers = estimate_poses(pts_all, focal, (W / 2, H / 2))     # demo.py:170-186 (PnP-RANSAC per frame)
-            import os
             tj = os.path.join(os.path.dirname(os.path.abspath(args.save_ply)), "transforms.json")
             save_transforms(tj, transforms_json(H, W, focal, list(poses_all), os.path.basename(args.save_ply)))
             print("wrote %d camera poses to %s (inlier fractions %.2f..%.2f)" % (len(poses_all), tj, inliers.min(), inliers.max()))
         else:
             print("degenerate pointmaps (no checkpoint loaded): poses / transforms.json skipped")
+    if args.vis:                                                                  # demo.py:221-225
+        from spann3r_amd import vis
+        pts_all = torch.cat([p["pts3d" if j == 0 else "pts3d_in_other_view"] for j, p in enumerate(preds)]).float()
+        conf_all = torch.cat([p["conf"] for p in preds]).float()
+        conf_sig_all = (conf_all - 1) / conf_all                                  # demo.py:213
+        images_all = (torch.cat([v["img"] for v in batch]).permute(0, 2, 3, 1).float() + 1.0) / 2.0
+        if images_all.shape[1:3] != pts_all.shape[1:3]:
+            images_all = images_all.swapaxes(1, 2)
+        camera = (vis.load_camera(args.vis_camera) if args.vis_camera else
+                  vis.fit_camera(pts_all, conf=conf_all, conf_thresh=args.conf_thresh))      # stands in for find_render_cam
+        vis.render_frames(pts_all, images_all, camera, args.vis, conf_all=conf_all, conf_thresh=args.conf_thresh, dynamic=args.dynamic,
+                          point_size=args.point_size)
+        vis.vis_pred_and_imgs(pts_all, args.vis, images_all=images_all, conf_all=conf_sig_all)
+        print("wrote %d rendered frames (%dx%d%s) and pts/ imgs/ confs/ to %s" %
+              (len(pts_all), camera.width, camera.height, ", dynamic" if args.dynamic else "", args.vis))
     pts = preds[-1]["pts3d_in_other_view"]
     print("last frame: pts3d_in_other_view", tuple(pts.shape), "conf mean %.3f" % float(preds[-1]["conf"].mean()))
 

@@ -685,6 +685,45 @@ int64_t sp3_sum_count_ws_bytes(int64_t n);
 int sp3_sum_count_f32(const float* x, int64_t n, float thresh, void* ws, double* out2, void* stream);
 int sp3_normal_dot(const float* na, const float* nb, const int* idx, int64_t n, int gather_a, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Headless point-cloud rendering (demo.py:221-225, spann3r/tools/vis.py; spann3r_amd/vis.py drives these).
+ *
+ * sp3_render_cam: a pinhole camera in the OpenCV convention of the rest of the package (+z forward, pixel centres at integer
+ *   coordinates): world-to-camera R (row-major) and t, intrinsics, image size, z_near >= 0 and the square point size (1..8).
+ * Projection rule: Xc = R X + t in fp32, every multiply and add rounded on its own, summed left to right.  A point is culled when
+ *   it or Xc is not finite or Xc.z <= z_near.  Otherwise u = fx Xc.x / Xc.z + cx, v = fy Xc.y / Xc.z + cy, its pixel is
+ *   (floor(u + 0.5), floor(v + 0.5)) and its footprint the point_size x point_size square of pixels whose top-left corner is
+ *   pixel - (point_size - 1) / 2 (integer division), clipped to the image.
+ * The z-buffer: one uint64 key per pixel, (bit pattern of fp32 Xc.z) << 32 | global point index; all-ones = empty.
+ * sp3_render_clear   : every key = all-ones.
+ * sp3_render_splat   : one point per lane; point i (global index index_base + i) does an agent-scope 64-bit unsigned atomic min of its
+ *   key on every pixel of its footprint: the nearest point wins, at equal depth the lowest index, whatever the arrival order.
+ *   conf (nullable, fp32 [n]): only points with (c - 1) / c > conf_thresh are drawn (the reference's mask, demo.py:213).
+ *   index_base + n must stay below 2^32 - 1.  n = 0 is a no-op.
+ * sp3_render_resolve : per pixel, index_out = low 32 bits of the key (-1: empty), depth_out = the fp32 of its high bits (+inf: empty),
+ *   rgb_out uint8 [H, W, 3] = the low three bytes of rgba[index] (background, packed the same way, when empty).  depth_out and
+ *   index_out may be null.
+ * sp3_pack_rgba8     : rgba[i] = r | g << 8 | b << 16 | 255 << 24 of img fp32 [n, 3], channel = clamp(floor(c * 255 + 0.5), 0, 255).
+ * sp3_colorize_hsv   : out uint8 [n, 3] = trunc(255 * hsv_to_rgb(1 - x)), x fp32 [n, 3] in [0, 1]; matplotlib.colors.hsv_to_rgb's
+ *   formula in fp32, every operation rounded on its own.
+ * sp3_colorize_lut   : out uint8 [n, 4] = lut[clamp(trunc(x * 256), 0, 255)], lut uint8 [256, 4]; lut and out 4-byte aligned. */
+typedef struct {
+  float R[9];
+  float t[3];
+  float fx, fy, cx, cy;
+  int width, height;
+  float z_near;
+  int point_size;
+} sp3_render_cam;
+int sp3_render_clear(uint64_t* keys, int64_t pixels, void* stream);
+int sp3_render_splat(const float* pts, const float* conf, float conf_thresh, int64_t n, int64_t index_base, const sp3_render_cam* cam,
+                     uint64_t* keys, void* stream);
+int sp3_render_resolve(const uint64_t* keys, const uint32_t* rgba, const sp3_render_cam* cam, uint32_t background, uint8_t* rgb_out,
+                       float* depth_out, int32_t* index_out, void* stream);
+int sp3_pack_rgba8(const float* img, int64_t n, uint32_t* rgba, void* stream);
+int sp3_colorize_hsv(const float* x, int64_t n, uint8_t* out, void* stream);
+int sp3_colorize_lut(const float* x, int64_t n, const uint8_t* lut, uint8_t* out, void* stream);
+
 /* small utilities */
 /* n (1..8) contiguous device-to-device copies in one launch; every copy 16-byte aligned and a multiple of 16 bytes.
  * (The sequence loop's per-frame bookkeeping -- torch .clone() / slice assignments around spann3r/model.py:523-531.) */

@@ -109,6 +109,12 @@ class NnGrid(C.Structure):
                 ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32)]
 
 
+class RenderCam(C.Structure):
+    """sp3_render_cam (include/spann3r_hip.h)"""
+    _fields_ = [("R", C.c_float * 9), ("t", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("width", C.c_int32), ("height", C.c_int32), ("z_near", C.c_float), ("point_size", C.c_int32)]
+
+
 _lib = None
 
 _PROTOS = {
@@ -232,6 +238,12 @@ _PROTOS = {
     "sp3_icp_accum": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     "sp3_sum_count_f32": [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p],
     "sp3_normal_dot": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p],
+    "sp3_render_clear": [C.c_void_p, C.c_int64, C.c_void_p],
+    "sp3_render_splat": [C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_int64, C.POINTER(RenderCam), C.c_void_p, C.c_void_p],
+    "sp3_render_resolve": [C.c_void_p, C.c_void_p, C.POINTER(RenderCam), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_pack_rgba8": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "sp3_colorize_hsv": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "sp3_colorize_lut": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
 }
 EXPORTS = sorted(list(_PROTOS) + ["sp3_last_error", "sp3_version", "sp3_conf_loss_ws_bytes", "sp3_ssi_loss_ws_bytes", "sp3_sumsq_blocks", "sp3_colsum_rows_ws",
                                   "sp3_nn_query_ws_bytes", "sp3_icp_accum_ws_bytes", "sp3_sum_count_ws_bytes"])
