@@ -31,6 +31,11 @@ def main():
     ap.add_argument("--vis_camera", default=None, metavar="camera.json", help="render from this Open3D PinholeCameraParameters file "
                     "(e.g. one picked with the reference's find_render_cam) instead of fitting a camera to the cloud")
     ap.add_argument("--point_size", type=int, default=1)
+    ap.add_argument("--vis_surface", action="store_true", help="with --vis: draw every frame as its triangle mesh (solid surfaces) "
+                    "instead of one pixel per point")
+    ap.add_argument("--save_glb", default=None, metavar="PATH", help="app.py's output: the confidence-masked reconstruction as one GLB, "
+                    "meshed and compacted on the device (spann3r_amd.mesh)")
+    ap.add_argument("--as_pointcloud", action="store_true", help="with --save_glb: app.py's as_pointcloud, points instead of a mesh")
     args = ap.parse_args()
     cfg = TINY if args.tiny else FULL
     device = "cuda"
@@ -103,10 +108,16 @@ def main():
         camera = (vis.load_camera(args.vis_camera) if args.vis_camera else
                   vis.fit_camera(pts_all, conf=conf_all, conf_thresh=args.conf_thresh))      # stands in for find_render_cam
         vis.render_frames(pts_all, images_all, camera, args.vis, conf_all=conf_all, conf_thresh=args.conf_thresh, dynamic=args.dynamic,
-                          point_size=args.point_size)
+                          point_size=args.point_size, surface=args.vis_surface)
         vis.vis_pred_and_imgs(pts_all, args.vis, images_all=images_all, conf_all=conf_sig_all)
         print("wrote %d rendered frames (%dx%d%s) and pts/ imgs/ confs/ to %s" %
-              (len(pts_all), camera.width, camera.height, ", dynamic" if args.dynamic else "", args.vis))
+              (len(pts_all), camera.width, camera.height, (", dynamic" if args.dynamic else "") + (", surface" if args.vis_surface else ""), args.vis))
+    if args.save_glb:                                                             # app.py:132-171
+        import os
+        from spann3r_amd import mesh
+        os.makedirs(os.path.dirname(os.path.abspath(args.save_glb)), exist_ok=True)
+        info = mesh.export_glb(args.save_glb, preds, batch, conf_thresh=args.conf_thresh, as_pointcloud=args.as_pointcloud)
+        print("wrote %d vertices, %d faces (%d bytes) to %s" % (info["vertices"], info["faces"], info["bytes"], args.save_glb))
     pts = preds[-1]["pts3d_in_other_view"]
     print("last frame: pts3d_in_other_view", tuple(pts.shape), "conf mean %.3f" % float(preds[-1]["conf"].mean()))
 

@@ -724,6 +724,61 @@ int sp3_pack_rgba8(const float* img, int64_t n, uint32_t* rgba, void* stream);
 int sp3_colorize_hsv(const float* x, int64_t n, uint8_t* out, void* stream);
 int sp3_colorize_lut(const float* x, int64_t n, const uint8_t* lut, uint8_t* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Pointmap meshes (app.py:68-105 pts3d_to_trimesh, :38-47 cat_meshes, :132-167; spann3r_amd/mesh.py and vis.py drive these).
+ * No entry point allocates, frees or synchronises; `ws` is caller-provided device scratch of the matching sp3_*_ws_bytes(),
+ * 16-byte aligned.  Vertex, pixel and face indices are int32: 4 t h w < 2^31.
+ *
+ * Validity of pixel p: (valid null or valid[p] != 0) and (conf null or (conf[p] - 1) / conf[p] > conf_thresh, sp3_render_splat's test;
+ *   a NaN confidence is invalid) and (pts null or the three coordinates of pts[p] finite).  valid and conf exclude each other.
+ * sp3_mesh_faces : the face list of t pointmaps of h x w pixels, vertex index of pixel (f, y, x) = (f h + y) w + x.  A cell is the
+ *   2 x 2 pixel square with top-left pixel (y, x), y < h - 1, x < w - 1, corners tl, tr, bl, br.  Candidates, in output order: frame
+ *   after frame; per frame four blocks, (tl, tr, bl), (bl, tr, tl), (tr, bl, br), (br, bl, tr); per block the cells row-major.  With
+ *   both_windings = 0 only the first and third block exist.  A candidate is kept when its three vertices are valid; the kept ones are
+ *   written densely in candidate order: faces int32 [F, 3], colour_px int32 [F] = tl for the first two blocks, br for the last two
+ *   (the pixel whose colour the reference gives the face).  faces / colour_px need room for every candidate: 4 (or 2) t (h-1)(w-1).
+ *   counts int32 [1 + blocks per frame * t]: counts[0] = F, counts[1 + f * blocks + b] = faces kept of block b of frame f.
+ *   Compaction is three launches -- counts per 256-cell tile, one single-workgroup exclusive scan, scatter -- behind one launch
+ *   that writes the validity bytes; no workgroup waits on another.  t = 0 is a no-op.
+ * sp3_mesh_compact_vertices : keeps vertex i of pts fp32 [n, 3] when a face references it (faces non-null, int32 [nfaces, 3];
+ *   valid / conf must be null) or, for a cloud (faces null), when pixel i is valid by the rule above, pts included.  Kept vertices
+ *   are written densely in index order: out_pos fp32 [V, 3] = M (scale * x), where scale * x rounds per coordinate and row r of the
+ *   row-major 4x4 transform16 (HOST pointer, null = identity; the fourth row is ignored) gives ((m0 x + m1 y) + m2 z) + m3, every
+ *   operation rounded on its own; out_rgba[V] = rgba[i] (both null: no colours).  faces are rewritten in place to rows of out_pos
+ *   (an index outside 0..n-1 becomes -1).  count[0] = V; minmax fp32 [6] = per-axis min (3) and max (3) of out_pos (+inf / -inf when
+ *   V = 0).  A mesh keeps a non-finite vertex only if a face references it: sp3_mesh_faces with pts given emits no such face.
+ *   n = 0 is a no-op.
+ * sp3_render_tris : draws triangles into the key buffer of sp3_render_splat, one triangle per lane.  Face i = vertices
+ *   faces[3i..3i+2] of pts fp32 [nverts, 3]; its key index is index_base + colour_px[i] (colour_px null: + faces[3i]); a face with a
+ *   vertex or colour index outside 0..nverts-1 is skipped.  index_base + nverts must stay below 2^32 - 1.  nfaces_dev (nullable,
+ *   device int32): only the first min(nfaces, *nfaces_dev) faces are drawn.  point_size is not used.  The rule:
+ *   - every vertex is projected as sp3_render_splat projects a point (same fp32 operations, same order, each rounded on its own);
+ *     the triangle is culled if any vertex is culled by that rule;
+ *   - X = floor(16 u + 0.5), Y = floor(16 v + 0.5) in fp32 (1/16 pixel); culled if any |X| or |Y| exceeds 2^20 or is not finite;
+ *   - A = (X1 - X0)(Y2 - Y0) - (X2 - X0)(Y1 - Y0) in int64; A = 0 draws nothing; A < 0: vertices 1 and 2 swap and A = -A (both
+ *     orientations are drawn);
+ *   - the box = pixels (px, py) with 16 px in [min X, max X] and 16 py in [min Y, max Y], clipped to the image; an empty box draws
+ *     nothing; a box of more than max_bbox_px (> 0) pixels culls the triangle (counted in *culled_big, a nullable device uint64
+ *     that the caller zeroes) -- the bound on every lane's loop, and the rule that a sheet stretched across a depth edge is no surface;
+ *   - for the directed edge a -> b, E(px, py) = (Xb - Xa)(16 py - Ya) - (Yb - Ya)(16 px - Xa) in int64: E0 of 1 -> 2, E1 of 2 -> 0,
+ *     E2 of 0 -> 1, so E0 + E1 + E2 = A.  A pixel is covered when every Ei > 0, or Ei = 0 on a top-left edge: one with Yb < Ya, or
+ *     Yb = Ya and Xb > Xa.  A pixel centre on an edge shared by two triangles is thus drawn by exactly one of them;
+ *   - depth = fp32(A) / ((fp32(E0) / z0' + fp32(E1) / z1') + fp32(E2) / z2') with /z' = multiplication by the rounded 1.0f / Xc.z of
+ *     that vertex: perspective-correct, every operation rounded on its own; a pixel whose depth is not finite is skipped;
+ *   - key = (bit pattern of depth) << 32 | index, agent-scope 64-bit unsigned atomic min: nearest wins, then the lowest index,
+ *     whatever the arrival order, among points and triangles alike; sp3_render_resolve reads the buffer unchanged.
+ *   nfaces = 0 is a no-op. */
+int64_t sp3_mesh_faces_ws_bytes(int t, int h, int w);
+int sp3_mesh_faces(const uint8_t* valid, const float* conf, float conf_thresh, const float* pts, int t, int h, int w, int both_windings,
+                   void* ws, int32_t* faces, int32_t* colour_px, int32_t* counts, void* stream);
+int64_t sp3_mesh_vertices_ws_bytes(int64_t n);
+int sp3_mesh_compact_vertices(const float* pts, const uint32_t* rgba, int64_t n, int32_t* faces, int64_t nfaces, const uint8_t* valid,
+                              const float* conf, float conf_thresh, float scale, const float* transform16, void* ws, float* out_pos,
+                              uint32_t* out_rgba, int32_t* count, float* minmax, void* stream);
+int sp3_render_tris(const float* pts, int64_t nverts, const int32_t* faces, const int32_t* colour_px, int64_t nfaces,
+                    const int32_t* nfaces_dev, int64_t index_base, const sp3_render_cam* cam, int max_bbox_px, uint64_t* keys,
+                    uint64_t* culled_big, void* stream);
+
 /* small utilities */
 /* n (1..8) contiguous device-to-device copies in one launch; every copy 16-byte aligned and a multiple of 16 bytes.
  * (The sequence loop's per-frame bookkeeping -- torch .clone() / slice assignments around spann3r/model.py:523-531.) */

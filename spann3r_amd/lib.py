@@ -244,9 +244,16 @@ _PROTOS = {
     "sp3_pack_rgba8": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
     "sp3_colorize_hsv": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
     "sp3_colorize_lut": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_mesh_faces": [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                       C.c_void_p, C.c_void_p],
+    "sp3_mesh_compact_vertices": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                  C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_render_tris": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(RenderCam), C.c_int,
+                        C.c_void_p, C.c_void_p, C.c_void_p],
 }
 EXPORTS = sorted(list(_PROTOS) + ["sp3_last_error", "sp3_version", "sp3_conf_loss_ws_bytes", "sp3_ssi_loss_ws_bytes", "sp3_sumsq_blocks", "sp3_colsum_rows_ws",
-                                  "sp3_nn_query_ws_bytes", "sp3_icp_accum_ws_bytes", "sp3_sum_count_ws_bytes"])
+                                  "sp3_nn_query_ws_bytes", "sp3_icp_accum_ws_bytes", "sp3_sum_count_ws_bytes",
+                                  "sp3_mesh_faces_ws_bytes", "sp3_mesh_vertices_ws_bytes"])
 
 
 def load():
@@ -269,7 +276,9 @@ def load():
     lib.sp3_sumsq_blocks.argtypes = [C.c_int64]
     lib.sp3_colsum_rows_ws.restype = C.c_int64
     lib.sp3_colsum_rows_ws.argtypes = [C.c_int, C.c_int]
-    for name in ("sp3_nn_query_ws_bytes", "sp3_icp_accum_ws_bytes", "sp3_sum_count_ws_bytes"):
+    lib.sp3_mesh_faces_ws_bytes.restype = C.c_int64
+    lib.sp3_mesh_faces_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    for name in ("sp3_nn_query_ws_bytes", "sp3_icp_accum_ws_bytes", "sp3_sum_count_ws_bytes", "sp3_mesh_vertices_ws_bytes"):
         getattr(lib, name).restype = C.c_int64
         getattr(lib, name).argtypes = [C.c_int64]
     for name, argtypes in _PROTOS.items():

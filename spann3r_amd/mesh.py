@@ -1,0 +1,214 @@
+"""Pointmap meshes and GLB export on the device (reference: app.py:38-47 cat_meshes, :68-105 pts3d_to_trimesh, :132-171 of reconstruct).
+
+The reference masks the predictions by confidence, turns every frame's pointmap into a triangle mesh on the host (two triangles per
+pixel cell, each in both windings, filtered with a fancy-indexed `valid[faces].all(-1)`), concatenates the frames and exports one
+GLB through trimesh.  Here the face list, the compaction of the vertices that survive and the x10 / transform of the positions are
+HIP kernels (csrc/mesh.hip: order-preserving scans, three launches each); the host reads the counts once, copies the compacted
+arrays and writes the file with struct / json.
+
+What this restates and what it does not:
+- `pts3d_to_mesh` / `cat_meshes` give the reference's vertices, faces and face_colors bit for bit, order and dtypes included
+  (tests/golden/mesh_faces.npz is the reference's own output).
+- `write_glb` writes vertex colours (each pixel's own colour): glTF has no face colours.  What trimesh makes of `face_colors` on
+  export, how it merges or orders vertices and how it rounds float colours cannot be checked here: parity unpinned vs trimesh.
+  Instead of the reference's duplicated reversed faces the material is `doubleSided`, which halves the index buffer.
+- `scene_mesh` also drops pixels whose point is not finite; the reference would export them.
+torch provides memory and the gather behind `face_colors`; trimesh, gradio and the ffmpeg frame extraction of app.py are not covered."""
+import ctypes as C
+import json
+import struct
+
+import numpy as np
+import torch
+
+from . import lib as L
+
+SCALE = 10.0                                      # app.py:143
+TRANSFORM = np.diag([-1.0, -1.0, 1.0, 1.0])       # app.py:165-167: inv(OPENGL @ rot_y(180 deg)) = inv(diag(1,-1,-1,1) diag(-1,1,-1,1))
+
+
+def _dev(x, name):
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("%s: expected a CUDA tensor, got %s" % (name, type(x).__name__))
+    if not x.is_cuda:
+        raise RuntimeError("%s: meshes are built on the GPU (HIP kernels); there is no CPU path -- pass a CUDA tensor" % name)
+    return x
+
+
+def _ws(nbytes, device):
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+
+
+def build_faces(t, h, w, device, valid=None, conf=None, conf_thresh=0.0, pts=None, both_windings=True, sync=True):
+    """sp3_mesh_faces: -> (faces int32 [F, 3], colour_px int32 [F], counts).  valid uint8 / bool [t, h, w] or conf fp32 [t, h, w] with
+    conf_thresh; pts fp32 [t, h, w, 3] adds the finiteness test.  With sync=True the host reads the counts once and the tensors are
+    cut to F (counts: a list, [F] + per frame and block); with sync=False they keep their full capacity and counts stays on the device."""
+    n = t * h * w
+    for name, x, dt in (("valid", valid, torch.uint8), ("conf", conf, torch.float32), ("pts", pts, torch.float32)):
+        if x is not None and (x.dtype != dt or not x.is_contiguous() or x.numel() != n * (3 if name == "pts" else 1)):
+            raise RuntimeError("build_faces: %s must be a contiguous %s tensor of %d x %d x %d pixels" % (name, dt, t, h, w))
+    lib = L.load()
+    nblk = 4 if both_windings else 2
+    cap = max(t * nblk * (h - 1) * (w - 1), 1)
+    faces = torch.empty((cap, 3), dtype=torch.int32, device=device)
+    colour_px = torch.empty(cap, dtype=torch.int32, device=device)
+    counts = torch.zeros(1 + nblk * t, dtype=torch.int32, device=device)
+    ws = _ws(lib.sp3_mesh_faces_ws_bytes(t, h, w), device)
+    L.check(lib.sp3_mesh_faces(L.ptr(valid), L.ptr(conf), float(conf_thresh), L.ptr(pts), t, h, w, int(both_windings), ws.data_ptr(),
+                               faces.data_ptr(), colour_px.data_ptr(), counts.data_ptr(), L.stream_ptr()), "sp3_mesh_faces")
+    if not sync:
+        return faces, colour_px, counts
+    counts = counts.cpu().tolist()
+    return faces[:counts[0]], colour_px[:counts[0]], counts
+
+
+def compact_vertices(pts, rgba=None, faces=None, valid=None, conf=None, conf_thresh=0.0, scale=1.0, transform=None):
+    """sp3_mesh_compact_vertices: pts fp32 [n, 3], rgba int32 [n] (optional), and either faces int32 [F, 3] (rewritten in place) or
+    valid / conf for a cloud -> (positions fp32 [V, 3], rgba int32 [V] or None, bounds float32 numpy [2, 3]).  One host read."""
+    n = pts.shape[0]
+    lib = L.load()
+    if n == 0 or (faces is not None and faces.shape[0] == 0):          # nothing to keep (and an empty tensor has no pointer to pass)
+        none = np.array([[np.inf] * 3, [-np.inf] * 3], np.float32)
+        return pts.new_empty((0, 3)), None if rgba is None else rgba[:0], none
+    out_pos = torch.empty((n, 3), dtype=torch.float32, device=pts.device)
+    out_rgba = torch.empty(n, dtype=torch.int32, device=pts.device) if rgba is not None else None
+    info = torch.zeros(8, dtype=torch.float32, device=pts.device)      # [0]: V (int32 bits), [2..8): min / max
+    info[2:5] = float("inf")
+    info[5:8] = float("-inf")
+    ws = _ws(lib.sp3_mesh_vertices_ws_bytes(n), pts.device)
+    m = None if transform is None else (C.c_float * 16)(*np.asarray(transform, np.float64).reshape(16))
+    L.check(lib.sp3_mesh_compact_vertices(pts.data_ptr(), L.ptr(rgba), n, L.ptr(faces), 0 if faces is None else faces.shape[0], L.ptr(valid),
+                                          L.ptr(conf), float(conf_thresh), float(scale), m, ws.data_ptr(), out_pos.data_ptr(), L.ptr(out_rgba),
+                                          info.data_ptr(), info.data_ptr() + 8, L.stream_ptr()), "sp3_mesh_compact_vertices")
+    host = info.cpu().numpy()
+    v = int(host[:1].view(np.int32)[0])
+    return out_pos[:v], None if out_rgba is None else out_rgba[:v], host[2:8].reshape(2, 3).copy()
+
+
+def pts3d_to_mesh(img, pts3d, valid=None):
+    """app.py:68-105 (pts3d_to_trimesh) for device tensors img, pts3d [h, w, 3] and valid bool [h, w]: dict(vertices [h w, 3],
+    faces int64 [F, 3], face_colors [F, 3]) with the reference's order: four blocks (tl, tr, bl), (bl, tr, tl), (tr, bl, br), (br, bl, tr),
+    row-major over the cells, faces with an invalid vertex removed; the first two blocks take the cell's top-left colour, the last
+    two its bottom-right colour."""
+    img, pts3d = _dev(img, "pts3d_to_mesh: img"), _dev(pts3d, "pts3d_to_mesh: pts3d")
+    if img.dim() != 3 or img.shape[-1] != 3 or img.shape != pts3d.shape:
+        raise RuntimeError("pts3d_to_mesh: img %s and pts3d %s must both be [h, w, 3]" % (tuple(img.shape), tuple(pts3d.shape)))
+    h, w = img.shape[:2]
+    if valid is not None:
+        if _dev(valid, "pts3d_to_mesh: valid").shape != (h, w):
+            raise RuntimeError("pts3d_to_mesh: valid %s does not match the %d x %d pointmap" % (tuple(valid.shape), h, w))
+        valid = valid.to(torch.uint8).contiguous()
+    faces, colour_px, _ = build_faces(1, h, w, img.device, valid=valid)
+    return dict(vertices=pts3d.reshape(-1, 3), faces=faces.long(), face_colors=img.reshape(-1, 3)[colour_px.long()])
+
+
+def cat_meshes(meshes):
+    """app.py:38-47: one mesh of several, the faces of mesh i shifted by the vertices before it (the inputs stay as they are; the
+    reference shifts them in place)"""
+    if len(meshes) == 0:
+        raise ValueError("cat_meshes: no meshes")
+    offs = np.cumsum([0] + [len(m["vertices"]) for m in meshes])
+    return dict(vertices=torch.cat([m["vertices"] for m in meshes]), face_colors=torch.cat([m["face_colors"] for m in meshes]),
+                faces=torch.cat([m["faces"] + int(o) for m, o in zip(meshes, offs)]))
+
+
+def scene_mesh(pts_all, images_all, conf_all, conf_thresh, as_pointcloud=False):
+    """app.py:132-167 in one call for device tensors pts_all, images_all [t, h, w, 3] (colours in [0, 1]) and conf_all [t, h, w]:
+    the pixels with (conf - 1) / conf > conf_thresh (and a finite point), as one mesh of all frames or, with as_pointcloud, as a cloud.
+    Positions are 10 x the points (app.py:143) under the transform of app.py:165-167, which evaluates to diag(-1, -1, 1, 1).
+    -> dict(vertices fp32 [V, 3], colors uint8 [V, 4], faces int32 [F, 3] (forward windings only; None for a cloud), bounds float32
+    numpy [2, 3] = per-axis min and max of the vertices), vertices / colors / faces on the device.  Only referenced vertices are kept."""
+    pts_all, images_all, conf_all = (_dev(x, "scene_mesh: " + n) for x, n in ((pts_all, "pts_all"), (images_all, "images_all"), (conf_all, "conf_all")))
+    if pts_all.dim() != 4 or pts_all.shape[-1] != 3 or images_all.shape != pts_all.shape or conf_all.shape != pts_all.shape[:3]:
+        raise RuntimeError("scene_mesh: mismatched shapes: pts_all %s and images_all %s must be [t, h, w, 3], conf_all %s [t, h, w]" %
+                           (tuple(pts_all.shape), tuple(images_all.shape), tuple(conf_all.shape)))
+    t, h, w = conf_all.shape
+    n = t * h * w
+    pts, conf = pts_all.float().contiguous(), conf_all.float().contiguous()
+    rgba = torch.empty(n, dtype=torch.int32, device=pts.device)
+    L.check(L.load().sp3_pack_rgba8(images_all.float().contiguous().data_ptr(), n, rgba.data_ptr(), L.stream_ptr()), "sp3_pack_rgba8")
+    faces = None
+    if as_pointcloud:
+        pos, col, bounds = compact_vertices(pts.reshape(-1, 3), rgba, conf=conf, conf_thresh=conf_thresh, scale=SCALE, transform=TRANSFORM)
+    else:
+        faces, _, _ = build_faces(t, h, w, pts.device, conf=conf, conf_thresh=conf_thresh, pts=pts, both_windings=False)
+        pos, col, bounds = compact_vertices(pts.reshape(-1, 3), rgba, faces=faces, scale=SCALE, transform=TRANSFORM)
+    return dict(vertices=pos, colors=col.view(torch.uint8).reshape(-1, 4), faces=faces, bounds=bounds)
+
+
+def _host(x):
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def write_glb(path, vertices, colors, faces=None, bounds=None):
+    """A glTF 2.0 binary file of one primitive: POSITION fp32 VEC3 (with min / max; `bounds` [2, 3] if already known), COLOR_0
+    normalised unsigned byte VEC4 (uint8 [V, 3] gets alpha 255), and with faces [F, 3] uint32 indices, mode 4 (TRIANGLES) and a
+    doubleSided material; without faces mode 0 (POINTS).  One buffer, every chunk and buffer view 4-byte aligned.  Tensors are copied
+    to the host.  Returns the file length."""
+    v = np.ascontiguousarray(_host(vertices), dtype="<f4")
+    c = _host(colors)
+    if v.ndim != 2 or v.shape[1] != 3 or v.shape[0] == 0:
+        raise ValueError("write_glb: vertices %s must be [V, 3] with V >= 1 (a glTF accessor cannot be empty)" % (v.shape,))
+    if c.dtype != np.uint8 or c.ndim != 2 or c.shape[1] not in (3, 4):
+        raise ValueError("write_glb: colors must be uint8 [V, 3] or [V, 4], got %s %s" % (c.dtype, c.shape))
+    if c.shape[0] != v.shape[0]:
+        raise ValueError("write_glb: mismatched lengths: %d vertices, %d colours" % (v.shape[0], c.shape[0]))
+    if c.shape[1] == 3:
+        c = np.concatenate([c, np.full((len(c), 1), 255, np.uint8)], axis=1)
+    c = np.ascontiguousarray(c)
+    if not np.isfinite(v).all():
+        raise ValueError("write_glb: non-finite vertex position")
+    lo, hi = (v.min(0), v.max(0)) if bounds is None else np.asarray(bounds, np.float32).reshape(2, 3)
+    views = [dict(buffer=0, byteOffset=0, byteLength=v.nbytes, target=34962),
+             dict(buffer=0, byteOffset=v.nbytes, byteLength=c.nbytes, target=34962)]
+    accessors = [dict(bufferView=0, componentType=5126, count=len(v), type="VEC3", min=[float(x) for x in lo], max=[float(x) for x in hi]),
+                 dict(bufferView=1, componentType=5121, normalized=True, count=len(v), type="VEC4")]
+    chunks = [v.tobytes(), c.tobytes()]
+    prim = dict(attributes=dict(POSITION=0, COLOR_0=1), mode=0)
+    doc = dict(asset=dict(version="2.0", generator="spann3r_amd.mesh"), scene=0, scenes=[dict(nodes=[0])], nodes=[dict(mesh=0)])
+    if faces is not None:
+        f = _host(faces)
+        if f.ndim != 2 or f.shape[1] != 3 or f.shape[0] == 0:
+            raise ValueError("write_glb: faces %s must be [F, 3] with F >= 1" % (f.shape,))
+        if f.min() < 0 or f.max() >= len(v):
+            raise ValueError("write_glb: face index outside 0..%d" % (len(v) - 1))
+        f = np.ascontiguousarray(f, dtype="<u4")
+        views.append(dict(buffer=0, byteOffset=v.nbytes + c.nbytes, byteLength=f.nbytes, target=34963))
+        accessors.append(dict(bufferView=2, componentType=5125, count=f.size, type="SCALAR"))
+        chunks.append(f.tobytes())
+        prim.update(indices=2, mode=4, material=0)
+        doc["materials"] = [dict(doubleSided=True, pbrMetallicRoughness=dict(metallicFactor=0.0, roughnessFactor=1.0))]
+    binary = b"".join(chunks)                          # (12 V + 4 V + 12 F bytes: every view starts and ends on a multiple of 4)
+    doc.update(meshes=[dict(primitives=[prim])], buffers=[dict(byteLength=len(binary))], bufferViews=views, accessors=accessors)
+    text = json.dumps(doc, separators=(",", ":")).encode()
+    text += b" " * (-len(text) % 4)
+    binary += b"\0" * (-len(binary) % 4)
+    total = 12 + 8 + len(text) + 8 + len(binary)
+    with open(path, "wb") as fh:
+        fh.write(struct.pack("<4sII", b"glTF", 2, total))
+        fh.write(struct.pack("<I4s", len(text), b"JSON"))
+        fh.write(text)
+        fh.write(struct.pack("<I4s", len(binary), b"BIN\0"))
+        fh.write(binary)
+    return total
+
+
+def sequence_tensors(preds, batch):
+    """model.forward's outputs as app.py:132-144 stacks them: pts_all [t, h, w, 3] (unscaled), images_all in [0, 1], conf_all [t, h, w]"""
+    pts_all = torch.cat([p["pts3d" if j == 0 else "pts3d_in_other_view"] for j, p in enumerate(preds)]).float()
+    conf_all = torch.cat([p["conf"] for p in preds]).float()
+    images_all = (torch.cat([v["img"] for v in batch]).to(pts_all.device).permute(0, 2, 3, 1).float() + 1.0) / 2.0
+    if images_all.shape[1:3] != pts_all.shape[1:3]:
+        images_all = images_all.swapaxes(1, 2)                                    # portrait frames were rectified to landscape
+    return pts_all, images_all, conf_all
+
+
+def export_glb(path, preds, batch, conf_thresh=1e-3, as_pointcloud=False):
+    """app.py:132-171: the GLB of a reconstruction from model.forward's `preds` and its `batch`.  -> dict(vertices, faces, bytes)."""
+    pts_all, images_all, conf_all = sequence_tensors(preds, batch)
+    scene = scene_mesh(pts_all, images_all, conf_all, conf_thresh, as_pointcloud)
+    nv, nf = scene["vertices"].shape[0], 0 if scene["faces"] is None else scene["faces"].shape[0]
+    if nv == 0 or (not as_pointcloud and nf == 0):
+        raise RuntimeError("export_glb: nothing passes conf_thresh %g: no %s to write" % (conf_thresh, "point" if as_pointcloud else "face"))
+    size = write_glb(path, scene["vertices"], scene["colors"], scene["faces"], bounds=scene["bounds"])
+    return dict(vertices=nv, faces=nf, bytes=size)

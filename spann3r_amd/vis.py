@@ -141,6 +141,7 @@ class PointRenderer:
         self.keys = torch.empty(self.width * self.height, dtype=torch.int64, device=self.device)
         self.rgba = torch.empty(0, dtype=torch.int32, device=self.device)
         self.count = 0
+        self.mesh_stats = None
         self.clear()
 
     def clear(self):
@@ -176,6 +177,48 @@ class PointRenderer:
                                            self.keys.data_ptr(), st), "sp3_render_splat")
         self.count += n
 
+    def add_mesh(self, pts, colors, conf=None, valid=None, max_bbox_px=4096):
+        """One frame's pointmap pts [h, w, 3] drawn as its mesh (app.py:68-105: two triangles per pixel cell, forward windings; the
+        rasteriser draws both orientations) instead of its points: sp3_mesh_faces builds the faces of the pixels that are finite,
+        pass `valid` bool [h, w] or (conf - 1) / conf > conf_thresh, and sp3_render_tris draws them into the same key buffer, so
+        add() and add_mesh() mix.  A triangle whose clipped bounding box holds more than max_bbox_px pixels is not drawn (a sheet
+        stretched across a depth edge is no surface).  The index image counts pixels as add() counts points; nothing is read back."""
+        from . import mesh as M
+        pts, colors = _dev(pts, "PointRenderer.add_mesh: pts"), _dev(colors, "PointRenderer.add_mesh: colors")
+        if pts.dim() != 3 or pts.shape[-1] != 3 or colors.shape != pts.shape:
+            raise RuntimeError("PointRenderer.add_mesh: pts %s and colors %s must both be [h, w, 3]" % (tuple(pts.shape), tuple(colors.shape)))
+        h, w = pts.shape[:2]
+        n = h * w
+        if conf is not None and valid is not None:
+            raise RuntimeError("PointRenderer.add_mesh: give conf or valid, not both")
+        if conf is not None:
+            conf = _dev(conf, "PointRenderer.add_mesh: conf").float().contiguous()
+            if conf.numel() != n:
+                raise RuntimeError("PointRenderer.add_mesh: mismatched lengths: %d points, %d confidences" % (n, conf.numel()))
+            if self.conf_thresh is None:
+                raise RuntimeError("PointRenderer.add_mesh: conf given but the renderer has no conf_thresh")
+        if valid is not None:
+            if _dev(valid, "PointRenderer.add_mesh: valid").numel() != n:
+                raise RuntimeError("PointRenderer.add_mesh: mismatched lengths: %d points, %d valid flags" % (n, valid.numel()))
+            valid = valid.to(torch.uint8).contiguous()
+        if int(max_bbox_px) <= 0:
+            raise ValueError("PointRenderer.add_mesh: max_bbox_px must be > 0")
+        pts, colors = pts.float().contiguous(), colors.float().contiguous()
+        if self.dynamic:
+            self.clear()
+        self._reserve(self.count + n)
+        st = L.stream_ptr()
+        L.check(self._lib.sp3_pack_rgba8(colors.data_ptr(), n, self.rgba.data_ptr() + 4 * self.count, st), "sp3_pack_rgba8")
+        faces, colour_px, counts = M.build_faces(1, h, w, self.device, valid=valid, conf=conf, conf_thresh=float(self.conf_thresh or 0.0), pts=pts,
+                                                 both_windings=False, sync=False)
+        if self.mesh_stats is None:
+            self.mesh_stats = torch.zeros(2, dtype=torch.int64, device=self.device)      # triangles given, culled by max_bbox_px
+        self.mesh_stats[0] += counts[0]
+        L.check(self._lib.sp3_render_tris(pts.data_ptr(), n, faces.data_ptr(), colour_px.data_ptr(), faces.shape[0], counts.data_ptr(), self.count,
+                                          C.byref(self.cam), int(max_bbox_px), self.keys.data_ptr(), self.mesh_stats.data_ptr() + 8, st),
+                "sp3_render_tris")
+        self.count += n
+
     def image(self, return_depth=False, return_index=False):
         """uint8 [H, W, 3] on the device; with the flags, also depth fp32 [H, W] (+inf: empty) and index int32 [H, W] (-1: empty;
         the index counts every point given to add(), kept or not, in order)."""
@@ -196,11 +239,13 @@ def _save_png(path, img):
 
 
 def render_frames(pts_all, images_all, camera, output_dir=None, mask=None, conf_all=None, conf_thresh=None, dynamic=False, save_camera=True,
-                  point_size=1, background=(0, 0, 0)):
+                  point_size=1, background=(0, 0, 0), surface=False, max_bbox_px=4096):
     """vis.py:17-76: t pictures of pts_all [t, h, w, 3] coloured by images_all [t, h, w, 3] (floats in [0, 1]) seen from `camera`:
     the cloud as it grows, or each frame's points alone with dynamic=True.  Returned as a uint8 [t, H, W, 3] device tensor and, when
     output_dir is given, written as output_dir/render_frames/frame_%03d.png (plus camera.json with save_camera).  Points are
     selected by the reference's boolean `mask` [t, h, w] or by conf_all [t, h, w] and conf_thresh, tested in the kernel.
+    With surface=True every frame is drawn as its mesh (PointRenderer.add_mesh, max_bbox_px) instead of its points: a solid
+    surface where the point splat leaves a dot screen.
     There is no mp4 output (the reference's save_video): imageio and ffmpeg are not available."""
     pts_all, images_all = _dev(pts_all, "render_frames: pts_all"), _dev(images_all, "render_frames: images_all")
     t = pts_all.shape[0]
@@ -216,7 +261,9 @@ def render_frames(pts_all, images_all, camera, output_dir=None, mask=None, conf_
                       dynamic=dynamic, device=pts_all.device)
     out = torch.empty((t, r.height, r.width, 3), dtype=torch.uint8, device=pts_all.device)
     for i in range(t):
-        if mask is not None:
+        if surface:
+            r.add_mesh(pts_all[i], images_all[i], None if conf_all is None else conf_all[i], None if mask is None else mask[i], max_bbox_px)
+        elif mask is not None:
             m = mask[i].reshape(-1)
             r.add(pts_all[i].reshape(-1, 3)[m], images_all[i].reshape(-1, 3)[m])
         else:
