@@ -36,6 +36,15 @@ def main():
     ap.add_argument("--save_glb", default=None, metavar="PATH", help="app.py's output: the confidence-masked reconstruction as one GLB, "
                     "meshed and compacted on the device (spann3r_amd.mesh)")
     ap.add_argument("--as_pointcloud", action="store_true", help="with --save_glb: app.py's as_pointcloud, points instead of a mesh")
+    ap.add_argument("--rgbd", default=None, metavar="DIR", help="folder of *.npz frames (rgb uint8 [H,W,3], depth uint16 or float32 [H,W], "
+                    "K [3,3], pose [4,4] cam2world; tools/make_rgbd_folder.py writes one): views with ground truth built on the GPU "
+                    "(spann3r_amd.views.build_views) instead of synthetic frames")
+    ap.add_argument("--eval", action="store_true", help="with --rgbd: eval.py's alignment and reconstruction metrics for the sequence "
+                    "(spann3r_amd.evaluate.evaluate_sequence)")
+    ap.add_argument("--depth_div", type=float, default=1000.0, help="with --rgbd: raw depth units per metre")
+    ap.add_argument("--raw_invalid", type=float, default=65535, help="with --rgbd: raw value that means no measurement")
+    ap.add_argument("--max_depth", type=float, default=10.0)
+    ap.add_argument("--min_depth", type=float, default=1e-3)
     args = ap.parse_args()
     cfg = TINY if args.tiny else FULL
     device = "cuda"
@@ -50,9 +59,29 @@ def main():
         names = sorted(n for n in os.listdir(args.demo_path) if n.lower().endswith((".jpg", ".jpeg", ".png")))
         batch = frames_from_images((np.asarray(Image.open(os.path.join(args.demo_path, n)).convert("RGB")) for n in names),
                                    resolution=args.size, device=device, kf_every=args.kf_every)
+    elif args.rgbd:                                                               # eval.py:79-87 (a data set + DataLoader(batch_size=1))
+        import os
+        import numpy as np
+        from spann3r_amd.views import build_views
+        names = sorted(n for n in os.listdir(args.rgbd) if n.endswith(".npz"))[::args.kf_every]
+        data = [np.load(os.path.join(args.rgbd, n)) for n in names]
+        cols = [[d[k] for d in data] for k in ("rgb", "depth", "K", "pose")]
+        kw = dict(resolution=args.size, device=device, depth_div=args.depth_div, raw_invalid=args.raw_invalid, min_depth=args.min_depth,
+                  max_depth=args.max_depth, labels=[os.path.join(os.path.basename(os.path.normpath(args.rgbd)), n) for n in names])
+        build_views(*cols, **kw)                                                  # warm-up: resampling tables, first launches
+        torch.cuda.synchronize()
+        start = time.time()
+        batch = build_views(*cols, **kw)
+        torch.cuda.synchronize()
+        end = time.time()
+        print("build_views: %d views of %dx%d -> %s in %.4f s, %.0f views/s, %.1f %% of the pixels valid" %
+              (len(batch), data[0]["rgb"].shape[1], data[0]["rgb"].shape[0], tuple(batch[0]["img"].shape[2:]), end - start,
+               len(batch) / (end - start), 100 * float(torch.cat([v["valid_mask"] for v in batch]).float().mean())))
     else:
         batch = synth_frames(args.frames, args.size, args.size)
-    for view in batch if not args.demo_path else []:                                                            # demo.py:94-95
+    if args.eval and not args.rgbd:
+        ap.error("--eval needs --rgbd (views with ground truth)")
+    for view in batch if not (args.demo_path or args.rgbd) else []:                                                            # demo.py:94-95
         view["img"] = view["img"].to(device, non_blocking=True)
         view["true_shape"] = torch.tensor(view["img"].shape[2:]).unsqueeze(0)     # demo.py:109 (stays on the CPU)
     if args.offline:                                                              # demo.py:98-121
@@ -74,6 +103,12 @@ def main():
         print("Time: %.4f s, FPS: %.1f  (%d frames, call %d: %s)" %
               (end - start, len(batch) / (end - start), len(batch), it,
                ["eager warm-up", "hipGraph capture", "hipGraph replay"][min(it, 2)]))
+    if args.eval:                                                                 # eval.py:128-221
+        from spann3r_amd.evaluate import evaluate_sequence
+        r = evaluate_sequence(batch, preds, preds_all, threshold=0.1)
+        print("Idx: %s, Acc: %s, Comp: %s, NC1: %s, NC2: %s - Acc_med: %s, Compc_med: %s, NC1c_med: %s, NC2c_med: %s  (%d points)" %
+              (batch[-1]["label"].rsplit("/", 1)[0], r["acc"], r["comp"], r["nc1"], r["nc2"], r["acc_med"], r["comp_med"], r["nc1_med"],
+               r["nc2_med"], len(r["pred_cloud"])))
     if args.save_ply:
         from spann3r_amd.postprocess import (estimate_focal_knowing_depth, confident_points, write_ply, estimate_poses,
                                              transforms_json, save_transforms)

@@ -475,6 +475,11 @@ int sp3_conf_loss_backward(const float* P, const float* Cf, const float* G, cons
 int64_t sp3_ssi_loss_ws_bytes(int n, int B, int HW);
 int sp3_ssi_loss_forward(const float* P, const float* G, const uint8_t* V, const float* pose0, int n, int B, int HW, int fix_first,
                          int gt_scale, void* ws, float* out, void* stream);
+/* The per-sample medians of Regr3D_t_ScaleShiftInv(L21, norm_mode=False, gt_scale=True).get_all_pts3d_t (the configuration of the
+ * reference's eval.py:55): the same selection without the avg_dis normalisation in front of it.  stats (device) fp32 [B, 4] =
+ * gt_shift_z, pred_shift_z, gt_scale, pred_scale (clipped to [1e-3, 1e3]).  Same buffers and scratch as sp3_ssi_loss_forward. */
+int sp3_ssi_align_stats(const float* P, const float* G, const uint8_t* V, const float* pose0, int n, int B, int HW, void* ws, float* stats,
+                        void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Pieces of the BACKWARD of the spatial-memory read in its training form (attn_thresh = 0, mem_dropout; forward:
@@ -778,6 +783,64 @@ int sp3_mesh_compact_vertices(const float* pts, const uint32_t* rgba, int64_t n,
 int sp3_render_tris(const float* pts, int64_t nverts, const int32_t* faces, const int32_t* colour_px, int64_t nfaces,
                     const int32_t* nfaces_dev, int64_t index_base, const sp3_render_cam* cam, int max_bbox_px, uint64_t* keys,
                     uint64_t* culled_big, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * RGB-D views (dust3r/datasets/base/base_stereo_view_dataset.py:63-119,143-194,215-220; dust3r/datasets/utils/cropping.py:54-112;
+ * dust3r/utils/geometry.py:165-217; the sanitising of spann3r/datasets/seven_scenes.py:123-126; spann3r_amd/views.py drives this).
+ * The depth side of a whole sequence in ONE launch: raw depth maps -> `depthmap`, `pts3d` (world) and `valid_mask` of every view,
+ * all views landscape and of one common size.  The entry point neither allocates nor synchronises.
+ *
+ * Per view a descriptor (below).  For output pixel (x, y) of the view's own orientation, 0 <= x < w, 0 <= y < h:
+ *   index   : xr = x + l2, yr = y + t2 (second crop, in the resized W2 x H2 image), then nearest-neighbour resize from the W1 x H1
+ *             window of the first crop by OpenCV's INTER_NEAREST rule for a given dsize:  ifx = 1.0 / ((double)W2 / W1),
+ *             sx = min((int)floor(xr * ifx), W1 - 1), every operation in double; the same rule for y.  The raw value is read at
+ *             column crop_l + sx, row crop_t + sy; no intermediate image exists.  (This is not floor(xr * W1 / W2): the two differ
+ *             e.g. for W1 = 36, W2 = 20 at xr = 15.)  Parity unpinned vs cv2: cv2 is not in the build image, the rule is restated.
+ *   sanitise: raw (uint16 or fp32) converted to fp32; raw == raw_invalid (when use_raw_invalid) -> 0; z = raw / depth_div, an fp32
+ *             DIVISION; z not finite -> 0; z > max_depth -> 0; z < min_depth -> 0.
+ *   unproject: x_cam = fp32(((double)x - cu) * z / fu), y_cam = fp32(((double)y - cv) * z / fv), every operation in double and ONE
+ *             rounding to fp32 (what numpy does for an int64 grid and fp32 scalars); z_cam = z.
+ *   world   : X_i = ((R_i0 x_cam + R_i1 y_cam) + R_i2 z_cam) + t_i in fp32, every operation rounded on its own; R | t = the 3x4
+ *             cam2world matrix, row-major in `pose`.
+ *   mask    : z > 0 and the three world coordinates finite.
+ *   store   : at [y, x] of the view's [h, w] maps, or at [x, y] of [w, h] maps when `transpose` (a portrait view rectified to
+ *             landscape): depth fp32 [n, out_h, out_w], pts fp32 [n, out_h, out_w, 3], mask uint8 [n, out_h, out_w] (0 / 1), and, when
+ *             xcam is non-null, the camera-frame point fp32 [n, out_h, out_w, 3].  (out_h, out_w) = (h, w), or (w, h) if transposed.
+ * descs_host and descs_dev hold the same n descriptors; the host copy is only read for the geometry checks of the call (every
+ * window inside its source, every view of the common output size).  n = 0 is a no-op. */
+typedef struct sp3_view_desc {
+  const void* src;          /* device: raw depth, row-major */
+  int64_t row_stride;       /* in elements */
+  int32_t dtype;            /* 0 = uint16, 1 = fp32 */
+  int32_t src_w, src_h;
+  int32_t crop_l, crop_t, W1, H1;
+  int32_t W2, H2;
+  int32_t l2, t2;
+  int32_t w, h;
+  int32_t transpose;
+  float fu, fv, cu, cv;
+  float pose[12];
+  int32_t use_raw_invalid;
+  float raw_invalid, depth_div, min_depth, max_depth;
+} sp3_view_desc;
+int sp3_view_depth(const sp3_view_desc* descs_host, const sp3_view_desc* descs_dev, int n, int out_h, int out_w, float* depth,
+                   float* pts, uint8_t* mask, float* xcam, void* stream);
+/* sp3_eval_align : the alignment of the reference's eval.py:128-168 and the masked clouds of :189-191.  pred fp32 [m, B, HW, 3]
+ * (camera of view 0), gt fp32 [n, B, HW, 3] (world), pose0 fp32 [B, 16] (cam2world of view 0), stats fp32 [B, 4] = gt_shift_z,
+ * pred_shift_z, gt_scale, pred_scale (sp3_ssi_align_stats), all on the device.  Per point, in double from the fp32 inputs and
+ * rounded to fp32 once:
+ *   pred: (x, y, z - pred_shift_z) * (gt_scale / pred_scale);   gt: pose0^-1 applied, then z - gt_shift_z
+ *   -- with to_world = 0 that is what Regr3D_t_ScaleShiftInv(norm_mode=False, gt_scale=True).get_all_pts3d_t returns;
+ *   to_world = 1: z + gt_shift_z, then pose0 applied: both stacks in the world of the ground truth (eval.py:152-156).
+ * pred_out / gt_out have the shapes of pred / gt.  With mask non-null (uint8 [n, HW]; needs B = 1 and m = n): images fp32
+ * [n, HW, 3] = (img + 1) / 2 of img fp32 [n, 3, HW], and the points p with mask[p] > 0 in row-major order over (frame, row, column)
+ * -- the order matters, ICP and the k-NN normals break ties by index -- written densely: cloud_pred, cloud_gt, cloud_rgb fp32
+ * [count, 3] (room for n HW points each), cloud_src int32 [count] = p, count int32 [1].  ws: sp3_eval_align_ws_bytes(n HW) bytes of
+ * device scratch, 4-byte aligned.  The compaction is the tile count / single-workgroup scan / scatter of the pointmap meshes. */
+int64_t sp3_eval_align_ws_bytes(int64_t npts);
+int sp3_eval_align(const float* pred, int m, const float* gt, int n, int B, int HW, const float* pose0, const float* stats, int to_world,
+                   float* pred_out, float* gt_out, const uint8_t* mask, const float* img, void* ws, float* images, float* cloud_pred,
+                   float* cloud_gt, float* cloud_rgb, int32_t* cloud_src, int32_t* count, void* stream);
 
 /* small utilities */
 /* n (1..8) contiguous device-to-device copies in one launch; every copy 16-byte aligned and a multiple of 16 bytes.

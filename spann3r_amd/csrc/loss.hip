@@ -330,7 +330,7 @@ struct SsiArgs {
 // med layout: [0, 2B): shift z (gt rows 0..B-1, pred B..2B-1); [2B, 8B): centres (gt x, y, z, pred x, y, z; B each); [8B, 10B): scales
 __device__ __forceinline__ void ssi_points(const SsiArgs& a, const float* Rt, int i, int b, int x, float (&g)[3], float (&p)[3]) {
   const float* gp = a.G + (((int64_t)i * a.B + b) * a.HW + x) * 3;
-  const float ifg = a.gt_scale ? 1.0f : 1.0f / a.fac[4 * b + 1], ifp = 1.0f / a.fac[4 * b];
+  const float ifg = (a.gt_scale || !a.fac) ? 1.0f : 1.0f / a.fac[4 * b + 1], ifp = a.fac ? 1.0f / a.fac[4 * b] : 1.0f;   // fac null: norm_mode=False
   g[0] = (Rt[0] * gp[0] + Rt[1] * gp[1] + Rt[2] * gp[2] + Rt[9]) * ifg;
   g[1] = (Rt[3] * gp[0] + Rt[4] * gp[1] + Rt[5] * gp[2] + Rt[10]) * ifg;
   g[2] = (Rt[6] * gp[0] + Rt[7] * gp[1] + Rt[8] * gp[2] + Rt[11]) * ifg;
@@ -427,6 +427,36 @@ __global__ void ssi_finish_kernel(const double* __restrict__ terms, const float*
   for (int k = 0; k < 4; ++k) out[2 + k] = (float)(m[k] / B);
 }
 
+// per-sample medians of the selection: stats [B][4] = gt_shift_z, pred_shift_z, gt_scale, pred_scale (clipped to [1e-3, 1e3])
+__global__ void ssi_stats_kernel(const float* __restrict__ med, int B, float* __restrict__ stats) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  stats[4 * b] = med[b];
+  stats[4 * b + 1] = med[B + b];
+  stats[4 * b + 2] = med[8 * B + b];
+  stats[4 * b + 3] = fminf(fmaxf(med[9 * B + b], 1e-3f), 1e3f);
+}
+
+// the three selection stages of the criterion: joint median depth, joint median centre, joint median norm.  a.fac null = no
+// avg_dis normalisation in front of them (norm_mode=False)
+int ssi_medians(SsiArgs a, unsigned* hist, unsigned* state, float* med, hipStream_t st, const char* what) {
+  const int B = a.B;
+  const int64_t L = (int64_t)a.n * a.HW, rows = 6 * (int64_t)B;
+  const int nrows[3] = {2 * B, 6 * B, 2 * B};
+  const int moff[3] = {0, 2 * B, 8 * B};
+  const int hb = (int)((L + 256 * 16 - 1) / (256 * 16)) < 1 ? 1 : (int)((L + 256 * 16 - 1) / (256 * 16));
+  for (int stage = 0; stage < 3; ++stage) {
+    a.stage = stage;
+    hipLaunchKernelGGL(ssi_values_kernel, dim3((a.HW + 255) / 256, a.n, B), dim3(256), 0, st, a);
+    if (hipMemsetAsync(hist, 0, (size_t)(rows * 256 + rows * 4) * 4, st) != hipSuccess) { sp3_set_error("%s: memset failed", what); return 2; }
+    for (int pass = 0; pass < 4; ++pass) {
+      hipLaunchKernelGGL(select_hist_kernel, dim3(hb, nrows[stage]), dim3(256), 0, st, a.vals, L, state, hist, pass);
+      hipLaunchKernelGGL(select_pick_kernel, dim3(nrows[stage]), dim3(256), 0, st, state, hist, pass, med + moff[stage]);
+    }
+  }
+  return 0;
+}
+
 }  // namespace
 
 // floats of device scratch the forward needs
@@ -453,20 +483,31 @@ extern "C" int sp3_ssi_loss_forward(const float* P, const float* G, const uint8_
   hipLaunchKernelGGL(loss_norm_sums, dim3(n, B), dim3(NT), 0, st, P, G, V, pose0, n, B, HW, sums);
   hipLaunchKernelGGL(loss_factors, dim3(1), dim3(64), 0, st, sums, n, B, fix_first, fac, scal);
   SsiArgs a{P, G, V, pose0, fac, med, vals, n, B, HW, gt_scale, 0};
-  const int nrows[3] = {2 * B, 6 * B, 2 * B};
-  const int moff[3] = {0, 2 * B, 8 * B};
-  const int hb = (int)((L + 256 * 16 - 1) / (256 * 16)) < 1 ? 1 : (int)((L + 256 * 16 - 1) / (256 * 16));
-  for (int stage = 0; stage < 3; ++stage) {
-    a.stage = stage;
-    hipLaunchKernelGGL(ssi_values_kernel, dim3((HW + 255) / 256, n, B), dim3(256), 0, st, a);
-    if (hipMemsetAsync(hist, 0, (size_t)(rows * 256 + rows * 4) * 4, st) != hipSuccess) { sp3_set_error("sp3_ssi_loss_forward: memset failed"); return 2; }
-    for (int pass = 0; pass < 4; ++pass) {
-      hipLaunchKernelGGL(select_hist_kernel, dim3(hb, nrows[stage]), dim3(256), 0, st, vals, L, state, hist, pass);
-      hipLaunchKernelGGL(select_pick_kernel, dim3(nrows[stage]), dim3(256), 0, st, state, hist, pass, med + moff[stage]);
-    }
-  }
+  if (int rc = ssi_medians(a, hist, state, med, st, "sp3_ssi_loss_forward")) return rc;
   hipLaunchKernelGGL(ssi_terms_kernel, dim3(E, B), dim3(NT), 0, st, a, terms);
   hipLaunchKernelGGL(ssi_finish_kernel, dim3(1), dim3(64), 0, st, terms, med, scal, E, B, gt_scale, out);
   SP3_LAUNCH_CHECK("sp3_ssi_loss_forward");
+  return 0;
+}
+
+// The per-sample medians of Regr3D_t_ScaleShiftInv(L21, norm_mode=False, gt_scale=True).get_all_pts3d_t (the configuration of the
+// reference's eval.py:55), by the same selection as sp3_ssi_loss_forward without the avg_dis normalisation in front of it:
+// stats fp32 [B][4] = gt_shift_z, pred_shift_z, gt_scale, pred_scale (clipped).  ws: sp3_ssi_loss_ws_bytes(n, B, HW).
+extern "C" int sp3_ssi_align_stats(const float* P, const float* G, const uint8_t* V, const float* pose0, int n, int B, int HW, void* ws,
+                                   float* stats, void* stream) {
+  SP3_CHECK(P && G && V && pose0 && ws && stats && n >= 2 && B > 0 && HW > 0, "sp3_ssi_align_stats: bad arguments");
+  SP3_CHECK((reinterpret_cast<uintptr_t>(ws) & 7) == 0 && 6 * B <= 65535, "sp3_ssi_align_stats: workspace alignment / batch");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int E = 2 * (n - 1);
+  const int64_t L = (int64_t)n * HW, rows = 6 * (int64_t)B;
+  double* terms = reinterpret_cast<double*>(ws) + (int64_t)n * B * 3;
+  float* vals = reinterpret_cast<float*>(terms + (int64_t)E * B * 2);
+  unsigned* hist = reinterpret_cast<unsigned*>(vals + rows * L);
+  unsigned* state = hist + rows * 256;
+  float* med = reinterpret_cast<float*>(state + rows * 4);
+  SsiArgs a{P, G, V, pose0, nullptr, med, vals, n, B, HW, 1, 0};
+  if (int rc = ssi_medians(a, hist, state, med, st, "sp3_ssi_align_stats")) return rc;
+  hipLaunchKernelGGL(ssi_stats_kernel, dim3((B + 63) / 64), dim3(64), 0, st, (const float*)med, B, stats);
+  SP3_LAUNCH_CHECK("sp3_ssi_align_stats");
   return 0;
 }

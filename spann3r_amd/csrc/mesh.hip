@@ -8,12 +8,10 @@
 // Every fp32 operation of the projection, the depth interpolation and the vertex transform is rounded on its own (no contraction
 // into FMAs): the file-level pragma below is what the compiler honours under its default -ffp-contract=fast-honor-pragmas.
 #include "common.h"
+#include "scan.h"
 #include <math.h>
 
 #pragma clang fp contract(off)
-
-#define MB 256              // threads of every tile kernel here = elements of one scan tile
-#define SCAN_T 1024         // threads of the single-workgroup scan
 
 namespace {
 
@@ -30,24 +28,6 @@ __device__ __forceinline__ bool pixel_ok(const uint8_t* __restrict__ valid, cons
   }
   if (pts != nullptr && !(isfinite(pts[3 * p]) && isfinite(pts[3 * p + 1]) && isfinite(pts[3 * p + 2]))) return false;
   return true;
-}
-
-// rank of this lane's flag among the block's flags (exclusive) and the block's total; every thread of the block calls it
-__device__ __forceinline__ int block_rank(bool flag, int& total) {
-  __shared__ int wsum[MB / SP3_WAVE];
-  const unsigned long long b = __ballot(flag);
-  const int lane = threadIdx.x & (SP3_WAVE - 1), wave = threadIdx.x / SP3_WAVE;
-  const int below = __popcll(b & ((1ull << lane) - 1ull));
-  if (lane == 0) wsum[wave] = __popcll(b);
-  __syncthreads();
-  int base = 0, sum = 0;
-#pragma unroll
-  for (int i = 0; i < MB / SP3_WAVE; ++i) {
-    if (i < wave) base += wsum[i];
-    sum += wsum[i];
-  }
-  total = sum;
-  return base + below;
 }
 
 __global__ __launch_bounds__(MB) void k_mesh_mask(const uint8_t* __restrict__ valid, const float* __restrict__ conf, float conf_thresh,
@@ -109,36 +89,6 @@ __global__ __launch_bounds__(MB) void k_mesh_face_scatter(const uint8_t* __restr
   faces[3 * dst + 1] = c.b;
   faces[3 * dst + 2] = c.c;
   colour_px[dst] = c.colour;
-}
-
-// counts[0..nb) -> exclusive offsets in place, counts[nb] = total; info[0] = total and, for nseg segments of tps tiles each,
-// info[1 + s] = the sum of segment s.  One workgroup; thread i owns the `per` consecutive counts from i * per.
-__global__ __launch_bounds__(SCAN_T) void k_mesh_scan(int* __restrict__ counts, int nb, int per, int* __restrict__ info, int nseg, int tps) {
-  __shared__ int part[SCAN_T];
-  const int i = threadIdx.x;
-  const int lo = min(i * per, nb), hi = min(lo + per, nb);
-  int s = 0;
-  for (int j = lo; j < hi; ++j) s += counts[j];
-  part[i] = s;
-  __syncthreads();
-  for (int d = 1; d < SCAN_T; d <<= 1) {      // inclusive scan of the 1024 partial sums
-    const int v = i >= d ? part[i - d] : 0;
-    __syncthreads();
-    part[i] += v;
-    __syncthreads();
-  }
-  int run = part[i] - s;
-  for (int j = lo; j < hi; ++j) {
-    const int c = counts[j];
-    counts[j] = run;
-    run += c;
-  }
-  if (i == SCAN_T - 1) {
-    counts[nb] = part[i];
-    info[0] = part[i];
-  }
-  __syncthreads();
-  for (int sg = i; sg < nseg; sg += SCAN_T) info[1 + sg] = tps > 0 ? counts[(sg + 1) * tps] - counts[sg * tps] : 0;
 }
 
 // ------------------------------------------------------------------------------------------------ vertex compaction
@@ -375,7 +325,7 @@ extern "C" int sp3_mesh_faces(const uint8_t* valid, const float* conf, float con
   SP3_CHECK(g.cells == 0 || (faces != nullptr && colour_px != nullptr), "sp3_mesh_faces: null faces/colour_px");
   hipLaunchKernelGGL(k_mesh_mask, dim3(blocks_for(n)), dim3(MB), 0, st, valid, conf, conf_thresh, pts, n, mask);
   if (nb > 0) hipLaunchKernelGGL(k_mesh_face_count, dim3(nb), dim3(MB), 0, st, (const uint8_t*)mask, g, offsets);
-  hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(SCAN_T), 0, st, offsets, nb, (nb + SCAN_T - 1) / SCAN_T, (int*)counts, nseg, g.tps);
+  hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(SCAN_T), 0, st, offsets, nb, (nb + SCAN_T - 1) / SCAN_T, (int*)counts, nseg, g.tps);
   if (nb > 0) hipLaunchKernelGGL(k_mesh_face_scatter, dim3(nb), dim3(MB), 0, st, (const uint8_t*)mask, g, (const int*)offsets, (int*)faces, (int*)colour_px);
   SP3_LAUNCH_CHECK("sp3_mesh_faces");
   return 0;
@@ -413,7 +363,7 @@ extern "C" int sp3_mesh_compact_vertices(const float* pts, const uint32_t* rgba,
   hipLaunchKernelGGL(k_mesh_flag_init, dim3(nb), dim3(MB), 0, st, valid, conf, conf_thresh, pts, n, cloud, remap);
   if (!cloud && elems > 0) hipLaunchKernelGGL(k_mesh_flag_faces, dim3(blocks_for(elems)), dim3(MB), 0, st, (const int*)faces, elems, n, remap);
   hipLaunchKernelGGL(k_mesh_flag_count, dim3(nb), dim3(MB), 0, st, (const int*)remap, n, offsets);
-  hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(SCAN_T), 0, st, offsets, nb, (nb + SCAN_T - 1) / SCAN_T, (int*)count, 0, 0);
+  hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(SCAN_T), 0, st, offsets, nb, (nb + SCAN_T - 1) / SCAN_T, (int*)count, 0, 0);
   hipLaunchKernelGGL(k_mesh_vertex_scatter, dim3(nb), dim3(MB), 0, st, pts, (const unsigned*)rgba, n, (const int*)offsets, xf, remap, out_pos,
                      (unsigned*)out_rgba, part);
   hipLaunchKernelGGL(k_mesh_minmax, dim3(1), dim3(MB), 0, st, (const float*)part, nb, minmax);

@@ -332,3 +332,64 @@ def evaluate_reconstruction(pred_points, gt_points, threshold=0.1):
     comp, comp_med, nc2, nc2_med = completion(gt, pred, gt_n, pred_n)
     return {"acc": acc, "comp": comp, "nc1": nc1, "nc2": nc2, "acc_med": acc_med, "comp_med": comp_med, "nc1_med": nc1_med,
             "nc2_med": nc2_med, "transformation": T}
+
+
+def _align(views, preds, preds_all, clouds):
+    from .loss import L21, Regr3D_t_ScaleShiftInv, _entries
+    n = len(views)
+    if len(preds) != n:
+        raise ValueError("align_to_ground_truth: %d views but %d predictions" % (n, len(preds)))
+    if views[0]["pts3d"].shape[0] != 1:
+        raise ValueError("align_to_ground_truth: batch size 1 only (one sequence at a time, as the reference's eval.py), got %d"
+                         % views[0]["pts3d"].shape[0])
+    crit = Regr3D_t_ScaleShiftInv(L21, norm_mode=False, gt_scale=True)
+    P, G, pose0, stats = crit.align_stats(views, preds_all)
+    dev = P.device
+    H, W = views[0]["pts3d"].shape[1:3]
+    HW = H * W
+    ent = _entries(n)
+    # eval.py:146: the left prediction of every frame but the last, the right prediction of the last pair for the last frame
+    pick = [next(e for e, (s, side) in enumerate(ent) if s == j and side == 0) for j in range(n - 1)] + [len(ent) - 1]
+    Psel = P[pick].contiguous()
+    pts, gt = torch.empty(n, H, W, 3, device=dev), torch.empty(n, H, W, 3, device=dev)
+    masks = torch.cat([v["valid_mask"].to(dev) for v in views]).contiguous()
+    conf = torch.cat([p["conf"].to(dev).float() for p in preds]).contiguous()
+    img = torch.cat([v["img"].to(dev, torch.float32) for v in views]).contiguous()
+    images = torch.empty(n, H, W, 3, device=dev)
+    lib = L.load()
+    ws = torch.empty(int(lib.sp3_eval_align_ws_bytes(n * HW)) // 4 + 1, dtype=torch.int32, device=dev)
+    cp, cg, cc = (torch.empty(n * HW, 3, device=dev) for _ in range(3))
+    src = torch.empty(n * HW, dtype=torch.int32, device=dev)
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    L.check(lib.sp3_eval_align(Psel.data_ptr(), n, G.data_ptr(), n, 1, HW, pose0.data_ptr(), stats.data_ptr(), 1, pts.data_ptr(),
+                               gt.data_ptr(), masks.view(torch.uint8).data_ptr(), img.data_ptr(), ws.data_ptr(), images.data_ptr(),
+                               cp.data_ptr(), cg.data_ptr(), cc.data_ptr(), src.data_ptr(), count.data_ptr(), L.stream_ptr()),
+            "sp3_eval_align")
+    out = dict(pts_all=pts, pts_gt_all=gt, masks_all=masks, images_all=images, conf_all=conf)
+    if clouds:
+        k = int(count.item())
+        out.update(pred_cloud=cp[:k], gt_cloud=cg[:k], cloud_colors=cc[:k], cloud_index=src[:k])
+    return out
+
+
+def align_to_ground_truth(views, preds, preds_all):
+    """eval.py:128-168 on the device for one sequence (batch size 1): the predictions, shift- and scale-aligned to the ground truth by
+    `Regr3D_t_ScaleShiftInv(L21, norm_mode=False, gt_scale=True).get_all_pts3d_t`'s medians, and the ground truth, both with
+    gt_shift_z added back and in the world of view 0's camera pose.  views: spann3r_amd.views.build_views (or the reference's
+    batch); preds, preds_all: Spann3R.forward.  -> dict of pts_all, pts_gt_all [n, H, W, 3], masks_all [n, H, W] bool,
+    images_all [n, H, W, 3] in [0, 1], conf_all [n, H, W], all on the device."""
+    return _align(views, preds, preds_all, False)
+
+
+def evaluate_sequence(views, preds, preds_all, threshold=0.1):
+    """eval.py:128-218 for one sequence: align_to_ground_truth, the masked clouds (eval.py:189-191, in the reference's order: ICP and
+    the k-NN normals are order-sensitive at ties) by a compaction on the device, then evaluate_reconstruction.  Returns that
+    function's dict plus pred_cloud, gt_cloud, cloud_colors [N, 3] and cloud_index [N] (the pixel each point came from)."""
+    a = _align(views, preds, preds_all, True)
+    if a["pred_cloud"].shape[0] == 0:
+        raise ValueError("evaluate_sequence: no valid pixel in any view (the masks are all false): nothing to evaluate")
+    if not bool(torch.isfinite(a["pred_cloud"]).all()):
+        raise ValueError("evaluate_sequence: non-finite predicted points under the valid masks")
+    out = evaluate_reconstruction(a["pred_cloud"], a["gt_cloud"], threshold)
+    out.update({k: a[k] for k in ("pred_cloud", "gt_cloud", "cloud_colors", "cloud_index")})
+    return out

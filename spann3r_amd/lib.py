@@ -115,6 +115,16 @@ class RenderCam(C.Structure):
                 ("width", C.c_int32), ("height", C.c_int32), ("z_near", C.c_float), ("point_size", C.c_int32)]
 
 
+class ViewDesc(C.Structure):
+    """sp3_view_desc (include/spann3r_hip.h)"""
+    _fields_ = [("src", C.c_void_p), ("row_stride", C.c_int64), ("dtype", C.c_int32), ("src_w", C.c_int32), ("src_h", C.c_int32),
+                ("crop_l", C.c_int32), ("crop_t", C.c_int32), ("W1", C.c_int32), ("H1", C.c_int32), ("W2", C.c_int32), ("H2", C.c_int32),
+                ("l2", C.c_int32), ("t2", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("transpose", C.c_int32),
+                ("fu", C.c_float), ("fv", C.c_float), ("cu", C.c_float), ("cv", C.c_float), ("pose", C.c_float * 12),
+                ("use_raw_invalid", C.c_int32), ("raw_invalid", C.c_float), ("depth_div", C.c_float), ("min_depth", C.c_float),
+                ("max_depth", C.c_float)]
+
+
 _lib = None
 
 _PROTOS = {
@@ -250,10 +260,14 @@ _PROTOS = {
                                   C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "sp3_render_tris": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(RenderCam), C.c_int,
                         C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_ssi_align_stats": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_eval_align": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_view_depth": [C.POINTER(ViewDesc), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
 }
 EXPORTS = sorted(list(_PROTOS) + ["sp3_last_error", "sp3_version", "sp3_conf_loss_ws_bytes", "sp3_ssi_loss_ws_bytes", "sp3_sumsq_blocks", "sp3_colsum_rows_ws",
                                   "sp3_nn_query_ws_bytes", "sp3_icp_accum_ws_bytes", "sp3_sum_count_ws_bytes",
-                                  "sp3_mesh_faces_ws_bytes", "sp3_mesh_vertices_ws_bytes"])
+                                  "sp3_mesh_faces_ws_bytes", "sp3_mesh_vertices_ws_bytes", "sp3_eval_align_ws_bytes"])
 
 
 def load():
@@ -278,7 +292,7 @@ def load():
     lib.sp3_colsum_rows_ws.argtypes = [C.c_int, C.c_int]
     lib.sp3_mesh_faces_ws_bytes.restype = C.c_int64
     lib.sp3_mesh_faces_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    for name in ("sp3_nn_query_ws_bytes", "sp3_icp_accum_ws_bytes", "sp3_sum_count_ws_bytes", "sp3_mesh_vertices_ws_bytes"):
+    for name in ("sp3_nn_query_ws_bytes", "sp3_icp_accum_ws_bytes", "sp3_sum_count_ws_bytes", "sp3_mesh_vertices_ws_bytes", "sp3_eval_align_ws_bytes"):
         getattr(lib, name).restype = C.c_int64
         getattr(lib, name).argtypes = [C.c_int64]
     for name, argtypes in _PROTOS.items():

@@ -8,7 +8,8 @@ The forward and the backward run in the HIP kernels of csrc/loss.hip (sp3_conf_l
 buffers; torch only stacks the per-frame tensors, owns the autograd edge back to the predictions and computes the two
 unmasked `conf_left / conf_right` monitoring means.  Supported: L21, norm_mode 'avg_dis', gt_scale False -- the
 configuration the reference trains with -- and `Regr3D_t_ScaleShiftInv(L21, gt_scale=...)`, the validation criterion of
-training.py:39 (forward only: it runs under torch.no_grad there); anything else raises NotImplementedError.  There is no CPU path."""
+training.py:39 (forward only: it runs under torch.no_grad there), plus its `get_all_pts3d_t` for the configuration eval.py:55
+builds (norm_mode=False, gt_scale=True); anything else raises NotImplementedError.  There is no CPU path."""
 import torch
 
 from . import lib as L
@@ -158,15 +159,56 @@ class Regr3D_t_ScaleShiftInv:
     `Regr3D_t_ScaleShiftInv(L21, gt_scale=True)` of training.py:39.  Forward only."""
 
     def __init__(self, criterion, norm_mode="avg_dis", gt_scale=False, fix_first=True):
-        if not isinstance(criterion, L21Loss) or norm_mode != "avg_dis":
-            raise NotImplementedError("Regr3D_t_ScaleShiftInv: L21 and norm_mode='avg_dis' only")
+        if not isinstance(criterion, L21Loss) or (norm_mode != "avg_dis" and norm_mode):
+            raise NotImplementedError("Regr3D_t_ScaleShiftInv: L21 and norm_mode='avg_dis' (or False, for get_all_pts3d_t) only")
         self.criterion, self.norm_mode, self.gt_scale, self.fix_first = criterion, norm_mode, gt_scale, fix_first
 
     def to(self, *_a, **_k):
         return self
 
     @torch.no_grad()
+    def align_stats(self, gts, preds):
+        """The stacked buffers of the criterion and the per-sample medians behind get_all_pts3d_t (sp3_ssi_align_stats):
+        (P [E, B, HW, 3], G [n, B, HW, 3], pose0 [B, 16], stats [B, 4] = gt_shift_z, pred_shift_z, gt_scale, clipped pred_scale)."""
+        if self.norm_mode or not self.gt_scale:
+            raise NotImplementedError("get_all_pts3d_t: norm_mode=False, gt_scale=True (the configuration of the reference's eval.py) only")
+        _, P, _, G, V, pose0 = _stack_inputs(gts, preds, False)
+        E, B, HW = P.shape[:3]
+        lib = L.load()
+        ws = torch.empty(int(lib.sp3_ssi_loss_ws_bytes(len(gts), B, HW)) // 8 + 1, dtype=torch.float64, device=P.device)
+        stats = torch.empty(B, 4, device=P.device)
+        L.check(lib.sp3_ssi_align_stats(P.data_ptr(), G.data_ptr(), V.data_ptr(), pose0.data_ptr(), len(gts), B, HW, ws.data_ptr(),
+                                        stats.data_ptr(), L.stream_ptr()), "sp3_ssi_align_stats")
+        return P, G, pose0, stats
+
+    @torch.no_grad()
+    def get_all_pts3d_t(self, gts, preds):
+        """spann3r/loss.py:298-364 for norm_mode=False, gt_scale=True, with the reference's return structure:
+        (gt_pts: n x [B, H, W, 3] in the camera of view 0 with the joint median depth subtracted;
+         (pred_l, pred_r): the n - 1 left and n - 1 right predictions, shifted by their joint median depth and scaled by
+         gt_scale / pred_scale; gt_factor = pr_factor = None; masks; monitoring = gt_shift_z, pred_shift_z, gt_scale, pred_scale:
+         0-d device tensors, the means over the batch).  The medians are the selection of csrc/loss.hip, the per-point arithmetic
+         sp3_eval_align (csrc/views.hip)."""
+        P, G, pose0, stats = self.align_stats(gts, preds)
+        E, B, HW = P.shape[:3]
+        n = len(gts)
+        H, W = gts[0]["pts3d"].shape[1:3]
+        Po, Go = torch.empty_like(P), torch.empty_like(G)
+        L.check(L.load().sp3_eval_align(P.data_ptr(), E, G.data_ptr(), n, B, HW, pose0.data_ptr(), stats.data_ptr(), 0, Po.data_ptr(),
+                                        Go.data_ptr(), 0, 0, 0, 0, 0, 0, 0, 0, 0, L.stream_ptr()), "sp3_eval_align")
+        ent = _entries(n)
+        Po = Po.reshape(E, B, H, W, 3)
+        pred_l = [Po[e] for e, (_, side) in enumerate(ent) if side == 0]
+        pred_r = [Po[e] for e, (_, side) in enumerate(ent) if side == 1]
+        m = stats.mean(0)
+        monitoring = dict(gt_shift_z=m[0], pred_shift_z=m[1], gt_scale=m[2], pred_scale=m[3])
+        masks = [g["valid_mask"].to(P.device).clone() for g in gts]
+        return [Go[i].reshape(B, H, W, 3) for i in range(n)], (pred_l, pred_r), None, None, masks, monitoring
+
+    @torch.no_grad()
     def compute_frame_loss(self, gts, preds):
+        if self.norm_mode != "avg_dis":
+            raise NotImplementedError("Regr3D_t_ScaleShiftInv.compute_frame_loss: norm_mode='avg_dis' only")
         ent, P, _, G, V, pose0 = _stack_inputs(gts, preds, False)
         E, B, HW = P.shape[:3]
         n = len(gts)

@@ -116,15 +116,10 @@ def plan_view(H, W, resolution, rng=None):
     return dict(crop0=(l, t, r, b), resize=(int(out_res[0]), int(out_res[1])), crop1=(int(l2), int(t2), int(l2) + res[0], int(t2) + res[1]), out=res)
 
 
-def preprocess_image(rgb, resolution, device="cuda", rng=None):
-    """rgb: uint8 [H, W, 3] (numpy array or torch tensor, host or device) -> (img fp32 [1, 3, h, w] on the device in
-    [-1, 1], rectified to landscape; true_shape int32 [1, 2] on the CPU)."""
-    t = torch.as_tensor(rgb)
-    if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
-        raise TypeError("expected a uint8 [H, W, 3] RGB frame")
-    src = t.to(device).contiguous()                       # the only host -> device copy: the raw bytes
+def run_plan(src, p, out=None):
+    """The two image kernels for one crop plan (plan_view, or views.plan_rgbd_view for real intrinsics): src uint8 [H, W, 3] on the
+    device -> fp32 [1, 3, h, w] in [-1, 1], landscape (written into `out` when given)."""
     H, W, _ = src.shape
-    p = plan_view(H, W, resolution, rng)
     l, tt, r, b = p["crop0"]
     W1, H1 = r - l, b - tt
     W2, H2 = p["resize"]
@@ -134,11 +129,31 @@ def preprocess_image(rgb, resolution, device="cuda", rng=None):
     l2, t2 = p["crop1"][:2]
     transpose = int(outH > outW)
     tmp = torch.empty(H1, W2, 3, dtype=torch.uint8, device=src.device)
-    out = torch.empty((1, 3, outW, outH) if transpose else (1, 3, outH, outW), device=src.device)
+    shape = (1, 3, outW, outH) if transpose else (1, 3, outH, outW)
+    if out is None:
+        out = torch.empty(shape, device=src.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("run_plan: out must be a contiguous fp32 %s" % (shape,))
     L.check(L.load().sp3_preprocess_image(src.data_ptr(), W * 3, l, tt, H1, W1, hb.data_ptr(), hk.data_ptr(), hks, W2,
                                           vb.data_ptr(), vk.data_ptr(), vks, H2, l2, t2, outW, outH, transpose,
                                           tmp.data_ptr(), out.data_ptr(), L.stream_ptr()), "sp3_preprocess_image")
-    return out, torch.tensor([[outH, outW]], dtype=torch.int32)
+    return out
+
+
+def _rgb_to_device(rgb, device):
+    t = torch.as_tensor(rgb)
+    if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
+        raise TypeError("expected a uint8 [H, W, 3] RGB frame")
+    return t.to(device).contiguous()                      # the only host -> device copy: the raw bytes
+
+
+def preprocess_image(rgb, resolution, device="cuda", rng=None):
+    """rgb: uint8 [H, W, 3] (numpy array or torch tensor, host or device) -> (img fp32 [1, 3, h, w] on the device in
+    [-1, 1], rectified to landscape; true_shape int32 [1, 2] on the CPU)."""
+    src = _rgb_to_device(rgb, device)
+    p = plan_view(src.shape[0], src.shape[1], resolution, rng)
+    outW, outH = p["out"]
+    return run_plan(src, p), torch.tensor([[outH, outW]], dtype=torch.int32)
 
 
 def frames_from_images(images, resolution=224, device="cuda", kf_every=1):
