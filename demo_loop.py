@@ -36,6 +36,12 @@ def main():
     ap.add_argument("--save_glb", default=None, metavar="PATH", help="app.py's output: the confidence-masked reconstruction as one GLB, "
                     "meshed and compacted on the device (spann3r_amd.mesh)")
     ap.add_argument("--as_pointcloud", action="store_true", help="with --save_glb: app.py's as_pointcloud, points instead of a mesh")
+    ap.add_argument("--fused", action="store_true", help="one welded surface instead of per-frame sheets (spann3r_amd.fusion: TSDF volume + "
+                    "marching tetrahedra on the device): with --save_glb the fused mesh is what is written, with --vis a last picture "
+                    "fused.png is added, with --rgbd --eval the fused prediction is scored against the fused ground truth")
+    ap.add_argument("--voxel_size", type=float, default=None, help="with --fused: voxel edge in the units of the pointmaps (default: the "
+                    "longest side of the confident points' box takes 256 voxels)")
+    ap.add_argument("--trunc_voxels", type=float, default=3.0, help="with --fused: truncation distance in voxels")
     ap.add_argument("--rgbd", default=None, metavar="DIR", help="folder of *.npz frames (rgb uint8 [H,W,3], depth uint16 or float32 [H,W], "
                     "K [3,3], pose [4,4] cam2world; tools/make_rgbd_folder.py writes one): views with ground truth built on the GPU "
                     "(spann3r_amd.views.build_views) instead of synthetic frames")
@@ -103,12 +109,40 @@ def main():
         print("Time: %.4f s, FPS: %.1f  (%d frames, call %d: %s)" %
               (end - start, len(batch) / (end - start), len(batch), it,
                ["eager warm-up", "hipGraph capture", "hipGraph replay"][min(it, 2)]))
+    fuse_kw = dict(voxel_size=args.voxel_size, trunc_voxels=args.trunc_voxels)
+
+    def fused_prediction(**kw):
+        """fusion.fuse_sequence of this run (demo.py's focal and poses); pointmaps without geometry (no checkpoint ships) are fused
+        through nominal cameras instead -- focal = the longer image side, identity poses -- and that is said"""
+        from spann3r_amd import fusion
+        try:
+            return fusion.fuse_sequence(preds, batch, conf_thresh=args.conf_thresh, **fuse_kw, **kw)
+        except RuntimeError as e:
+            if "degenerate pointmaps" not in str(e):
+                raise
+            import numpy as np
+            _, H, W, _ = preds[0]["pts3d"].shape
+            print("%s: fusing through nominal cameras (focal %d, identity poses)" % (e, max(H, W)))
+            return fusion.fuse_sequence(preds, batch, conf_thresh=args.conf_thresh, focal=float(max(H, W)),
+                                        poses=np.stack([np.eye(4)] * len(preds)), **fuse_kw, **kw)
+
     if args.eval:                                                                 # eval.py:128-221
         from spann3r_amd.evaluate import evaluate_sequence
         r = evaluate_sequence(batch, preds, preds_all, threshold=0.1)
         print("Idx: %s, Acc: %s, Comp: %s, NC1: %s, NC2: %s - Acc_med: %s, Compc_med: %s, NC1c_med: %s, NC2c_med: %s  (%d points)" %
               (batch[-1]["label"].rsplit("/", 1)[0], r["acc"], r["comp"], r["nc1"], r["nc2"], r["acc_med"], r["comp_med"], r["nc1_med"],
                r["nc2_med"], len(r["pred_cloud"])))
+        if args.fused:                                                            # the surfaces instead of the per-pixel clouds
+            from spann3r_amd import fusion
+            from spann3r_amd.evaluate import align_to_ground_truth, evaluate_reconstruction
+            a = align_to_ground_truth(batch, preds, preds_all)
+            gt_mesh = fusion.fuse_views(batch, **fuse_kw)
+            pred_mesh = fusion.fuse_pointmaps(a["pts_all"], torch.cat([v["camera_intrinsics"] for v in batch]),
+                                              torch.cat([v["camera_pose"] for v in batch]), a["masks_all"], a["images_all"], **fuse_kw)
+            rf = evaluate_reconstruction(pred_mesh["vertices"], gt_mesh["vertices"], threshold=0.1)
+            print("Fused: Acc: %s, Comp: %s, NC1: %s, NC2: %s  (prediction %d vertices / %d faces, ground truth %d vertices / %d faces)" %
+                  (rf["acc"], rf["comp"], rf["nc1"], rf["nc2"], pred_mesh["vertices"].shape[0], pred_mesh["faces"].shape[0],
+                   gt_mesh["vertices"].shape[0], gt_mesh["faces"].shape[0]))
     if args.save_ply:
         from spann3r_amd.postprocess import (estimate_focal_knowing_depth, confident_points, write_ply, estimate_poses,
                                              transforms_json, save_transforms)
@@ -145,13 +179,27 @@ def main():
         vis.render_frames(pts_all, images_all, camera, args.vis, conf_all=conf_all, conf_thresh=args.conf_thresh, dynamic=args.dynamic,
                           point_size=args.point_size, surface=args.vis_surface)
         vis.vis_pred_and_imgs(pts_all, args.vis, images_all=images_all, conf_all=conf_sig_all)
+        if args.fused:
+            import os
+            fm = fused_prediction()
+            r = vis.PointRenderer(camera=camera)
+            r.add_triangles(fm["vertices"], fm["faces"], fm["colors"])
+            vis._save_png(os.path.join(args.vis, "render_frames", "fused.png"), r.image().cpu().numpy())
+            print("wrote the fused surface (%d vertices, %d faces) as render_frames/fused.png" % (fm["vertices"].shape[0], fm["faces"].shape[0]))
         print("wrote %d rendered frames (%dx%d%s) and pts/ imgs/ confs/ to %s" %
               (len(pts_all), camera.width, camera.height, (", dynamic" if args.dynamic else "") + (", surface" if args.vis_surface else ""), args.vis))
     if args.save_glb:                                                             # app.py:132-171
         import os
         from spann3r_amd import mesh
         os.makedirs(os.path.dirname(os.path.abspath(args.save_glb)), exist_ok=True)
-        info = mesh.export_glb(args.save_glb, preds, batch, conf_thresh=args.conf_thresh, as_pointcloud=args.as_pointcloud)
+        if args.fused:
+            fm = fused_prediction(scale=mesh.SCALE, transform=mesh.TRANSFORM)      # app.py's x10 and axis flip, as export_glb
+            if fm["faces"].shape[0] == 0:
+                raise RuntimeError("--fused: the volume holds no surface (nothing passes conf_thresh %g with weight >= 1)" % args.conf_thresh)
+            size = mesh.write_glb(args.save_glb, fm["vertices"], fm["colors"], fm["faces"], bounds=fm["bounds"])
+            info = dict(vertices=fm["vertices"].shape[0], faces=fm["faces"].shape[0], bytes=size)
+        else:
+            info = mesh.export_glb(args.save_glb, preds, batch, conf_thresh=args.conf_thresh, as_pointcloud=args.as_pointcloud)
         print("wrote %d vertices, %d faces (%d bytes) to %s" % (info["vertices"], info["faces"], info["bytes"], args.save_glb))
     pts = preds[-1]["pts3d_in_other_view"]
     print("last frame: pts3d_in_other_view", tuple(pts.shape), "conf mean %.3f" % float(preds[-1]["conf"].mean()))

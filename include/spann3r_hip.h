@@ -842,6 +842,85 @@ int sp3_eval_align(const float* pred, int m, const float* gt, int n, int B, int 
                    float* pred_out, float* gt_out, const uint8_t* mask, const float* img, void* ws, float* images, float* cloud_pred,
                    float* cloud_gt, float* cloud_rgb, int32_t* cloud_src, int32_t* count, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * TSDF fusion (spann3r_amd/fusion.py drives these; csrc/fusion.hip).  One welded surface per reconstruction: a truncated signed
+ * distance volume integrated from depth maps or world pointmaps, and the indexed triangle mesh of its zero level by marching
+ * tetrahedra.  There is no reference implementation of either stage (the reference's eval.py:241 ends in the comment
+ * "Get depth from pcd and run TSDFusion"); the rules below are the contract and tests/fusion_ref.py restates them in numpy.
+ * No entry point allocates, frees or synchronises.  Every fp32 operation is rounded on its own and sums run left to right.
+ *
+ * Volume: nx x ny x nz voxels, voxel (i, j, k) at linear index (k ny + j) nx + i; its centre is (origin.x + fp32(i) * voxel,
+ *   origin.y + fp32(j) * voxel, origin.z + fp32(k) * voxel): one rounded multiply, one rounded add.  origin3 is a HOST pointer to
+ *   three finite fp32; voxel and trunc are finite and > 0.  State: tsdf fp32 [n] (initial 1), weight fp32 [n] (initial 0), rgb fp32
+ *   [n, 3] in [0, 1] (nullable: no colours).  Vertex and face indices are int32: 7 n < 2^31 (sp3_tsdf_extract, whose face counter
+ *   can reach 12 per cell: 12 n < 2^31).  n = 0 is a no-op.
+ *
+ * sp3_tsdf_integrate: T frames into the volume in ONE launch.  frames_host and frames_dev hold the same T descriptors; the host
+ *   copy is only read for the checks of the call.  A frame has either depth (fp32, camera z) or pts (fp32 world points, 3 per pixel)
+ *   -- exactly one -- and nullable valid, pixel_weight and rgba maps; pixel (px, py) of every map of a frame is element
+ *   p = py * row_stride + px (pts: 3 p .. 3 p + 2).  With rgb non-null every frame needs rgba (packed as sp3_pack_rgba8 packs);
+ *   with rgb null rgba is ignored.  M = w2c, the 3 x 4 world-to-camera matrix, row-major.
+ *   One lane owns one voxel, loads its state once, walks the frames in table order and stores the state once.  Per frame, for the
+ *   voxel centre (x, y, z):
+ *     Xc_r = ((M_r0 x + M_r1 y) + M_r2 z) + M_r3 (sp3_view_depth's world step);  skip unless Xc.z > 0;
+ *     u = fu * Xc.x / Xc.z + cu, v = fv * Xc.y / Xc.z + cv (multiply, divide, add);  px = floor(u + 0.5), py = floor(v + 0.5);
+ *     skip unless 0 <= px < w and 0 <= py < h (compared in fp32, a NaN fails);  skip if valid[p] == 0;
+ *     d = depth[p], or from pts[p] = (X, Y, Z): d = ((M_20 X + M_21 Y) + M_22 Z) + M_23;  skip if d is not finite or d <= 0;
+ *     s = d - Xc.z;  skip if s < -trunc;  f = min(1, s / trunc) (a division);
+ *     a = pixel_weight[p], or 1;  skip unless a > 0 and finite;
+ *     W' = weight + a;  tsdf = (weight * tsdf + a * f) / W';  with colours, per channel c of rgba: rgb_c = (weight * rgb_c + a * q) / W',
+ *     q = fp32(byte c) / 255;  weight = W'.
+ *   No atomics, no workgroup waits on another.  The state between two frames is the fp32 state a call would store, so two calls with
+ *   frames A then B give the bits of one call with A followed by B.  T = 0 is a no-op.
+ *
+ * sp3_tsdf_extract: marching tetrahedra.  Inside means tsdf < 0 (0 is outside).  Voxel v is observed when weight[v] >= min_weight
+ *   (min_weight > 0).  Corner code of a cube: c = dx + 2 dy + 4 dz.
+ *   Cells: cell v is the cube of the voxels v + (dx, dy, dz), for i < nx - 1, j < ny - 1, k < nz - 1; it is live when all 8 are
+ *     observed.  Every cell is cut into the 6 tetrahedra of the Kuhn triangulation around the diagonal 0-7, in this order and vertex
+ *     order (corner codes; each has det(v1 - v0, v2 - v0, v3 - v0) > 0):
+ *       T0 = (0, 1, 3, 7), T1 = (0, 5, 1, 7), T2 = (0, 3, 2, 7), T3 = (0, 2, 6, 7), T4 = (0, 4, 5, 7), T5 = (0, 6, 4, 7).
+ *   Vertices: a tetrahedron edge joins two voxels whose offsets differ by one of 7 steps; it belongs to its endpoint a with the
+ *     lower linear index, in slot 0..6 = +x, +y, +z, +x+y, +y+z, +x+z, +x+y+z.  Slot s of voxel a carries a vertex when the other
+ *     endpoint b lies in the volume, a and b are both observed and exactly one of them is inside (so a vertex on an edge that no
+ *     live cell uses may be emitted; sp3_mesh_compact_vertices drops it).  The vertex: t = tsdf_a / (tsdf_a - tsdf_b), per coordinate
+ *     p = p_a + t * (p_b - p_a) with p_a, p_b the voxel centres by the rule above; colour per channel c = rgb_a + t * (rgb_b - rgb_a),
+ *     packed as sp3_pack_rgba8 packs (rgb null: 0xffffffff).  Vertices are written densely in (owner index, slot) order: vertices
+ *     fp32 [V, 3], rgba uint32 [V] (nullable).
+ *   Faces: per live cell in index order, per tetrahedron T0..T5, with m the vertices (positions 0..3 of the tetrahedron) that are
+ *     inside.  "(a, b, c, d) even" means the permutation has an even number of inversions.  P_xy = the vertex on the edge between
+ *     tetrahedron vertices x and y.
+ *       none or all inside: nothing.
+ *       one inside (lone = it) or one outside (lone = it): the other three in increasing position (a, b, c); swap b and c unless
+ *         (lone, a, b, c) is even; swap them once more if the lone vertex is the outside one; one triangle (P_lone,a, P_lone,b, P_lone,c).
+ *       two inside (m < n) and two outside (q < r): swap q and r unless (m, n, q, r) is even; two triangles (P_mq, P_mr, P_nr) and
+ *         (P_mq, P_nr, P_nq).
+ *     With linear interpolation every triangle's normal ((p1 - p0) x (p2 - p0)) then points to the positive (outside) side.  The cut
+ *     is the same in every cell, so faces of neighbouring cells match and the surface is closed wherever the cells are live; all
+ *     cells that share an edge share its one vertex: the mesh is welded by construction.  faces int32 [F, 3] are written densely in
+ *     (cell index, tetrahedron, triangle) order and hold rows of `vertices`.
+ *   counts int32 [2] = V, F, the true totals.  Nothing is written at or beyond row max_vertices of vertices / rgba or row max_faces
+ *     of faces (a face within capacity may name a vertex beyond it): the caller compares, allocates and calls again.
+ *   Both compactions are the tile count / single-workgroup scan / scatter of csrc/scan.h (6 launches in all).  ws: device scratch of
+ *     sp3_tsdf_extract_ws_bytes(), 16-byte aligned: a 7-bit edge mask and one exclusive vertex offset per voxel (5 n bytes), and
+ *     the two tile tables; a face finds a vertex as offset[owner] + popcount(mask[owner] below its slot). */
+typedef struct sp3_tsdf_frame {
+  const float* depth;          /* device fp32 [h, row_stride], camera z; or null */
+  const float* pts;            /* device fp32 [h, row_stride, 3], world points; or null */
+  const uint8_t* valid;        /* nullable */
+  const float* pixel_weight;   /* nullable */
+  const uint32_t* rgba;        /* nullable (required when the volume has colours) */
+  int64_t row_stride;          /* in pixels, common to the maps of the frame */
+  int32_t w, h;
+  float fu, fv, cu, cv;
+  float w2c[12];
+} sp3_tsdf_frame;
+int sp3_tsdf_integrate(const sp3_tsdf_frame* frames_host, const sp3_tsdf_frame* frames_dev, int T, int nx, int ny, int nz,
+                       const float* origin3, float voxel, float trunc, float* tsdf, float* weight, float* rgb, void* stream);
+int64_t sp3_tsdf_extract_ws_bytes(int nx, int ny, int nz);
+int sp3_tsdf_extract(const float* tsdf, const float* weight, const float* rgb, int nx, int ny, int nz, const float* origin3, float voxel,
+                     float min_weight, void* ws, int64_t max_vertices, int64_t max_faces, float* vertices, uint32_t* rgba, int32_t* faces,
+                     int32_t* counts, void* stream);
+
 /* small utilities */
 /* n (1..8) contiguous device-to-device copies in one launch; every copy 16-byte aligned and a multiple of 16 bytes.
  * (The sequence loop's per-frame bookkeeping -- torch .clone() / slice assignments around spann3r/model.py:523-531.) */

@@ -1,6 +1,7 @@
-// Order-preserving compaction in plain multi-launch form, shared by csrc/mesh.hip (faces, vertices) and csrc/views.hip (the masked
-// clouds of the evaluation): one count per 256-element tile (block_rank), one single-workgroup exclusive scan of the counts
-// (k_tile_scan), one scatter to offsets[tile] + rank.  No workgroup waits on another; the launch boundaries are the only hand-offs.
+// Order-preserving compaction in plain multi-launch form, shared by csrc/mesh.hip (faces, vertices), csrc/views.hip (the masked
+// clouds of the evaluation) and csrc/fusion.hip (surface vertices and faces of a TSDF volume): one count per 256-element tile
+// (block_rank, or block_excl_sum where an element gives several), one single-workgroup exclusive scan of the counts (k_tile_scan),
+// one scatter to offsets[tile] + rank.  No workgroup waits on another; the launch boundaries are the only hand-offs.
 // Integer work only.  Everything here is per translation unit (anonymous namespace).
 #pragma once
 #include "common.h"
@@ -26,6 +27,29 @@ __device__ __forceinline__ int block_rank(bool flag, int& total) {
   }
   total = sum;
   return base + below;
+}
+
+// the same for a small count per lane instead of a flag (csrc/fusion.hip: vertices per voxel, faces per cell): the exclusive sum of
+// `v` over the lanes below this one and the block's total; every thread of the block calls it
+__device__ __forceinline__ int block_excl_sum(int v, int& total) {
+  __shared__ int wtot[MB / SP3_WAVE];
+  const int lane = threadIdx.x & (SP3_WAVE - 1), wave = threadIdx.x / SP3_WAVE;
+  int inc = v;
+#pragma unroll
+  for (int o = 1; o < SP3_WAVE; o <<= 1) {
+    const int up = __shfl_up(inc, o);
+    if (lane >= o) inc += up;
+  }
+  if (lane == SP3_WAVE - 1) wtot[wave] = inc;
+  __syncthreads();
+  int base = 0, sum = 0;
+#pragma unroll
+  for (int i = 0; i < MB / SP3_WAVE; ++i) {
+    if (i < wave) base += wtot[i];
+    sum += wtot[i];
+  }
+  total = sum;
+  return base + inc - v;
 }
 
 // counts[0..nb) -> exclusive offsets in place, counts[nb] = total; info[0] = total and, for nseg segments of tps tiles each,

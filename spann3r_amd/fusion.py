@@ -1,0 +1,339 @@
+"""TSDF fusion on the device: one welded surface per reconstruction.
+
+The reference stops at per-frame pointmap sheets (app.py's triangle soup) and at the comment `# Get depth from pcd and run TSDFusion`
+(eval.py:241).  Here a truncated signed distance volume is integrated from depth maps or world pointmaps (sp3_tsdf_integrate: one
+launch for all frames of a call, one lane per voxel) and the zero level is extracted by marching tetrahedra as a welded, indexed
+triangle mesh (sp3_tsdf_extract: two order-preserving compactions); csrc/fusion.hip, rules in include/spann3r_hip.h "TSDF fusion".
+`mesh.compact_vertices` then drops the vertices no face uses, applies scale / transform and gives the bounds, so `extract_mesh`
+returns the dict shape of `mesh.scene_mesh` and `mesh.write_glb` takes it as it is.
+
+What is unpinned: there is no reference implementation of the fusion (Open3D is not available and the reference has only the
+comment); tests/fusion_ref.py restates the header's rules in numpy and the kernels are checked against that.  `fuse_sequence`
+inherits whatever error `estimate_poses` and the single shared focal of `estimate_focal_knowing_depth` have.
+torch provides memory; there is no CPU path."""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import lib as L
+from . import mesh as M
+
+INDEX_LIMIT = (2 ** 31 - 1) // 7        # voxels: 7 n < 2^31 (int32 vertex indices, 7 edge slots per voxel)
+
+
+def _dev(x, name):
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("%s: expected a CUDA tensor, got %s" % (name, type(x).__name__))
+    if not x.is_cuda:
+        raise RuntimeError("%s: fusion runs on the GPU (HIP kernels); there is no CPU path -- pass a CUDA tensor" % name)
+    return x
+
+
+def _check_dims(dims):
+    dims = tuple(int(d) for d in dims)
+    if len(dims) != 3 or min(dims) < 0:
+        raise ValueError("TSDFVolume: dims %s must be three sizes (nx, ny, nz) >= 0" % (dims,))
+    if dims[0] * dims[1] * dims[2] > INDEX_LIMIT:
+        raise ValueError("TSDFVolume: dims %s over the index limit: %d voxels, 7 nx ny nz must stay below 2^31 (int32 vertex and face indices)"
+                         % (dims, dims[0] * dims[1] * dims[2]))
+    return dims
+
+
+def _frames_list(x, name, tail, optional=False):
+    """a [T, h, w(, 3)] stack or a list of [h, w(, 3)] maps -> list of device tensors (None stays None; with `optional` a list may hold
+    None for a frame without that map)"""
+    if x is None:
+        return None
+    if isinstance(x, torch.Tensor):
+        if x.dim() != 3 + len(tail):
+            raise RuntimeError("integrate: %s %s must be a [T, h, w%s] stack or a list of maps" % (name, tuple(x.shape), ", 3" if tail else ""))
+        x = list(x)
+    out = []
+    for i, m in enumerate(x):
+        if m is None and optional:
+            out.append(None)
+            continue
+        m = _dev(m, "integrate: %s[%d]" % (name, i))
+        if m.dim() != 2 + len(tail) or tuple(m.shape[2:]) != tail:
+            raise RuntimeError("integrate: %s[%d] %s must be [h, w%s]" % (name, i, tuple(m.shape), ", 3" if tail else ""))
+        out.append(m)
+    return out
+
+
+def _host_mats(x, T, shape, name):
+    """one matrix or T of them (array, tensor or list, host or device) -> float64 numpy [T, *shape]"""
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    elif isinstance(x, (list, tuple)):
+        x = np.stack([m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else np.asarray(m) for m in x])
+    x = np.asarray(x, np.float64)
+    if x.shape == shape:
+        x = np.broadcast_to(x, (T,) + shape)
+    if x.shape != (T,) + shape:
+        raise ValueError("integrate: %s %s must be %s or [%d, %d, %d]" % (name, x.shape, list(shape), T, shape[0], shape[1]))
+    return x
+
+
+def camera_tables(intrinsics, cam2world, T):
+    """The host side of `integrate`: intrinsics [3, 3] or [T, 3, 3], cam2world [T, 4, 4] -> (fu, fv, cu, cv float64 [T, 4],
+    world-to-camera fp32 [T, 12]), the poses inverted in float64.  Raises for a skewed K or a non-finite or singular pose."""
+    K = _host_mats(intrinsics, T, (3, 3), "intrinsics")
+    P = _host_mats(cam2world, T, (4, 4), "cam2world")
+    for i in range(T):
+        if K[i, 0, 1] != 0.0 or K[i, 1, 0] != 0.0:
+            raise ValueError("integrate: frame %d: intrinsics with a skew term" % i)
+        if not np.isfinite(K[i]).all():
+            raise ValueError("integrate: frame %d: non-finite intrinsics" % i)
+        if not np.isfinite(P[i]).all():
+            raise ValueError("integrate: frame %d: camera pose must be a finite 4x4 cam2world matrix" % i)
+    try:
+        w2c = np.linalg.inv(P) if T else P
+    except np.linalg.LinAlgError:
+        raise ValueError("integrate: a camera pose is singular")
+    if not np.isfinite(w2c).all():
+        raise ValueError("integrate: a camera pose is singular")
+    return np.stack([K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]], axis=1), w2c[:, :3, :].reshape(T, 12).astype(np.float32)
+
+
+class TSDFVolume:
+    """A truncated signed distance volume on the device: tsdf fp32 [nz, ny, nx] (initial 1), weight (initial 0) and, with color,
+    rgb fp32 [nz, ny, nx, 3] in [0, 1].  Voxel (i, j, k) has its centre at origin + (i, j, k) * voxel_size.  trunc defaults to
+    3 voxels."""
+
+    def __init__(self, origin, voxel_size, dims, trunc=None, color=True, device="cuda"):
+        self.dims = _check_dims(dims)
+        origin = np.asarray(origin, np.float64).reshape(-1)
+        if origin.shape != (3,) or not np.isfinite(origin).all():
+            raise ValueError("TSDFVolume: origin must be three finite numbers")
+        self.voxel_size = float(np.float32(voxel_size))
+        if not (self.voxel_size > 0 and math.isfinite(self.voxel_size)):
+            raise ValueError("TSDFVolume: voxel_size must be positive and finite, got %r" % (voxel_size,))
+        self.trunc = float(np.float32(3.0 * self.voxel_size if trunc is None else trunc))
+        if not (self.trunc > 0 and math.isfinite(self.trunc)):
+            raise ValueError("TSDFVolume: trunc must be positive and finite, got %r" % (trunc,))
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("TSDFVolume: fusion runs on the GPU (HIP kernels); there is no CPU path")
+        self.origin = origin.astype(np.float32)
+        self._origin_c = (C.c_float * 3)(*self.origin.tolist())
+        nx, ny, nz = self.dims
+        self.tsdf = torch.empty((nz, ny, nx), dtype=torch.float32, device=self.device)
+        self.weight = torch.empty((nz, ny, nx), dtype=torch.float32, device=self.device)
+        self.rgb = torch.empty((nz, ny, nx, 3), dtype=torch.float32, device=self.device) if color else None
+        self.launches = 0                   # sp3_tsdf_integrate launches so far
+        self.reset()
+
+    def reset(self):
+        self.tsdf.fill_(1.0)
+        self.weight.zero_()
+        if self.rgb is not None:
+            self.rgb.zero_()
+
+    def integrate(self, depth=None, pts=None, intrinsics=None, cam2world=None, valid=None, weight=None, images=None):
+        """T frames into the volume in ONE launch.  depth [T, h, w] (camera z) or pts [T, h, w, 3] (world points; the depth of a pixel
+        is the z of its point in that frame's camera) -- stacks or lists of device tensors; intrinsics [3, 3] or [T, 3, 3];
+        cam2world [T, 4, 4], inverted in float64 on the host; valid bool / uint8, weight fp32 (lists of these may hold None for single
+        frames) and images (floats in [0, 1], [T, h, w, 3]; required when the volume has colours) are optional.  Nothing synchronises."""
+        if (depth is None) == (pts is None):
+            raise ValueError("integrate: give depth or pts, exactly one")
+        if intrinsics is None or cam2world is None:
+            raise ValueError("integrate: intrinsics and cam2world are required")
+        src = _frames_list(depth, "depth", ()) if depth is not None else _frames_list(pts, "pts", (3,))
+        T = len(src)
+        if T == 0:
+            return self
+        return self.integrate_table(self.frame_table(src, depth is not None, intrinsics, cam2world, valid, weight, images))
+
+    def frame_table(self, src, is_depth, intrinsics, cam2world, valid=None, weight=None, images=None):
+        """The descriptor table of `integrate` for the list `src` of depth maps (is_depth) or pointmaps: (host table, device copy, T,
+        the tensors it points to).  integrate_table launches it; a table can be launched again as long as its tensors live."""
+        T = len(src)
+        depth = src if is_depth else None
+        fk, w2c = camera_tables(intrinsics, cam2world, T)
+        maps = {"valid": _frames_list(valid, "valid", (), True), "weight": _frames_list(weight, "weight", (), True),
+                "images": _frames_list(images, "images", (3,))}
+        for name, m in maps.items():
+            if m is not None and len(m) != T:
+                raise RuntimeError("integrate: mismatched lengths: %d frames, %d %s maps" % (T, len(m), name))
+        if self.rgb is not None and maps["images"] is None:
+            raise ValueError("integrate: the volume has colours: pass images (or build it with color=False)")
+        lib = L.load()
+        st = L.stream_ptr()
+        table = (L.TsdfFrame * T)()
+        keep = []
+        for i in range(T):
+            s = src[i].float().contiguous()
+            h, w = s.shape[:2]
+            e = table[i]
+            if depth is not None:
+                e.depth, e.pts = s.data_ptr(), None
+            else:
+                e.depth, e.pts = None, s.data_ptr()
+            keep.append(s)
+            for name, m in maps.items():
+                if m is not None and m[i] is not None and tuple(m[i].shape[:2]) != (h, w):
+                    raise RuntimeError("integrate: mismatched shapes: frame %d is %d x %d, its %s map %s" % (i, h, w, name, tuple(m[i].shape)))
+            if maps["valid"] is not None and maps["valid"][i] is not None:
+                v = maps["valid"][i].to(torch.uint8).contiguous()
+                e.valid = v.data_ptr()
+                keep.append(v)
+            if maps["weight"] is not None and maps["weight"][i] is not None:
+                a = maps["weight"][i].float().contiguous()
+                e.pixel_weight = a.data_ptr()
+                keep.append(a)
+            if maps["images"] is not None and self.rgb is not None:
+                c = maps["images"][i].float().contiguous()
+                rgba = torch.empty(h * w, dtype=torch.int32, device=self.device)
+                L.check(lib.sp3_pack_rgba8(c.data_ptr(), h * w, rgba.data_ptr(), st), "sp3_pack_rgba8")
+                e.rgba = rgba.data_ptr()
+                keep += [c, rgba]
+            e.row_stride, e.w, e.h = w, w, h
+            e.fu, e.fv, e.cu, e.cv = (float(x) for x in fk[i])
+            e.w2c[:] = w2c[i].tolist()
+        table_d = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(self.device)
+        return table, table_d, T, keep
+
+    def integrate_table(self, tbl):
+        """one sp3_tsdf_integrate launch of a frame_table"""
+        table, table_d, T, _ = tbl
+        lib, st = L.load(), L.stream_ptr()
+        nx, ny, nz = self.dims
+        L.check(lib.sp3_tsdf_integrate(table, table_d.data_ptr(), T, nx, ny, nz, self._origin_c, self.voxel_size, self.trunc,
+                                       self.tsdf.data_ptr(), self.weight.data_ptr(), L.ptr(self.rgb), st), "sp3_tsdf_integrate")
+        self.launches += 1
+        return self
+
+    def extract_raw(self, min_weight=1.0, max_vertices=None, max_faces=None):
+        """sp3_tsdf_extract as it is: -> (vertices fp32 [cap, 3], rgba int32 [cap], faces int32 [cap, 3], counts int32 [2] on the
+        device = the true V and F).  Nothing beyond the capacities is written; nothing synchronises."""
+        nx, ny, nz = self.dims
+        n = nx * ny * nz
+        lib = L.load()
+        cap_v = int(max_vertices) if max_vertices is not None else min(7 * n, max(4096, n // 4))
+        cap_f = int(max_faces) if max_faces is not None else min(12 * n, 2 * cap_v)
+        vertices = torch.empty((max(cap_v, 1), 3), dtype=torch.float32, device=self.device)
+        rgba = torch.empty(max(cap_v, 1), dtype=torch.int32, device=self.device)
+        faces = torch.empty((max(cap_f, 1), 3), dtype=torch.int32, device=self.device)
+        counts = torch.zeros(2, dtype=torch.int32, device=self.device)
+        ws = torch.empty(max(int(lib.sp3_tsdf_extract_ws_bytes(nx, ny, nz)), 16), dtype=torch.uint8, device=self.device)
+        L.check(lib.sp3_tsdf_extract(self.tsdf.data_ptr(), self.weight.data_ptr(), L.ptr(self.rgb), nx, ny, nz, self._origin_c, self.voxel_size,
+                                     float(min_weight), ws.data_ptr(), cap_v, cap_f, vertices.data_ptr(), rgba.data_ptr(), faces.data_ptr(),
+                                     counts.data_ptr(), L.stream_ptr()), "sp3_tsdf_extract")
+        return vertices[:cap_v], rgba[:cap_v], faces[:cap_f], counts
+
+    def extract_mesh(self, min_weight=1.0, scale=1.0, transform=None):
+        """The zero level as a welded mesh of the voxels seen with weight >= min_weight: dict(vertices fp32 [V, 3], colors uint8
+        [V, 4], faces int32 [F, 3], bounds float32 numpy [2, 3]), the shape of mesh.scene_mesh; positions are transform (scale x).
+        The counts are read once on the host; if the first guess of the capacities was too small the extraction runs once more with
+        the reported sizes.  Vertices that no face uses are dropped (mesh.compact_vertices)."""
+        if not min_weight > 0:
+            raise ValueError("extract_mesh: min_weight must be > 0, got %r" % (min_weight,))
+        vertices, rgba, faces, counts = self.extract_raw(min_weight)
+        nv, nf = counts.cpu().tolist()
+        if nv > vertices.shape[0] or nf > faces.shape[0]:
+            vertices, rgba, faces, counts = self.extract_raw(min_weight, nv, nf)
+            nv2, nf2 = counts.cpu().tolist()
+            if (nv2, nf2) != (nv, nf):
+                raise RuntimeError("extract_mesh: the volume changed between two extractions (%d, %d) -> (%d, %d)" % (nv, nf, nv2, nf2))
+        faces = faces[:nf].contiguous()
+        pos, col, bounds = M.compact_vertices(vertices[:nv].contiguous(), rgba[:nv].contiguous(), faces=faces, scale=scale, transform=transform)
+        if pos.shape[0] == 0:
+            faces = faces[:0]
+        return dict(vertices=pos, colors=col.contiguous().view(torch.uint8).reshape(-1, 4), faces=faces, bounds=bounds)
+
+
+def volume_for_points(points, voxel_size=None, dims_max=256, trunc_voxels=3.0, color=True):
+    """The volume whose box is that of `points` (device fp32 [n, 3], all finite) padded by trunc = trunc_voxels voxels.  voxel_size
+    None: the largest voxel with which the longest side fits dims_max voxels."""
+    pts = _dev(points, "volume_for_points: points").reshape(-1, 3).float()
+    if pts.shape[0] == 0:
+        raise RuntimeError("volume_for_points: no point to fit a volume to")
+    box = torch.stack([pts.amin(0), pts.amax(0)]).double().cpu().numpy()
+    if not np.isfinite(box).all():
+        raise RuntimeError("volume_for_points: non-finite point")
+    extent = box[1] - box[0]
+    if dims_max < 2 * trunc_voxels + 2:
+        raise ValueError("volume_for_points: dims_max %d leaves no room inside a padding of %g voxels" % (dims_max, trunc_voxels))
+    if voxel_size is None:
+        voxel_size = max(float(extent.max()), 1e-6) / (dims_max - 1 - 2 * math.ceil(trunc_voxels))
+    trunc = trunc_voxels * voxel_size
+    pad = math.ceil(trunc_voxels) * voxel_size
+    dims = tuple(int(math.ceil((e + 2 * pad) / voxel_size - 1e-9)) + 1 for e in extent)
+    if max(dims) > dims_max:
+        raise ValueError("volume_for_points: voxel_size %g needs %s voxels, over dims_max %d" % (voxel_size, dims, dims_max))
+    return TSDFVolume(box[0] - pad, voxel_size, dims, trunc=trunc, color=color, device=pts.device)
+
+
+def fuse_sequence(preds, batch, conf_thresh=1e-3, voxel_size=None, dims_max=256, trunc_voxels=3.0, min_weight=1.0, scale=1.0,
+                  transform=None, color=True, return_volume=False, focal=None, poses=None):
+    """The fused surface of a reconstruction from model.forward's `preds` and its `batch`: demo.py's own sequence -- the stacked
+    pointmaps (mesh.sequence_tensors), the focal of frame 0 (estimate_focal_knowing_depth), one pose per frame (estimate_poses) --
+    then the pointmaps of the pixels with (conf - 1) / conf > conf_thresh integrated through the `pts` path into a volume around
+    the confident points.  -> the mesh dict of TSDFVolume.extract_mesh (and the volume with return_volume).
+    focal / poses (cam2world [t, 4, 4]) given: used instead of the estimates.  Pointmaps without geometry (seeded random weights)
+    give a focal near 0: that raises rather than fusing through meaningless cameras."""
+    from .postprocess import estimate_focal_knowing_depth, estimate_poses
+    pts_all, images_all, conf_all = M.sequence_tensors(preds, batch)
+    _dev(pts_all, "fuse_sequence: pts3d")
+    t, h, w, _ = pts_all.shape
+    pp = (w / 2, h / 2)
+    if focal is None:
+        focal = float(estimate_focal_knowing_depth(pts_all[:1], torch.tensor(pp), focal_mode="weiszfeld").item())
+        if not (focal > 1e-3 and math.isfinite(focal)):
+            raise RuntimeError("fuse_sequence: degenerate pointmaps: the focal of the first frame came out as %g" % focal)
+    focal = float(focal)
+    if not (focal > 0 and math.isfinite(focal)):
+        raise ValueError("fuse_sequence: focal must be positive and finite, got %r" % focal)
+    if poses is None:
+        poses, _ = estimate_poses(pts_all, focal, pp)
+    valid = (conf_all - 1) / conf_all > conf_thresh
+    K = np.array([[focal, 0, pp[0]], [0, focal, pp[1]], [0, 0, 1]], np.float64)
+    return fuse_pointmaps(pts_all, K, np.asarray(poses, np.float64), valid, images_all, voxel_size, dims_max, trunc_voxels, min_weight, scale,
+                          transform, color, return_volume)
+
+
+def fuse_pointmaps(pts_all, intrinsics, cam2world, valid, images=None, voxel_size=None, dims_max=256, trunc_voxels=3.0, min_weight=1.0,
+                   scale=1.0, transform=None, color=True, return_volume=False):
+    """World pointmaps pts_all [t, h, w, 3] with their cameras, integrated through the `pts` path into a volume around the valid
+    (and finite) points -> the mesh dict of TSDFVolume.extract_mesh (and the volume with return_volume)."""
+    pts_all = _dev(pts_all, "fuse_pointmaps: pts_all").float()
+    if pts_all.dim() != 4 or pts_all.shape[-1] != 3 or _dev(valid, "fuse_pointmaps: valid").shape != pts_all.shape[:3]:
+        raise RuntimeError("fuse_pointmaps: mismatched shapes: pts_all %s must be [t, h, w, 3], valid %s [t, h, w]" %
+                           (tuple(pts_all.shape), tuple(valid.shape)))
+    valid = valid.bool() & torch.isfinite(pts_all).all(-1)
+    if not bool(valid.any()):
+        raise RuntimeError("fuse_pointmaps: no valid point (nothing passes the confidence threshold)")
+    color = color and images is not None
+    vol = volume_for_points(pts_all[valid], voxel_size, dims_max, trunc_voxels, color)
+    vol.integrate(pts=pts_all, intrinsics=intrinsics, cam2world=cam2world, valid=valid, images=images if color else None)
+    out = vol.extract_mesh(min_weight, scale, transform)
+    return (out, vol) if return_volume else out
+
+
+def fuse_views(views, voxel_size=None, dims_max=256, trunc_voxels=3.0, min_weight=1.0, scale=1.0, transform=None, color=True,
+               return_volume=False):
+    """The ground-truth surface of an RGB-D sequence: the views of views.build_views integrated through `depthmap`,
+    `camera_intrinsics`, `camera_pose` and `valid_mask` into a volume around their valid `pts3d`.  -> as fuse_sequence.
+    Landscape views only: a portrait view rectified to landscape carries row-permuted intrinsics, which are refused as skewed."""
+    if len(views) == 0:
+        raise ValueError("fuse_views: no views")
+    depth = torch.cat([_dev(v["depthmap"], "fuse_views: depthmap") for v in views]).float()
+    valid = torch.cat([v["valid_mask"] for v in views])
+    pts = torch.cat([v["pts3d"] for v in views]).float()
+    if depth.dim() != 3 or valid.shape != depth.shape or pts.shape != depth.shape + (3,):
+        raise RuntimeError("fuse_views: mismatched shapes: depthmap %s, valid_mask %s, pts3d %s" % (tuple(depth.shape), tuple(valid.shape), tuple(pts.shape)))
+    if not bool(valid.any()):
+        raise RuntimeError("fuse_views: no valid pixel")
+    K = torch.cat([v["camera_intrinsics"] for v in views]).double().cpu().numpy()
+    poses = torch.cat([v["camera_pose"] for v in views]).double().cpu().numpy()
+    images = None
+    if color:
+        images = (torch.cat([v["img"] for v in views]).to(depth.device).permute(0, 2, 3, 1).float() + 1.0) / 2.0
+        if images.shape[1:3] != depth.shape[1:3]:
+            raise RuntimeError("fuse_views: img %s does not match depthmap %s" % (tuple(images.shape), tuple(depth.shape)))
+    vol = volume_for_points(pts[valid], voxel_size, dims_max, trunc_voxels, color)
+    vol.integrate(depth=depth, intrinsics=K, cam2world=poses, valid=valid, images=images)
+    out = vol.extract_mesh(min_weight, scale, transform)
+    return (out, vol) if return_volume else out

@@ -125,6 +125,13 @@ class ViewDesc(C.Structure):
                 ("max_depth", C.c_float)]
 
 
+class TsdfFrame(C.Structure):
+    """sp3_tsdf_frame (include/spann3r_hip.h)"""
+    _fields_ = [("depth", C.c_void_p), ("pts", C.c_void_p), ("valid", C.c_void_p), ("pixel_weight", C.c_void_p), ("rgba", C.c_void_p),
+                ("row_stride", C.c_int64), ("w", C.c_int32), ("h", C.c_int32), ("fu", C.c_float), ("fv", C.c_float), ("cu", C.c_float),
+                ("cv", C.c_float), ("w2c", C.c_float * 12)]
+
+
 _lib = None
 
 _PROTOS = {
@@ -264,10 +271,15 @@ _PROTOS = {
     "sp3_eval_align": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "sp3_view_depth": [C.POINTER(ViewDesc), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_tsdf_integrate": [C.POINTER(TsdfFrame), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_float,
+                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_tsdf_extract": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_void_p,
+                         C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
 }
 EXPORTS = sorted(list(_PROTOS) + ["sp3_last_error", "sp3_version", "sp3_conf_loss_ws_bytes", "sp3_ssi_loss_ws_bytes", "sp3_sumsq_blocks", "sp3_colsum_rows_ws",
                                   "sp3_nn_query_ws_bytes", "sp3_icp_accum_ws_bytes", "sp3_sum_count_ws_bytes",
-                                  "sp3_mesh_faces_ws_bytes", "sp3_mesh_vertices_ws_bytes", "sp3_eval_align_ws_bytes"])
+                                  "sp3_mesh_faces_ws_bytes", "sp3_mesh_vertices_ws_bytes", "sp3_eval_align_ws_bytes",
+                                  "sp3_tsdf_extract_ws_bytes"])
 
 
 def load():
@@ -292,6 +304,8 @@ def load():
     lib.sp3_colsum_rows_ws.argtypes = [C.c_int, C.c_int]
     lib.sp3_mesh_faces_ws_bytes.restype = C.c_int64
     lib.sp3_mesh_faces_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.sp3_tsdf_extract_ws_bytes.restype = C.c_int64
+    lib.sp3_tsdf_extract_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     for name in ("sp3_nn_query_ws_bytes", "sp3_icp_accum_ws_bytes", "sp3_sum_count_ws_bytes", "sp3_mesh_vertices_ws_bytes", "sp3_eval_align_ws_bytes"):
         getattr(lib, name).restype = C.c_int64
         getattr(lib, name).argtypes = [C.c_int64]

@@ -219,6 +219,40 @@ class PointRenderer:
                 "sp3_render_tris")
         self.count += n
 
+    def add_triangles(self, vertices, faces, colors, max_bbox_px=4096):
+        """An indexed mesh -- vertices fp32 [V, 3], faces int32 [F, 3], colors uint8 [V, 4] / [V, 3] or floats in [0, 1] [V, 3] (the
+        dict of fusion.TSDFVolume.extract_mesh or mesh.scene_mesh) -- drawn through sp3_render_tris into the same key buffer as add()
+        and add_mesh().  A face takes the colour of its first vertex.  The index image counts the vertices as add() counts points."""
+        vertices, faces, colors = (_dev(x, "PointRenderer.add_triangles: " + n) for x, n in ((vertices, "vertices"), (faces, "faces"), (colors, "colors")))
+        if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+            raise RuntimeError("PointRenderer.add_triangles: vertices %s must be [V, 3] and faces %s [F, 3]" % (tuple(vertices.shape), tuple(faces.shape)))
+        n = vertices.shape[0]
+        if colors.dim() != 2 or colors.shape[0] != n or colors.shape[1] not in (3, 4):
+            raise RuntimeError("PointRenderer.add_triangles: mismatched lengths: %d vertices, colours %s" % (n, tuple(colors.shape)))
+        if int(max_bbox_px) <= 0:
+            raise ValueError("PointRenderer.add_triangles: max_bbox_px must be > 0")
+        if self.dynamic:
+            self.clear()
+        if n == 0 or faces.shape[0] == 0:
+            return
+        vertices, faces = vertices.float().contiguous(), faces.to(torch.int32).contiguous()
+        self._reserve(self.count + n)
+        st = L.stream_ptr()
+        if colors.dtype == torch.uint8:
+            if colors.shape[1] == 3:
+                colors = torch.cat([colors, torch.full((n, 1), 255, dtype=torch.uint8, device=colors.device)], dim=1)
+            self.rgba[self.count:self.count + n] = colors.contiguous().view(torch.int32).reshape(-1)
+        else:
+            if colors.shape[1] != 3:
+                raise RuntimeError("PointRenderer.add_triangles: float colours must be [V, 3]")
+            L.check(self._lib.sp3_pack_rgba8(colors.float().contiguous().data_ptr(), n, self.rgba.data_ptr() + 4 * self.count, st), "sp3_pack_rgba8")
+        if self.mesh_stats is None:
+            self.mesh_stats = torch.zeros(2, dtype=torch.int64, device=self.device)
+        self.mesh_stats[0] += faces.shape[0]
+        L.check(self._lib.sp3_render_tris(vertices.data_ptr(), n, faces.data_ptr(), 0, faces.shape[0], 0, self.count, C.byref(self.cam),
+                                          int(max_bbox_px), self.keys.data_ptr(), self.mesh_stats.data_ptr() + 8, st), "sp3_render_tris")
+        self.count += n
+
     def image(self, return_depth=False, return_index=False):
         """uint8 [H, W, 3] on the device; with the flags, also depth fp32 [H, W] (+inf: empty) and index int32 [H, W] (-1: empty;
         the index counts every point given to add(), kept or not, in order)."""
