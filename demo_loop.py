@@ -3,6 +3,7 @@
 move only view['img'] to the device, time model.forward(batch), report FPS = len(batch) / seconds (with the device sync the
 reference omits).  The real demo.py cannot be imported in this image (cv2 / open3d / torchvision are not installed)."""
 import argparse
+import math
 import time
 
 import torch
@@ -38,7 +39,10 @@ def main():
     ap.add_argument("--as_pointcloud", action="store_true", help="with --save_glb: app.py's as_pointcloud, points instead of a mesh")
     ap.add_argument("--fused", action="store_true", help="one welded surface instead of per-frame sheets (spann3r_amd.fusion: TSDF volume + "
                     "marching tetrahedra on the device): with --save_glb the fused mesh is what is written, with --vis a last picture "
-                    "fused.png is added, with --rgbd --eval the fused prediction is scored against the fused ground truth")
+                    "fused.png is added (and fused_raycast.png, the volume ray-cast and Lambert-shaded), with --rgbd --eval the fused prediction is scored against the fused ground truth")
+    ap.add_argument("--track", action="store_true", help="with --fused: register every frame after the first to the model before it is "
+                    "integrated (ray-cast the volume from the frame's pose, point-to-plane Gauss-Newton against it); prints how many "
+                    "frames were tracked and the largest correction")
     ap.add_argument("--voxel_size", type=float, default=None, help="with --fused: voxel edge in the units of the pointmaps (default: the "
                     "longest side of the confident points' box takes 256 voxels)")
     ap.add_argument("--trunc_voxels", type=float, default=3.0, help="with --fused: truncation distance in voxels")
@@ -112,19 +116,26 @@ def main():
     fuse_kw = dict(voxel_size=args.voxel_size, trunc_voxels=args.trunc_voxels)
 
     def fused_prediction(**kw):
-        """fusion.fuse_sequence of this run (demo.py's focal and poses); pointmaps without geometry (no checkpoint ships) are fused
-        through nominal cameras instead -- focal = the longer image side, identity poses -- and that is said"""
+        """fusion.fuse_sequence of this run (demo.py's focal and poses) -> (mesh, volume); pointmaps without geometry (no checkpoint
+        ships) are fused through nominal cameras instead -- focal = the longer image side, identity poses -- and that is said.
+        With --track the frames are registered to the model first and the corrections are reported."""
         from spann3r_amd import fusion
+        import numpy as np
+        kw = dict(conf_thresh=args.conf_thresh, return_volume=True, track=args.track, return_poses=args.track, **fuse_kw, **kw)
         try:
-            return fusion.fuse_sequence(preds, batch, conf_thresh=args.conf_thresh, **fuse_kw, **kw)
+            fm, vol = fusion.fuse_sequence(preds, batch, **kw)
         except RuntimeError as e:
             if "degenerate pointmaps" not in str(e):
                 raise
-            import numpy as np
             _, H, W, _ = preds[0]["pts3d"].shape
             print("%s: fusing through nominal cameras (focal %d, identity poses)" % (e, max(H, W)))
-            return fusion.fuse_sequence(preds, batch, conf_thresh=args.conf_thresh, focal=float(max(H, W)),
-                                        poses=np.stack([np.eye(4)] * len(preds)), **fuse_kw, **kw)
+            fm, vol = fusion.fuse_sequence(preds, batch, focal=float(max(H, W)), poses=np.stack([np.eye(4)] * len(preds)), **kw)
+        if args.track:
+            T = fm["corrections"][1:]
+            ang = [math.degrees(math.acos(min(max((np.trace(t[:3, :3]) - 1) * 0.5, -1.0), 1.0))) for t in T]
+            print("%d frames tracked of %d; largest correction %.3f degrees, %.3f voxels" %
+                  (sum(fm["tracked"][1:]), len(T), max(ang, default=0.0), max((np.linalg.norm(t[:3, 3]) for t in T), default=0.0) / vol.voxel_size))
+        return fm, vol
 
     if args.eval:                                                                 # eval.py:128-221
         from spann3r_amd.evaluate import evaluate_sequence
@@ -181,11 +192,20 @@ def main():
         vis.vis_pred_and_imgs(pts_all, args.vis, images_all=images_all, conf_all=conf_sig_all)
         if args.fused:
             import os
-            fm = fused_prediction()
+            fm, vol = fused_prediction()
             r = vis.PointRenderer(camera=camera)
             r.add_triangles(fm["vertices"], fm["faces"], fm["colors"])
             vis._save_png(os.path.join(args.vis, "render_frames", "fused.png"), r.image().cpu().numpy())
             print("wrote the fused surface (%d vertices, %d faces) as render_frames/fused.png" % (fm["vertices"].shape[0], fm["faces"].shape[0]))
+            import numpy as np
+            c2w = np.linalg.inv(camera.extrinsic)                                 # the same volume with no meshing: ray-cast, Lambert-shaded
+            rc = vol.raycast(camera.intrinsic, c2w, (camera.height, camera.width))
+            view = rc["vertices"][0] - torch.from_numpy(c2w[:3, 3]).to(rc["vertices"])
+            view = view / view.norm(dim=-1, keepdim=True).clamp_min(1e-30)
+            shade = (-(rc["normals"][0] * view).sum(-1)).clamp_min(0.0) * (rc["depth"][0] > 0)
+            colour = rc["colors"][0][..., :3].float() if "colors" in rc else torch.full_like(rc["vertices"][0], 255.0)
+            vis._save_png(os.path.join(args.vis, "render_frames", "fused_raycast.png"), (colour * shade[..., None]).round().to(torch.uint8).cpu().numpy())
+            print("wrote the ray-cast volume (%d of %d pixels hit) as render_frames/fused_raycast.png" % (int((rc["depth"] > 0).sum()), rc["depth"].numel()))
         print("wrote %d rendered frames (%dx%d%s) and pts/ imgs/ confs/ to %s" %
               (len(pts_all), camera.width, camera.height, (", dynamic" if args.dynamic else "") + (", surface" if args.vis_surface else ""), args.vis))
     if args.save_glb:                                                             # app.py:132-171
@@ -193,7 +213,7 @@ def main():
         from spann3r_amd import mesh
         os.makedirs(os.path.dirname(os.path.abspath(args.save_glb)), exist_ok=True)
         if args.fused:
-            fm = fused_prediction(scale=mesh.SCALE, transform=mesh.TRANSFORM)      # app.py's x10 and axis flip, as export_glb
+            fm, _ = fused_prediction(scale=mesh.SCALE, transform=mesh.TRANSFORM)      # app.py's x10 and axis flip, as export_glb
             if fm["faces"].shape[0] == 0:
                 raise RuntimeError("--fused: the volume holds no surface (nothing passes conf_thresh %g with weight >= 1)" % args.conf_thresh)
             size = mesh.write_glb(args.save_glb, fm["vertices"], fm["colors"], fm["faces"], bounds=fm["bounds"])

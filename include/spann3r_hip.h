@@ -921,6 +921,75 @@ int sp3_tsdf_extract(const float* tsdf, const float* weight, const float* rgb, i
                      float min_weight, void* ws, int64_t max_vertices, int64_t max_faces, float* vertices, uint32_t* rgba, int32_t* faces,
                      int32_t* counts, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * TSDF ray-casting and frame-to-model tracking (spann3r_amd/fusion.py drives these; csrc/raycast.hip): the zero level of a volume
+ * of "TSDF fusion" seen from cameras with no meshing, and the KinectFusion step that registers a frame to the model before it is
+ * integrated.  Neither stage has a reference implementation; the rules below are the contract and tests/raycast_ref.py restates
+ * them in numpy.  No entry point allocates, frees or synchronises.
+ *
+ * sp3_tsdf_raycast: T views of one volume in ONE launch.  views_host and views_dev hold the same T descriptors; the host copy is
+ *   only read for the checks of the call.  The volume is given as to sp3_tsdf_integrate (tsdf, weight, nullable rgb; read only).
+ *   A view writes depth (required) and the nullable vertex, normal and rgba maps; pixel (px, py) of every map is element
+ *   p = py * row_stride + px (vertex, normal: 3 p .. 3 p + 2); nothing is written at columns >= w of a row.  rgba non-null while
+ *   rgb is null is an error.  c2w = the row-major 3 x 4 camera-to-world matrix: R its 3 x 3 part, eye its last column.
+ *   0 <= near <= far, far may be +inf; fu, fv not 0; min_weight > 0; step (metric) > 0 and finite.  T <= 65535.
+ *   cap = ceil(2 (nx + ny + nz) * voxel / step), computed by the callee in double from the fp32 voxel and step, is a hard bound on
+ *   the samples of a ray (cap > 2^24 is an error): no input makes a lane loop without end.  T = 0 and n = 0 are no-ops.
+ *   Every fp32 operation is rounded on its own, sums run left to right, division and square root are IEEE; min / max of two
+ *   numbers are comparisons (b < a ? b : a).  One lane owns one pixel (px, py):
+ *   Ray:  xn = (fp32(px) - cu) / fu, yn = (fp32(py) - cv) / fv;  dir_r = (R_r0 xn + R_r1 yn) + R_r2;
+ *     len = sqrt((dx^2 + dy^2) + dz^2), dl = step / len.  The ray parameter lambda is camera z; the point at lambda is
+ *     eye_r + dir_r * lambda (one multiply, one add).
+ *   Box:  the voxel-centre lattice, lo_a = origin_a, hi_a = origin_a + fp32(n_a - 1) * voxel.  Per axis a = x, y, z: if dir_a == 0
+ *     the axis constrains nothing when lo_a <= eye_a <= hi_a and the ray misses otherwise; else q1 = (lo_a - eye_a) / dir_a,
+ *     q2 = (hi_a - eye_a) / dir_a, enter = max(enter, min(q1, q2)), exit = min(exit, max(q1, q2)), from -inf and +inf.
+ *     lambda0 = max(enter, near), lambda1 = min(exit, far); the ray misses unless lambda0 <= lambda1 (a NaN fails).
+ *   Samples:  lambda_i = lambda0 + fp32(i) * dl for i = 0, 1, .. while lambda_i <= lambda1 and i < cap; each recomputed from i.
+ *   Cell of a point p:  g_a = (p_a - origin_a) / voxel, i_a = floor(g_a);  valid when 0 <= i_a <= n_a - 2 on every axis (compared in
+ *     fp32, a NaN fails) and all eight corners (i + dx, j + dy, k + dz) have weight >= min_weight.  t_a = g_a - fp32(i_a).  Value:
+ *     trilinear in lerp form a + t (b - a): along x on the four x-edges, then along y, then along z.
+ *   March, with state (prev_valid = false, f_prev):  an invalid sample clears prev_valid.  A valid sample with value f:
+ *     prev_valid and f_prev >= 0 and f < 0: a hit, lambda* = lambda_{i-1} + dl * (f_prev / (f_prev - f)), stop;
+ *     prev_valid and f_prev < 0 and f >= 0: a back face, stop, a miss;  otherwise f_prev = f, prev_valid = true.
+ *   At a hit:  p* = eye + dir * lambda*; its cell is evaluated again by the same rule and an invalid cell makes the pixel a miss.
+ *     Gradient of the same interpolant: d/dx = the four x-edge differences (v1jk - v0jk) lerped along y, then z; d/dy = the four
+ *     y-edge differences lerped along x, then z; d/dz = the four z-edge differences lerped along x, then y.
+ *     normal = grad / sqrt((gx^2 + gy^2) + gz^2); a zero or non-finite length makes the pixel a miss.  The normal points to the
+ *     positive (outside) side, as the faces of sp3_tsdf_extract do.  Colour: per channel the same trilinear lerps of rgb, packed as
+ *     sp3_pack_rgba8 packs.
+ *   Outputs:  hit: depth = lambda*, vertex = p*, normal, rgba;  miss: depth 0, vertex and normal 0, rgba 0.
+ *   A workgroup is a 16 x 16 pixel block of one view (a wave: an 8 x 8 tile); no atomics, no workgroup waits on another.
+ *
+ * sp3_tsdf_track_accum: the normal equations of projective point-to-plane registration of ONE frame against the ray-cast maps of
+ *   the model, in fp64 and a fixed order (per-workgroup partials in ws, a last launch adds them in index order; the scheme of
+ *   sp3_icp_accum).  pts fp32 [n, 3] = the frame's world points, valid uint8 [n] (nullable), T12 = the correction under refinement
+ *   and w2c12 = the world-to-camera matrix of the model view, both DEVICE double [12], row-major R (9) | t (3) as sp3_pnp_gn_accum
+ *   takes its pose; vertex, normal, depth = the model view's maps of sp3_tsdf_raycast with w, h, row_stride, fu, fv, cu, cv.
+ *   Per point p with valid != 0, in double from the fp32 inputs:  y = R p + t, skip a non-finite p;  yc = M y, skip unless yc.z > 0;
+ *     u = fu yc.x / yc.z + cu, v = fv yc.y / yc.z + cv;  px = floor(u + 0.5), py = floor(v + 0.5), skip unless 0 <= px < w and
+ *     0 <= py < h;  skip if depth there is 0;  q, nrm = vertex, normal there;  d = y - q, skip unless d.d <= dist_max^2;
+ *     r = nrm.d,  J = (y x nrm, nrm): the parameters are (omega, delta) of y' = y + omega x y + delta, the left perturbation of
+ *     sp3_pnp_gn_accum.  There is no normal-compatibility gate: the frame has no normals of its own.
+ *   out29 = J^T J (21: upper triangle, row-major), J^T r (6), sum r^2, the number of pairs.  n = 0 gives zeros.
+ *   ws: device scratch of sp3_tsdf_track_accum_ws_bytes(n). */
+typedef struct sp3_tsdf_view {
+  float* depth;                /* device fp32 [h, row_stride], camera z of the hit, 0 = miss */
+  float* vertex;               /* device fp32 [h, row_stride, 3], world; nullable */
+  float* normal;               /* device fp32 [h, row_stride, 3], unit, outward; nullable */
+  uint32_t* rgba;              /* nullable (needs a volume with colours) */
+  int64_t row_stride;          /* in pixels, common to the maps of the view */
+  int32_t w, h;
+  float fu, fv, cu, cv;
+  float c2w[12];
+  float near, far;
+} sp3_tsdf_view;
+int sp3_tsdf_raycast(const sp3_tsdf_view* views_host, const sp3_tsdf_view* views_dev, int T, int nx, int ny, int nz, const float* origin3,
+                     float voxel, const float* tsdf, const float* weight, const float* rgb, float min_weight, float step, void* stream);
+int64_t sp3_tsdf_track_accum_ws_bytes(int64_t n);
+int sp3_tsdf_track_accum(const float* pts, const uint8_t* valid, int64_t n, const double* T12, const float* vertex, const float* normal,
+                         const float* depth, int w, int h, int64_t row_stride, float fu, float fv, float cu, float cv, const double* w2c12,
+                         float dist_max, void* ws, double* out29, void* stream);
+
 /* small utilities */
 /* n (1..8) contiguous device-to-device copies in one launch; every copy 16-byte aligned and a multiple of 16 bytes.
  * (The sequence loop's per-frame bookkeeping -- torch .clone() / slice assignments around spann3r/model.py:523-531.) */

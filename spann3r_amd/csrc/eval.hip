@@ -16,6 +16,7 @@
 //   * Sums (ICP correspondences, metric means) are fp64 per workgroup into partial slabs, finished by a second kernel in a
 //     fixed order: no float atomics.
 #include "common.h"
+#include "slab.h"
 #include <math.h>
 
 namespace {
@@ -23,7 +24,6 @@ namespace {
 constexpr int KNN_MAX = 32;
 constexpr int KNN_BLOCK = 128;
 constexpr int BRUTE_TILE = 1024;
-constexpr int SLAB_BLOCKS = 1024;
 
 struct Rec { float x, y, z; int i; };   // 16 bytes: one global_load_dwordx4 / ds_read_b128 per point
 static_assert(sizeof(Rec) == 16, "record size");
@@ -302,31 +302,6 @@ __global__ __launch_bounds__(256) void transform_points_kernel(const float* __re
   out[3 * i + 2] = (float)(T.m[6] * x + T.m[7] * y + T.m[8] * z + T.m[11]);
 }
 
-// ---- fp64 partial slabs: NV running sums per thread -> wave (shuffles) -> workgroup (LDS, fixed order) -> slab[block][NV]
-template <int NV>
-__device__ __forceinline__ void block_slab(double (&v)[NV], double* __restrict__ slab) {
-  __shared__ double sh[4][NV];
-#pragma unroll
-  for (int e = 0; e < NV; ++e) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[e] += __shfl_xor(v[e], o);
-  }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int e = 0; e < NV; ++e) sh[w][e] = v[e];
-  }
-  __syncthreads();
-  if (threadIdx.x < NV) slab[(int64_t)blockIdx.x * NV + threadIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
-}
-
-__global__ __launch_bounds__(64) void slab_finish_kernel(const double* __restrict__ slab, int blocks, int nv, double* __restrict__ out) {
-  if ((int)threadIdx.x >= nv) return;
-  double s = 0.0;
-  for (int b = 0; b < blocks; ++b) s += slab[(int64_t)b * nv + threadIdx.x];
-  out[threadIdx.x] = s;
-}
-
 // (p_i, q = tgt[idx_i]) for idx_i >= 0: count, sum p (3), sum q (3), sum p q^T (9, row-major), sum |p - q|^2
 __global__ __launch_bounds__(256) void icp_accum_kernel(const float* __restrict__ p, const float* __restrict__ tgt, const int* __restrict__ idx,
                                                         int64_t n, double* __restrict__ slab) {
@@ -371,7 +346,6 @@ __global__ __launch_bounds__(256) void normal_dot_kernel(const float* __restrict
   out[i] = fabsf((float)((double)na[3 * ia] * nb[3 * ib] + (double)na[3 * ia + 1] * nb[3 * ib + 1] + (double)na[3 * ia + 2] * nb[3 * ib + 2]));
 }
 
-inline int slab_blocks(int64_t n) { return (int)(n <= 0 ? 1 : (n + 255) / 256 < SLAB_BLOCKS ? (n + 255) / 256 : SLAB_BLOCKS); }
 inline unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
 constexpr int64_t N_MAX = 0x7fffffff;   // indices travel as int32
 

@@ -62,13 +62,18 @@ def _frames_list(x, name, tail, optional=False):
     return out
 
 
-def _host_mats(x, T, shape, name):
-    """one matrix or T of them (array, tensor or list, host or device) -> float64 numpy [T, *shape]"""
+def _host_array(x):
+    """an array, a tensor (host or device) or a non-empty list of them -> float64 numpy"""
     if isinstance(x, torch.Tensor):
         x = x.detach().cpu().numpy()
-    elif isinstance(x, (list, tuple)):
+    elif isinstance(x, (list, tuple)) and len(x):
         x = np.stack([m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else np.asarray(m) for m in x])
-    x = np.asarray(x, np.float64)
+    return np.asarray(x, np.float64)
+
+
+def _host_mats(x, T, shape, name):
+    """one matrix or T of them (array, tensor or list, host or device) -> float64 numpy [T, *shape]"""
+    x = _host_array(x)
     if x.shape == shape:
         x = np.broadcast_to(x, (T,) + shape)
     if x.shape != (T,) + shape:
@@ -123,6 +128,7 @@ class TSDFVolume:
         self.weight = torch.empty((nz, ny, nx), dtype=torch.float32, device=self.device)
         self.rgb = torch.empty((nz, ny, nx, 3), dtype=torch.float32, device=self.device) if color else None
         self.launches = 0                   # sp3_tsdf_integrate launches so far
+        self.raycasts = 0                   # sp3_tsdf_raycast launches so far
         self.reset()
 
     def reset(self):
@@ -243,6 +249,74 @@ class TSDFVolume:
             faces = faces[:0]
         return dict(vertices=pos, colors=col.contiguous().view(torch.uint8).reshape(-1, 4), faces=faces, bounds=bounds)
 
+    def raycast(self, intrinsics, cam2world, size, near=0.0, far=math.inf, step_voxels=1.0, min_weight=1.0, vertices=True, normals=True,
+                colors=None):
+        """The zero level seen from T cameras in ONE launch, with no meshing (sp3_tsdf_raycast): intrinsics [3, 3] or [T, 3, 3],
+        cam2world [T, 4, 4] (or one [4, 4]), size = (h, w).  -> dict of device tensors: depth fp32 [T, h, w] (camera z, 0 = miss) and, as
+        asked, vertices fp32 [T, h, w, 3] (world), normals fp32 [T, h, w, 3] (unit, outward), colors uint8 [T, h, w, 4] (default: whether
+        the volume has colours).  The march takes steps of step_voxels (>= 0.25) voxels of ray length between near and far (camera z).
+        Skewed intrinsics and non-finite or singular poses are refused as `camera_tables` refuses them.  Nothing synchronises."""
+        return self.raycast_table(self.view_table(intrinsics, cam2world, size, near, far, vertices, normals, colors), step_voxels, min_weight)
+
+    def view_table(self, intrinsics, cam2world, size, near=0.0, far=math.inf, vertices=True, normals=True, colors=None):
+        """The descriptor table of `raycast` and the maps it points to: (host table, device copy, T, the dict `raycast` returns).
+        raycast_table launches it; a table can be launched again, into the same maps."""
+        h, w = (int(x) for x in size)
+        if h < 1 or w < 1:
+            raise ValueError("raycast: size %s must be (h, w) >= 1" % (size,))
+        if not (0.0 <= near <= far):
+            raise ValueError("raycast: 0 <= near <= far, got near %r, far %r" % (near, far))
+        colors = self.rgb is not None if colors is None else bool(colors)
+        if colors and self.rgb is None:
+            raise ValueError("raycast: colors asked of a volume without colours")
+        P = _host_array(cam2world)
+        P = P[None] if P.ndim == 2 else P.reshape(-1, 4, 4) if P.size == 0 else P
+        if P.ndim != 3 or P.shape[1:] != (4, 4):
+            raise ValueError("raycast: cam2world %s must be [4, 4] or [T, 4, 4]" % (P.shape,))
+        T = P.shape[0]
+        fk, _ = camera_tables(intrinsics, P, T)                  # (the inverse is only computed for its checks)
+        if not (fk[:, :2] != 0).all():
+            raise ValueError("raycast: intrinsics with a zero focal length")
+        out = dict(depth=torch.empty((T, h, w), dtype=torch.float32, device=self.device))
+        if vertices:
+            out["vertices"] = torch.empty((T, h, w, 3), dtype=torch.float32, device=self.device)
+        if normals:
+            out["normals"] = torch.empty((T, h, w, 3), dtype=torch.float32, device=self.device)
+        if colors:
+            rgba = torch.empty((T, h, w), dtype=torch.int32, device=self.device)
+            out["colors"] = rgba.view(torch.uint8).reshape(T, h, w, 4)
+        if T == 0:
+            return None, None, 0, out
+        table = (L.TsdfView * T)()
+        for i in range(T):
+            e = table[i]
+            e.depth = out["depth"][i].data_ptr()
+            e.vertex = out["vertices"][i].data_ptr() if vertices else None
+            e.normal = out["normals"][i].data_ptr() if normals else None
+            e.rgba = rgba[i].data_ptr() if colors else None
+            e.row_stride, e.w, e.h = w, w, h
+            e.fu, e.fv, e.cu, e.cv = (float(x) for x in fk[i])
+            e.c2w[:] = P[i, :3].reshape(12).astype(np.float32).tolist()
+            e.near, e.far = float(near), float(far)
+        table_d = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(self.device)
+        return table, table_d, T, out
+
+    def raycast_table(self, tbl, step_voxels=1.0, min_weight=1.0):
+        """one sp3_tsdf_raycast launch of a view_table -> its maps"""
+        table, table_d, T, out = tbl
+        if not (step_voxels >= 0.25 and math.isfinite(step_voxels)):
+            raise ValueError("raycast: step_voxels must be finite and >= 0.25, got %r" % (step_voxels,))
+        if not min_weight > 0:
+            raise ValueError("raycast: min_weight must be > 0, got %r" % (min_weight,))
+        if T == 0:
+            return out
+        nx, ny, nz = self.dims
+        step = float(np.float32(np.float32(step_voxels) * np.float32(self.voxel_size)))
+        L.check(L.load().sp3_tsdf_raycast(table, table_d.data_ptr(), T, nx, ny, nz, self._origin_c, self.voxel_size, self.tsdf.data_ptr(),
+                                          self.weight.data_ptr(), L.ptr(self.rgb), float(min_weight), step, L.stream_ptr()), "sp3_tsdf_raycast")
+        self.raycasts += 1
+        return out
+
 
 def volume_for_points(points, voxel_size=None, dims_max=256, trunc_voxels=3.0, color=True):
     """The volume whose box is that of `points` (device fp32 [n, 3], all finite) padded by trunc = trunc_voxels voxels.  voxel_size
@@ -266,13 +340,121 @@ def volume_for_points(points, voxel_size=None, dims_max=256, trunc_voxels=3.0, c
     return TSDFVolume(box[0] - pad, voxel_size, dims, trunc=trunc, color=color, device=pts.device)
 
 
+def _expm_se3(xi):
+    """(omega, delta) of y' = y + omega x y + delta -> the rigid 4 x 4 [exp(omega) | delta], the update of estimate_poses"""
+    from .postprocess import _expm_so3
+    U = np.eye(4)
+    U[:3, :3], U[:3, 3] = _expm_so3(xi[:3]), xi[3:]
+    return U
+
+
+def _rt12(M):
+    """4 x 4 -> the 12 doubles row-major R (9) | t (3) of sp3_pnp_gn_accum's pose"""
+    return np.concatenate([M[:3, :3].reshape(9), M[:3, 3]])
+
+
+def track_frame(vol, pts, valid, intrinsics, cam2world, iterations=10, recasts=2, dist_max=None, min_pairs=64, step_voxels=1.0,
+                min_weight=1.0, relative_rmse=1e-6, timings=None):
+    """The KinectFusion registration of one frame against the model in `vol`, which must not contain the frame yet: pts fp32 [h, w, 3]
+    (the frame's world points), valid [h, w] (nullable), intrinsics [3, 3], cam2world [4, 4] as the frame claims them.
+    -> (T float64 [4, 4], info): the rigid correction to apply on the left of the points and of the pose.
+    `recasts` times: the volume is ray-cast from the currently corrected pose (one launch), then up to `iterations` Gauss-Newton
+    steps of projective point-to-plane registration run against those maps: one sp3_tsdf_track_accum launch and one read of 29
+    doubles each, the 6 x 6 system solved on the host in float64 (lstsq), T <- exp(xi) T.  A recast stops early when the rmse changes
+    by less than relative_rmse (icp_point_to_point's rule).  dist_max defaults to vol.trunc.  A frame is not tracked when fewer than
+    min_pairs pairs are found or a non-finite or rank-deficient system appears (a singular value of H below 1e-9 of the largest):
+    T is then the identity and info["tracked"] False; nothing raises.  info: tracked, pairs, rmse, iterations.
+    timings (a dict, optional) accumulates the host seconds spent in `raycast`, `accumulate` (launch and read-back) and `solve`, and
+    the number of `round_trips` (one per Gauss-Newton step)."""
+    import time
+    pts = _dev(pts, "track_frame: pts").float().contiguous()
+    if pts.dim() != 3 or pts.shape[-1] != 3:
+        raise RuntimeError("track_frame: pts %s must be [h, w, 3]" % (tuple(pts.shape),))
+    h, w = pts.shape[:2]
+    n = h * w
+    v = None
+    if valid is not None:
+        v = _dev(valid, "track_frame: valid").to(torch.uint8).contiguous()
+        if tuple(v.shape) != (h, w):
+            raise RuntimeError("track_frame: mismatched shapes: pts %s, valid %s" % (tuple(pts.shape), tuple(v.shape)))
+    P0 = _host_mats(cam2world, 1, (4, 4), "cam2world")[0]
+    fk, _ = camera_tables(intrinsics, P0[None], 1)
+    K = _host_mats(intrinsics, 1, (3, 3), "intrinsics")[0]
+    dist_max = vol.trunc if dist_max is None else float(dist_max)
+    lib, dev = L.load(), vol.device
+    ws = torch.empty(max(int(lib.sp3_tsdf_track_accum_ws_bytes(n)), 16), dtype=torch.uint8, device=dev)
+    out_d = torch.empty(29, dtype=torch.float64, device=dev)
+    fu, fv, cu, cv = (float(np.float32(x)) for x in fk[0])
+    T = np.eye(4)
+    info = dict(tracked=False, pairs=0, rmse=float("nan"), iterations=0)
+    clock = (lambda: time.perf_counter()) if timings is not None else (lambda: 0.0)
+
+    def spent(key, t0):
+        if timings is not None:
+            timings[key] = timings.get(key, 0.0) + clock() - t0
+
+    for _ in range(int(recasts)):
+        t0 = clock()
+        P = T @ P0
+        model = vol.raycast(K, P[None], (h, w), step_voxels=step_voxels, min_weight=min_weight, colors=False)
+        w2c_d = torch.from_numpy(_rt12(np.linalg.inv(P))).to(dev)
+        spent("raycast", t0)
+        last = None
+        for _ in range(int(iterations)):
+            t0 = clock()
+            T_d = torch.from_numpy(_rt12(T)).to(dev)
+            L.check(lib.sp3_tsdf_track_accum(pts.data_ptr(), L.ptr(v), n, T_d.data_ptr(), model["vertices"].data_ptr(),
+                                             model["normals"].data_ptr(), model["depth"].data_ptr(), w, h, w, fu, fv, cu, cv, w2c_d.data_ptr(),
+                                             dist_max, ws.data_ptr(), out_d.data_ptr(), L.stream_ptr()), "sp3_tsdf_track_accum")
+            out = out_d.cpu().numpy()
+            spent("accumulate", t0)
+            if timings is not None:
+                timings["round_trips"] = timings.get("round_trips", 0) + 1
+            t0 = clock()
+            info["iterations"] += 1
+            info["pairs"] = int(out[28]) if math.isfinite(out[28]) else 0
+            if not out[28] >= min_pairs:
+                return np.eye(4), info
+            rmse = math.sqrt(out[27] / out[28]) if out[27] >= 0 else float("nan")
+            info["rmse"] = rmse
+            if last is not None and abs(rmse - last) < relative_rmse:
+                spent("solve", t0)
+                break
+            last = rmse
+            H = np.zeros((6, 6))
+            H[np.triu_indices(6)] = out[:21]
+            H = H + np.triu(H, 1).T
+            g = out[21:27]
+            if not (np.isfinite(H).all() and np.isfinite(g).all()):
+                return np.eye(4), info
+            sv = np.linalg.svd(H, compute_uv=False)
+            if not (sv[0] > 0 and sv[-1] >= 1e-9 * sv[0]):
+                return np.eye(4), info
+            T = _expm_se3(np.linalg.lstsq(H, -g, rcond=None)[0]) @ T
+            spent("solve", t0)
+    info["tracked"] = True
+    return T, info
+
+
+def _transform_points(pts, T):
+    """T [4, 4] float64 applied to device points fp32 [..., 3] (sp3_transform_points: fp64, rounded to fp32)"""
+    src = pts.float().contiguous()
+    out = torch.empty_like(src)
+    n = src.numel() // 3
+    if n:
+        L.check(L.load().sp3_transform_points(src.data_ptr(), n, (C.c_double * 12)(*_rt12(T).tolist()), out.data_ptr(), L.stream_ptr()),
+                "sp3_transform_points")
+    return out
+
+
 def fuse_sequence(preds, batch, conf_thresh=1e-3, voxel_size=None, dims_max=256, trunc_voxels=3.0, min_weight=1.0, scale=1.0,
-                  transform=None, color=True, return_volume=False, focal=None, poses=None):
+                  transform=None, color=True, return_volume=False, focal=None, poses=None, track=False, return_poses=False):
     """The fused surface of a reconstruction from model.forward's `preds` and its `batch`: demo.py's own sequence -- the stacked
     pointmaps (mesh.sequence_tensors), the focal of frame 0 (estimate_focal_knowing_depth), one pose per frame (estimate_poses) --
     then the pointmaps of the pixels with (conf - 1) / conf > conf_thresh integrated through the `pts` path into a volume around
     the confident points.  -> the mesh dict of TSDFVolume.extract_mesh (and the volume with return_volume).
-    focal / poses (cam2world [t, 4, 4]) given: used instead of the estimates.  Pointmaps without geometry (seeded random weights)
+    focal / poses (cam2world [t, 4, 4]) given: used instead of the estimates.  track / return_poses: as fuse_pointmaps (every frame
+    after the first is registered to the model before it is integrated).  Pointmaps without geometry (seeded random weights)
     give a focal near 0: that raises rather than fusing through meaningless cameras."""
     from .postprocess import estimate_focal_knowing_depth, estimate_poses
     pts_all, images_all, conf_all = M.sequence_tensors(preds, batch)
@@ -291,13 +473,19 @@ def fuse_sequence(preds, batch, conf_thresh=1e-3, voxel_size=None, dims_max=256,
     valid = (conf_all - 1) / conf_all > conf_thresh
     K = np.array([[focal, 0, pp[0]], [0, focal, pp[1]], [0, 0, 1]], np.float64)
     return fuse_pointmaps(pts_all, K, np.asarray(poses, np.float64), valid, images_all, voxel_size, dims_max, trunc_voxels, min_weight, scale,
-                          transform, color, return_volume)
+                          transform, color, return_volume, track, return_poses)
 
 
 def fuse_pointmaps(pts_all, intrinsics, cam2world, valid, images=None, voxel_size=None, dims_max=256, trunc_voxels=3.0, min_weight=1.0,
-                   scale=1.0, transform=None, color=True, return_volume=False):
+                   scale=1.0, transform=None, color=True, return_volume=False, track=False, return_poses=False, track_args=None):
     """World pointmaps pts_all [t, h, w, 3] with their cameras, integrated through the `pts` path into a volume around the valid
-    (and finite) points -> the mesh dict of TSDFVolume.extract_mesh (and the volume with return_volume)."""
+    (and finite) points -> the mesh dict of TSDFVolume.extract_mesh (and the volume with return_volume).
+    track=False: one integrate launch for all frames.  track=True: the KinectFusion sequence -- frame 0 is integrated; every later
+    frame is registered to the model that does not contain it yet (track_frame, keywords from track_args), its pointmap moved by the
+    correction T (sp3_transform_points), its pose set to T @ pose, and only then integrated: one launch per frame.  The volume is
+    still fitted to the points as predicted; the trunc padding absorbs the corrections.  return_poses adds to the mesh dict `poses`
+    (the cam2world used, float64 [t, 4, 4]), `corrections` (the T of every frame) and `tracked` (a list of bool: frame 0, the model's own
+    frame, counts as tracked; all False without track)."""
     pts_all = _dev(pts_all, "fuse_pointmaps: pts_all").float()
     if pts_all.dim() != 4 or pts_all.shape[-1] != 3 or _dev(valid, "fuse_pointmaps: valid").shape != pts_all.shape[:3]:
         raise RuntimeError("fuse_pointmaps: mismatched shapes: pts_all %s must be [t, h, w, 3], valid %s [t, h, w]" %
@@ -307,8 +495,26 @@ def fuse_pointmaps(pts_all, intrinsics, cam2world, valid, images=None, voxel_siz
         raise RuntimeError("fuse_pointmaps: no valid point (nothing passes the confidence threshold)")
     color = color and images is not None
     vol = volume_for_points(pts_all[valid], voxel_size, dims_max, trunc_voxels, color)
-    vol.integrate(pts=pts_all, intrinsics=intrinsics, cam2world=cam2world, valid=valid, images=images if color else None)
+    t = pts_all.shape[0]
+    poses = _host_mats(cam2world, t, (4, 4), "cam2world").copy()
+    corrections, tracked = np.stack([np.eye(4)] * t), [bool(track)] + [False] * (t - 1)      # (frame 0 is the model's own frame)
+    if not track:
+        vol.integrate(pts=pts_all, intrinsics=intrinsics, cam2world=cam2world, valid=valid, images=images if color else None)
+    else:
+        K = _host_mats(intrinsics, t, (3, 3), "intrinsics")
+        for i in range(t):
+            pts_i = pts_all[i]
+            if i > 0:
+                T, info = track_frame(vol, pts_i, valid[i], K[i], poses[i], **(track_args or {}))
+                tracked[i] = bool(info["tracked"])
+                if tracked[i]:
+                    corrections[i], poses[i] = T, T @ poses[i]
+                    pts_i = _transform_points(pts_i, T)
+            vol.integrate(pts=pts_i[None], intrinsics=K[i], cam2world=poses[i:i + 1], valid=valid[i:i + 1],
+                          images=images[i:i + 1] if color else None)
     out = vol.extract_mesh(min_weight, scale, transform)
+    if return_poses:
+        out.update(poses=poses, corrections=corrections, tracked=tracked)
     return (out, vol) if return_volume else out
 
 

@@ -132,6 +132,13 @@ class TsdfFrame(C.Structure):
                 ("cv", C.c_float), ("w2c", C.c_float * 12)]
 
 
+class TsdfView(C.Structure):
+    """sp3_tsdf_view (include/spann3r_hip.h)"""
+    _fields_ = [("depth", C.c_void_p), ("vertex", C.c_void_p), ("normal", C.c_void_p), ("rgba", C.c_void_p), ("row_stride", C.c_int64),
+                ("w", C.c_int32), ("h", C.c_int32), ("fu", C.c_float), ("fv", C.c_float), ("cu", C.c_float), ("cv", C.c_float),
+                ("c2w", C.c_float * 12), ("near", C.c_float), ("far", C.c_float)]
+
+
 _lib = None
 
 _PROTOS = {
@@ -275,11 +282,15 @@ _PROTOS = {
                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "sp3_tsdf_extract": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_void_p,
                          C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_tsdf_raycast": [C.POINTER(TsdfView), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_void_p,
+                         C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p],
+    "sp3_tsdf_track_accum": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64,
+                             C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p],
 }
 EXPORTS = sorted(list(_PROTOS) + ["sp3_last_error", "sp3_version", "sp3_conf_loss_ws_bytes", "sp3_ssi_loss_ws_bytes", "sp3_sumsq_blocks", "sp3_colsum_rows_ws",
                                   "sp3_nn_query_ws_bytes", "sp3_icp_accum_ws_bytes", "sp3_sum_count_ws_bytes",
                                   "sp3_mesh_faces_ws_bytes", "sp3_mesh_vertices_ws_bytes", "sp3_eval_align_ws_bytes",
-                                  "sp3_tsdf_extract_ws_bytes"])
+                                  "sp3_tsdf_extract_ws_bytes", "sp3_tsdf_track_accum_ws_bytes"])
 
 
 def load():
@@ -306,7 +317,8 @@ def load():
     lib.sp3_mesh_faces_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.sp3_tsdf_extract_ws_bytes.restype = C.c_int64
     lib.sp3_tsdf_extract_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    for name in ("sp3_nn_query_ws_bytes", "sp3_icp_accum_ws_bytes", "sp3_sum_count_ws_bytes", "sp3_mesh_vertices_ws_bytes", "sp3_eval_align_ws_bytes"):
+    for name in ("sp3_nn_query_ws_bytes", "sp3_icp_accum_ws_bytes", "sp3_sum_count_ws_bytes", "sp3_mesh_vertices_ws_bytes", "sp3_eval_align_ws_bytes",
+                 "sp3_tsdf_track_accum_ws_bytes"):
         getattr(lib, name).restype = C.c_int64
         getattr(lib, name).argtypes = [C.c_int64]
     for name, argtypes in _PROTOS.items():
