@@ -12,6 +12,63 @@ from spann3r_amd import Spann3R, FULL, TINY
 from spann3r_amd.weights import synth_state_dict, synth_frames
 
 
+def stream_loop(model, batch, args):
+    """--stream: the batch through a streaming session, frame by frame, as a camera loop would (a synchronise after every push; the
+    sequence `--repeat` times on the same session, the last pass is reported).  -> (preds, preds_all) as forward returns them."""
+    import os
+    import numpy as np
+    from spann3r_amd import vis
+
+    def image_of(i):
+        img = (batch[i]["img"].permute(0, 2, 3, 1).float() + 1.0) / 2.0
+        return img.swapaxes(1, 2) if img.shape[1:3] != shape else img
+
+    n = len(batch)
+    with model.stream() as s:
+        for it in range(args.repeat):
+            last = it == args.repeat - 1
+            draw = args.vis if last else None
+            s.reset()
+            steps, lat, r, replays0 = [], [], None, s.replays
+            torch.cuda.synchronize()
+            start = time.time()
+            for t, view in enumerate(batch):
+                t0 = time.perf_counter()
+                step = s.push(view)
+                torch.cuda.synchronize()
+                lat.append((time.perf_counter() - t0) * 1e3)
+                if step is None:
+                    continue
+                steps.append(step)
+                if draw:                                                          # final = frame t - 1, complete as of now
+                    key = "pts3d" if t == 1 else "pts3d_in_other_view"
+                    shape = step.final[key].shape[1:3]
+                    if r is None:
+                        d = os.path.join(draw, "render_frames")
+                        os.makedirs(d, exist_ok=True)
+                        camera = (vis.load_camera(args.vis_camera) if args.vis_camera else
+                                  vis.fit_camera(torch.cat([step.final["pts3d"], step.latest["pts3d_in_other_view"]]).float(),
+                                                 conf=torch.cat([step.final["conf"], step.latest["conf"]]).float(), conf_thresh=args.conf_thresh))
+                        r = vis.PointRenderer(camera=camera, point_size=args.point_size, conf_thresh=args.conf_thresh, dynamic=args.dynamic)
+                    todo = [(t - 1, step.final[key], step.final["conf"])]
+                    if t == n - 1:                                                # the sequence ends here: its last frame is `latest`
+                        todo.append((t, step.latest["pts3d_in_other_view"], step.latest["conf"]))
+                    for i, pts, conf in todo:
+                        r.add(pts[0].float(), image_of(i)[0], conf[0].float())
+                        vis._save_png(os.path.join(d, "frame_%03d.png" % i), r.image().cpu().numpy())
+            torch.cuda.synchronize()
+            end = time.time()
+            print("Time: %.4f s, FPS: %.1f  (%d frames pushed one by one, pass %d%s)" %
+                  (end - start, n / (end - start), n, it, ", drawing" if draw else ""))
+        step_ms = lat[2:] or lat[1:]
+        print("push latency (push + synchronise%s): median %.3f ms, p95 %.3f ms, max %.3f ms; first step %.3f ms; %d of %d pushes replayed a graph" %
+              (", drawing included" if args.vis else "", float(np.median(step_ms)), float(np.percentile(step_ms, 95)), max(step_ms), lat[1],
+               s.replays - replays0, n - 1))
+        if args.vis:
+            print("wrote %d rendered frames to %s as they arrived" % (n, os.path.join(args.vis, "render_frames")))
+    return [st.final for st in steps] + [steps[-1].latest], [st.pair for st in steps]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=10)
@@ -26,6 +83,9 @@ def main():
                     "estimated focal of the first camera (demo.py:147-151)")
     ap.add_argument("--conf_thresh", type=float, default=1e-3)
     ap.add_argument("--offline", action="store_true", help="demo.py --offline: DUSt3R pair graph + next-best-view order")
+    ap.add_argument("--stream", action="store_true", help="feed the frames one at a time through model.stream() (spann3r_amd/stream.py), "
+                    "synchronising after every push: prints the push latency distribution, the overall frames/s and how many pushes "
+                    "replayed a graph; with --vis every frame is drawn as its prediction arrives")
     ap.add_argument("--vis", default=None, metavar="DIR", help="demo.py --vis, headless: write DIR/render_frames/frame_XXX.png (the cloud as "
                     "it grows, drawn on the device) and the pts/ imgs/ confs/ folders of vis_pred_and_imgs (spann3r_amd.vis)")
     ap.add_argument("--dynamic", action="store_true", help="demo.py --dynamic: each rendered frame shows its own points alone")
@@ -104,7 +164,9 @@ def main():
         end = time.time()
         print("Time: %.4f s, FPS: %.1f  (offline, order %s)" % (end - start, len(batch) / (end - start), idx_used))
         return
-    for it in range(args.repeat):
+    if args.stream:
+        preds, preds_all = stream_loop(model, batch, args)
+    for it in range(0 if args.stream else args.repeat):
         torch.cuda.synchronize()
         start = time.time()
         preds, preds_all = model.forward(batch)                                   # demo.py:125
@@ -177,7 +239,7 @@ def main():
             print("wrote %d camera poses to %s (inlier fractions %.2f..%.2f)" % (len(poses_all), tj, inliers.min(), inliers.max()))
         else:
             print("degenerate pointmaps (no checkpoint loaded): poses / transforms.json skipped")
-    if args.vis:                                                                  # demo.py:221-225
+    if args.vis and not args.stream:                                              # demo.py:221-225 (--stream drew as it went)
         from spann3r_amd import vis
         pts_all = torch.cat([p["pts3d" if j == 0 else "pts3d_in_other_view"] for j, p in enumerate(preds)]).float()
         conf_all = torch.cat([p["conf"] for p in preds]).float()

@@ -630,8 +630,9 @@ class Engine:
         E = self.cfg.enc_dim
         return self.wspg("keyg_packed", R, E), self.ws("keyg_stats", (2, R, E // 32, 2))
 
-    def encode_feat_keys_grouped(self, feat1, feat2, normed1, normed2, R, out1, out2, feat1p=None, feat2p=None):
+    def encode_feat_keys_grouped(self, feat1, feat2, normed1, normed2, R, out1, out2, feat1p=None, feat2p=None, aux=None):
         """both key MLPs (spann3r/model.py:299-303) as one grouped launch per layer; normed1/2 = the decoders' last outputs.
+        aux: the caller's own (PackedAct.group(2, R, enc_dim), statistics [2, R, enc_dim/32, 2]) instead of the engine's key_aux.
         feat1p / feat2p: fragment-order bf16 copies of the features (written by enc_norm): with the packed copy of the decoder
         outputs (decoder_grouped) the first layer runs on a lean split-A instance instead of converting fp32 rows on load."""
         self.activate()
@@ -661,7 +662,7 @@ class Engine:
         else:
             ops.gemm(feat1, w["keyg.0.w"], h, M=R, N=Kd, K=Kd, lda=E, ldc=Kd, bias=w["keyg.0.b"], act=ACT_GELU, A2=normed1, lda2=D, K1=E,
                      batch=2, strideA=dF // 4, strideW=w["keyg.0.w"].stride, strideC=h.stride, sb={"bias": Kd * 4, "A2": dN})
-        kp, kst = self.key_aux(R)
+        kp, kst = aux or self.key_aux(R)
         ops.gemm(h, w["keyg.2.w"], out1, M=R, N=E, K=Kd, lda=Kd, ldc=E, bias=w["keyg.2.b"], stats_out=kst, c2=kp,
                  batch=2, strideA=h.stride, strideW=w["keyg.2.w"].stride, strideC=dO // 4,
                  sb={"bias": E * 4, "stats_out": R * (E // 32) * 8, "c2": kp.stride * es})
@@ -670,7 +671,7 @@ class Engine:
     def encode_feat_key(self, feat, dec_last, R, num, out, aux=False):
         """spann3r/model.py:299-303: Linear(1792,1792) -> GELU -> Linear(1792,1024) on cat(feat, dec[-1]);
         the concatenation is never materialised (split-A GEMM).  aux: also write the fragment-order copy and the
-        row-statistics partials of the key (returned; see key_aux)."""
+        row-statistics partials of the key (returned; see key_aux) -- True: into the engine's buffers, or the caller's own pair."""
         self.activate()
         cfg, w = self.cfg, self.w
         E, D, Kd = cfg.enc_dim, cfg.dec_dim, cfg.key_dim
@@ -679,7 +680,7 @@ class Engine:
         ops.gemm(feat, w[pre + "0.w"], h, M=R, N=Kd, K=Kd, lda=E, ldc=Kd, bias=w[pre + "0.b"], act=ACT_GELU,
                  A2=dec_last, lda2=D, K1=E)
         if aux:
-            kp, kst = self.key_aux(R)
+            kp, kst = self.key_aux(R) if aux is True else aux
             ops.gemm(h, w[pre + "2.w"], out, M=R, N=E, K=Kd, lda=Kd, ldc=E, bias=w[pre + "2.b"], stats_out=kst[num - 1],
                      c2=kp.at(num - 1))
             return kp.at(num - 1), kst[num - 1]

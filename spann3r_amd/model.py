@@ -567,6 +567,7 @@ class _GraphCache:
         self.live = collections.OrderedDict()        # key -> (hipGraph, device bytes its capture allocated), least recently used first
         self.seen = set()
         self.pool = self.capture_stream = None
+        self.last = None                             # what the last run() did: "eager", "capture" or "replay"
         self.clear()
 
     def __len__(self):
@@ -609,11 +610,13 @@ class _GraphCache:
             self.drop(lambda k: k in self.length_keys)
         if per_length:
             self.length_keys.add(key)
+        self.last = "eager"
         if not use_graphs or (per_length and self.length_keys_eager):
             fn()
         elif key in self.live:
             self.live.move_to_end(key)
             self.live[key][0].replay()
+            self.last = "replay"
         elif key in self.seen:
             if self.pool is None or not self.live:
                 # a pool whose last graph is gone is retired by the allocator (its blocks are freed at the next empty_cache / OOM
@@ -654,6 +657,7 @@ class _GraphCache:
                 self.graph_bytes -= ob
                 del old
             g.replay()
+            self.last = "capture"
         else:
             self.seen.add(key)
             fn()
@@ -711,6 +715,16 @@ class _SequenceRunner:
         self.seq_dec2 = None          # per hook: [steps*B*P, D] copies of the side-2 decoder tokens of every step
         self.dec2_hooks = None
         self.head2_out = {}
+        self.own_aux = None           # streaming session: (fragment-order copies, statistics) of both keys in buffers of this runner
+
+    def own_key_aux(self):
+        """The key MLPs leave the fragment-order copy and the row statistics of feat_k2 in an engine workspace that every runner of the
+        geometry shares, and the NEXT step's memory read consumes them.  Inside one forward call nothing runs in between; between two
+        pushes of a streaming session anything may (a forward call, another session), so a session's runner gives the key MLPs
+        buffers of its own to write them to."""
+        eng, R = self.eng, self.B * self.P
+        self.own_aux = (ops.PackedAct.group(2, R, self.E, eng.adt, eng.device),
+                        torch.empty(2, R, self.E // 32, 2, device=eng.device))
 
     @property
     def model(self):
@@ -830,10 +844,13 @@ class _SequenceRunner:
         ops.copy_multi(self.pair_copies(i))
 
     # ---- the kernel sequences (spann3r/model.py:485-531) ----------------------------------------------------
-    def _part1(self, first, has_next, scores_to_host):
+    def _part1(self, first, has_next, scores_to_host, stream=False):
         """Everything up to the similarity scores: (memory read) + decoder + key MLPs + check_sim's cosine scores.
         The two decoder sides run on two streams (or as grouped launches); a third stream encodes the NEXT frame in
         the frame-by-frame mode (each frame is encoded exactly once, spann3r/model.py:293-295).
+        stream (a streaming session's step, spann3r_amd/stream.py): the frame in img_next is THIS step's view 2 -- it only just
+        arrived, so its encoder cannot run a step ahead; it runs on the third stream next to the memory read, which depends on the
+        previous step's key only.
         scores_to_host: the scores go straight to the buffer the host polls, where the kernel can do that (SpatialMemory.sim_scores)."""
         eng, mem, B, P, E = self.eng, self.mem, self.B, self.P, self.E
         main = torch.cuda.current_stream()
@@ -848,7 +865,12 @@ class _SequenceRunner:
                 eng.encode_image(self.img_pair, out=self.featpair)
             f1, f1p = self.feat1, p1
         else:
-            if not self.batched:
+            if stream:
+                ops.copy2d(self.feat2, E, self.feat1, E, B * P, E)      # feat1 <- previous feat2 (:294)
+                st[3].wait_stream(main)
+                with torch.cuda.stream(st[3]):                          # (the prefetch encoder's workspaces: none shared with the read)
+                    eng.encode_image(self.img_next, out=self.feat2, tag="_pre")
+            elif not self.batched:
                 ops.copy2d(self.feat2, E, self.feat1, E, B * P, E)      # feat1 <- previous feat2 (:294)
                 ops.copy2d(self.feat_pre, E, self.feat2, E, B * P, E)   # feat2 <- the frame encoded during the previous step
             # reads k2 (and its fragment-order copy / statistics) before the key MLP of this step overwrites them
@@ -856,6 +878,8 @@ class _SequenceRunner:
                             out_packed=self.fuse_p if packed else None)
             f1 = self.fuse
             f1p = self.fuse_p if (packed and mem.wrote_packed) else None
+            if stream:
+                main.wait_stream(st[3])
         if has_next:
             st[3].wait_stream(main)
             with torch.cuda.stream(st[3]):
@@ -864,12 +888,12 @@ class _SequenceRunner:
             # both decoder sides and both key MLPs as grouped launches on the main stream: no per-layer fork/join
             dec1, dec2 = eng.decoder_grouped(f1, self.feat2, B, self.nh, self.nw, f1p=f1p, f2p=p2 if f1p is not None else None)
             self.k2_aux = eng.encode_feat_keys_grouped(self.feat1, self.feat2, dec1[-1], dec2[-1], B * P, self.k1, self.k2,
-                                                       feat1p=p1, feat2p=p2)
+                                                       feat1p=p1, feat2p=p2, aux=self.own_aux)
         else:
             dec1, dec2 = eng.decoder(f1, self.feat2, B, self.nh, self.nw, self.nh, self.nw, streams=st)   # joined on return
             st[2].wait_stream(main)
             with torch.cuda.stream(st[2]):
-                self.k2_aux = eng.encode_feat_key(self.feat2, dec2[-1], B * P, 2, self.k2, aux=True)
+                self.k2_aux = eng.encode_feat_key(self.feat2, dec2[-1], B * P, 2, self.k2, aux=self.own_aux or True)
             eng.encode_feat_key(self.feat1, dec1[-1], B * P, 1, self.k1)
             main.wait_stream(st[2])
         if not self.training and mem.sim_needed():
@@ -903,18 +927,20 @@ class _SequenceRunner:
             main.wait_stream(st[2])
         self.out = (pts1, conf1, pts2, conf2)
 
-    def run(self, first, has_next, use_graphs, post_copies=()):
+    def run(self, first, has_next, use_graphs, post_copies=(), stream=False):
         """One step: ONE function -- _part1, the hand-off of the similarity scores to the host, _part2 -- captured and replayed
         as one hipGraph, or called (use_graphs False, a profiler, or a sequence whose per-length steps launch eagerly).  The host
         polls the pinned score buffer and takes the memory decision while the second half (head, value encoder) still runs -> the
         next step's launches are queued before the GPU runs dry.  The reference syncs at the same point of the data flow (:114).
         post_copies: (src, dst) pairs issued with the step's own result copies in ONE launch after the step
-        (decoder hooks -> sequence slots, the next pair of encoder features): six eager launches per frame became one"""
+        (decoder hooks -> sequence slots, the next pair of encoder features): six eager launches per frame became one
+        stream: a streaming session's step (see _part1); part of the graph key, so such steps never share a graph with forward's"""
         mem = self.mem
         has_next = has_next and not self.batched                # nothing to prefetch: the sequence is already encoded
         gk = mem.graph_key()
         # the bank length itself is in the key (see _GraphCache.run): a long bank's steps, EVERY step where the fill level is a launch argument
-        per_length = 0 if gk[0] in ("s", "p") else self._out_steps if mem.state is None else 1
+        # (a stream has no known length: the count-unknown branch)
+        per_length = 0 if gk[0] in ("s", "p") else 1 if (stream or mem.state is not None) else self._out_steps
         if not use_graphs and ops._prof is not None:
             ops._prof.step_begin()
         need_sim = not self.training and mem.sim_needed()
@@ -922,11 +948,12 @@ class _SequenceRunner:
             mem.arm_score_poll()
 
         def whole():
-            self._part1(first, has_next, need_sim)
+            self._part1(first, has_next, need_sim, stream)
             if need_sim and mem.state is None:              # (device-resident bank state: cos_mean stored into the pinned buffer itself)
                 mem.copy_scores_to_host()
             self._part2()
-        key = ("whole", first, need_sim) + gk + (has_next, self.batched, self.defer2, self.model.grouped_decoder, self.model.packed_features)
+        key = ("whole", first, need_sim) + gk + (has_next, self.batched, self.defer2, self.model.grouped_decoder, self.model.packed_features,
+                                                 stream)
         self.graphs.run(key, whole, use_graphs and ops._prof is None, per_length)
         if not first:
             mem.note_deferred_read()            # (a replayed graph ran no Python)
@@ -1285,6 +1312,12 @@ class Spann3R(nn.Module):
             return T.forward_train(P, frames, self.cfg, dropout_p=self.mem_dropout.p, return_memory=return_memory)
         with torch.no_grad():
             return self._forward_inference(frames, return_memory)
+
+    def stream(self):
+        """A streaming session (spann3r_amd/stream.py): frames go in one at a time, push() returns what forward would return for
+        the prefix seen so far.  Eval policy only."""
+        from .stream import Spann3RStream
+        return Spann3RStream(self)
 
     def _forward_inference(self, frames, return_memory):
         self._pinned = None
