@@ -12,6 +12,55 @@ from spann3r_amd import Spann3R, FULL, TINY
 from spann3r_amd.weights import synth_state_dict, synth_frames
 
 
+class StreamFuser:
+    """--stream --fused --bricks: every frame, as its prediction completes, is posed on its own -- the focal of the first frame
+    (estimate_focal_knowing_depth), estimate_poses on that frame alone -- and pushed into a fusion.FusionSession: a brick TSDF volume
+    inside --extent (default: a cube of +-4 units around the first camera), tracked with --track.  With --vis the model is ray-cast
+    from the frame's camera every --kf_every frames.  Pointmaps without geometry (no checkpoint ships) go through nominal cameras --
+    focal = the longer image side, identity poses -- and that is said."""
+
+    def __init__(self, args):
+        self.args, self.session, self.focal, self.nominal, self.pictures = args, None, None, False, 0
+
+    def push(self, i, pts, conf, image):
+        """pts [1, h, w, 3], conf [1, h, w], image [1, h, w, 3] of frame i"""
+        import os
+        import numpy as np
+        from spann3r_amd import fusion, vis
+        from spann3r_amd.postprocess import estimate_focal_knowing_depth, estimate_poses
+        args = self.args
+        _, h, w, _ = pts.shape
+        pp = (w / 2, h / 2)
+        if self.session is None:
+            self.focal = float(estimate_focal_knowing_depth(pts, torch.tensor(pp), focal_mode="weiszfeld").item())
+            self.nominal = not (self.focal > 1e-3 and math.isfinite(self.focal))
+            if self.nominal:
+                self.focal = float(max(h, w))
+                print("degenerate pointmaps: the focal of the first frame came out near 0: fusing through nominal cameras (focal %d, identity poses)"
+                      % max(h, w))
+        pose = np.eye(4) if self.nominal else np.asarray(estimate_poses(pts, self.focal, pp)[0][0], np.float64)
+        if self.session is None:
+            lo, hi = (pose[:3, 3] - 4.0, pose[:3, 3] + 4.0) if args.extent is None else (args.extent[:3], args.extent[3:])
+            self.session = fusion.FusionSession(args.voxel_size, (lo, hi), trunc_voxels=args.trunc_voxels, track=args.track)
+        K = np.array([[self.focal, 0, pp[0]], [0, self.focal, pp[1]], [0, 0, 1]], np.float64)
+        used, _ = self.session.push(pts[0], K, pose, (conf[0] - 1) / conf[0] > args.conf_thresh, image[0])
+        if args.vis and i % args.kf_every == 0:
+            rc = self.session.raycast(K, used[None], (h, w))
+            view = rc["vertices"][0] - torch.from_numpy(used[:3, 3]).to(rc["vertices"])
+            view = view / view.norm(dim=-1, keepdim=True).clamp_min(1e-30)
+            shade = (-(rc["normals"][0] * view).sum(-1)).clamp_min(0.0) * (rc["depth"][0] > 0)
+            d = os.path.join(args.vis, "render_frames")
+            os.makedirs(d, exist_ok=True)
+            vis._save_png(os.path.join(d, "fused_raycast_%03d.png" % i), (rc["colors"][0][..., :3].float() * shade[..., None]).round().to(torch.uint8).cpu().numpy())
+            self.pictures += 1
+
+    def report(self):
+        v = self.session.volume
+        print("fused %d frames as they arrived: %d bricks of %d in a virtual grid of %s voxels, %.1f MB held, %d of %d frames tracked%s" %
+              (self.session.frames, v.n_bricks, v.table.numel(), v.dims, v.memory_bytes / 1e6, sum(self.session.tracked[1:]),
+               max(self.session.frames - 1, 0), ", %d ray-cast pictures written" % self.pictures if self.args.vis else ""))
+
+
 def stream_loop(model, batch, args):
     """--stream: the batch through a streaming session, frame by frame, as a camera loop would (a synchronise after every push; the
     sequence `--repeat` times on the same session, the last pass is reported).  -> (preds, preds_all) as forward returns them."""
@@ -30,6 +79,7 @@ def stream_loop(model, batch, args):
             draw = args.vis if last else None
             s.reset()
             steps, lat, r, replays0 = [], [], None, s.replays
+            fuser = StreamFuser(args) if last and args.fused and args.bricks else None
             torch.cuda.synchronize()
             start = time.time()
             for t, view in enumerate(batch):
@@ -40,9 +90,16 @@ def stream_loop(model, batch, args):
                 if step is None:
                     continue
                 steps.append(step)
-                if draw:                                                          # final = frame t - 1, complete as of now
+                if draw or fuser:                                                 # final = frame t - 1, complete as of now
                     key = "pts3d" if t == 1 else "pts3d_in_other_view"
                     shape = step.final[key].shape[1:3]
+                    todo = [(t - 1, step.final[key], step.final["conf"])]
+                    if t == n - 1:                                                # the sequence ends here: its last frame is `latest`
+                        todo.append((t, step.latest["pts3d_in_other_view"], step.latest["conf"]))
+                if fuser:
+                    for i, pts, conf in todo:
+                        fuser.push(i, pts.float(), conf.float(), image_of(i))
+                if draw:
                     if r is None:
                         d = os.path.join(draw, "render_frames")
                         os.makedirs(d, exist_ok=True)
@@ -50,16 +107,15 @@ def stream_loop(model, batch, args):
                                   vis.fit_camera(torch.cat([step.final["pts3d"], step.latest["pts3d_in_other_view"]]).float(),
                                                  conf=torch.cat([step.final["conf"], step.latest["conf"]]).float(), conf_thresh=args.conf_thresh))
                         r = vis.PointRenderer(camera=camera, point_size=args.point_size, conf_thresh=args.conf_thresh, dynamic=args.dynamic)
-                    todo = [(t - 1, step.final[key], step.final["conf"])]
-                    if t == n - 1:                                                # the sequence ends here: its last frame is `latest`
-                        todo.append((t, step.latest["pts3d_in_other_view"], step.latest["conf"]))
                     for i, pts, conf in todo:
                         r.add(pts[0].float(), image_of(i)[0], conf[0].float())
                         vis._save_png(os.path.join(d, "frame_%03d.png" % i), r.image().cpu().numpy())
             torch.cuda.synchronize()
             end = time.time()
             print("Time: %.4f s, FPS: %.1f  (%d frames pushed one by one, pass %d%s)" %
-                  (end - start, n / (end - start), n, it, ", drawing" if draw else ""))
+                  (end - start, n / (end - start), n, it, (", drawing" if draw else "") + (", fusing into bricks" if fuser else "")))
+            if fuser and fuser.session is not None:
+                fuser.report()
         step_ms = lat[2:] or lat[1:]
         print("push latency (push + synchronise%s): median %.3f ms, p95 %.3f ms, max %.3f ms; first step %.3f ms; %d of %d pushes replayed a graph" %
               (", drawing included" if args.vis else "", float(np.median(step_ms)), float(np.percentile(step_ms, 95)), max(step_ms), lat[1],
@@ -103,6 +159,12 @@ def main():
     ap.add_argument("--track", action="store_true", help="with --fused: register every frame after the first to the model before it is "
                     "integrated (ray-cast the volume from the frame's pose, point-to-plane Gauss-Newton against it); prints how many "
                     "frames were tracked and the largest correction")
+    ap.add_argument("--bricks", action="store_true", help="with --fused: fuse into a brick TSDF volume (fusion.BrickTSDFVolume: 8x8x8-voxel bricks "
+                    "allocated where measurements land) instead of the dense one; needs --voxel_size.  With --stream --fused --bricks every "
+                    "frame is posed on its own and pushed into a fusion.FusionSession as it arrives (with --vis a ray-cast picture every "
+                    "--kf_every frames)")
+    ap.add_argument("--extent", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"), help="with --stream --fused "
+                    "--bricks: the box the session may fuse in (default: a cube of +-4 units around the first camera)")
     ap.add_argument("--voxel_size", type=float, default=None, help="with --fused: voxel edge in the units of the pointmaps (default: the "
                     "longest side of the confident points' box takes 256 voxels)")
     ap.add_argument("--trunc_voxels", type=float, default=3.0, help="with --fused: truncation distance in voxels")
@@ -116,6 +178,8 @@ def main():
     ap.add_argument("--max_depth", type=float, default=10.0)
     ap.add_argument("--min_depth", type=float, default=1e-3)
     args = ap.parse_args()
+    if args.bricks and not (args.fused and args.voxel_size):
+        ap.error("--bricks needs --fused and --voxel_size")
     cfg = TINY if args.tiny else FULL
     device = "cuda"
     model = Spann3R(dus3r_name=None, cfg=cfg, init_weights=False).to(device)      # demo.py:81-82
@@ -183,7 +247,7 @@ def main():
         With --track the frames are registered to the model first and the corrections are reported."""
         from spann3r_amd import fusion
         import numpy as np
-        kw = dict(conf_thresh=args.conf_thresh, return_volume=True, track=args.track, return_poses=args.track, **fuse_kw, **kw)
+        kw = dict(conf_thresh=args.conf_thresh, return_volume=True, track=args.track, return_poses=args.track, bricks=args.bricks, **fuse_kw, **kw)
         try:
             fm, vol = fusion.fuse_sequence(preds, batch, **kw)
         except RuntimeError as e:

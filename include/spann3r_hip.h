@@ -990,6 +990,82 @@ int sp3_tsdf_track_accum(const float* pts, const uint8_t* valid, int64_t n, cons
                          const float* depth, int w, int h, int64_t row_stride, float fu, float fv, float cu, float cv, const double* w2c12,
                          float dist_max, void* ws, double* out29, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Brick TSDF volume (spann3r_amd/fusion.py BrickTSDFVolume drives these; csrc/bricks.hip): the volume of "TSDF fusion" on two
+ * levels, so that a session can fuse inside a generous virtual box without holding its voxels: a table of 8 x 8 x 8-voxel bricks,
+ * allocated where depth measurements land, and a pool that holds only those bricks.  There is no reference implementation;
+ * tests/bricks_ref.py restates mark, alloc, integrate and to_dense in numpy, and the dense kernels above are the anchor of the
+ * integration and of the ray-caster.  No entry point allocates, frees or synchronises.  Every fp32 operation is rounded on its own
+ * and sums run left to right.  No atomics; no workgroup waits on another.
+ *
+ * Layout: the virtual grid is nx x ny x nz voxels, every dimension a multiple of 8 (anything else is an error); voxel centres follow
+ *   the dense rule, origin_a + fp32(i_a) * voxel.  The brick grid is bx = nx / 8, by = ny / 8, bz = nz / 8; brick (I, J, K) has
+ *   linear index (K by + J) bx + I.  table int32 [bx by bz]: -1 = absent, otherwise a pool slot.  slot_brick int32 [capacity]: the
+ *   linear brick index of a slot.  Pool: tsdf fp32 [capacity, 512], weight fp32 [capacity, 512], rgb fp32 [capacity, 512, 3]
+ *   (nullable: no colours); voxel (i, j, k) lives in the brick (i >> 3, j >> 3, k >> 3) at place (k & 7) 64 + (j & 7) 8 + (i & 7).
+ *   count: DEVICE int32 [1], the slots in use.  The voxels of an absent brick read as tsdf 1, weight 0, rgb 0: that is "the
+ *   densified volume" below.  bx by bz + capacity + 256 must stay below 2^31 (int32 brick indices, slots, the scan's tile table and
+ *   `need`), a side below 2^20 voxels; pool indices are 64-bit.
+ *
+ * sp3_tsdf_brick_mark: T frames (T <= 65535) in ONE launch, a lane owns a pixel.  The frames are sp3_tsdf_frame as
+ *   sp3_tsdf_integrate takes them (rgba is ignored); c2w_dev is a device fp32 [T, 12] array of row-major 3 x 4 camera-to-world
+ *   matrices (R | eye), read for frames with depth only (required when there is one).  A pixel (px, py) counts when it passes the
+ *   pixel tests of the integrate rule: valid[p] != 0, d finite and > 0 (d = depth[p], or from pts[p] by the frame's w2c as there),
+ *   pixel_weight[p] > 0 and finite.  Its point P: for a pts frame the point itself; for a depth frame
+ *     xn = (fp32(px) - cu) / fu, yn = (fp32(py) - cv) / fv, Xc = (xn * d, yn * d, d), P_r = ((R_r0 Xc.x + R_r1 Xc.y) + R_r2 Xc.z) + eye_r.
+ *   A non-finite P is skipped.  band is metric, > 0 and at most 8 voxel.  Per axis a:
+ *     lo_a = floor(((P_a - band) - origin_a) / voxel),  hi_a = floor(((P_a + band) - origin_a) / voxel) + 1  (in fp32);
+ *     the pixel is skipped unless hi_a >= 0 and lo_a <= n_a - 1 on every axis (a NaN fails); then lo_a and hi_a are clamped to
+ *     [0, n_a - 1] and flags[brick] = 1 for every brick of lo_a >> 3 .. hi_a >> 3 on each axis (at most 4 per axis, 3 when band
+ *     stays below 7 voxels).  flags is uint8 [bx by bz]; the writes are plain stores of the same value, so the result does not depend
+ *     on order.  mark never clears a flag.  T = 0 is a no-op.
+ *
+ * sp3_tsdf_brick_alloc: order-preserving, all or nothing.  A brick is new when its flag is set and its table entry is -1.  With
+ *   need = count + the number of new bricks:  need <= capacity: every new brick, in linear brick order, gets slot count + its
+ *   exclusive rank among the new bricks; table and slot_brick are filled, the 512 voxels of the slot are set to tsdf 1, weight 0,
+ *   rgb 0, all flags are cleared and count = need.  need > capacity: nothing is written to flags, table, slot_brick, the pool or
+ *   count, so the caller grows the pool (copying the slots in use) and calls alloc again without marking again.  In both cases
+ *   counts2 int32 [2] = (count after the call, need).  It is the tile count / single-workgroup scan / scatter of csrc/scan.h plus
+ *   the slot initialisation and one single-lane launch that alone changes count (5 launches).  ws: device scratch of
+ *   sp3_tsdf_brick_alloc_ws_bytes(), 16-byte aligned.
+ *
+ * sp3_tsdf_brick_integrate: T frames into the slots 0 .. n_bricks - 1 in ONE launch; n_bricks is the count the host read from
+ *   counts2 (that one read-back per call is accepted).  A workgroup owns a brick and a lane a voxel: it loads its state once, walks
+ *   the frames in table order and stores once.  The per-frame rule is the text of sp3_tsdf_integrate, word for word, on the voxel's
+ *   centre by the dense rule: an allocated voxel ends with the bits sp3_tsdf_integrate gives the same voxel of the same grid after
+ *   the same frames.  (A brick allocated by a later call starts from tsdf 1, weight 0 then: what earlier frames would have
+ *   contributed to it is not there.)  T = 0 and n_bricks = 0 are no-ops.
+ *
+ * sp3_tsdf_brick_raycast: the rule of sp3_tsdf_raycast on the densified volume of the virtual grid: the same sp3_tsdf_view table,
+ *   cap (from the virtual dims), workgroup shape and outputs; a corner in an absent brick is unobserved.  One freedom is added: a
+ *   lane may pass over samples it can prove invalid without evaluating them -- every sample is recomputed from its index, so later
+ *   samples do not change, and an invalid sample only clears prev_valid.  The proof used: corner 0 of a sample's cell lies in an
+ *   absent brick, and so does corner 0 of a later sample; the lattice coordinates of corner 0 are monotone in the sample index
+ *   (every rounded operation of the sample rule is monotone), so every sample in between has its corner 0 in that brick as well.
+ *   The brick table is the only skip structure; nothing approximate decides a skip.
+ *
+ * sp3_tsdf_brick_to_dense: the densified volume of a box of voxels: lo3, size3 HOST int32 [3] with 0 <= lo_a, lo_a + size_a <= n_a
+ *   and 7 sx sy sz < 2^31; out_tsdf, out_weight fp32 [sz, sy, sx], out_rgb fp32 [sz, sy, sx, 3] (nullable; needs a pool with
+ *   colours).  A lane owns a voxel of the box: allocated voxels are copied, absent ones set to (1, 0, 0).  This is how a brick volume
+ *   reaches sp3_tsdf_extract.
+ *
+ * Errors, by the usual codes: a dimension that is not a multiple of 8; band outside (0, 8 voxel]; capacity or bx by bz over the
+ *   index limit; a frame with both or neither of depth and pts; a frame without rgba while the pool has colours (integrate); rgba
+ *   views on a pool without colours. */
+int sp3_tsdf_brick_mark(const sp3_tsdf_frame* frames_host, const sp3_tsdf_frame* frames_dev, const float* c2w_dev, int T, int nx, int ny,
+                        int nz, const float* origin3, float voxel, float band, uint8_t* flags, void* stream);
+int64_t sp3_tsdf_brick_alloc_ws_bytes(int nx, int ny, int nz);
+int sp3_tsdf_brick_alloc(uint8_t* flags, int nx, int ny, int nz, int32_t* table, int32_t* slot_brick, int32_t* count, int64_t capacity,
+                         float* tsdf, float* weight, float* rgb, void* ws, int32_t* counts2, void* stream);
+int sp3_tsdf_brick_integrate(const sp3_tsdf_frame* frames_host, const sp3_tsdf_frame* frames_dev, int T, int nx, int ny, int nz,
+                             const float* origin3, float voxel, float trunc, const int32_t* slot_brick, int n_bricks, float* tsdf,
+                             float* weight, float* rgb, void* stream);
+int sp3_tsdf_brick_raycast(const sp3_tsdf_view* views_host, const sp3_tsdf_view* views_dev, int T, int nx, int ny, int nz,
+                           const float* origin3, float voxel, const int32_t* table, const float* tsdf, const float* weight, const float* rgb,
+                           float min_weight, float step, void* stream);
+int sp3_tsdf_brick_to_dense(int nx, int ny, int nz, const int32_t* table, const float* tsdf, const float* weight, const float* rgb,
+                            const int32_t* lo3, const int32_t* size3, float* out_tsdf, float* out_weight, float* out_rgb, void* stream);
+
 /* small utilities */
 /* n (1..8) contiguous device-to-device copies in one launch; every copy 16-byte aligned and a multiple of 16 bytes.
  * (The sequence loop's per-frame bookkeeping -- torch .clone() / slice assignments around spann3r/model.py:523-531.) */

@@ -318,6 +318,210 @@ class TSDFVolume:
         return out
 
 
+class BrickTSDFVolume:
+    """The volume of TSDFVolume on two levels (include/spann3r_hip.h "Brick TSDF volume", csrc/bricks.hip): a virtual grid of `dims`
+    voxels (rounded up to multiples of 8) whose 8 x 8 x 8 bricks are allocated where measurements land -- every brick within `band`
+    (metric, default trunc, at most 8 voxels) of a measured point -- and a pool of `capacity` bricks that doubles when it runs out.
+    Memory follows the surface, not the box, and the extent need not be known: give a generous box.  An allocated voxel holds the
+    bits the dense volume gives it after the same frames; a brick born in a later call does not hold what earlier frames would have
+    given it.  `integrate`, `frame_table`, `raycast`, `view_table` and `raycast_table` take and return what TSDFVolume's do;
+    `track_frame` takes a brick volume as it is."""
+
+    def __init__(self, origin, voxel_size, dims, trunc=None, band=None, color=True, capacity=4096, device="cuda"):
+        dims = tuple(int(d) for d in dims)
+        if len(dims) != 3 or min(dims) < 0:
+            raise ValueError("BrickTSDFVolume: dims %s must be three sizes (nx, ny, nz) >= 0" % (dims,))
+        self.dims = tuple(-(-d // 8) * 8 for d in dims)
+        self.bricks = tuple(d // 8 for d in self.dims)
+        n_table = self.bricks[0] * self.bricks[1] * self.bricks[2]
+        capacity = int(capacity)
+        if capacity < 1:
+            raise ValueError("BrickTSDFVolume: capacity must be >= 1, got %r" % (capacity,))
+        if max(self.dims) >= 2 ** 20 or 2 * n_table + 256 >= 2 ** 31:
+            raise ValueError("BrickTSDFVolume: dims %s over the index limit: %d bricks (bricks + capacity must stay below 2^31)" % (self.dims, n_table))
+        origin = np.asarray(origin, np.float64).reshape(-1)
+        if origin.shape != (3,) or not np.isfinite(origin).all():
+            raise ValueError("BrickTSDFVolume: origin must be three finite numbers")
+        self.voxel_size = float(np.float32(voxel_size))
+        if not (self.voxel_size > 0 and math.isfinite(self.voxel_size)):
+            raise ValueError("BrickTSDFVolume: voxel_size must be positive and finite, got %r" % (voxel_size,))
+        self.trunc = float(np.float32(3.0 * self.voxel_size if trunc is None else trunc))
+        if not (self.trunc > 0 and math.isfinite(self.trunc)):
+            raise ValueError("BrickTSDFVolume: trunc must be positive and finite, got %r" % (trunc,))
+        self.band = float(np.float32(self.trunc if band is None else band))
+        if not (0 < self.band <= float(np.float32(8.0) * np.float32(self.voxel_size))):
+            raise ValueError("BrickTSDFVolume: band %r must lie in (0, 8 voxels = %g]" % (self.band, 8 * self.voxel_size))
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("BrickTSDFVolume: fusion runs on the GPU (HIP kernels); there is no CPU path")
+        self.origin = origin.astype(np.float32)
+        self._origin_c = (C.c_float * 3)(*self.origin.tolist())
+        self.color = bool(color)
+        dev = self.device
+        self.table = torch.empty(max(n_table, 1), dtype=torch.int32, device=dev)[:n_table]
+        self.flags = torch.empty(max(n_table, 1), dtype=torch.uint8, device=dev)[:n_table]
+        self.count = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._counts = torch.zeros(2, dtype=torch.int32, device=dev)
+        self._ws = torch.empty(max(int(L.load().sp3_tsdf_brick_alloc_ws_bytes(*self.dims)), 16), dtype=torch.uint8, device=dev)
+        self._pool(min(capacity, max(n_table, 1)))          # (a grid has no use for more slots than bricks)
+        self.launches = 0                   # sp3_tsdf_brick_integrate launches so far
+        self.raycasts = 0                   # sp3_tsdf_brick_raycast launches so far
+        self.grown = 0                      # times the pool doubled
+        self.reset()
+
+    def _pool(self, capacity):
+        """a fresh pool of `capacity` slots (alloc initialises a slot when it hands it out)"""
+        dev = self.device
+        self.capacity = capacity
+        self.slot_brick = torch.empty(capacity, dtype=torch.int32, device=dev)
+        self.tsdf = torch.empty((capacity, 512), dtype=torch.float32, device=dev)
+        self.weight = torch.empty((capacity, 512), dtype=torch.float32, device=dev)
+        self.rgb = torch.empty((capacity, 512, 3), dtype=torch.float32, device=dev) if self.color else None
+
+    def reset(self):
+        self.table.fill_(-1)
+        self.flags.zero_()
+        self.count.zero_()
+        self.n_bricks = 0
+
+    @property
+    def memory_bytes(self):
+        """bytes held on the device: table, flags, slot_brick and the pool"""
+        ts = [self.table, self.flags, self.slot_brick, self.tsdf, self.weight, self.count, self._counts, self._ws] + ([self.rgb] if self.color else [])
+        return sum(t.numel() * t.element_size() for t in ts)
+
+    # the argument handling, the frame and view descriptors are TSDFVolume's own (they use self.rgb and self.device only)
+    integrate = TSDFVolume.integrate
+    raycast = TSDFVolume.raycast
+    view_table = TSDFVolume.view_table
+
+    def frame_table(self, src, is_depth, intrinsics, cam2world, valid=None, weight=None, images=None):
+        """TSDFVolume.frame_table plus, as a fifth entry, the device fp32 [T, 12] camera-to-world matrices `mark` reads for depth frames"""
+        tbl = TSDFVolume.frame_table(self, src, is_depth, intrinsics, cam2world, valid, weight, images)
+        P = _host_mats(cam2world, tbl[2], (4, 4), "cam2world")
+        c2w = torch.from_numpy(np.ascontiguousarray(P[:, :3, :].reshape(tbl[2], 12).astype(np.float32))).to(self.device)
+        return tbl + (c2w,)
+
+    def allocate(self, depth=None, pts=None, intrinsics=None, cam2world=None, valid=None, weight=None, images=None):
+        """`mark` + `alloc` for T frames (the arguments of `integrate`; images are not needed): the bricks within `band` of their points
+        exist afterwards.  One read of two int32 per alloc call."""
+        if (depth is None) == (pts is None):
+            raise ValueError("allocate: give depth or pts, exactly one")
+        if intrinsics is None or cam2world is None:
+            raise ValueError("allocate: intrinsics and cam2world are required")
+        src = _frames_list(depth, "depth", ()) if depth is not None else _frames_list(pts, "pts", (3,))
+        if len(src) == 0:
+            return self
+        rgb, self.rgb = self.rgb, None          # (no colour maps needed to mark)
+        try:
+            tbl = self.frame_table(src, depth is not None, intrinsics, cam2world, valid, weight, None)
+        finally:
+            self.rgb = rgb
+        return self.allocate_table(tbl)
+
+    def allocate_table(self, tbl):
+        table, table_d, T, _, c2w = tbl
+        lib, st = L.load(), L.stream_ptr()
+        nx, ny, nz = self.dims
+        L.check(lib.sp3_tsdf_brick_mark(table, table_d.data_ptr(), c2w.data_ptr(), T, nx, ny, nz, self._origin_c, self.voxel_size, self.band,
+                                        self.flags.data_ptr(), st), "sp3_tsdf_brick_mark")
+        while True:
+            L.check(lib.sp3_tsdf_brick_alloc(self.flags.data_ptr(), nx, ny, nz, self.table.data_ptr(), self.slot_brick.data_ptr(),
+                                             self.count.data_ptr(), self.capacity, self.tsdf.data_ptr(), self.weight.data_ptr(), L.ptr(self.rgb),
+                                             self._ws.data_ptr(), self._counts.data_ptr(), st), "sp3_tsdf_brick_alloc")
+            count, need = self._counts.cpu().tolist()
+            if need <= self.capacity:
+                self.n_bricks = count
+                return self
+            old = (self.slot_brick, self.tsdf, self.weight, self.rgb)
+            capacity = self.capacity
+            while capacity < need:
+                capacity *= 2
+            self._pool(min(capacity, self.table.numel()))
+            for new, o in zip((self.slot_brick, self.tsdf, self.weight, self.rgb), old):
+                if o is not None:
+                    new[:count].copy_(o[:count])
+            self.grown += 1
+
+    def integrate_table(self, tbl):
+        """mark, alloc, then one sp3_tsdf_brick_integrate launch of a frame_table"""
+        self.allocate_table(tbl)
+        table, table_d, T, _, _ = tbl
+        nx, ny, nz = self.dims
+        L.check(L.load().sp3_tsdf_brick_integrate(table, table_d.data_ptr(), T, nx, ny, nz, self._origin_c, self.voxel_size, self.trunc,
+                                                  self.slot_brick.data_ptr(), self.n_bricks, self.tsdf.data_ptr(), self.weight.data_ptr(),
+                                                  L.ptr(self.rgb), L.stream_ptr()), "sp3_tsdf_brick_integrate")
+        self.launches += 1
+        return self
+
+    def raycast_table(self, tbl, step_voxels=1.0, min_weight=1.0):
+        """one sp3_tsdf_brick_raycast launch of a view_table -> its maps"""
+        table, table_d, T, out = tbl
+        if not (step_voxels >= 0.25 and math.isfinite(step_voxels)):
+            raise ValueError("raycast: step_voxels must be finite and >= 0.25, got %r" % (step_voxels,))
+        if not min_weight > 0:
+            raise ValueError("raycast: min_weight must be > 0, got %r" % (min_weight,))
+        if T == 0:
+            return out
+        nx, ny, nz = self.dims
+        step = float(np.float32(np.float32(step_voxels) * np.float32(self.voxel_size)))
+        L.check(L.load().sp3_tsdf_brick_raycast(table, table_d.data_ptr(), T, nx, ny, nz, self._origin_c, self.voxel_size, self.table.data_ptr(),
+                                                self.tsdf.data_ptr(), self.weight.data_ptr(), L.ptr(self.rgb), float(min_weight), step,
+                                                L.stream_ptr()), "sp3_tsdf_brick_raycast")
+        self.raycasts += 1
+        return out
+
+    def brick_box(self):
+        """(lo, size) in voxels of the bounding box of the allocated bricks; size 0 without any"""
+        if self.n_bricks == 0:
+            return (0, 0, 0), (0, 0, 0)
+        b = self.slot_brick[:self.n_bricks].cpu().numpy().astype(np.int64)
+        bx, by, _ = self.bricks
+        ijk = np.stack([b % bx, (b // bx) % by, b // (bx * by)], 1)
+        lo, hi = ijk.min(0), ijk.max(0) + 1
+        return tuple(int(x) * 8 for x in lo), tuple(int(x) * 8 for x in hi - lo)
+
+    def to_dense(self, box=None, dims_limit=512):
+        """The densified volume of a box of voxels, box = (lo, size) (default: the bounding box of the allocated bricks), as a TSDFVolume:
+        allocated voxels copied, absent ones (1, 0, 0).  Its origin is origin + fp32(lo) * voxel_size, rounded per axis, and it
+        places its voxels from there by its own rule.  More than dims_limit voxels on an axis raises ValueError."""
+        lo, size = self.brick_box() if box is None else (tuple(int(x) for x in box[0]), tuple(int(x) for x in box[1]))
+        if len(lo) != 3 or len(size) != 3 or min(lo) < 0 or min(size) < 0 or any(l + s > d for l, s, d in zip(lo, size, self.dims)):
+            raise ValueError("to_dense: box (lo %s, size %s) must lie inside the grid of %s voxels" % (lo, size, self.dims))
+        if max(size) > dims_limit:
+            raise ValueError("to_dense: a box of %s voxels is over dims_limit %d per axis" % (size, dims_limit))
+        origin = self.origin + np.asarray(lo, np.float32) * np.float32(self.voxel_size)
+        out = TSDFVolume(origin, self.voxel_size, size, trunc=self.trunc, color=self.color, device=self.device)
+        nx, ny, nz = self.dims
+        L.check(L.load().sp3_tsdf_brick_to_dense(nx, ny, nz, self.table.data_ptr(), self.tsdf.data_ptr(), self.weight.data_ptr(), L.ptr(self.rgb),
+                                                 (C.c_int32 * 3)(*lo), (C.c_int32 * 3)(*size), out.tsdf.data_ptr(), out.weight.data_ptr(),
+                                                 L.ptr(out.rgb), L.stream_ptr()), "sp3_tsdf_brick_to_dense")
+        return out
+
+    def extract_mesh(self, min_weight=1.0, scale=1.0, transform=None, dims_limit=512):
+        """to_dense().extract_mesh(...): the surface of the allocated bricks' bounding box (marching tetrahedra on the bricks
+        themselves is not there yet)"""
+        return self.to_dense(dims_limit=dims_limit).extract_mesh(min_weight, scale, transform)
+
+
+def _extent_box(extent):
+    box = np.asarray([np.asarray(e, np.float64).reshape(-1) for e in extent], np.float64)
+    if box.shape != (2, 3) or not np.isfinite(box).all() or not (box[1] >= box[0]).all():
+        raise ValueError("extent must be (lo, hi): two finite points with lo <= hi, got %r" % (extent,))
+    return box
+
+
+def brick_volume_for_extent(extent, voxel_size, trunc_voxels=3.0, color=True, capacity=4096, device="cuda"):
+    """The BrickTSDFVolume whose virtual grid covers the box extent = (lo, hi) padded by trunc = trunc_voxels voxels (the padding
+    rule of volume_for_points)."""
+    box = _extent_box(extent)
+    if voxel_size is None or not (voxel_size > 0 and math.isfinite(voxel_size)):
+        raise ValueError("a brick volume needs voxel_size (positive, finite), got %r" % (voxel_size,))
+    pad = math.ceil(trunc_voxels) * voxel_size
+    dims = tuple(int(math.ceil((e + 2 * pad) / voxel_size - 1e-9)) + 1 for e in box[1] - box[0])
+    return BrickTSDFVolume(box[0] - pad, voxel_size, dims, trunc=trunc_voxels * voxel_size, color=color, capacity=capacity, device=device)
+
+
 def volume_for_points(points, voxel_size=None, dims_max=256, trunc_voxels=3.0, color=True):
     """The volume whose box is that of `points` (device fp32 [n, 3], all finite) padded by trunc = trunc_voxels voxels.  voxel_size
     None: the largest voxel with which the longest side fits dims_max voxels."""
@@ -447,14 +651,74 @@ def _transform_points(pts, T):
     return out
 
 
+def _fuse_frame(vol, pts, valid, K, pose, image, track, track_args=None):
+    """One step of the KinectFusion sequence on `vol` (dense or bricks): with `track` the frame -- pts [h, w, 3] world points, valid
+    [h, w], K [3, 3], pose = its claimed cam2world [4, 4], image [h, w, 3] or None -- is registered to the model that does not contain
+    it yet (track_frame), its pointmap moved by the correction T (sp3_transform_points) and its pose set to T @ pose; then it is
+    integrated in one launch.  -> (the pose used, T, track_frame's info or None)."""
+    T, info = np.eye(4), None
+    if track:
+        Tt, info = track_frame(vol, pts, valid, K, pose, **(track_args or {}))
+        if info["tracked"]:
+            T, pose = Tt, Tt @ pose
+            pts = _transform_points(pts, T)
+    vol.integrate(pts=pts[None], intrinsics=K, cam2world=pose[None], valid=valid[None], images=None if image is None else image[None])
+    return pose, T, info
+
+
+class FusionSession:
+    """Fusion one frame at a time, with no knowledge of the frames to come: a BrickTSDFVolume of voxel_size inside the generous box
+    extent = (lo, hi).  push() runs the step of fuse_pointmaps(track=True, bricks=True) -- the same function -- so a session over the
+    frames of a sequence ends in the state that call ends in."""
+
+    def __init__(self, voxel_size, extent, trunc_voxels=3.0, color=True, track=True, track_args=None, capacity=4096, device="cuda"):
+        self.volume = brick_volume_for_extent(extent, voxel_size, trunc_voxels, color, capacity, device)
+        self.track, self.track_args = bool(track), track_args
+        self.frames = 0
+        self.poses, self.corrections, self.tracked = [], [], []
+
+    def push(self, pts, intrinsics, cam2world, valid, image=None):
+        """pts fp32 [h, w, 3] (world points), intrinsics [3, 3], cam2world [4, 4] as the frame claims it, valid [h, w], image [h, w, 3]
+        in [0, 1] (required when the session has colours).  -> (the cam2world used, info): info is track_frame's from the second frame
+        on (tracked False: the pose was used as claimed), dict(tracked=...) for the first frame and without tracking."""
+        pts = _dev(pts, "push: pts").float()
+        if pts.dim() != 3 or pts.shape[-1] != 3 or _dev(valid, "push: valid").shape != pts.shape[:2]:
+            raise RuntimeError("push: mismatched shapes: pts %s must be [h, w, 3], valid %s [h, w]" % (tuple(pts.shape), tuple(valid.shape)))
+        if self.volume.color and image is None:
+            raise ValueError("push: the session has colours: pass image (or build it with color=False)")
+        valid = valid.bool() & torch.isfinite(pts).all(-1)
+        K = _host_mats(intrinsics, 1, (3, 3), "intrinsics")[0]
+        pose = _host_mats(cam2world, 1, (4, 4), "cam2world")[0].copy()
+        first = self.frames == 0
+        pose, T, info = _fuse_frame(self.volume, pts, valid, K, pose, image if self.volume.color else None, self.track and not first,
+                                    self.track_args)
+        if info is None:
+            info = dict(tracked=bool(self.track and first))        # (frame 0 is the model's own frame)
+        self.frames += 1
+        self.poses.append(pose)
+        self.corrections.append(T)
+        self.tracked.append(bool(info["tracked"]))
+        return pose, info
+
+    def raycast(self, intrinsics, cam2world, size, **kw):
+        """BrickTSDFVolume.raycast of the model so far"""
+        return self.volume.raycast(intrinsics, cam2world, size, **kw)
+
+    def mesh(self, min_weight=1.0, scale=1.0, transform=None, dims_limit=512):
+        """BrickTSDFVolume.extract_mesh of the model so far"""
+        return self.volume.extract_mesh(min_weight, scale, transform, dims_limit)
+
+
 def fuse_sequence(preds, batch, conf_thresh=1e-3, voxel_size=None, dims_max=256, trunc_voxels=3.0, min_weight=1.0, scale=1.0,
-                  transform=None, color=True, return_volume=False, focal=None, poses=None, track=False, return_poses=False):
+                  transform=None, color=True, return_volume=False, focal=None, poses=None, track=False, return_poses=False, bricks=False,
+                  extent=None):
     """The fused surface of a reconstruction from model.forward's `preds` and its `batch`: demo.py's own sequence -- the stacked
     pointmaps (mesh.sequence_tensors), the focal of frame 0 (estimate_focal_knowing_depth), one pose per frame (estimate_poses) --
     then the pointmaps of the pixels with (conf - 1) / conf > conf_thresh integrated through the `pts` path into a volume around
     the confident points.  -> the mesh dict of TSDFVolume.extract_mesh (and the volume with return_volume).
     focal / poses (cam2world [t, 4, 4]) given: used instead of the estimates.  track / return_poses: as fuse_pointmaps (every frame
-    after the first is registered to the model before it is integrated).  Pointmaps without geometry (seeded random weights)
+    after the first is registered to the model before it is integrated).  bricks / extent: as fuse_pointmaps (a BrickTSDFVolume at
+    voxel_size instead of the dense volume).  Pointmaps without geometry (seeded random weights)
     give a focal near 0: that raises rather than fusing through meaningless cameras."""
     from .postprocess import estimate_focal_knowing_depth, estimate_poses
     pts_all, images_all, conf_all = M.sequence_tensors(preds, batch)
@@ -473,11 +737,12 @@ def fuse_sequence(preds, batch, conf_thresh=1e-3, voxel_size=None, dims_max=256,
     valid = (conf_all - 1) / conf_all > conf_thresh
     K = np.array([[focal, 0, pp[0]], [0, focal, pp[1]], [0, 0, 1]], np.float64)
     return fuse_pointmaps(pts_all, K, np.asarray(poses, np.float64), valid, images_all, voxel_size, dims_max, trunc_voxels, min_weight, scale,
-                          transform, color, return_volume, track, return_poses)
+                          transform, color, return_volume, track, return_poses, bricks=bricks, extent=extent)
 
 
 def fuse_pointmaps(pts_all, intrinsics, cam2world, valid, images=None, voxel_size=None, dims_max=256, trunc_voxels=3.0, min_weight=1.0,
-                   scale=1.0, transform=None, color=True, return_volume=False, track=False, return_poses=False, track_args=None):
+                   scale=1.0, transform=None, color=True, return_volume=False, track=False, return_poses=False, track_args=None,
+                   bricks=False, extent=None):
     """World pointmaps pts_all [t, h, w, 3] with their cameras, integrated through the `pts` path into a volume around the valid
     (and finite) points -> the mesh dict of TSDFVolume.extract_mesh (and the volume with return_volume).
     track=False: one integrate launch for all frames.  track=True: the KinectFusion sequence -- frame 0 is integrated; every later
@@ -485,16 +750,29 @@ def fuse_pointmaps(pts_all, intrinsics, cam2world, valid, images=None, voxel_siz
     correction T (sp3_transform_points), its pose set to T @ pose, and only then integrated: one launch per frame.  The volume is
     still fitted to the points as predicted; the trunc padding absorbs the corrections.  return_poses adds to the mesh dict `poses`
     (the cam2world used, float64 [t, 4, 4]), `corrections` (the T of every frame) and `tracked` (a list of bool: frame 0, the model's own
-    frame, counts as tracked; all False without track)."""
+    frame, counts as tracked; all False without track).
+    bricks=True: the volume is a BrickTSDFVolume at voxel_size (required then) over the box of the valid points, or over
+    extent = (lo, hi) when given -- the points are then not consulted at all, which is what a stream needs; the mesh comes from
+    to_dense() of the allocated bricks' bounding box, which may have max(512, dims_max) voxels per axis."""
     pts_all = _dev(pts_all, "fuse_pointmaps: pts_all").float()
     if pts_all.dim() != 4 or pts_all.shape[-1] != 3 or _dev(valid, "fuse_pointmaps: valid").shape != pts_all.shape[:3]:
         raise RuntimeError("fuse_pointmaps: mismatched shapes: pts_all %s must be [t, h, w, 3], valid %s [t, h, w]" %
                            (tuple(pts_all.shape), tuple(valid.shape)))
     valid = valid.bool() & torch.isfinite(pts_all).all(-1)
-    if not bool(valid.any()):
+    if extent is not None and not bricks:
+        raise ValueError("fuse_pointmaps: extent is for bricks=True (the dense volume is fitted to the points)")
+    if bricks and voxel_size is None:
+        raise ValueError("fuse_pointmaps: bricks=True needs voxel_size")
+    if extent is None and not bool(valid.any()):
         raise RuntimeError("fuse_pointmaps: no valid point (nothing passes the confidence threshold)")
     color = color and images is not None
-    vol = volume_for_points(pts_all[valid], voxel_size, dims_max, trunc_voxels, color)
+    if not bricks:
+        vol = volume_for_points(pts_all[valid], voxel_size, dims_max, trunc_voxels, color)
+    else:
+        if extent is None:
+            sel = pts_all[valid]
+            extent = torch.stack([sel.amin(0), sel.amax(0)]).double().cpu().numpy()
+        vol = brick_volume_for_extent(extent, voxel_size, trunc_voxels, color, device=pts_all.device)
     t = pts_all.shape[0]
     poses = _host_mats(cam2world, t, (4, 4), "cam2world").copy()
     corrections, tracked = np.stack([np.eye(4)] * t), [bool(track)] + [False] * (t - 1)      # (frame 0 is the model's own frame)
@@ -503,16 +781,12 @@ def fuse_pointmaps(pts_all, intrinsics, cam2world, valid, images=None, voxel_siz
     else:
         K = _host_mats(intrinsics, t, (3, 3), "intrinsics")
         for i in range(t):
-            pts_i = pts_all[i]
+            poses[i], T, info = _fuse_frame(vol, pts_all[i], valid[i], K[i], poses[i], images[i] if color else None, i > 0, track_args)
             if i > 0:
-                T, info = track_frame(vol, pts_i, valid[i], K[i], poses[i], **(track_args or {}))
                 tracked[i] = bool(info["tracked"])
                 if tracked[i]:
-                    corrections[i], poses[i] = T, T @ poses[i]
-                    pts_i = _transform_points(pts_i, T)
-            vol.integrate(pts=pts_i[None], intrinsics=K[i], cam2world=poses[i:i + 1], valid=valid[i:i + 1],
-                          images=images[i:i + 1] if color else None)
-    out = vol.extract_mesh(min_weight, scale, transform)
+                    corrections[i] = T
+    out = vol.extract_mesh(min_weight, scale, transform, dims_limit=max(512, dims_max)) if bricks else vol.extract_mesh(min_weight, scale, transform)
     if return_poses:
         out.update(poses=poses, corrections=corrections, tracked=tracked)
     return (out, vol) if return_volume else out
