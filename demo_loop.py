@@ -163,6 +163,8 @@ def main():
                     "allocated where measurements land) instead of the dense one; needs --voxel_size.  With --stream --fused --bricks every "
                     "frame is posed on its own and pushed into a fusion.FusionSession as it arrives (with --vis a ray-cast picture every "
                     "--kf_every frames)")
+    ap.add_argument("--direct_mesh", action="store_true", help="with --fused --bricks: mesh the bricks themselves (marching tetrahedra on the "
+                    "pool, BrickTSDFVolume.extract_mesh(direct=True)) instead of densifying their bounding box first: no limit on the extent")
     ap.add_argument("--extent", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"), help="with --stream --fused "
                     "--bricks: the box the session may fuse in (default: a cube of +-4 units around the first camera)")
     ap.add_argument("--voxel_size", type=float, default=None, help="with --fused: voxel edge in the units of the pointmaps (default: the "
@@ -180,6 +182,8 @@ def main():
     args = ap.parse_args()
     if args.bricks and not (args.fused and args.voxel_size):
         ap.error("--bricks needs --fused and --voxel_size")
+    if args.direct_mesh and not args.bricks:
+        ap.error("--direct_mesh needs --bricks")
     cfg = TINY if args.tiny else FULL
     device = "cuda"
     model = Spann3R(dus3r_name=None, cfg=cfg, init_weights=False).to(device)      # demo.py:81-82
@@ -247,7 +251,8 @@ def main():
         With --track the frames are registered to the model first and the corrections are reported."""
         from spann3r_amd import fusion
         import numpy as np
-        kw = dict(conf_thresh=args.conf_thresh, return_volume=True, track=args.track, return_poses=args.track, bricks=args.bricks, **fuse_kw, **kw)
+        kw = dict(conf_thresh=args.conf_thresh, return_volume=True, track=args.track, return_poses=args.track, bricks=args.bricks,
+                  direct_mesh=args.direct_mesh, **fuse_kw, **kw)
         try:
             fm, vol = fusion.fuse_sequence(preds, batch, **kw)
         except RuntimeError as e:

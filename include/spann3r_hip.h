@@ -1066,6 +1066,43 @@ int sp3_tsdf_brick_raycast(const sp3_tsdf_view* views_host, const sp3_tsdf_view*
 int sp3_tsdf_brick_to_dense(int nx, int ny, int nz, const int32_t* table, const float* tsdf, const float* weight, const float* rgb,
                             const int32_t* lo3, const int32_t* size3, float* out_tsdf, float* out_weight, float* out_rgb, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Brick mesh extraction (spann3r_amd/fusion.py BrickTSDFVolume.extract_raw drives it; csrc/brick_mesh.hip): marching tetrahedra on
+ * the pool of "Brick TSDF volume" itself.  Work and scratch follow the allocated bricks: there is no dense intermediate and the
+ * extent of the virtual grid does not enter.  tests/brick_mesh_ref.py restates it in numpy.  The call does not allocate, free or
+ * synchronise; its only read-back is the caller's read of counts.  No atomics; no workgroup waits on another.
+ *
+ * sp3_tsdf_brick_extract: the rule of sp3_tsdf_extract ("TSDF fusion" above) on the densified volume of the WHOLE virtual grid --
+ *   absent voxels read tsdf 1, weight 0, so they are unobserved.  Taken from there word for word: observed (weight >= min_weight,
+ *   min_weight > 0) and inside (tsdf < 0); the corner code and the 6 Kuhn tetrahedra T0..T5; the 7 edge slots and their owner (the
+ *   endpoint with the lower coordinates); when a slot carries a vertex (the other endpoint lies in the grid, both are observed,
+ *   exactly one is inside -- whether or not a live cell uses the edge); t, the vertex formula and the colour formula (rgb null:
+ *   0xffffffff; rgba nullable); the face cases and their orientation; counts int32 [2] = the true V and F; nothing is written at or
+ *   beyond row max_vertices of vertices / rgba or row max_faces of faces (a face within capacity may name a vertex beyond it).
+ *   Two points differ:
+ *   Positions: voxel centres are the virtual grid's, origin_a + fp32(i_a) * voxel with i_a the index in the virtual grid -- the
+ *     centre sp3_tsdf_brick_integrate used, not the shifted origin a box of sp3_tsdf_brick_to_dense would give the dense kernel.
+ *   Order: by pool slot.  Vertices are written densely in (slot, place in the brick, edge slot) order, place = (k & 7) 64 +
+ *     (j & 7) 8 + (i & 7) as in the pool; faces in (slot of the brick of the cell's corner 0, place of corner 0, tetrahedron,
+ *     triangle) order.  Only a cell whose corner 0 lies in an allocated brick can be live and only an allocated voxel can own a
+ *     vertex, so the work set is the slots 0 .. n_bricks - 1 (n_bricks: the count the host read from counts2 of
+ *     sp3_tsdf_brick_alloc) and nothing else.  The output is deterministic: the same pool gives the same bits every call.
+ *   table, slot_brick and the pool are those of "Brick TSDF volume"; a table entry >= n_bricks counts as absent.  Vertex and face
+ *   indices are int32: 12 * 512 * n_bricks < 2^31, anything more is an error (checked before anything is launched).
+ *   n_bricks = 0 writes counts = (0, 0) and launches nothing else.
+ *   The launch structure is sp3_tsdf_extract's with a 256-voxel half brick as the scan tile (5 launches: one count of vertices and
+ *   faces, two single-workgroup scans, two scatters).  A workgroup looks up the 7 `+` neighbours of its brick once (outside the
+ *   grid or absent: unobserved) and stages the observed and inside bits of the 9 x 9 x 5 halo of its half brick in LDS; the edge
+ *   mask, a cell's inside byte and its liveness come from there.  ws: device scratch of sp3_tsdf_brick_extract_ws_bytes(n_bricks),
+ *   16-byte aligned: a 7-bit edge mask and one exclusive vertex offset per ALLOCATED voxel (5 * 512 * n_bricks bytes) and the two
+ *   tile tables; a face finds a vertex as offset[owner] + popcount(mask[owner] below its slot), the owner through
+ *   table -> slot -> slot * 512 + place. */
+int64_t sp3_tsdf_brick_extract_ws_bytes(int n_bricks);
+int sp3_tsdf_brick_extract(int nx, int ny, int nz, const float* origin3, float voxel, const int32_t* table, const int32_t* slot_brick,
+                           int n_bricks, const float* tsdf, const float* weight, const float* rgb, float min_weight, void* ws,
+                           int64_t max_vertices, int64_t max_faces, float* vertices, uint32_t* rgba, int32_t* faces, int32_t* counts,
+                           void* stream);
+
 /* small utilities */
 /* n (1..8) contiguous device-to-device copies in one launch; every copy 16-byte aligned and a multiple of 16 bytes.
  * (The sequence loop's per-frame bookkeeping -- torch .clone() / slice assignments around spann3r/model.py:523-531.) */

@@ -6,14 +6,14 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libspann3r_hip.so")
-SOURCES = ["error.cpp", "gemm.hip", "gemm_sm.hip", "norm_rope.hip", "attention.hip", "memory.hip", "dpt.hip", "conv.hip", "preproc.hip", "loss.hip", "train.hip", "train2.hip", "postproc.hip", "eval.hip", "render.hip", "mesh.hip", "views.hip", "fusion.hip", "raycast.hip", "bricks.hip"]
+SOURCES = ["error.cpp", "gemm.hip", "gemm_sm.hip", "norm_rope.hip", "attention.hip", "memory.hip", "dpt.hip", "conv.hip", "preproc.hip", "loss.hip", "train.hip", "train2.hip", "postproc.hip", "eval.hip", "render.hip", "mesh.hip", "views.hip", "fusion.hip", "raycast.hip", "bricks.hip", "brick_mesh.hip"]
 
 
 STAMP = LIB + ".srchash"
 
 
 def _deps():
-    return [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_sm.h"), os.path.join(CSRC, "scan.h"),
+    return [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_sm.h"), os.path.join(CSRC, "scan.h"), os.path.join(CSRC, "tets.h"),
                                                       os.path.join(HERE, "..", "include", "spann3r_hip.h"), os.path.abspath(__file__)]
 
 

@@ -9,12 +9,14 @@
 // sp3_tsdf_extract is two order-preserving compactions in the multi-launch form of csrc/scan.h (count per 256-element tile, one
 // single-workgroup scan, scatter): the surface vertices in (owner voxel, slot) order, then the faces in (cell, tetrahedron, triangle)
 // order.  A face finds a vertex by offset[owner] + popcount(mask[owner] below its slot): one byte and one int32 of scratch per voxel.
-// The 16 cases of a tetrahedron are generated at compile time from the rule in the header (make_cases); no table is copied.
+// The 16 cases of a tetrahedron are generated at compile time from the rule in the header (make_cases, csrc/tets.h); no table is
+// copied.
 //
 // Every fp32 operation of the projection, the running average and the interpolation is rounded on its own (no contraction into
 // FMAs): the file-level pragma below is what the compiler honours under its default -ffp-contract=fast-honor-pragmas.
 #include "common.h"
 #include "scan.h"
+#include "tets.h"
 #include <math.h>
 
 #pragma clang fp contract(off)
@@ -98,75 +100,7 @@ __global__ __launch_bounds__(BRICK_X * BRICK_Y * BRICK_Z) void k_tsdf_integrate(
 }
 
 // ------------------------------------------------------------------------------------------------ marching tetrahedra
-// Cube corner code c = dx + 2 dy + 4 dz.  The six tetrahedra of the Kuhn cut around the diagonal 0-7, each listed with positive
-// orientation, det(v1 - v0, v2 - v0, v3 - v0) > 0 (the header's table).
-__device__ const signed char TET[6][4] = {{0, 1, 3, 7}, {0, 5, 1, 7}, {0, 3, 2, 7}, {0, 2, 6, 7}, {0, 4, 5, 7}, {0, 6, 4, 7}};
-// slot of the edge whose endpoints differ by corner code c (1..7): +x, +y, +z, +x+y, +y+z, +x+z, +x+y+z
-__device__ const signed char SLOT_OF[8] = {-1, 0, 1, 3, 2, 5, 4, 6};
-__device__ const signed char SLOT_CODE[7] = {1, 2, 4, 3, 6, 5, 7};
-
-struct Cases {
-  signed char ntri[16];
-  signed char e[16][2][3][2];      // [case][triangle][corner of the triangle] = the tetrahedron edge (vertex, vertex) it lies on
-};
-
-constexpr bool even4(int a, int b, int c, int d) {
-  const int p[4] = {a, b, c, d};
-  int inv = 0;
-  for (int i = 0; i < 4; ++i)
-    for (int j = i + 1; j < 4; ++j) inv += p[i] > p[j];
-  return (inv & 1) == 0;
-}
-
-// The header's rule.  Bit m of the case = vertex m of the tetrahedron is inside.
-constexpr Cases make_cases() {
-  Cases t{};
-  for (int c = 0; c < 16; ++c) {
-    int in[4] = {0, 0, 0, 0}, out[4] = {0, 0, 0, 0}, ni = 0, no = 0;
-    for (int m = 0; m < 4; ++m) {
-      if ((c >> m) & 1) in[ni++] = m;
-      else out[no++] = m;
-    }
-    if (ni == 0 || ni == 4) continue;
-    if (ni == 2) {
-      const int m = in[0], n = in[1];
-      int q = out[0], r = out[1];
-      if (!even4(m, n, q, r)) {
-        const int s = q;
-        q = r;
-        r = s;
-      }
-      t.ntri[c] = 2;
-      const int quad[4][2] = {{m, q}, {m, r}, {n, r}, {n, q}};
-      const int pick[2][3] = {{0, 1, 2}, {0, 2, 3}};
-      for (int k = 0; k < 2; ++k)
-        for (int x = 0; x < 3; ++x) {
-          t.e[c][k][x][0] = (signed char)quad[pick[k][x]][0];
-          t.e[c][k][x][1] = (signed char)quad[pick[k][x]][1];
-        }
-    } else {
-      const int lone = ni == 1 ? in[0] : out[0];
-      const int* rest = ni == 1 ? out : in;
-      int a = rest[0], b = rest[1], d = rest[2];
-      bool swap = !even4(lone, a, b, d);
-      if (ni == 3) swap = !swap;      // the lone vertex is outside: the triangle turns round
-      if (swap) {
-        const int s = b;
-        b = d;
-        d = s;
-      }
-      t.ntri[c] = 1;
-      const int o[3] = {a, b, d};
-      for (int x = 0; x < 3; ++x) {
-        t.e[c][0][x][0] = (signed char)lone;
-        t.e[c][0][x][1] = (signed char)o[x];
-      }
-    }
-  }
-  return t;
-}
-__device__ const Cases CASES = make_cases();
-
+// The Kuhn cut, the edge slots and the 16 cases of a tetrahedron: csrc/tets.h.
 struct Grid {
   int nx, ny, nz;
   int64_t n;
@@ -199,11 +133,6 @@ __global__ __launch_bounds__(MB) void k_tsdf_edge_count(const float* __restrict_
   int total;
   block_excl_sum(__popc(m), total);
   if (threadIdx.x == 0) counts[blockIdx.x] = total;
-}
-
-__device__ __forceinline__ unsigned unorm8(float c) {      // sp3_pack_rgba8's channel: floor(c * 255 + 0.5), clamped; NaN gives 0
-  const float s = floorf(c * 255.0f + 0.5f);
-  return s >= 255.0f ? 255u : (s > 0.0f ? (unsigned)s : 0u);
 }
 
 __global__ __launch_bounds__(MB) void k_tsdf_vertex_scatter(const float* __restrict__ tsdf, const float* __restrict__ rgb, Grid g,

@@ -21,6 +21,7 @@ from . import lib as L
 from . import mesh as M
 
 INDEX_LIMIT = (2 ** 31 - 1) // 7        # voxels: 7 n < 2^31 (int32 vertex indices, 7 edge slots per voxel)
+BRICK_MESH_LIMIT = (2 ** 31 - 1) // (12 * 512)      # bricks: 12 * 512 n_bricks < 2^31 (sp3_tsdf_brick_extract's int32 indices)
 
 
 def _dev(x, name):
@@ -324,8 +325,8 @@ class BrickTSDFVolume:
     (metric, default trunc, at most 8 voxels) of a measured point -- and a pool of `capacity` bricks that doubles when it runs out.
     Memory follows the surface, not the box, and the extent need not be known: give a generous box.  An allocated voxel holds the
     bits the dense volume gives it after the same frames; a brick born in a later call does not hold what earlier frames would have
-    given it.  `integrate`, `frame_table`, `raycast`, `view_table` and `raycast_table` take and return what TSDFVolume's do;
-    `track_frame` takes a brick volume as it is."""
+    given it.  `integrate`, `frame_table`, `raycast`, `view_table`, `raycast_table` and `extract_raw` take and return what
+    TSDFVolume's do; `track_frame` takes a brick volume as it is.  `extract_mesh(direct=True)` meshes the bricks themselves."""
 
     def __init__(self, origin, voxel_size, dims, trunc=None, band=None, color=True, capacity=4096, device="cuda"):
         dims = tuple(int(d) for d in dims)
@@ -377,6 +378,7 @@ class BrickTSDFVolume:
         self.tsdf = torch.empty((capacity, 512), dtype=torch.float32, device=dev)
         self.weight = torch.empty((capacity, 512), dtype=torch.float32, device=dev)
         self.rgb = torch.empty((capacity, 512, 3), dtype=torch.float32, device=dev) if self.color else None
+        self._mesh_ws = None                # extract_raw's scratch: sized for the pool, so it goes with it
 
     def reset(self):
         self.table.fill_(-1)
@@ -386,8 +388,9 @@ class BrickTSDFVolume:
 
     @property
     def memory_bytes(self):
-        """bytes held on the device: table, flags, slot_brick and the pool"""
+        """bytes held on the device: table, flags, slot_brick, the pool and, once extract_raw has run, its scratch"""
         ts = [self.table, self.flags, self.slot_brick, self.tsdf, self.weight, self.count, self._counts, self._ws] + ([self.rgb] if self.color else [])
+        ts += [self._mesh_ws] if self._mesh_ws is not None else []
         return sum(t.numel() * t.element_size() for t in ts)
 
     # the argument handling, the frame and view descriptors are TSDFVolume's own (they use self.rgb and self.device only)
@@ -498,10 +501,42 @@ class BrickTSDFVolume:
                                                  L.ptr(out.rgb), L.stream_ptr()), "sp3_tsdf_brick_to_dense")
         return out
 
-    def extract_mesh(self, min_weight=1.0, scale=1.0, transform=None, dims_limit=512):
-        """to_dense().extract_mesh(...): the surface of the allocated bricks' bounding box (marching tetrahedra on the bricks
-        themselves is not there yet)"""
-        return self.to_dense(dims_limit=dims_limit).extract_mesh(min_weight, scale, transform)
+    def extract_raw(self, min_weight=1.0, max_vertices=None, max_faces=None):
+        """sp3_tsdf_brick_extract as it is, on the bricks themselves: -> the tuple of TSDFVolume.extract_raw (vertices fp32 [cap, 3],
+        rgba int32 [cap], faces int32 [cap, 3], counts int32 [2] on the device = the true V and F), in pool-slot order, positions by
+        the virtual grid's own origin.  The first guesses of the capacities are TSDFVolume's with n = 512 * n_bricks.  The scratch
+        (5 bytes per allocated voxel) is kept on the volume and regrown with the pool.  Nothing beyond the capacities is written;
+        nothing synchronises."""
+        if self.n_bricks > BRICK_MESH_LIMIT:
+            raise ValueError("extract_raw: %d bricks over the index limit: 12 * 512 * n_bricks must stay below 2^31 (int32 vertex and face "
+                             "indices), at most %d bricks" % (self.n_bricks, BRICK_MESH_LIMIT))
+        n = 512 * self.n_bricks
+        lib = L.load()
+        cap_v = int(max_vertices) if max_vertices is not None else min(7 * n, max(4096, n // 4))
+        cap_f = int(max_faces) if max_faces is not None else min(12 * n, 2 * cap_v)
+        vertices = torch.empty((max(cap_v, 1), 3), dtype=torch.float32, device=self.device)
+        rgba = torch.empty(max(cap_v, 1), dtype=torch.int32, device=self.device)
+        faces = torch.empty((max(cap_f, 1), 3), dtype=torch.int32, device=self.device)
+        counts = torch.zeros(2, dtype=torch.int32, device=self.device)
+        if self._mesh_ws is None:
+            self._mesh_ws = torch.empty(max(int(lib.sp3_tsdf_brick_extract_ws_bytes(min(self.capacity, BRICK_MESH_LIMIT))), 16), dtype=torch.uint8,
+                                        device=self.device)
+        nx, ny, nz = self.dims
+        L.check(lib.sp3_tsdf_brick_extract(nx, ny, nz, self._origin_c, self.voxel_size, self.table.data_ptr(), self.slot_brick.data_ptr(),
+                                           self.n_bricks, self.tsdf.data_ptr(), self.weight.data_ptr(), L.ptr(self.rgb), float(min_weight),
+                                           self._mesh_ws.data_ptr(), cap_v, cap_f, vertices.data_ptr(), rgba.data_ptr(), faces.data_ptr(),
+                                           counts.data_ptr(), L.stream_ptr()), "sp3_tsdf_brick_extract")
+        return vertices[:cap_v], rgba[:cap_v], faces[:cap_f], counts
+
+    def extract_mesh(self, min_weight=1.0, scale=1.0, transform=None, dims_limit=512, direct=False):
+        """direct=False: to_dense().extract_mesh(...), the surface of the allocated bricks' bounding box through the dense kernel (a box
+        of more than dims_limit voxels on an axis raises).  direct=True: marching tetrahedra on the bricks themselves
+        (sp3_tsdf_brick_extract) -- no dense intermediate, no limit on the extent, dims_limit ignored; the same surface as a set of
+        triangles, its vertices and faces in pool-slot order and its positions from the virtual grid's own origin (the dense route
+        places them from the box's).  Capacities, the one retry and the dict are TSDFVolume.extract_mesh's."""
+        if not direct:
+            return self.to_dense(dims_limit=dims_limit).extract_mesh(min_weight, scale, transform)
+        return TSDFVolume.extract_mesh(self, min_weight, scale, transform)
 
 
 def _extent_box(extent):
@@ -704,21 +739,21 @@ class FusionSession:
         """BrickTSDFVolume.raycast of the model so far"""
         return self.volume.raycast(intrinsics, cam2world, size, **kw)
 
-    def mesh(self, min_weight=1.0, scale=1.0, transform=None, dims_limit=512):
-        """BrickTSDFVolume.extract_mesh of the model so far"""
-        return self.volume.extract_mesh(min_weight, scale, transform, dims_limit)
+    def mesh(self, min_weight=1.0, scale=1.0, transform=None, dims_limit=512, direct=False):
+        """BrickTSDFVolume.extract_mesh of the model so far (direct=True: meshed on the bricks, whatever the extent)"""
+        return self.volume.extract_mesh(min_weight, scale, transform, dims_limit, direct)
 
 
 def fuse_sequence(preds, batch, conf_thresh=1e-3, voxel_size=None, dims_max=256, trunc_voxels=3.0, min_weight=1.0, scale=1.0,
                   transform=None, color=True, return_volume=False, focal=None, poses=None, track=False, return_poses=False, bricks=False,
-                  extent=None):
+                  extent=None, direct_mesh=False):
     """The fused surface of a reconstruction from model.forward's `preds` and its `batch`: demo.py's own sequence -- the stacked
     pointmaps (mesh.sequence_tensors), the focal of frame 0 (estimate_focal_knowing_depth), one pose per frame (estimate_poses) --
     then the pointmaps of the pixels with (conf - 1) / conf > conf_thresh integrated through the `pts` path into a volume around
     the confident points.  -> the mesh dict of TSDFVolume.extract_mesh (and the volume with return_volume).
     focal / poses (cam2world [t, 4, 4]) given: used instead of the estimates.  track / return_poses: as fuse_pointmaps (every frame
-    after the first is registered to the model before it is integrated).  bricks / extent: as fuse_pointmaps (a BrickTSDFVolume at
-    voxel_size instead of the dense volume).  Pointmaps without geometry (seeded random weights)
+    after the first is registered to the model before it is integrated).  bricks / extent / direct_mesh: as fuse_pointmaps (a
+    BrickTSDFVolume at voxel_size instead of the dense volume).  Pointmaps without geometry (seeded random weights)
     give a focal near 0: that raises rather than fusing through meaningless cameras."""
     from .postprocess import estimate_focal_knowing_depth, estimate_poses
     pts_all, images_all, conf_all = M.sequence_tensors(preds, batch)
@@ -737,12 +772,12 @@ def fuse_sequence(preds, batch, conf_thresh=1e-3, voxel_size=None, dims_max=256,
     valid = (conf_all - 1) / conf_all > conf_thresh
     K = np.array([[focal, 0, pp[0]], [0, focal, pp[1]], [0, 0, 1]], np.float64)
     return fuse_pointmaps(pts_all, K, np.asarray(poses, np.float64), valid, images_all, voxel_size, dims_max, trunc_voxels, min_weight, scale,
-                          transform, color, return_volume, track, return_poses, bricks=bricks, extent=extent)
+                          transform, color, return_volume, track, return_poses, bricks=bricks, extent=extent, direct_mesh=direct_mesh)
 
 
 def fuse_pointmaps(pts_all, intrinsics, cam2world, valid, images=None, voxel_size=None, dims_max=256, trunc_voxels=3.0, min_weight=1.0,
                    scale=1.0, transform=None, color=True, return_volume=False, track=False, return_poses=False, track_args=None,
-                   bricks=False, extent=None):
+                   bricks=False, extent=None, direct_mesh=False):
     """World pointmaps pts_all [t, h, w, 3] with their cameras, integrated through the `pts` path into a volume around the valid
     (and finite) points -> the mesh dict of TSDFVolume.extract_mesh (and the volume with return_volume).
     track=False: one integrate launch for all frames.  track=True: the KinectFusion sequence -- frame 0 is integrated; every later
@@ -753,7 +788,8 @@ def fuse_pointmaps(pts_all, intrinsics, cam2world, valid, images=None, voxel_siz
     frame, counts as tracked; all False without track).
     bricks=True: the volume is a BrickTSDFVolume at voxel_size (required then) over the box of the valid points, or over
     extent = (lo, hi) when given -- the points are then not consulted at all, which is what a stream needs; the mesh comes from
-    to_dense() of the allocated bricks' bounding box, which may have max(512, dims_max) voxels per axis."""
+    to_dense() of the allocated bricks' bounding box, which may have max(512, dims_max) voxels per axis, or with direct_mesh=True
+    from the bricks themselves (BrickTSDFVolume.extract_mesh(direct=True): no such limit)."""
     pts_all = _dev(pts_all, "fuse_pointmaps: pts_all").float()
     if pts_all.dim() != 4 or pts_all.shape[-1] != 3 or _dev(valid, "fuse_pointmaps: valid").shape != pts_all.shape[:3]:
         raise RuntimeError("fuse_pointmaps: mismatched shapes: pts_all %s must be [t, h, w, 3], valid %s [t, h, w]" %
@@ -761,6 +797,8 @@ def fuse_pointmaps(pts_all, intrinsics, cam2world, valid, images=None, voxel_siz
     valid = valid.bool() & torch.isfinite(pts_all).all(-1)
     if extent is not None and not bricks:
         raise ValueError("fuse_pointmaps: extent is for bricks=True (the dense volume is fitted to the points)")
+    if direct_mesh and not bricks:
+        raise ValueError("fuse_pointmaps: direct_mesh is for bricks=True (the dense volume has one extraction)")
     if bricks and voxel_size is None:
         raise ValueError("fuse_pointmaps: bricks=True needs voxel_size")
     if extent is None and not bool(valid.any()):
@@ -786,7 +824,10 @@ def fuse_pointmaps(pts_all, intrinsics, cam2world, valid, images=None, voxel_siz
                 tracked[i] = bool(info["tracked"])
                 if tracked[i]:
                     corrections[i] = T
-    out = vol.extract_mesh(min_weight, scale, transform, dims_limit=max(512, dims_max)) if bricks else vol.extract_mesh(min_weight, scale, transform)
+    if bricks:
+        out = vol.extract_mesh(min_weight, scale, transform, dims_limit=max(512, dims_max), direct=direct_mesh)
+    else:
+        out = vol.extract_mesh(min_weight, scale, transform)
     if return_poses:
         out.update(poses=poses, corrections=corrections, tracked=tracked)
     return (out, vol) if return_volume else out
