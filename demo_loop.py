@@ -165,6 +165,10 @@ def main():
                     "--kf_every frames)")
     ap.add_argument("--direct_mesh", action="store_true", help="with --fused --bricks: mesh the bricks themselves (marching tetrahedra on the "
                     "pool, BrickTSDFVolume.extract_mesh(direct=True)) instead of densifying their bounding box first: no limit on the extent")
+    ap.add_argument("--min_component", type=int, default=0, metavar="N", help="with --fused: drop the floaters -- connected components of the "
+                    "fused mesh with fewer than N faces (mesh.filter_components' rule, on the device) -- from --save_glb, --vis' fused.png and "
+                    "the fused --eval line; prints how many components and faces went")
+    ap.add_argument("--largest_component", action="store_true", help="with --fused: keep only the connected component with the most faces")
     ap.add_argument("--extent", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"), help="with --stream --fused "
                     "--bricks: the box the session may fuse in (default: a cube of +-4 units around the first camera)")
     ap.add_argument("--voxel_size", type=float, default=None, help="with --fused: voxel edge in the units of the pointmaps (default: the "
@@ -184,6 +188,10 @@ def main():
         ap.error("--bricks needs --fused and --voxel_size")
     if args.direct_mesh and not args.bricks:
         ap.error("--direct_mesh needs --bricks")
+    if (args.min_component or args.largest_component) and not args.fused:
+        ap.error("--min_component / --largest_component need --fused")
+    if args.min_component < 0:
+        ap.error("--min_component must be >= 0")
     cfg = TINY if args.tiny else FULL
     device = "cuda"
     model = Spann3R(dus3r_name=None, cfg=cfg, init_weights=False).to(device)      # demo.py:81-82
@@ -243,7 +251,14 @@ def main():
         print("Time: %.4f s, FPS: %.1f  (%d frames, call %d: %s)" %
               (end - start, len(batch) / (end - start), len(batch), it,
                ["eager warm-up", "hipGraph capture", "hipGraph replay"][min(it, 2)]))
-    fuse_kw = dict(voxel_size=args.voxel_size, trunc_voxels=args.trunc_voxels)
+    fuse_kw = dict(voxel_size=args.voxel_size, trunc_voxels=args.trunc_voxels, min_component_faces=args.min_component,
+                   keep_largest=1 if args.largest_component else None)
+
+    def report_components(what, fm):
+        c = fm.get("components")
+        if c is not None:
+            print("%s: %d connected components, %d kept; %d components and %d faces removed" %
+                  (what, c["total"], c["kept"], c["total"] - c["kept"], c["faces_removed"]))
 
     def fused_prediction(**kw):
         """fusion.fuse_sequence of this run (demo.py's focal and poses) -> (mesh, volume); pointmaps without geometry (no checkpoint
@@ -266,6 +281,7 @@ def main():
             ang = [math.degrees(math.acos(min(max((np.trace(t[:3, :3]) - 1) * 0.5, -1.0), 1.0))) for t in T]
             print("%d frames tracked of %d; largest correction %.3f degrees, %.3f voxels" %
                   (sum(fm["tracked"][1:]), len(T), max(ang, default=0.0), max((np.linalg.norm(t[:3, 3]) for t in T), default=0.0) / vol.voxel_size))
+        report_components("fused surface", fm)
         return fm, vol
 
     if args.eval:                                                                 # eval.py:128-221
@@ -281,6 +297,8 @@ def main():
             gt_mesh = fusion.fuse_views(batch, **fuse_kw)
             pred_mesh = fusion.fuse_pointmaps(a["pts_all"], torch.cat([v["camera_intrinsics"] for v in batch]),
                                               torch.cat([v["camera_pose"] for v in batch]), a["masks_all"], a["images_all"], **fuse_kw)
+            report_components("fused ground truth", gt_mesh)
+            report_components("fused prediction", pred_mesh)
             rf = evaluate_reconstruction(pred_mesh["vertices"], gt_mesh["vertices"], threshold=0.1)
             print("Fused: Acc: %s, Comp: %s, NC1: %s, NC2: %s  (prediction %d vertices / %d faces, ground truth %d vertices / %d faces)" %
                   (rf["acc"], rf["comp"], rf["nc1"], rf["nc2"], pred_mesh["vertices"].shape[0], pred_mesh["faces"].shape[0],
@@ -345,6 +363,9 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.save_glb)), exist_ok=True)
         if args.fused:
             fm, _ = fused_prediction(scale=mesh.SCALE, transform=mesh.TRANSFORM)      # app.py's x10 and axis flip, as export_glb
+            if fm["faces"].shape[0] == 0 and fm.get("components", {}).get("total", 0) > 0:
+                raise RuntimeError("--fused: --min_component %d%s removed every one of the %d components of the surface" %
+                                   (args.min_component, " / --largest_component" if args.largest_component else "", fm["components"]["total"]))
             if fm["faces"].shape[0] == 0:
                 raise RuntimeError("--fused: the volume holds no surface (nothing passes conf_thresh %g with weight >= 1)" % args.conf_thresh)
             size = mesh.write_glb(args.save_glb, fm["vertices"], fm["colors"], fm["faces"], bounds=fm["bounds"])

@@ -1103,6 +1103,59 @@ int sp3_tsdf_brick_extract(int nx, int ny, int nz, const float* origin3, float v
                            int64_t max_vertices, int64_t max_faces, float* vertices, uint32_t* rgba, int32_t* faces, int32_t* counts,
                            void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh components (spann3r_amd/mesh.py components / filter_components drive these; csrc/mesh_components.hip): the connected pieces
+ * of an indexed triangle mesh, so that the specks of a fused surface can be dropped on the device.  tests/mesh_components_ref.py
+ * restates the rule in numpy.  No entry point allocates, frees or synchronises; `ws` is caller-provided device scratch of the
+ * matching sp3_*_ws_bytes(), 16-byte aligned.  Indices are int32: nverts, nfaces and ncomponents must stay below 2^31 - 1 (checked
+ * before anything is launched).  All outputs are integers and functions of the graph alone: two runs give the same bits, and a
+ * permuted face list gives the same vertex_component and the face_component permuted alike.
+ *
+ * The rule.  Vertices 0..V-1, faces int32 [F, 3].  A face is VALID when its three indices lie in 0..V-1; an invalid face is never
+ *   dereferenced and counts nowhere but in info[1].  Two vertices are connected when a valid face names both -- vertex connectivity,
+ *   so two fans that touch in one vertex are ONE component.  (Open3D's cluster_connected_triangles joins triangles across shared
+ *   EDGES only and would report those fans as two clusters; on a mesh where every contact is along an edge the two agree.  Parity
+ *   with it is unpinned: Open3D is not available to test against.)  A COMPONENT is a connectivity class with at least one valid
+ *   face; a vertex that no valid face names belongs to none.  Components are numbered 0..C-1 by ascending smallest vertex index.
+ *   A degenerate face (a == b) and a duplicated face are valid and count.
+ * sp3_mesh_components :
+ *   vertex_component int32 [V] = the component of the vertex, -1 for a vertex no valid face names;
+ *   face_component int32 [F] = the component of the face's vertices, -1 for an invalid face;
+ *   component_faces, component_vertices int32 [C] = valid faces and vertices per component; nothing is written at or beyond entry
+ *     max_components of either (both may be null when max_components = 0);
+ *   info int32 [2] = (C, the number of invalid faces): the true C, whatever the capacity.
+ *   F = 0 or V = 0: C = 0, every vertex -1, every face -1 and invalid when V = 0.
+ *   Labelling is a lock-free union-find with the root as the smallest index.  parent[v] = v at the start (a launch of its own);
+ *   per valid face one lane hooks (a, b) and (a, c): find both roots, atomicCAS(&parent[hi], hi, lo) with hi the larger root and lo
+ *   the smaller, on failure continue from the value the CAS returned; a later launch flattens, label[v] = find(v).  (Two vertices
+ *   whose parent entries are equal hang under one vertex already: that hook ends there.)  Invariants:
+ *   - parent[v] <= v always and an entry only ever decreases; every write to parent after the first launch is an agent-scope
+ *     atomicCAS or atomicMin (the latter shortcuts a hooked vertex to the root just found).  Every chain walk therefore strictly
+ *     descends and ends after at most v steps, a failed CAS restarts from a strictly smaller index, no input makes a lane loop
+ *     without end, and no lane ever waits for another lane's store.  Trees only merge, and the root of a tree is its smallest vertex.
+ *   - invalid faces are dropped before any walk starts: an index outside 0..V-1 never starts or extends a walk.
+ *   - the L2s of the XCDs are not coherent and a CU's L1 is never refreshed: inside the hooking launch parent is read with
+ *     agent-scope atomic loads, and the result does not depend on their freshness -- a load returns a value the entry held at some
+ *     time, the vertex itself or a smaller vertex of its tree; a stale self-pointer only makes the next CAS fail, and the CAS
+ *     returns the true value.  Launch boundaries are the only other hand-offs.
+ *   - faces and vertices per root are counted with integer atomicAdd (deterministic), aggregated in the wave first because a
+ *     typical mesh has nearly all faces in ONE component: peel by the first active lane's label, ballot the lanes that share it,
+ *     one add of the popcount; at most 64 rounds.
+ *   - dense ids: roots with a non-zero face count are flagged, counted per 256-vertex tile, scanned (one workgroup) and scattered.
+ *   8 launches.  ws: four int32 per vertex (parent, the two counts, root -> id) and the tile table.
+ * sp3_mesh_select_faces : face i is kept when c = face_component[i] lies in 0..ncomponents-1 and keep[c] != 0 (keep: device
+ *   uint8 [ncomponents]); the kept rows of faces are written densely, in their original order and with their indices unchanged, to
+ *   out_faces (room for nfaces rows); count[0] = the number kept.  Count per 256-face tile, scan, scatter.  The vertices then go
+ *   through sp3_mesh_compact_vertices(faces = out_faces), which rewrites the indices and drops what nothing references.
+ *   nfaces = 0 or ncomponents = 0 writes count = 0 and nothing else. */
+int64_t sp3_mesh_components_ws_bytes(int64_t nverts);
+int sp3_mesh_components(const int32_t* faces, int64_t nfaces, int64_t nverts, void* ws, int64_t max_components,
+                        int32_t* vertex_component, int32_t* face_component, int32_t* component_faces, int32_t* component_vertices,
+                        int32_t* info, void* stream);
+int64_t sp3_mesh_select_faces_ws_bytes(int64_t nfaces);
+int sp3_mesh_select_faces(const int32_t* faces, const int32_t* face_component, int64_t nfaces, const uint8_t* keep, int64_t ncomponents,
+                          void* ws, int32_t* out_faces, int32_t* count, void* stream);
+
 /* small utilities */
 /* n (1..8) contiguous device-to-device copies in one launch; every copy 16-byte aligned and a multiple of 16 bytes.
  * (The sequence loop's per-frame bookkeeping -- torch .clone() / slice assignments around spann3r/model.py:523-531.) */

@@ -85,6 +85,113 @@ def compact_vertices(pts, rgba=None, faces=None, valid=None, conf=None, conf_thr
     return out_pos[:v], None if out_rgba is None else out_rgba[:v], host[2:8].reshape(2, 3).copy()
 
 
+def _components_raw(lib, faces, n_vertices, cap):
+    dev, nf = faces.device, faces.shape[0]
+    out = dict(vertex_component=torch.empty(n_vertices, dtype=torch.int32, device=dev),
+               face_component=torch.empty(nf, dtype=torch.int32, device=dev),
+               component_faces=torch.empty(max(cap, 1), dtype=torch.int32, device=dev),
+               component_vertices=torch.empty(max(cap, 1), dtype=torch.int32, device=dev))
+    info = torch.zeros(2, dtype=torch.int32, device=dev)
+    ws = _ws(lib.sp3_mesh_components_ws_bytes(n_vertices), dev)
+    L.check(lib.sp3_mesh_components(faces.data_ptr(), nf, n_vertices, ws.data_ptr(), cap, out["vertex_component"].data_ptr(),
+                                    out["face_component"].data_ptr(), out["component_faces"].data_ptr(),
+                                    out["component_vertices"].data_ptr(), info.data_ptr(), L.stream_ptr()), "sp3_mesh_components")
+    return out, info
+
+
+def components(faces, n_vertices):
+    """sp3_mesh_components: the connected pieces of the mesh faces int32 [F, 3] over vertices 0..n_vertices-1, by vertex
+    connectivity (include/spann3r_hip.h "Mesh components").  -> dict(vertex_component int32 [V] (-1: no valid face names the vertex),
+    face_component int32 [F] (-1: a face with an index outside 0..V-1), component_faces / component_vertices int32 [C], on the
+    device; n_components, invalid_faces: ints).  Components are numbered by ascending smallest vertex.  One host read (C and the
+    invalid count); if the first guess of the capacity for C was short the call runs once more at the reported size.  F = 0 or
+    V = 0 returns empties (every face invalid when V = 0) and launches nothing."""
+    faces = _dev(faces, "components: faces")
+    n_vertices = int(n_vertices)
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise RuntimeError("components: faces must be int32 [F, 3], got %s %s" % (faces.dtype, tuple(faces.shape)))
+    if not 0 <= n_vertices < 2 ** 31 - 1 or faces.shape[0] >= 2 ** 31 - 1:
+        raise ValueError("components: %d vertices, %d faces: both must stay below 2^31 - 1 (int32 indices)" % (n_vertices, faces.shape[0]))
+    dev, nf = faces.device, faces.shape[0]
+    if nf == 0 or n_vertices == 0:
+        empty = torch.empty(0, dtype=torch.int32, device=dev)
+        return dict(vertex_component=torch.full((n_vertices,), -1, dtype=torch.int32, device=dev),
+                    face_component=torch.full((nf,), -1, dtype=torch.int32, device=dev), component_faces=empty,
+                    component_vertices=empty.clone(), n_components=0, invalid_faces=nf)
+    faces = faces.contiguous()
+    lib = L.load()
+    cap = min(n_vertices, max(4096, n_vertices // 16))
+    out, info = _components_raw(lib, faces, n_vertices, cap)
+    c, invalid = info.cpu().tolist()
+    if c > cap:
+        out, info = _components_raw(lib, faces, n_vertices, c)
+        c2, invalid = info.cpu().tolist()
+        if c2 != c:
+            raise RuntimeError("components: the faces changed between two runs (%d -> %d components)" % (c, c2))
+    out["component_faces"], out["component_vertices"] = out["component_faces"][:c], out["component_vertices"][:c]
+    out.update(n_components=c, invalid_faces=invalid)
+    return out
+
+
+def keep_mask(component_faces, min_faces=0, keep_largest=None):
+    """The selection rule of filter_components on the host: component_faces (array of C counts) -> bool [C].  A component is kept when
+    it has at least min_faces faces and, with keep_largest = k, is among the first k in the order (faces descending, id ascending)."""
+    cf = np.asarray(component_faces, np.int64).reshape(-1)
+    keep = cf >= int(min_faces)
+    if keep_largest is not None:
+        k = int(keep_largest)
+        if k < 0:
+            raise ValueError("keep_largest must be >= 0, got %r" % (keep_largest,))
+        first = np.zeros(len(cf), bool)
+        first[np.lexsort((np.arange(len(cf)), -cf))[:k]] = True
+        keep &= first
+    return keep
+
+
+def select_components(faces, n_vertices, min_faces=0, keep_largest=None):
+    """components + keep_mask + sp3_mesh_select_faces: -> (the faces of the kept components int32 [K, 3], in their original order and
+    with their indices unchanged; dict(total, kept, faces_removed)).  Faces with an index outside 0..n_vertices-1 are removed too.
+    Host reads: the one of `components` and the component_faces that rank the components."""
+    comp = components(faces, n_vertices)
+    nf, c = faces.shape[0], comp["n_components"]
+    cf = comp["component_faces"].cpu().numpy().astype(np.int64)
+    keep = keep_mask(cf, min_faces, keep_largest)
+    kept_faces = int(cf[keep].sum())
+    stats = dict(total=c, kept=int(keep.sum()), faces_removed=nf - kept_faces)
+    if kept_faces == 0:
+        return faces.new_empty((0, 3)), stats
+    lib = L.load()
+    faces = faces.contiguous()
+    keep_d = torch.from_numpy(keep.astype(np.uint8)).to(faces.device)
+    out = torch.empty((nf, 3), dtype=torch.int32, device=faces.device)
+    count = torch.zeros(1, dtype=torch.int32, device=faces.device)
+    ws = _ws(lib.sp3_mesh_select_faces_ws_bytes(nf), faces.device)
+    L.check(lib.sp3_mesh_select_faces(faces.data_ptr(), comp["face_component"].data_ptr(), nf, keep_d.data_ptr(), c,
+                                      ws.data_ptr(), out.data_ptr(), count.data_ptr(), L.stream_ptr()), "sp3_mesh_select_faces")
+    return out[:kept_faces], stats              # (the count the kernel reports is the sum of the kept components' faces)
+
+
+def filter_components(m, min_faces=0, keep_largest=None):
+    """Drop the floaters of a mesh: m is the dict scene_mesh / extract_mesh return (vertices fp32 [V, 3], colors uint8 [V, 4], faces
+    int32 [F, 3], on the device).  A component (vertex connectivity) is kept when it has at least min_faces faces and, with
+    keep_largest = k, is among the first k in the order (faces descending, id ascending).  -> the same kind of dict -- vertices, colors,
+    faces, bounds recomputed -- plus components = dict(total, kept, faces_removed).  Kept faces and vertices stay in their original
+    relative order, positions and colours bit for bit; everything removed gives an empty mesh, not an error."""
+    if m.get("faces") is None:
+        raise ValueError("filter_components: a point cloud has no faces to connect")
+    vertices, faces = _dev(m["vertices"], "filter_components: vertices").float().contiguous(), _dev(m["faces"], "filter_components: faces")
+    colors = m["colors"].contiguous()
+    if colors.dtype != torch.uint8 or colors.shape != (vertices.shape[0], 4):
+        raise RuntimeError("filter_components: colors must be uint8 [V, 4], got %s %s" % (colors.dtype, tuple(colors.shape)))
+    kept, stats = select_components(faces, vertices.shape[0], min_faces, keep_largest)
+    # (`kept` is select_components' own buffer, never the caller's faces: compact_vertices may rewrite its indices in place)
+    pos, col, bounds = compact_vertices(vertices, colors.view(torch.int32).reshape(-1), faces=kept)
+    out = {k: v for k, v in m.items() if k not in ("vertices", "colors", "faces", "bounds", "components")}
+    out.update(vertices=pos, colors=col.contiguous().view(torch.uint8).reshape(-1, 4), faces=kept[:0] if pos.shape[0] == 0 else kept,
+               bounds=bounds, components=stats)
+    return out
+
+
 def pts3d_to_mesh(img, pts3d, valid=None):
     """app.py:68-105 (pts3d_to_trimesh) for device tensors img, pts3d [h, w, 3] and valid bool [h, w]: dict(vertices [h w, 3],
     faces int64 [F, 3], face_colors [F, 3]) with the reference's order: four blocks (tl, tr, bl), (bl, tr, tl), (tr, bl, br), (br, bl, tr),
