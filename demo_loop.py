@@ -169,6 +169,10 @@ def main():
                     "fused mesh with fewer than N faces (mesh.filter_components' rule, on the device) -- from --save_glb, --vis' fused.png and "
                     "the fused --eval line; prints how many components and faces went")
     ap.add_argument("--largest_component", action="store_true", help="with --fused: keep only the connected component with the most faces")
+    ap.add_argument("--simplify", type=float, default=None, metavar="CELL", help="simplify the mesh by vertex clustering on a grid of CELL, in "
+                    "the units of the pointmaps (mesh.simplify, on the device): with --fused the fused surface, after --min_component; with "
+                    "--save_glb alone the per-frame sheets, which it welds into one vertex set; prints the faces before and after")
+    ap.add_argument("--simplify_voxels", type=float, default=None, metavar="K", help="with --fused: --simplify with a cell of K voxels")
     ap.add_argument("--extent", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"), help="with --stream --fused "
                     "--bricks: the box the session may fuse in (default: a cube of +-4 units around the first camera)")
     ap.add_argument("--voxel_size", type=float, default=None, help="with --fused: voxel edge in the units of the pointmaps (default: the "
@@ -192,6 +196,15 @@ def main():
         ap.error("--min_component / --largest_component need --fused")
     if args.min_component < 0:
         ap.error("--min_component must be >= 0")
+    if args.simplify_voxels is not None and not args.fused:
+        ap.error("--simplify_voxels needs --fused (a voxel size)")
+    if args.simplify is not None and not (args.fused or args.save_glb):
+        ap.error("--simplify needs --fused or --save_glb (a mesh to simplify)")
+    if args.simplify is not None and args.simplify_voxels is not None:
+        ap.error("--simplify and --simplify_voxels exclude each other")
+    for name in ("simplify", "simplify_voxels"):
+        if getattr(args, name) is not None and not (getattr(args, name) > 0 and math.isfinite(getattr(args, name))):
+            ap.error("--%s must be positive and finite" % name)
     cfg = TINY if args.tiny else FULL
     device = "cuda"
     model = Spann3R(dus3r_name=None, cfg=cfg, init_weights=False).to(device)      # demo.py:81-82
@@ -253,6 +266,17 @@ def main():
                ["eager warm-up", "hipGraph capture", "hipGraph replay"][min(it, 2)]))
     fuse_kw = dict(voxel_size=args.voxel_size, trunc_voxels=args.trunc_voxels, min_component_faces=args.min_component,
                    keep_largest=1 if args.largest_component else None)
+    if args.simplify is not None:
+        fuse_kw["simplify_cell"] = args.simplify
+    elif args.simplify_voxels is not None and args.voxel_size:
+        fuse_kw["simplify_cell"] = args.simplify_voxels * args.voxel_size
+
+    def report_simplify(what, fm):
+        s = fm.get("simplify")
+        if s is not None:
+            print("%s: simplified on a grid of %g: %d faces -> %d (%d collapsed, %d duplicate, %d invalid), %d clusters -> %d vertices" %
+                  (what, s["cell"], s["faces_in"], 0 if fm["faces"] is None else fm["faces"].shape[0], s["faces_collapsed"], s["faces_duplicate"],
+                   s["faces_invalid"], s["clusters"], fm["vertices"].shape[0]))
 
     def report_components(what, fm):
         c = fm.get("components")
@@ -276,12 +300,16 @@ def main():
             _, H, W, _ = preds[0]["pts3d"].shape
             print("%s: fusing through nominal cameras (focal %d, identity poses)" % (e, max(H, W)))
             fm, vol = fusion.fuse_sequence(preds, batch, focal=float(max(H, W)), poses=np.stack([np.eye(4)] * len(preds)), **kw)
+        if args.simplify_voxels is not None and "simplify_cell" not in kw:      # no --voxel_size: the cell follows the volume's own voxel
+            fm = dict(fm, **vol.extract_mesh(scale=kw.get("scale", 1.0), transform=kw.get("transform"), min_component_faces=args.min_component,
+                                             keep_largest=kw["keep_largest"], simplify_cell=args.simplify_voxels * vol.voxel_size))
         if args.track:
             T = fm["corrections"][1:]
             ang = [math.degrees(math.acos(min(max((np.trace(t[:3, :3]) - 1) * 0.5, -1.0), 1.0))) for t in T]
             print("%d frames tracked of %d; largest correction %.3f degrees, %.3f voxels" %
                   (sum(fm["tracked"][1:]), len(T), max(ang, default=0.0), max((np.linalg.norm(t[:3, 3]) for t in T), default=0.0) / vol.voxel_size))
         report_components("fused surface", fm)
+        report_simplify("fused surface", fm)
         return fm, vol
 
     if args.eval:                                                                 # eval.py:128-221
@@ -370,6 +398,14 @@ def main():
                 raise RuntimeError("--fused: the volume holds no surface (nothing passes conf_thresh %g with weight >= 1)" % args.conf_thresh)
             size = mesh.write_glb(args.save_glb, fm["vertices"], fm["colors"], fm["faces"], bounds=fm["bounds"])
             info = dict(vertices=fm["vertices"].shape[0], faces=fm["faces"].shape[0], bytes=size)
+        elif args.simplify is not None:                                           # the sheets welded: one vertex per cell of all frames
+            scene = mesh.scene_mesh(*mesh.sequence_tensors(preds, batch), args.conf_thresh, args.as_pointcloud)
+            scene = mesh.simplify(scene, args.simplify * mesh.SCALE)                 # (the sheets are already in the GLB's x10 units)
+            report_simplify("per-frame sheets", scene)
+            if scene["vertices"].shape[0] == 0:
+                raise RuntimeError("--simplify %g left nothing of the sheets to write" % args.simplify)
+            size = mesh.write_glb(args.save_glb, scene["vertices"], scene["colors"], scene["faces"], bounds=scene["bounds"])
+            info = dict(vertices=scene["vertices"].shape[0], faces=0 if scene["faces"] is None else scene["faces"].shape[0], bytes=size)
         else:
             info = mesh.export_glb(args.save_glb, preds, batch, conf_thresh=args.conf_thresh, as_pointcloud=args.as_pointcloud)
         print("wrote %d vertices, %d faces (%d bytes) to %s" % (info["vertices"], info["faces"], info["bytes"], args.save_glb))

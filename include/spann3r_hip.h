@@ -1156,6 +1156,73 @@ int64_t sp3_mesh_select_faces_ws_bytes(int64_t nfaces);
 int sp3_mesh_select_faces(const int32_t* faces, const int32_t* face_component, int64_t nfaces, const uint8_t* keep, int64_t ncomponents,
                           void* ws, int32_t* out_faces, int32_t* count, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh simplification (spann3r_amd/mesh.py cluster_vertices / simplify drive these; csrc/mesh_simplify.hip): vertex clustering on
+ * a uniform grid, so that a fused surface has the triangle count its user chose and the overlapping per-frame sheets of
+ * sp3_mesh_faces become one welded vertex set.  tests/mesh_simplify_ref.py restates the rule in numpy; Open3D's
+ * simplify_vertex_clustering is not available to test against, so that restatement is the anchor (parity unpinned).  No entry point
+ * allocates, frees or synchronises; `ws` is caller-provided device scratch of the matching sp3_*_ws_bytes(), 16-byte aligned.
+ * Indices are int32: nverts and nfaces must stay below 2^31 - 1, and a table has 2^table_log2 slots, 1 <= table_log2 <= 31, MORE
+ * slots than items (all checked before anything is launched).  Every output is a function of the input alone: the sums are
+ * integers, so two runs give the same bits, whatever the order of the atomics, the table size or the hash function.
+ *
+ * The rule.  vertices fp32 [V, 3], rgba uint32 [V] (nullable), faces int32 [F, 3], origin3 HOST fp32 [3], cell > 0 and finite,
+ *   inv = fp32(1) / cell computed on the host.
+ *   1. Cell of a vertex.  Per axis u = (p - o) * inv, two separately rounded fp32 operations (no contraction: the file is compiled
+ *      under `#pragma clang fp contract(off)`); i = floorf(u).  A vertex is USABLE when all three u are finite and |i| < 2^30; an
+ *      unusable vertex belongs to no cluster (vertex_cluster = -1).  r = u - i, one rounded fp32 subtraction, and
+ *      q = min((int)(r * 65536.0f), 65535), in 0..65535.  (u - i is exact unless -0.5 < u < 0, where 1 - |u| may round, for
+ *      |u| <= 2^-25 up to r = 1; the min keeps q in range there.)
+ *   2. Cluster.  The usable vertices that share (ix, iy, iz).  Clusters are numbered 0..C-1 by ascending smallest member vertex
+ *      index, the convention of sp3_mesh_components.
+ *   3. Representative.  Per axis pos = (float)((double)o + ((double)i + (double)Sq / (double)n / 65536.0) * (double)cell): Sq the
+ *      unsigned 64-bit sum of the members' q, n the member count, every fp64 operation rounded on its own (no FMA), left to right as
+ *      written.  Colour per byte, alpha included: (2 Sc + n) / (2 n) in integers (round half up), Sc in 64 bits.
+ *   4. Faces.  A face is VALID when its three indices lie in 0..V-1 and name usable vertices; an invalid face is never dereferenced
+ *      beyond the index check.  A valid face is remapped to cluster ids and dropped as COLLAPSED when two of its ids are equal.
+ *      With dedup the survivors are grouped by their triple rotated so that the smallest id comes first -- rotation keeps the
+ *      winding, so a face and its mirror image are two different faces -- and of each group the face with the lowest original index
+ *      is kept.  Kept faces are written densely, in original order and in their original rotation.
+ *   5. sp3_mesh_compact_vertices(faces = the kept faces) then drops the clusters no kept face names, renumbers and gives the bounds.
+ *
+ * The table.  Both groupings use the same lock-free open-addressing table of int32 slots.  A slot holds an ITEM index (a vertex, a
+ *   face), not a key; the key of a slot is recomputed from the item it holds: for a vertex the cell of that vertex, for a face the
+ *   rotated cluster triple read from the remapped-face buffer an earlier launch wrote.  So any V and C work without packing a key
+ *   into 64 bits.  Insert: probe linearly from hash(key), wrapping at the end; read the slot with an agent-scope atomic load; if it
+ *   is EMPTY, agent-scope atomicCAS(slot, EMPTY, me); if the slot then or already holds g with key(g) == key(me), atomicMin(slot, me)
+ *   and stop (the atomicMin is skipped when g < me: the slot only decreases, so it is below me already); otherwise go on to the next
+ *   slot.  Invariants:
+ *   - a claimed slot never changes its key, and a slot's value only ever decreases, within one key;
+ *   - a lane inserts only at the first EMPTY slot of its probe sequence, so one key owns exactly one slot, which ends at the
+ *     smallest item of the key;
+ *   - the table holds more slots than items, so every probe ends at a match or at an EMPTY slot (the loops are bounded by the
+ *     table size all the same);
+ *   - no lane waits for another lane's store, and a stale read only costs a failed CAS, which returns the true value (a stale item
+ *     is one the slot held earlier: same key, not smaller than the current one);
+ *   - the keys are immutable during the launch that hashes them.
+ *   The L2s of the XCDs are not coherent and a CU's L1 is never refreshed: inside an insert launch only the atomics carry
+ *   information, and launch boundaries are the only other hand-offs.  After the insert launch, in launches of their own, each item
+ *   finds its slot again with plain loads; a vertex is its cluster's leader, and a face is kept, when the slot holds its own index;
+ *   leader and kept flags are counted per 256-item tile, scanned (one workgroup) and scattered, which gives the dense ids and the
+ *   dense face list in original order.
+ *
+ * sp3_mesh_cluster : positions fp32 [C, 3] and out_rgba [C] (null exactly when rgba is null) need room for nverts rows; only the
+ *   first C are written.  vertex_cluster int32 [V].  info int32 [1] = C.  Members add q, the four colour bytes and 1 to their
+ *   cluster's unsigned 64-bit sums with agent-scope atomic adds (one add per lane and sum; no aggregation in the wave).  7 launches.
+ *   ws: the table, two int32 per vertex (leader -> id, id -> leader), the tile table and 64 bytes of sums per vertex of capacity
+ *   (only the first C are touched).  nverts = 0 writes info = 0 and nothing else.
+ * sp3_mesh_cluster_faces : vertex_cluster int32 [nverts] as sp3_mesh_cluster wrote it (any entry < 0: unusable).  out_faces int32
+ *   needs room for nfaces rows; info int32 [4] = (kept, invalid, collapsed, duplicate), kept + invalid + collapsed + duplicate =
+ *   nfaces.  dedup = 0: every survivor is kept, no table is used and table_log2 is ignored (pass 0 to the ws function too).
+ *   6 launches (5 without dedup).  ws: the table, the remapped faces (12 bytes a face), one flag byte a face and the tile table.
+ *   nfaces = 0 writes info = 0 and nothing else; nverts = 0 makes every face invalid. */
+int64_t sp3_mesh_cluster_ws_bytes(int64_t nverts, int table_log2);
+int sp3_mesh_cluster(const float* vertices, const uint32_t* rgba, int64_t nverts, const float* origin3, float cell, int table_log2,
+                     void* ws, float* positions, uint32_t* out_rgba, int32_t* vertex_cluster, int32_t* info, void* stream);
+int64_t sp3_mesh_cluster_faces_ws_bytes(int64_t nfaces, int table_log2);
+int sp3_mesh_cluster_faces(const int32_t* faces, int64_t nfaces, const int32_t* vertex_cluster, int64_t nverts, int dedup, int table_log2,
+                           void* ws, int32_t* out_faces, int32_t* info, void* stream);
+
 /* small utilities */
 /* n (1..8) contiguous device-to-device copies in one launch; every copy 16-byte aligned and a multiple of 16 bytes.
  * (The sequence loop's per-frame bookkeeping -- torch .clone() / slice assignments around spann3r/model.py:523-531.) */

@@ -192,6 +192,139 @@ def filter_components(m, min_faces=0, keep_largest=None):
     return out
 
 
+def _table_log2(items):
+    """the table of sp3_mesh_cluster / sp3_mesh_cluster_faces: the next power of two >= 2 x items"""
+    return max(1, (2 * int(items) - 1).bit_length())
+
+
+def _grid(cell, origin, what):
+    """(cell as a float that fp32 holds, origin as a ctypes float[3]); raises before anything is launched"""
+    try:
+        c = float(np.float32(cell))
+    except (TypeError, ValueError):
+        raise ValueError("%s: cell must be a number, got %r" % (what, cell))
+    if not (c > 0 and np.isfinite(c)):
+        raise ValueError("%s: cell must be positive and finite (in fp32), got %r" % (what, cell))
+    o = np.zeros(3, np.float32) if origin is None else np.asarray(_host(origin), np.float32).reshape(-1)
+    if o.shape != (3,) or not np.isfinite(o).all():
+        raise ValueError("%s: origin must be 3 finite numbers, got %r" % (what, origin))
+    return c, (C.c_float * 3)(*o.tolist())
+
+
+def _cluster_raw(lib, vertices, rgba, cell, origin3, table_log2):
+    """sp3_mesh_cluster at full capacity, no host read: -> (positions [V, 3], rgba [V] or None, vertex_cluster [V], info int32 [1])"""
+    nv, dev = vertices.shape[0], vertices.device
+    log2 = _table_log2(nv) if table_log2 is None else int(table_log2)
+    if not (1 <= log2 <= 31 and 2 ** log2 > nv):
+        raise ValueError("cluster_vertices: table_log2 %r: the table needs 2^1 .. 2^31 slots and more slots than the %d vertices" % (table_log2, nv))
+    pos = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    col = torch.empty(nv, dtype=torch.int32, device=dev) if rgba is not None else None
+    vc = torch.empty(nv, dtype=torch.int32, device=dev)
+    info = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = _ws(lib.sp3_mesh_cluster_ws_bytes(nv, log2), dev)
+    L.check(lib.sp3_mesh_cluster(vertices.data_ptr(), L.ptr(rgba), nv, origin3, cell, log2, ws.data_ptr(), pos.data_ptr(), L.ptr(col),
+                                 vc.data_ptr(), info.data_ptr(), L.stream_ptr()), "sp3_mesh_cluster")
+    return pos, col, vc, info
+
+
+def _cluster_faces_raw(lib, faces, vc, dedup, table_log2=None):
+    """sp3_mesh_cluster_faces at full capacity, no host read: -> (faces [F, 3], info int32 [4] = kept, invalid, collapsed, duplicate)"""
+    nf, dev = faces.shape[0], faces.device
+    log2 = 0 if not dedup else _table_log2(nf) if table_log2 is None else int(table_log2)
+    out = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+    info = torch.zeros(4, dtype=torch.int32, device=dev)
+    ws = _ws(lib.sp3_mesh_cluster_faces_ws_bytes(nf, log2), dev)
+    L.check(lib.sp3_mesh_cluster_faces(faces.data_ptr(), nf, vc.data_ptr(), vc.shape[0], int(bool(dedup)), log2, ws.data_ptr(), out.data_ptr(),
+                                       info.data_ptr(), L.stream_ptr()), "sp3_mesh_cluster_faces")
+    return out, info
+
+
+def _check_vertices(vertices, rgba, what):
+    vertices = _dev(vertices, what + ": vertices")
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise RuntimeError("%s: vertices must be [V, 3], got %s" % (what, tuple(vertices.shape)))
+    if vertices.shape[0] >= 2 ** 31 - 1:
+        raise ValueError("%s: %d vertices: must stay below 2^31 - 1 (int32 indices)" % (what, vertices.shape[0]))
+    vertices = vertices.float().contiguous()
+    if rgba is not None:
+        rgba = _dev(rgba, what + ": rgba").contiguous()
+        if rgba.dtype == torch.uint8 and rgba.shape == (vertices.shape[0], 4):
+            rgba = rgba.reshape(-1).view(torch.int32)              # (flat first: an empty [0, 4] has no unit stride to view through)
+        if rgba.dtype != torch.int32 or rgba.shape != (vertices.shape[0],):
+            raise RuntimeError("%s: colours must be int32 [V] (packed rgba) or uint8 [V, 4], got %s %s" % (what, rgba.dtype, tuple(rgba.shape)))
+    return vertices, rgba
+
+
+def cluster_vertices(vertices, cell, origin=None, rgba=None, table_log2=None):
+    """sp3_mesh_cluster: vertex clustering on the uniform grid of `cell` from `origin` (include/spann3r_hip.h "Mesh simplification").
+    vertices fp32 [V, 3], rgba int32 [V] (or uint8 [V, 4]; optional) -> dict(positions fp32 [C, 3], rgba int32 [C] or None,
+    vertex_cluster int32 [V] (-1: a vertex that is not finite or beyond 2^30 cells), on the device; n_clusters).  A cluster is the
+    set of vertices of one cell, numbered by its smallest vertex; its position is origin + (cell index + mean 16-bit fraction) * cell
+    from integer sums, its colour the rounded mean per byte: the same bits every run.  origin defaults to zeros and never depends
+    on the data, so two meshes simplified with the same cell share a grid.  table_log2: the hash table's size (default: the next
+    power of two >= 2 V); the result does not depend on it.  One host read (C)."""
+    cell, origin3 = _grid(cell, origin, "cluster_vertices")
+    vertices, rgba = _check_vertices(vertices, rgba, "cluster_vertices")
+    if vertices.shape[0] == 0:
+        return dict(positions=vertices.new_empty((0, 3)), rgba=None if rgba is None else rgba[:0], n_clusters=0,
+                    vertex_cluster=torch.empty(0, dtype=torch.int32, device=vertices.device))
+    pos, col, vc, info = _cluster_raw(L.load(), vertices, rgba, cell, origin3, table_log2)
+    c = int(info.cpu().item())
+    return dict(positions=pos[:c], rgba=None if col is None else col[:c], vertex_cluster=vc, n_clusters=c)
+
+
+def simplify(m, cell, origin=None, dedup=True, return_map=False, scale=1.0, transform=None):
+    """Vertex clustering of a mesh (include/spann3r_hip.h "Mesh simplification"): m is the dict scene_mesh / extract_mesh return
+    (vertices fp32 [V, 3], colors uint8 [V, 4], faces int32 [F, 3] or None, on the device).  Every vertex moves to the representative
+    of its cell of the grid (cell, origin) -- cluster_vertices -- faces whose corners then coincide are dropped as collapsed, with
+    dedup so are all but the first of the faces that became the same triangle with the same winding, and the clusters no kept face
+    names are dropped.  -> the same kind of dict -- vertices, colors, faces, bounds recomputed -- plus simplify = dict(cell, clusters,
+    faces_in, faces_collapsed, faces_duplicate, faces_invalid) and, with return_map, vertex_cluster int32 [V] (the cluster of every
+    input vertex in the numbering of cluster_vertices, -1: unusable).  Kept faces stay in their original order and rotation.  A
+    face with an index outside 0..V-1 or at an unusable vertex is invalid and dropped.  A cloud (faces None) is clustered too and
+    comes back as a cloud; everything collapsed gives an empty mesh, not an error.  scale / transform: applied to the
+    representatives by the final compaction, as extract_mesh applies them.  One host read of the counts (C and the four face
+    counts), then compact_vertices' own of V and the bounds."""
+    cell, origin3 = _grid(cell, origin, "simplify")
+    colors = m["colors"]
+    vertices, rgba = _check_vertices(m["vertices"], colors, "simplify")
+    if colors.dtype != torch.uint8 or colors.shape != (vertices.shape[0], 4):
+        raise RuntimeError("simplify: colors must be uint8 [V, 4], got %s %s" % (colors.dtype, tuple(colors.shape)))
+    faces = m.get("faces")
+    if faces is not None:
+        faces = _dev(faces, "simplify: faces")
+        if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+            raise RuntimeError("simplify: faces must be int32 [F, 3], got %s %s" % (faces.dtype, tuple(faces.shape)))
+        if faces.shape[0] >= 2 ** 31 - 1:
+            raise ValueError("simplify: %d faces: must stay below 2^31 - 1 (int32 indices)" % faces.shape[0])
+        faces = faces.contiguous()
+    nv, nf, dev = vertices.shape[0], 0 if faces is None else faces.shape[0], vertices.device
+    lib = L.load()
+    none = np.array([[np.inf] * 3, [-np.inf] * 3], np.float32)
+    c, kept, invalid, collapsed, duplicate = 0, 0, nf, 0, 0
+    vc = torch.empty(0, dtype=torch.int32, device=dev)
+    pos, col, bounds, out_faces = vertices[:0], rgba[:0], none, None if faces is None else faces[:0]
+    if nv > 0:
+        cpos, ccol, vc, info = _cluster_raw(lib, vertices, rgba, cell, origin3, None)
+        if nf > 0:
+            kfaces, finfo = _cluster_faces_raw(lib, faces, vc, dedup)
+            c, kept, invalid, collapsed, duplicate = torch.cat([info, finfo]).cpu().tolist()
+            if kept > 0:
+                out_faces = kfaces[:kept]
+                pos, col, bounds = compact_vertices(cpos[:c], ccol[:c], faces=out_faces, scale=scale, transform=transform)
+        else:
+            c = int(info.cpu().item())
+            if faces is None and c > 0:
+                ok = torch.ones(c, dtype=torch.uint8, device=dev)
+                pos, col, bounds = compact_vertices(cpos[:c], ccol[:c], valid=ok, scale=scale, transform=transform)
+    out = {k: v for k, v in m.items() if k not in ("vertices", "colors", "faces", "bounds", "simplify", "vertex_cluster")}
+    out.update(vertices=pos, colors=col.contiguous().view(torch.uint8).reshape(-1, 4), faces=out_faces, bounds=bounds,
+               simplify=dict(cell=cell, clusters=c, faces_in=nf, faces_collapsed=collapsed, faces_duplicate=duplicate, faces_invalid=invalid))
+    if return_map:
+        out["vertex_cluster"] = vc
+    return out
+
+
 def pts3d_to_mesh(img, pts3d, valid=None):
     """app.py:68-105 (pts3d_to_trimesh) for device tensors img, pts3d [h, w, 3] and valid bool [h, w]: dict(vertices [h w, 3],
     faces int64 [F, 3], face_colors [F, 3]) with the reference's order: four blocks (tl, tr, bl), (bl, tr, tl), (tr, bl, br), (br, bl, tr),
