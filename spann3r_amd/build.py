@@ -13,8 +13,9 @@ STAMP = LIB + ".srchash"
 
 
 def _deps():
-    return [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_sm.h"), os.path.join(CSRC, "scan.h"), os.path.join(CSRC, "tets.h"),
-                                                      os.path.join(HERE, "..", "include", "spann3r_hip.h"), os.path.abspath(__file__)]
+    """the sources, every header of csrc/ (by rule: a new header is covered without being listed), the public header, this recipe"""
+    headers = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))
+    return [os.path.join(CSRC, f) for f in SOURCES + headers] + [os.path.join(HERE, "..", "include", "spann3r_hip.h"), os.path.abspath(__file__)]
 
 
 def source_hash():

@@ -6,18 +6,23 @@
 // sp3_tsdf_brick_alloc: the new bricks get slots in linear brick order by the tile count / single-workgroup scan / scatter of
 //   csrc/scan.h; every kernel of the chain computes need = count + new itself and writes nothing when it exceeds the capacity.
 // sp3_tsdf_brick_integrate: a workgroup owns a brick (512 lanes, a wave an 8 x 8 slab of one z), a lane a voxel; the per-frame
-//   rule is k_tsdf_integrate's (csrc/fusion.hip), restated here operation for operation so that file keeps its bits.
-// sp3_tsdf_brick_raycast: k_tsdf_raycast's march (csrc/raycast.hip), restated, with the cell gathered through the table.  A sample
-//   whose corner 0 lies in an absent brick is invalid; the lane then looks for a later sample whose corner 0 lies in the SAME brick.
-//   The coordinates of corner 0 are monotone in the sample index (every rounded operation of the sample rule is monotone), so all
-//   samples in between lie in that brick too and are invalid: they are passed over without being evaluated.  The jump is a guess
-//   from the ray's slope; the proof is the check of the sample it lands on.
+//   rule is integrate_voxel (csrc/tsdf.h), the one k_tsdf_integrate (csrc/fusion.hip) calls.
+// sp3_tsdf_brick_raycast: the march of raycast_pixel (csrc/tsdf.h), the one k_tsdf_raycast (csrc/raycast.hip) calls, with the cell
+//   gathered through the table.  A sample whose corner 0 lies in an absent brick is invalid; the lane then looks for a later sample
+//   whose corner 0 lies in the SAME brick.  The coordinates of corner 0 are monotone in the sample index (every rounded operation
+//   of the sample rule is monotone), so all samples in between lie in that brick too and are invalid: they are passed over without
+//   being evaluated.  The jump is a guess from the ray's slope; the proof is the check of the sample it lands on.
 // sp3_tsdf_brick_to_dense: a lane owns a voxel of the box.
+//
+// The shared rules keep both volumes' bits: csrc/tsdf.h switches contraction off for its own text and nothing is built with
+// fast-math, so every fp32 operation is one IEEE operation wherever it is inlined.  Compiled for gfx950, the integrate kernels of
+// both volumes came out of the move with the same instructions (profiles/tsdf_shared.txt).
 //
 // Every fp32 operation is rounded on its own (no contraction into FMAs): the file-level pragma below is what the compiler honours
 // under its default -ffp-contract=fast-honor-pragmas.  No atomics, no workgroup waits on another.
 #include "common.h"
 #include "scan.h"
+#include "tsdf.h"
 #include <math.h>
 
 #pragma clang fp contract(off)
@@ -26,7 +31,6 @@ namespace {
 
 #define BRK 8                // voxels per brick side
 #define BRK_VOX 512          // voxels per brick = lanes of an integrate workgroup
-#define RC_TILE 16           // a ray-cast workgroup's pixel block; its four waves are the 8 x 8 quadrants
 #define INIT_BLOCKS 1024     // workgroups of the slot initialisation (they stride over the new slots)
 
 struct BVol {
@@ -139,7 +143,6 @@ __global__ void k_brick_alloc_finish(int* __restrict__ count, const int* __restr
 }
 
 // ------------------------------------------------------------------------------------------------ integrate
-// The per-frame rule is k_tsdf_integrate's (csrc/fusion.hip), operation for operation.
 template <bool RGB>
 __global__ __launch_bounds__(BRK_VOX) void k_brick_integrate(const sp3_tsdf_frame* __restrict__ frames, int T, BVol g,
                                                             const int* __restrict__ slot_brick, float* __restrict__ tsdf,
@@ -157,43 +160,7 @@ __global__ __launch_bounds__(BRK_VOX) void k_brick_integrate(const sp3_tsdf_fram
     cg = rgb[3 * v + 1];
     cb = rgb[3 * v + 2];
   }
-  for (int f = 0; f < T; ++f) {      // (f is wave-uniform: the descriptor fields arrive by scalar loads)
-    const sp3_tsdf_frame& fr = frames[f];
-    const float* m = fr.w2c;
-    const float zc = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
-    if (!(zc > 0.f)) continue;
-    const float xc = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
-    const float yc = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
-    const float u = fr.fu * xc / zc + fr.cu, w_ = fr.fv * yc / zc + fr.cv;
-    const float fpx = floorf(u + 0.5f), fpy = floorf(w_ + 0.5f);
-    if (!(fpx >= 0.f && fpx < (float)fr.w && fpy >= 0.f && fpy < (float)fr.h)) continue;      // (a NaN fails the test)
-    const int64_t p = (int64_t)fpy * fr.row_stride + (int64_t)fpx;
-    if (fr.valid != nullptr && fr.valid[p] == 0) continue;
-    float d;
-    if (fr.depth != nullptr) {
-      d = fr.depth[p];
-    } else {
-      const float X = fr.pts[3 * p], Y = fr.pts[3 * p + 1], Z = fr.pts[3 * p + 2];
-      d = ((m[8] * X + m[9] * Y) + m[10] * Z) + m[11];
-    }
-    if (!isfinite(d) || d <= 0.f) continue;
-    const float s = d - zc;
-    if (s < -g.trunc) continue;
-    const float q = s / g.trunc;
-    const float fv = q < 1.0f ? q : 1.0f;
-    const float a = fr.pixel_weight != nullptr ? fr.pixel_weight[p] : 1.0f;
-    if (!(a > 0.f) || !isfinite(a)) continue;
-    const float Wn = W + a;
-    D = (W * D + a * fv) / Wn;
-    if (RGB) {
-      const unsigned c = fr.rgba[p];
-      const float r = (float)(c & 255u) / 255.0f, gch = (float)((c >> 8) & 255u) / 255.0f, b = (float)((c >> 16) & 255u) / 255.0f;
-      cr = (W * cr + a * r) / Wn;
-      cg = (W * cg + a * gch) / Wn;
-      cb = (W * cb + a * b) / Wn;
-    }
-    W = Wn;
-  }
+  integrate_voxel<RGB>(frames, T, x, y, z, g.trunc, D, W, cr, cg, cb);
   tsdf[v] = D;
   weight[v] = W;
   if (RGB) {
@@ -204,39 +171,8 @@ __global__ __launch_bounds__(BRK_VOX) void k_brick_integrate(const sp3_tsdf_fram
 }
 
 // ------------------------------------------------------------------------------------------------ ray-casting
-struct BRcVol {
-  int nx, ny, nz, bx, by, bz;
-  float ox, oy, oz, voxel, min_weight, step;
-  int cap;
-};
-
-__device__ __forceinline__ float lerp(float a, float b, float t) { return a + t * (b - a); }
-
-__device__ __forceinline__ float lerp2(float v00, float v10, float v01, float v11, float t1, float t2) {
-  return lerp(lerp(v00, v10, t1), lerp(v01, v11, t1), t2);
-}
-
-__device__ __forceinline__ unsigned rc_unorm8(float c) {      // sp3_pack_rgba8's channel
-  const float s = floorf(c * 255.0f + 0.5f);
-  return s >= 255.0f ? 255u : (s > 0.0f ? (unsigned)s : 0u);
-}
-
-__device__ __forceinline__ float trilinear(const float (&v)[8], float tx, float ty, float tz) {
-  const float e00 = lerp(v[0], v[1], tx), e10 = lerp(v[2], v[3], tx), e01 = lerp(v[4], v[5], tx), e11 = lerp(v[6], v[7], tx);
-  return lerp(lerp(e00, e10, ty), lerp(e01, e11, ty), tz);
-}
-
-struct BCell {
-  int64_t q[8];      // pool index of corner code c = dx + 2 dy + 4 dz
-  float tx, ty, tz;
-  float v[8];
-  int bI, bJ, bK;    // the brick of corner 0
-};
-
-enum { CELL_INVALID = 0, CELL_VALID = 1, CELL_ABSENT = 2 };      // ABSENT: invalid because the brick of corner 0 is absent
-
 // lattice coordinates of corner 0 of the cell of a point, by the header's rule; false outside the lattice (a NaN fails)
-__device__ __forceinline__ bool cell_floor(const BRcVol& g, float px, float py, float pz, float& gx, float& gy, float& gz, float& fx, float& fy,
+__device__ __forceinline__ bool cell_floor(const RcVol& g, float px, float py, float pz, float& gx, float& gy, float& gz, float& fx, float& fy,
                                            float& fz) {
   gx = (px - g.ox) / g.voxel;
   gy = (py - g.oy) / g.voxel;
@@ -247,82 +183,93 @@ __device__ __forceinline__ bool cell_floor(const BRcVol& g, float px, float py, 
   return fx >= 0.f && fx <= (float)(g.nx - 2) && fy >= 0.f && fy <= (float)(g.ny - 2) && fz >= 0.f && fz <= (float)(g.nz - 2);
 }
 
-// The cell of point (px, py, pz) on the densified volume: a corner in an absent brick has weight 0 < min_weight.
-__device__ __forceinline__ int load_cell(const BRcVol& g, const int* __restrict__ table, const float* __restrict__ tsdf,
-                                         const float* __restrict__ weight, float px, float py, float pz, BCell& c) {
-  float gx, gy, gz, fx, fy, fz;
-  if (!cell_floor(g, px, py, pz, gx, gy, gz, fx, fy, fz)) return CELL_INVALID;
-  const int i = (int)fx, j = (int)fy, k = (int)fz;
-  c.bI = i >> 3;
-  c.bJ = j >> 3;
-  c.bK = k >> 3;
-  const int s0 = table[((int64_t)c.bK * g.by + c.bJ) * g.bx + c.bI];
-  if (s0 < 0) return CELL_ABSENT;
-  c.tx = gx - fx;
-  c.ty = gy - fy;
-  c.tz = gz - fz;
-  const bool inner = (i & 7) < 7 && (j & 7) < 7 && (k & 7) < 7;      // all eight corners in the brick of corner 0
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int ci = i + (e & 1), cj = j + ((e >> 1) & 1), ck = k + (e >> 2);      // (<= n - 1 per axis: inside the table)
-    int s = s0;
-    if (!inner) {
-      const int cI = ci >> 3, cJ = cj >> 3, cK = ck >> 3;
-      if (cI != c.bI || cJ != c.bJ || cK != c.bK) s = table[((int64_t)cK * g.by + cJ) * g.bx + cI];
-    }
-    if (s < 0) return CELL_INVALID;
-    const int64_t q = (int64_t)s * BRK_VOX + (((ck & 7) << 6) | ((cj & 7) << 3) | (ci & 7));
-    if (!(weight[q] >= g.min_weight)) return CELL_INVALID;
-    c.q[e] = q;
-    c.v[e] = tsdf[q];
-  }
-  return CELL_VALID;
-}
+// the brick volume as raycast_pixel's Vol (csrc/tsdf.h)
+struct BrickVol {
+  const RcVol& g;
+  const int* __restrict__ table;
+  const float* __restrict__ tsdf;
+  const float* __restrict__ weight;
 
-struct Ray {
-  float ex, ey, ez, dx, dy, dz, lam0, lam1, dl;
+  struct Cell {
+    int64_t q[8];      // pool index of corner code c = dx + 2 dy + 4 dz
+    float tx, ty, tz;
+    float v[8];
+    int bI, bJ, bK;    // the brick of corner 0
+  };
+
+  __device__ __forceinline__ int64_t corner(const Cell& c, int e) const { return c.q[e]; }
+
+  // The cell of point (px, py, pz) on the densified volume: a corner in an absent brick has weight 0 < min_weight.
+  __device__ __forceinline__ int load(float px, float py, float pz, Cell& c) const {
+    float gx, gy, gz, fx, fy, fz;
+    if (!cell_floor(g, px, py, pz, gx, gy, gz, fx, fy, fz)) return CELL_INVALID;
+    const int i = (int)fx, j = (int)fy, k = (int)fz;
+    c.bI = i >> 3;
+    c.bJ = j >> 3;
+    c.bK = k >> 3;
+    const int s0 = table[((int64_t)c.bK * g.by + c.bJ) * g.bx + c.bI];
+    if (s0 < 0) return CELL_ABSENT;
+    c.tx = gx - fx;
+    c.ty = gy - fy;
+    c.tz = gz - fz;
+    const bool inner = (i & 7) < 7 && (j & 7) < 7 && (k & 7) < 7;      // all eight corners in the brick of corner 0
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int ci = i + (e & 1), cj = j + ((e >> 1) & 1), ck = k + (e >> 2);      // (<= n - 1 per axis: inside the table)
+      int s = s0;
+      if (!inner) {
+        const int cI = ci >> 3, cJ = cj >> 3, cK = ck >> 3;
+        if (cI != c.bI || cJ != c.bJ || cK != c.bK) s = table[((int64_t)cK * g.by + cJ) * g.bx + cI];
+      }
+      if (s < 0) return CELL_INVALID;
+      const int64_t q = (int64_t)s * BRK_VOX + (((ck & 7) << 6) | ((cj & 7) << 3) | (ci & 7));
+      if (!(weight[q] >= g.min_weight)) return CELL_INVALID;
+      c.q[e] = q;
+      c.v[e] = tsdf[q];
+    }
+    return CELL_VALID;
+  }
+
+  // Sample i's corner 0 lies in the absent brick (c.bI, c.bJ, c.bK).  -> the largest index found (>= i) whose sample is inside the
+  // march (index < cap, lambda <= lambda1) and has its corner 0 in the same brick; every sample from i to it is then invalid (see the
+  // head of the file).  The guess comes from the slope; only the check decides.
+  __device__ __forceinline__ int skip(const Ray& r, int i, const Cell& c) const {
+    const float lam = r.lam0 + (float)i * r.dl;
+    float gx, gy, gz, fx, fy, fz;
+    cell_floor(g, r.ex + r.dx * lam, r.ey + r.dy * lam, r.ez + r.dz * lam, gx, gy, gz, fx, fy, fz);
+    const float lo3[3] = {(float)(c.bI * BRK), (float)(c.bJ * BRK), (float)(c.bK * BRK)};
+    const float g3[3] = {gx, gy, gz}, d3[3] = {r.dx, r.dy, r.dz};
+    float room = 64.0f;      // samples; a brick's diagonal is under 56 samples at the smallest step (a quarter voxel)
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const float per = d3[a] * r.dl / g.voxel;      // lattice units per sample
+      if (per > 0.f) {
+        const float q = (lo3[a] + (float)BRK - g3[a]) / per;
+        room = q < room ? q : room;
+      } else if (per < 0.f) {
+        const float q = (lo3[a] - g3[a]) / per;
+        room = q < room ? q : room;
+      }
+    }
+    int n = room > 0.f ? (int)room : 0;
+    if (n > g.cap - 1 - i) n = g.cap - 1 - i;
+    bool first = true;
+    while (n > 0) {
+      const float l2 = r.lam0 + (float)(i + n) * r.dl;
+      if (l2 <= r.lam1) {
+        cell_floor(g, r.ex + r.dx * l2, r.ey + r.dy * l2, r.ez + r.dz * l2, gx, gy, gz, fx, fy, fz);
+        if (fx >= lo3[0] && fx < lo3[0] + (float)BRK && fy >= lo3[1] && fy < lo3[1] + (float)BRK && fz >= lo3[2] && fz < lo3[2] + (float)BRK)
+          return i + n;
+      }
+      n = first ? n - 1 : n >> 1;
+      first = false;
+    }
+    return i;
+  }
 };
 
-// Sample i's corner 0 lies in the absent brick (bI, bJ, bK).  -> the largest index found (>= i) whose sample is inside the march
-// (index < cap, lambda <= lambda1) and has its corner 0 in the same brick; every sample from i to it is then invalid (see the head
-// of the file).  The guess comes from the slope; only the check decides.
-__device__ __forceinline__ int last_in_brick(const BRcVol& g, const Ray& r, int i, int bI, int bJ, int bK) {
-  const float lam = r.lam0 + (float)i * r.dl;
-  float gx, gy, gz, fx, fy, fz;
-  cell_floor(g, r.ex + r.dx * lam, r.ey + r.dy * lam, r.ez + r.dz * lam, gx, gy, gz, fx, fy, fz);
-  const float lo3[3] = {(float)(bI * BRK), (float)(bJ * BRK), (float)(bK * BRK)};
-  const float g3[3] = {gx, gy, gz}, d3[3] = {r.dx, r.dy, r.dz};
-  float room = 64.0f;      // samples; a brick's diagonal is under 56 samples at the smallest step (a quarter voxel)
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float per = d3[a] * r.dl / g.voxel;      // lattice units per sample
-    if (per > 0.f) {
-      const float q = (lo3[a] + (float)BRK - g3[a]) / per;
-      room = q < room ? q : room;
-    } else if (per < 0.f) {
-      const float q = (lo3[a] - g3[a]) / per;
-      room = q < room ? q : room;
-    }
-  }
-  int n = room > 0.f ? (int)room : 0;
-  if (n > g.cap - 1 - i) n = g.cap - 1 - i;
-  bool first = true;
-  while (n > 0) {
-    const float l2 = r.lam0 + (float)(i + n) * r.dl;
-    if (l2 <= r.lam1) {
-      cell_floor(g, r.ex + r.dx * l2, r.ey + r.dy * l2, r.ez + r.dz * l2, gx, gy, gz, fx, fy, fz);
-      if (fx >= lo3[0] && fx < lo3[0] + (float)BRK && fy >= lo3[1] && fy < lo3[1] + (float)BRK && fz >= lo3[2] && fz < lo3[2] + (float)BRK)
-        return i + n;
-    }
-    n = first ? n - 1 : n >> 1;
-    first = false;
-  }
-  return i;
-}
-
-// k_tsdf_raycast's rule (csrc/raycast.hip), operation for operation, on the densified volume.
 template <bool RGB>
-__global__ __launch_bounds__(RC_TILE * RC_TILE) void k_brick_raycast(const sp3_tsdf_view* __restrict__ views, BRcVol g,
+__global__ __launch_bounds__(RC_TILE * RC_TILE) void k_brick_raycast(const sp3_tsdf_view* __restrict__ views, RcVol g,
                                                                     const int* __restrict__ table, const float* __restrict__ tsdf,
                                                                     const float* __restrict__ weight, const float* __restrict__ rgb) {
   const sp3_tsdf_view& vw = views[blockIdx.z];      // (wave-uniform: the descriptor fields arrive by scalar loads)
@@ -330,114 +277,7 @@ __global__ __launch_bounds__(RC_TILE * RC_TILE) void k_brick_raycast(const sp3_t
   const int px = blockIdx.x * RC_TILE + (wave & 1) * 8 + (lane & 7);
   const int py = blockIdx.y * RC_TILE + (wave >> 1) * 8 + (lane >> 3);
   if (px >= vw.w || py >= vw.h) return;
-  const float* m = vw.c2w;
-  const float xn = ((float)px - vw.cu) / vw.fu, yn = ((float)py - vw.cv) / vw.fv;
-  Ray r;
-  r.dx = (m[0] * xn + m[1] * yn) + m[2];
-  r.dy = (m[4] * xn + m[5] * yn) + m[6];
-  r.dz = (m[8] * xn + m[9] * yn) + m[10];
-  r.ex = m[3];
-  r.ey = m[7];
-  r.ez = m[11];
-  const float len = sqrtf((r.dx * r.dx + r.dy * r.dy) + r.dz * r.dz);
-  r.dl = g.step / len;
-  // the voxel-centre lattice's box by slabs
-  float enter = -INFINITY, leave = INFINITY;
-  bool alive = true;
-  {
-    const float d3[3] = {r.dx, r.dy, r.dz}, e3[3] = {r.ex, r.ey, r.ez}, o3[3] = {g.ox, g.oy, g.oz};
-    const int n3[3] = {g.nx, g.ny, g.nz};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const float lo = o3[a], hi = o3[a] + (float)(n3[a] - 1) * g.voxel;
-      if (d3[a] == 0.f) {
-        alive = alive && lo <= e3[a] && e3[a] <= hi;
-      } else {
-        const float q1 = (lo - e3[a]) / d3[a], q2 = (hi - e3[a]) / d3[a];
-        const float small = q2 < q1 ? q2 : q1, large = q2 < q1 ? q1 : q2;
-        enter = small > enter ? small : enter;
-        leave = large < leave ? large : leave;
-      }
-    }
-  }
-  r.lam0 = vw.near > enter ? vw.near : enter;
-  r.lam1 = vw.far < leave ? vw.far : leave;
-  alive = alive && r.lam0 <= r.lam1;      // (a NaN fails)
-  bool hit = false, prev_valid = false;
-  float f_prev = 0.f, lam_star = 0.f;
-  BCell c;
-  if (alive) {
-    for (int i = 0; i < g.cap; ++i) {      // (the cap is a hard bound: no input makes a lane loop without end)
-      const float lam = r.lam0 + (float)i * r.dl;
-      if (!(lam <= r.lam1)) break;
-      const int st = load_cell(g, table, tsdf, weight, r.ex + r.dx * lam, r.ey + r.dy * lam, r.ez + r.dz * lam, c);
-      if (st != CELL_VALID) {
-        prev_valid = false;
-        if (st == CELL_ABSENT) i = last_in_brick(g, r, i, c.bI, c.bJ, c.bK);      // (all invalid up to there)
-        continue;
-      }
-      const float f = trilinear(c.v, c.tx, c.ty, c.tz);
-      if (prev_valid && f_prev >= 0.f && f < 0.f) {
-        const float lam_prev = r.lam0 + (float)(i - 1) * r.dl;
-        lam_star = lam_prev + r.dl * (f_prev / (f_prev - f));
-        hit = true;
-        break;
-      }
-      if (prev_valid && f_prev < 0.f && f >= 0.f) break;      // a back face
-      f_prev = f;
-      prev_valid = true;
-    }
-  }
-  float vx = 0.f, vy = 0.f, vz = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
-  unsigned word = 0u;
-  if (hit) {
-    vx = r.ex + r.dx * lam_star;
-    vy = r.ey + r.dy * lam_star;
-    vz = r.ez + r.dz * lam_star;
-    hit = load_cell(g, table, tsdf, weight, vx, vy, vz, c) == CELL_VALID;
-    if (hit) {
-      const float* v = c.v;
-      // d/dx: the four x-edge differences, lerped along y then z; d/dy: the y-edge differences along x then z; d/dz: along x then y
-      const float gx = lerp2(v[1] - v[0], v[3] - v[2], v[5] - v[4], v[7] - v[6], c.ty, c.tz);
-      const float gy = lerp2(v[2] - v[0], v[3] - v[1], v[6] - v[4], v[7] - v[5], c.tx, c.tz);
-      const float gz = lerp2(v[4] - v[0], v[5] - v[1], v[6] - v[2], v[7] - v[3], c.tx, c.ty);
-      const float gl = sqrtf((gx * gx + gy * gy) + gz * gz);
-      hit = gl > 0.f && isfinite(gl);
-      if (hit) {
-        nx = gx / gl;
-        ny = gy / gl;
-        nz = gz / gl;
-        if (RGB) {
-          word = 255u << 24;
-#pragma unroll
-          for (int ch = 0; ch < 3; ++ch) {
-            float col[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) col[e] = rgb[3 * c.q[e] + ch];
-            word |= rc_unorm8(trilinear(col, c.tx, c.ty, c.tz)) << (8 * ch);
-          }
-        }
-      }
-    }
-  }
-  if (!hit) {
-    lam_star = 0.f;
-    vx = vy = vz = nx = ny = nz = 0.f;
-    word = 0u;
-  }
-  const int64_t p = (int64_t)py * vw.row_stride + px;
-  vw.depth[p] = lam_star;
-  if (vw.vertex != nullptr) {
-    vw.vertex[3 * p] = vx;
-    vw.vertex[3 * p + 1] = vy;
-    vw.vertex[3 * p + 2] = vz;
-  }
-  if (vw.normal != nullptr) {
-    vw.normal[3 * p] = nx;
-    vw.normal[3 * p + 1] = ny;
-    vw.normal[3 * p + 2] = nz;
-  }
-  if (vw.rgba != nullptr) vw.rgba[p] = word;
+  raycast_pixel<RGB>(vw, px, py, BrickVol{g, table, tsdf, weight}, rgb);
 }
 
 // ------------------------------------------------------------------------------------------------ to_dense
@@ -498,24 +338,6 @@ int check_origin(const char* what, const float* origin3, BVol& g) {
   SP3_CHECK(origin3 != nullptr, "%s: null origin", what);
   SP3_CHECK(isfinite(origin3[0]) && isfinite(origin3[1]) && isfinite(origin3[2]), "%s: origin is not finite", what);
   g.ox = origin3[0]; g.oy = origin3[1]; g.oz = origin3[2];
-  return 0;
-}
-
-// the frame checks of sp3_tsdf_integrate; with_rgb: every frame needs rgba
-int check_frames(const char* what, const sp3_tsdf_frame* frames_host, int T, bool with_rgb, int64_t* max_pixels) {
-  int64_t mp = 0;
-  for (int f = 0; f < T; ++f) {
-    const sp3_tsdf_frame& d = frames_host[f];
-    SP3_CHECK((d.depth != nullptr) != (d.pts != nullptr), "%s: frame %d: give depth or pts, exactly one", what, f);
-    SP3_CHECK(d.w >= 1 && d.h >= 1 && d.w <= (1 << 24) && d.h <= (1 << 24) && d.row_stride >= d.w && (int64_t)d.h * d.row_stride < 0x7fffffffLL,
-              "%s: frame %d: bad geometry: %d x %d, row stride %lld", what, f, d.w, d.h, (long long)d.row_stride);
-    SP3_CHECK(!with_rgb || d.rgba != nullptr, "%s: frame %d has no rgba but the pool has colours", what, f);
-    for (int e = 0; e < 12; ++e) SP3_CHECK(isfinite(d.w2c[e]), "%s: frame %d: world-to-camera matrix is not finite", what, f);
-    SP3_CHECK(isfinite(d.fu) && isfinite(d.fv) && isfinite(d.cu) && isfinite(d.cv), "%s: frame %d: intrinsics are not finite", what, f);
-    const int64_t px = (int64_t)d.w * d.h;
-    mp = px > mp ? px : mp;
-  }
-  if (max_pixels != nullptr) *max_pixels = mp;
   return 0;
 }
 
@@ -604,38 +426,20 @@ extern "C" int sp3_tsdf_brick_raycast(const sp3_tsdf_view* views_host, const sp3
   BVol b;
   if (check_grid("sp3_tsdf_brick_raycast", nx, ny, nz, voxel, 0, b)) return 1;
   SP3_CHECK(T >= 0 && T <= 65535, "sp3_tsdf_brick_raycast: T %d must be in 0 .. 65535", T);
-  SP3_CHECK(min_weight > 0.f, "sp3_tsdf_brick_raycast: min_weight %g must be > 0", (double)min_weight);
-  SP3_CHECK(isfinite(step) && step > 0.f, "sp3_tsdf_brick_raycast: step %g must be finite and > 0", (double)step);
-  const double capd = ceil(2.0 * ((double)nx + ny + nz) * (double)voxel / (double)step);
-  SP3_CHECK(capd <= (double)(1 << 24), "sp3_tsdf_brick_raycast: step %g is too small for a grid of %d x %d x %d voxels of %g: over 2^24 samples per ray",
-            (double)step, nx, ny, nz, (double)voxel);
+  RcVol g;
+  g.nx = nx; g.ny = ny; g.nz = nz;
+  g.bx = b.bx; g.by = b.by; g.bz = b.bz;
+  g.voxel = voxel;
+  if (check_march("sp3_tsdf_brick_raycast", min_weight, step, g)) return 1;
   if (T == 0) return 0;
-  SP3_CHECK(views_host != nullptr && views_dev != nullptr, "sp3_tsdf_brick_raycast: null views");
-  int wmax = 0, hmax = 0;
-  for (int f = 0; f < T; ++f) {
-    const sp3_tsdf_view& d = views_host[f];
-    SP3_CHECK(d.depth != nullptr, "sp3_tsdf_brick_raycast: view %d: null depth", f);
-    SP3_CHECK(d.w >= 1 && d.h >= 1 && d.w <= (1 << 24) && d.h <= (1 << 24) && d.row_stride >= d.w && (int64_t)d.h * d.row_stride < 0x7fffffffLL,
-              "sp3_tsdf_brick_raycast: view %d: bad geometry: %d x %d, row stride %lld", f, d.w, d.h, (long long)d.row_stride);
-    SP3_CHECK(d.rgba == nullptr || rgb != nullptr, "sp3_tsdf_brick_raycast: view %d asks for rgba but the pool has no colours", f);
-    for (int e = 0; e < 12; ++e) SP3_CHECK(isfinite(d.c2w[e]), "sp3_tsdf_brick_raycast: view %d: camera-to-world matrix is not finite", f);
-    SP3_CHECK(isfinite(d.fu) && isfinite(d.fv) && isfinite(d.cu) && isfinite(d.cv) && d.fu != 0.f && d.fv != 0.f,
-              "sp3_tsdf_brick_raycast: view %d: intrinsics must be finite, fu and fv not 0", f);
-    SP3_CHECK(d.near >= 0.f && d.near <= d.far, "sp3_tsdf_brick_raycast: view %d: near %g, far %g: 0 <= near <= far", f, (double)d.near, (double)d.far);
-    wmax = d.w > wmax ? d.w : wmax;
-    hmax = d.h > hmax ? d.h : hmax;
-  }
+  int wmax, hmax;
+  if (check_views("sp3_tsdf_brick_raycast", views_host, views_dev, T, rgb != nullptr, wmax, hmax)) return 1;
   if ((int64_t)nx * ny * nz == 0) return 0;
   SP3_CHECK(table != nullptr, "sp3_tsdf_brick_raycast: null table");
   if (check_origin("sp3_tsdf_brick_raycast", origin3, b)) return 1;
-  BRcVol g;
-  g.nx = nx; g.ny = ny; g.nz = nz;
-  g.bx = b.bx; g.by = b.by; g.bz = b.bz;
   g.ox = b.ox; g.oy = b.oy; g.oz = b.oz;
-  g.voxel = voxel; g.min_weight = min_weight; g.step = step;
-  g.cap = (int)capd;
-  const dim3 grid((unsigned)((wmax + RC_TILE - 1) / RC_TILE), (unsigned)((hmax + RC_TILE - 1) / RC_TILE), (unsigned)T);
-  SP3_CHECK(grid.y <= 65535u, "sp3_tsdf_brick_raycast: a view of %d rows: the height must stay below 2^20", hmax);
+  dim3 grid;
+  if (view_grid("sp3_tsdf_brick_raycast", wmax, hmax, T, grid)) return 1;
   hipStream_t st = (hipStream_t)stream;
   if (rgb != nullptr)
     hipLaunchKernelGGL(k_brick_raycast<true>, grid, dim3(RC_TILE * RC_TILE), 0, st, views_dev, g, (const int*)table, tsdf, weight, rgb);

@@ -12,11 +12,15 @@
 // The 16 cases of a tetrahedron are generated at compile time from the rule in the header (make_cases, csrc/tets.h); no table is
 // copied.
 //
+// The per-frame rule of a voxel is integrate_voxel (csrc/tsdf.h), shared with the brick volume (csrc/bricks.hip).
+//
 // Every fp32 operation of the projection, the running average and the interpolation is rounded on its own (no contraction into
-// FMAs): the file-level pragma below is what the compiler honours under its default -ffp-contract=fast-honor-pragmas.
+// FMAs): the file-level pragma below (csrc/tsdf.h and csrc/tets.h set the same for their own text) is what the compiler honours
+// under its default -ffp-contract=fast-honor-pragmas.
 #include "common.h"
 #include "scan.h"
 #include "tets.h"
+#include "tsdf.h"
 #include <math.h>
 
 #pragma clang fp contract(off)
@@ -53,43 +57,7 @@ __global__ __launch_bounds__(BRICK_X * BRICK_Y * BRICK_Z) void k_tsdf_integrate(
     cg = rgb[3 * v + 1];
     cb = rgb[3 * v + 2];
   }
-  for (int f = 0; f < T; ++f) {      // (f is wave-uniform: the descriptor fields arrive by scalar loads)
-    const sp3_tsdf_frame& fr = frames[f];
-    const float* m = fr.w2c;
-    const float zc = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
-    if (!(zc > 0.f)) continue;
-    const float xc = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
-    const float yc = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
-    const float u = fr.fu * xc / zc + fr.cu, w_ = fr.fv * yc / zc + fr.cv;
-    const float fpx = floorf(u + 0.5f), fpy = floorf(w_ + 0.5f);
-    if (!(fpx >= 0.f && fpx < (float)fr.w && fpy >= 0.f && fpy < (float)fr.h)) continue;      // (a NaN fails the test)
-    const int64_t p = (int64_t)fpy * fr.row_stride + (int64_t)fpx;
-    if (fr.valid != nullptr && fr.valid[p] == 0) continue;
-    float d;
-    if (fr.depth != nullptr) {
-      d = fr.depth[p];
-    } else {
-      const float X = fr.pts[3 * p], Y = fr.pts[3 * p + 1], Z = fr.pts[3 * p + 2];
-      d = ((m[8] * X + m[9] * Y) + m[10] * Z) + m[11];
-    }
-    if (!isfinite(d) || d <= 0.f) continue;
-    const float s = d - zc;
-    if (s < -g.trunc) continue;
-    const float q = s / g.trunc;
-    const float fv = q < 1.0f ? q : 1.0f;
-    const float a = fr.pixel_weight != nullptr ? fr.pixel_weight[p] : 1.0f;
-    if (!(a > 0.f) || !isfinite(a)) continue;
-    const float Wn = W + a;
-    D = (W * D + a * fv) / Wn;
-    if (RGB) {
-      const unsigned c = fr.rgba[p];
-      const float r = (float)(c & 255u) / 255.0f, gch = (float)((c >> 8) & 255u) / 255.0f, b = (float)((c >> 16) & 255u) / 255.0f;
-      cr = (W * cr + a * r) / Wn;
-      cg = (W * cg + a * gch) / Wn;
-      cb = (W * cb + a * b) / Wn;
-    }
-    W = Wn;
-  }
+  integrate_voxel<RGB>(frames, T, x, y, z, g.trunc, D, W, cr, cg, cb);
   tsdf[v] = D;
   weight[v] = W;
   if (RGB) {
@@ -260,15 +228,7 @@ extern "C" int sp3_tsdf_integrate(const sp3_tsdf_frame* frames_host, const sp3_t
   SP3_CHECK(frames_host != nullptr && frames_dev != nullptr && origin3 != nullptr && tsdf != nullptr && weight != nullptr,
             "sp3_tsdf_integrate: null frames/origin/tsdf/weight");
   SP3_CHECK(isfinite(origin3[0]) && isfinite(origin3[1]) && isfinite(origin3[2]), "sp3_tsdf_integrate: origin is not finite");
-  for (int f = 0; f < T; ++f) {
-    const sp3_tsdf_frame& d = frames_host[f];
-    SP3_CHECK((d.depth != nullptr) != (d.pts != nullptr), "sp3_tsdf_integrate: frame %d: give depth or pts, exactly one", f);
-    SP3_CHECK(d.w >= 1 && d.h >= 1 && d.w <= (1 << 24) && d.h <= (1 << 24) && d.row_stride >= d.w && (int64_t)d.h * d.row_stride < 0x7fffffffLL,
-              "sp3_tsdf_integrate: frame %d: bad geometry: %d x %d, row stride %lld", f, d.w, d.h, (long long)d.row_stride);
-    SP3_CHECK(rgb == nullptr || d.rgba != nullptr, "sp3_tsdf_integrate: frame %d has no rgba but the volume has colours", f);
-    for (int e = 0; e < 12; ++e) SP3_CHECK(isfinite(d.w2c[e]), "sp3_tsdf_integrate: frame %d: world-to-camera matrix is not finite", f);
-    SP3_CHECK(isfinite(d.fu) && isfinite(d.fv) && isfinite(d.cu) && isfinite(d.cv), "sp3_tsdf_integrate: frame %d: intrinsics are not finite", f);
-  }
+  if (check_frames("sp3_tsdf_integrate", frames_host, T, rgb != nullptr, nullptr)) return 1;
   Vol g;
   g.nx = nx; g.ny = ny; g.nz = nz;
   g.ox = origin3[0]; g.oy = origin3[1]; g.oz = origin3[2];

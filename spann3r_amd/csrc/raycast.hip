@@ -9,66 +9,59 @@
 //
 // sp3_tsdf_track_accum is the fp64 fixed-order sum of csrc/slab.h over the points of the frame: 29 running sums per thread.
 //
-// Every fp32 operation of the ray-caster is rounded on its own (no contraction into FMAs): the file-level pragma below is what the
-// compiler honours under its default -ffp-contract=fast-honor-pragmas.  tests/raycast_ref.py restates it operation for operation.
+// The march of a pixel is raycast_pixel (csrc/tsdf.h), shared with the brick volume (csrc/bricks.hip); this file supplies the dense
+// volume's cell gather.
+//
+// Every fp32 operation of the ray-caster is rounded on its own (no contraction into FMAs): the file-level pragma below (csrc/tsdf.h
+// sets the same for its own text) is what the compiler honours under its default -ffp-contract=fast-honor-pragmas.
+// tests/raycast_ref.py restates it operation for operation.
 #include "common.h"
 #include "slab.h"
+#include "tsdf.h"
 #include <math.h>
 
 #pragma clang fp contract(off)
 
 namespace {
 
-#define RC_TILE 16      // a workgroup's pixel block; its four waves are the 8 x 8 quadrants
+// the dense volume as raycast_pixel's Vol
+struct DenseVol {
+  const RcVol& g;
+  const float* __restrict__ tsdf;
+  const float* __restrict__ weight;
 
-struct RcVol {
-  int nx, ny, nz;
-  float ox, oy, oz, voxel, min_weight, step;
-  int cap;
-};
+  struct Cell {
+    int64_t base;      // linear index of corner 0
+    float tx, ty, tz;
+    float v[8];        // tsdf of corner code c = dx + 2 dy + 4 dz
+  };
 
-__device__ __forceinline__ float lerp(float a, float b, float t) { return a + t * (b - a); }
-
-// the y-then-z (or whichever two axes remain, in the header's order) lerp of four values indexed [first axis][second axis]
-__device__ __forceinline__ float lerp2(float v00, float v10, float v01, float v11, float t1, float t2) {
-  return lerp(lerp(v00, v10, t1), lerp(v01, v11, t1), t2);
-}
-
-__device__ __forceinline__ unsigned rc_unorm8(float c) {      // sp3_pack_rgba8's channel
-  const float s = floorf(c * 255.0f + 0.5f);
-  return s >= 255.0f ? 255u : (s > 0.0f ? (unsigned)s : 0u);
-}
-
-struct Cell {
-  int64_t base;      // linear index of corner 0
-  float tx, ty, tz;
-  float v[8];        // tsdf of corner code c = dx + 2 dy + 4 dz
-};
-
-// The cell of point (px, py, pz) by the header's rule; false: outside the lattice or a corner below min_weight.
-__device__ __forceinline__ bool load_cell(const RcVol& g, const float* __restrict__ tsdf, const float* __restrict__ weight, float px, float py,
-                                          float pz, Cell& c) {
-  const float gx = (px - g.ox) / g.voxel, gy = (py - g.oy) / g.voxel, gz = (pz - g.oz) / g.voxel;
-  const float fx = floorf(gx), fy = floorf(gy), fz = floorf(gz);
-  if (!(fx >= 0.f && fx <= (float)(g.nx - 2) && fy >= 0.f && fy <= (float)(g.ny - 2) && fz >= 0.f && fz <= (float)(g.nz - 2))) return false;
-  c.base = ((int64_t)(int)fz * g.ny + (int)fy) * g.nx + (int)fx;      // (every corner index stays inside the volume: i <= n - 2 per axis)
-  c.tx = gx - fx;
-  c.ty = gy - fy;
-  c.tz = gz - fz;
-  bool seen = true;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int64_t q = c.base + (k & 1) + (int64_t)g.nx * (((k >> 1) & 1) + (int64_t)g.ny * (k >> 2));
-    seen = seen && weight[q] >= g.min_weight;
-    c.v[k] = tsdf[q];
+  __device__ __forceinline__ int64_t corner(const Cell& c, int e) const {
+    return c.base + (e & 1) + (int64_t)g.nx * (((e >> 1) & 1) + (int64_t)g.ny * (e >> 2));
   }
-  return seen;
-}
 
-__device__ __forceinline__ float trilinear(const float (&v)[8], float tx, float ty, float tz) {
-  const float e00 = lerp(v[0], v[1], tx), e10 = lerp(v[2], v[3], tx), e01 = lerp(v[4], v[5], tx), e11 = lerp(v[6], v[7], tx);
-  return lerp(lerp(e00, e10, ty), lerp(e01, e11, ty), tz);
-}
+  // The cell of point (px, py, pz) by the header's rule; INVALID: outside the lattice or a corner below min_weight.
+  __device__ __forceinline__ int load(float px, float py, float pz, Cell& c) const {
+    const float gx = (px - g.ox) / g.voxel, gy = (py - g.oy) / g.voxel, gz = (pz - g.oz) / g.voxel;
+    const float fx = floorf(gx), fy = floorf(gy), fz = floorf(gz);
+    if (!(fx >= 0.f && fx <= (float)(g.nx - 2) && fy >= 0.f && fy <= (float)(g.ny - 2) && fz >= 0.f && fz <= (float)(g.nz - 2)))
+      return CELL_INVALID;
+    c.base = ((int64_t)(int)fz * g.ny + (int)fy) * g.nx + (int)fx;      // (every corner index stays inside the volume: i <= n - 2 per axis)
+    c.tx = gx - fx;
+    c.ty = gy - fy;
+    c.tz = gz - fz;
+    bool seen = true;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int64_t q = corner(c, e);
+      seen = seen && weight[q] >= g.min_weight;
+      c.v[e] = tsdf[q];
+    }
+    return seen ? CELL_VALID : CELL_INVALID;
+  }
+
+  __device__ __forceinline__ int skip(const Ray&, int i, const Cell&) const { return i; }      // (load never says ABSENT)
+};
 
 template <bool RGB>
 __global__ __launch_bounds__(RC_TILE * RC_TILE) void k_tsdf_raycast(const sp3_tsdf_view* __restrict__ views, RcVol g,
@@ -79,108 +72,7 @@ __global__ __launch_bounds__(RC_TILE * RC_TILE) void k_tsdf_raycast(const sp3_ts
   const int px = blockIdx.x * RC_TILE + (wave & 1) * 8 + (lane & 7);
   const int py = blockIdx.y * RC_TILE + (wave >> 1) * 8 + (lane >> 3);
   if (px >= vw.w || py >= vw.h) return;
-  const float* m = vw.c2w;
-  const float xn = ((float)px - vw.cu) / vw.fu, yn = ((float)py - vw.cv) / vw.fv;
-  const float dx = (m[0] * xn + m[1] * yn) + m[2], dy = (m[4] * xn + m[5] * yn) + m[6], dz = (m[8] * xn + m[9] * yn) + m[10];
-  const float ex = m[3], ey = m[7], ez = m[11];
-  const float len = sqrtf((dx * dx + dy * dy) + dz * dz);
-  const float dl = g.step / len;
-  // the voxel-centre lattice's box by slabs
-  float enter = -INFINITY, leave = INFINITY;
-  bool alive = true;
-  {
-    const float d3[3] = {dx, dy, dz}, e3[3] = {ex, ey, ez}, o3[3] = {g.ox, g.oy, g.oz};
-    const int n3[3] = {g.nx, g.ny, g.nz};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const float lo = o3[a], hi = o3[a] + (float)(n3[a] - 1) * g.voxel;
-      if (d3[a] == 0.f) {
-        alive = alive && lo <= e3[a] && e3[a] <= hi;
-      } else {
-        const float q1 = (lo - e3[a]) / d3[a], q2 = (hi - e3[a]) / d3[a];
-        const float small = q2 < q1 ? q2 : q1, large = q2 < q1 ? q1 : q2;
-        enter = small > enter ? small : enter;
-        leave = large < leave ? large : leave;
-      }
-    }
-  }
-  const float lam0 = vw.near > enter ? vw.near : enter, lam1 = vw.far < leave ? vw.far : leave;
-  alive = alive && lam0 <= lam1;      // (a NaN fails)
-  bool hit = false, prev_valid = false;
-  float f_prev = 0.f, lam_star = 0.f;
-  Cell c;
-  if (alive) {
-    for (int i = 0; i < g.cap; ++i) {      // (the cap is a hard bound: no input makes a lane loop without end)
-      const float lam = lam0 + (float)i * dl;
-      if (!(lam <= lam1)) break;
-      const bool ok = load_cell(g, tsdf, weight, ex + dx * lam, ey + dy * lam, ez + dz * lam, c);
-      if (!ok) {
-        prev_valid = false;
-        continue;
-      }
-      const float f = trilinear(c.v, c.tx, c.ty, c.tz);
-      if (prev_valid && f_prev >= 0.f && f < 0.f) {
-        const float lam_prev = lam0 + (float)(i - 1) * dl;
-        lam_star = lam_prev + dl * (f_prev / (f_prev - f));
-        hit = true;
-        break;
-      }
-      if (prev_valid && f_prev < 0.f && f >= 0.f) break;      // a back face
-      f_prev = f;
-      prev_valid = true;
-    }
-  }
-  float vx = 0.f, vy = 0.f, vz = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
-  unsigned word = 0u;
-  if (hit) {
-    vx = ex + dx * lam_star;
-    vy = ey + dy * lam_star;
-    vz = ez + dz * lam_star;
-    hit = load_cell(g, tsdf, weight, vx, vy, vz, c);
-    if (hit) {
-      const float* v = c.v;
-      // d/dx: the four x-edge differences, lerped along y then z; d/dy: the y-edge differences along x then z; d/dz: along x then y
-      const float gx = lerp2(v[1] - v[0], v[3] - v[2], v[5] - v[4], v[7] - v[6], c.ty, c.tz);
-      const float gy = lerp2(v[2] - v[0], v[3] - v[1], v[6] - v[4], v[7] - v[5], c.tx, c.tz);
-      const float gz = lerp2(v[4] - v[0], v[5] - v[1], v[6] - v[2], v[7] - v[3], c.tx, c.ty);
-      const float gl = sqrtf((gx * gx + gy * gy) + gz * gz);
-      hit = gl > 0.f && isfinite(gl);
-      if (hit) {
-        nx = gx / gl;
-        ny = gy / gl;
-        nz = gz / gl;
-        if (RGB) {
-          word = 255u << 24;
-#pragma unroll
-          for (int ch = 0; ch < 3; ++ch) {
-            float col[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-              col[k] = rgb[3 * (c.base + (k & 1) + (int64_t)g.nx * (((k >> 1) & 1) + (int64_t)g.ny * (k >> 2))) + ch];
-            word |= rc_unorm8(trilinear(col, c.tx, c.ty, c.tz)) << (8 * ch);
-          }
-        }
-      }
-    }
-  }
-  if (!hit) {
-    lam_star = 0.f;
-    vx = vy = vz = nx = ny = nz = 0.f;
-    word = 0u;
-  }
-  const int64_t p = (int64_t)py * vw.row_stride + px;
-  vw.depth[p] = lam_star;
-  if (vw.vertex != nullptr) {
-    vw.vertex[3 * p] = vx;
-    vw.vertex[3 * p + 1] = vy;
-    vw.vertex[3 * p + 2] = vz;
-  }
-  if (vw.normal != nullptr) {
-    vw.normal[3 * p] = nx;
-    vw.normal[3 * p + 1] = ny;
-    vw.normal[3 * p + 2] = nz;
-  }
-  if (vw.rgba != nullptr) vw.rgba[p] = word;
+  raycast_pixel<RGB>(vw, px, py, DenseVol{g, tsdf, weight}, rgb);
 }
 
 // ------------------------------------------------------------------------------------------------ tracking
@@ -252,37 +144,20 @@ extern "C" int sp3_tsdf_raycast(const sp3_tsdf_view* views_host, const sp3_tsdf_
                                 float step, void* stream) {
   if (check_rc_volume("sp3_tsdf_raycast", nx, ny, nz, voxel)) return 1;
   SP3_CHECK(T >= 0 && T <= 65535, "sp3_tsdf_raycast: T %d must be in 0 .. 65535", T);
-  SP3_CHECK(min_weight > 0.f, "sp3_tsdf_raycast: min_weight %g must be > 0", (double)min_weight);
-  SP3_CHECK(isfinite(step) && step > 0.f, "sp3_tsdf_raycast: step %g must be finite and > 0", (double)step);
-  const double capd = ceil(2.0 * ((double)nx + ny + nz) * (double)voxel / (double)step);
-  SP3_CHECK(capd <= (double)(1 << 24), "sp3_tsdf_raycast: step %g is too small for a volume of %d x %d x %d voxels of %g: over 2^24 samples per ray",
-            (double)step, nx, ny, nz, (double)voxel);
+  RcVol g;
+  g.nx = nx; g.ny = ny; g.nz = nz;
+  g.bx = g.by = g.bz = 0;
+  g.voxel = voxel;
+  if (check_march("sp3_tsdf_raycast", min_weight, step, g)) return 1;
   if (T == 0) return 0;
-  SP3_CHECK(views_host != nullptr && views_dev != nullptr, "sp3_tsdf_raycast: null views");
-  int wmax = 0, hmax = 0;
-  for (int f = 0; f < T; ++f) {
-    const sp3_tsdf_view& d = views_host[f];
-    SP3_CHECK(d.depth != nullptr, "sp3_tsdf_raycast: view %d: null depth", f);
-    SP3_CHECK(d.w >= 1 && d.h >= 1 && d.w <= (1 << 24) && d.h <= (1 << 24) && d.row_stride >= d.w && (int64_t)d.h * d.row_stride < 0x7fffffffLL,
-              "sp3_tsdf_raycast: view %d: bad geometry: %d x %d, row stride %lld", f, d.w, d.h, (long long)d.row_stride);
-    SP3_CHECK(d.rgba == nullptr || rgb != nullptr, "sp3_tsdf_raycast: view %d asks for rgba but the volume has no colours", f);
-    for (int e = 0; e < 12; ++e) SP3_CHECK(isfinite(d.c2w[e]), "sp3_tsdf_raycast: view %d: camera-to-world matrix is not finite", f);
-    SP3_CHECK(isfinite(d.fu) && isfinite(d.fv) && isfinite(d.cu) && isfinite(d.cv) && d.fu != 0.f && d.fv != 0.f,
-              "sp3_tsdf_raycast: view %d: intrinsics must be finite, fu and fv not 0", f);
-    SP3_CHECK(d.near >= 0.f && d.near <= d.far, "sp3_tsdf_raycast: view %d: near %g, far %g: 0 <= near <= far", f, (double)d.near, (double)d.far);
-    wmax = d.w > wmax ? d.w : wmax;
-    hmax = d.h > hmax ? d.h : hmax;
-  }
+  int wmax, hmax;
+  if (check_views("sp3_tsdf_raycast", views_host, views_dev, T, rgb != nullptr, wmax, hmax)) return 1;
   if ((int64_t)nx * ny * nz == 0) return 0;
   SP3_CHECK(origin3 != nullptr && tsdf != nullptr && weight != nullptr, "sp3_tsdf_raycast: null origin/tsdf/weight");
   SP3_CHECK(isfinite(origin3[0]) && isfinite(origin3[1]) && isfinite(origin3[2]), "sp3_tsdf_raycast: origin is not finite");
-  RcVol g;
-  g.nx = nx; g.ny = ny; g.nz = nz;
   g.ox = origin3[0]; g.oy = origin3[1]; g.oz = origin3[2];
-  g.voxel = voxel; g.min_weight = min_weight; g.step = step;
-  g.cap = (int)capd;
-  const dim3 grid((unsigned)((wmax + RC_TILE - 1) / RC_TILE), (unsigned)((hmax + RC_TILE - 1) / RC_TILE), (unsigned)T);
-  SP3_CHECK(grid.y <= 65535u, "sp3_tsdf_raycast: a view of %d rows: the height must stay below 2^20", hmax);
+  dim3 grid;
+  if (view_grid("sp3_tsdf_raycast", wmax, hmax, T, grid)) return 1;
   hipStream_t st = (hipStream_t)stream;
   if (rgb != nullptr)
     hipLaunchKernelGGL(k_tsdf_raycast<true>, grid, dim3(RC_TILE * RC_TILE), 0, st, views_dev, g, tsdf, weight, rgb);

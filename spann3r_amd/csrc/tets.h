@@ -1,14 +1,11 @@
 // The marching-tetrahedra rule of include/spann3r_hip.h ("TSDF fusion", sp3_tsdf_extract) as tables and helpers, shared by
 // csrc/fusion.hip (the dense volume) and csrc/brick_mesh.hip (the brick pool) so that both extractions use one statement of it:
-// the Kuhn cut, the 7 edge slots, the 16 cases of a tetrahedron (generated at compile time from the header's rule; no table is
-// copied) and the colour channel's rounding.  Everything here is per translation unit (anonymous namespace).
+// the Kuhn cut, the 7 edge slots and the 16 cases of a tetrahedron (generated at compile time from the header's rule; no table is
+// copied).  The colour channel's rounding, unorm8, comes with csrc/tsdf.h, which switches contraction off for itself and for what
+// follows it.  Everything here is per translation unit (anonymous namespace).
 #pragma once
 #include "common.h"
-#include <math.h>
-
-// unorm8's multiply and add are rounded one by one, like every fp32 operation of the two files that include this one (which set
-// the same pragma for themselves; it holds from here to the end of the translation unit).
-#pragma clang fp contract(off)
+#include "tsdf.h"
 
 namespace {
 
@@ -80,10 +77,5 @@ constexpr Cases make_cases() {
   return t;
 }
 __device__ const Cases CASES = make_cases();
-
-__device__ __forceinline__ unsigned unorm8(float c) {      // sp3_pack_rgba8's channel: floor(c * 255 + 0.5), clamped; NaN gives 0
-  const float s = floorf(c * 255.0f + 0.5f);
-  return s >= 255.0f ? 255u : (s > 0.0f ? (unsigned)s : 0u);
-}
 
 }  // namespace

@@ -103,40 +103,28 @@ def camera_tables(intrinsics, cam2world, T):
     return np.stack([K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]], axis=1), w2c[:, :3, :].reshape(T, 12).astype(np.float32)
 
 
-class TSDFVolume:
-    """A truncated signed distance volume on the device: tsdf fp32 [nz, ny, nx] (initial 1), weight (initial 0) and, with color,
-    rgb fp32 [nz, ny, nx, 3] in [0, 1].  Voxel (i, j, k) has its centre at origin + (i, j, k) * voxel_size.  trunc defaults to
-    3 voxels."""
+class _Volume:
+    """What TSDFVolume and BrickTSDFVolume share: the lattice parameters, the frame and view descriptor tables, the argument handling
+    of integrate / raycast / extract.  A volume class adds its storage (tsdf, weight, rgb or None, dims) and its launches:
+    integrate_table, _raycast_launch, extract_raw."""
 
-    def __init__(self, origin, voxel_size, dims, trunc=None, color=True, device="cuda"):
-        self.dims = _check_dims(dims)
+    def _set_lattice(self, origin, voxel_size, trunc, device):
+        """origin, voxel_size, trunc (None: 3 voxels) and device, validated; messages carry the volume class's name"""
+        name = type(self).__name__
         origin = np.asarray(origin, np.float64).reshape(-1)
         if origin.shape != (3,) or not np.isfinite(origin).all():
-            raise ValueError("TSDFVolume: origin must be three finite numbers")
+            raise ValueError("%s: origin must be three finite numbers" % name)
         self.voxel_size = float(np.float32(voxel_size))
         if not (self.voxel_size > 0 and math.isfinite(self.voxel_size)):
-            raise ValueError("TSDFVolume: voxel_size must be positive and finite, got %r" % (voxel_size,))
+            raise ValueError("%s: voxel_size must be positive and finite, got %r" % (name, voxel_size))
         self.trunc = float(np.float32(3.0 * self.voxel_size if trunc is None else trunc))
         if not (self.trunc > 0 and math.isfinite(self.trunc)):
-            raise ValueError("TSDFVolume: trunc must be positive and finite, got %r" % (trunc,))
+            raise ValueError("%s: trunc must be positive and finite, got %r" % (name, trunc))
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise RuntimeError("TSDFVolume: fusion runs on the GPU (HIP kernels); there is no CPU path")
+            raise RuntimeError("%s: fusion runs on the GPU (HIP kernels); there is no CPU path" % name)
         self.origin = origin.astype(np.float32)
         self._origin_c = (C.c_float * 3)(*self.origin.tolist())
-        nx, ny, nz = self.dims
-        self.tsdf = torch.empty((nz, ny, nx), dtype=torch.float32, device=self.device)
-        self.weight = torch.empty((nz, ny, nx), dtype=torch.float32, device=self.device)
-        self.rgb = torch.empty((nz, ny, nx, 3), dtype=torch.float32, device=self.device) if color else None
-        self.launches = 0                   # sp3_tsdf_integrate launches so far
-        self.raycasts = 0                   # sp3_tsdf_raycast launches so far
-        self.reset()
-
-    def reset(self):
-        self.tsdf.fill_(1.0)
-        self.weight.zero_()
-        if self.rgb is not None:
-            self.rgb.zero_()
 
     def integrate(self, depth=None, pts=None, intrinsics=None, cam2world=None, valid=None, weight=None, images=None):
         """T frames into the volume in ONE launch.  depth [T, h, w] (camera z) or pts [T, h, w, 3] (world points; the depth of a pixel
@@ -153,9 +141,10 @@ class TSDFVolume:
             return self
         return self.integrate_table(self.frame_table(src, depth is not None, intrinsics, cam2world, valid, weight, images))
 
-    def frame_table(self, src, is_depth, intrinsics, cam2world, valid=None, weight=None, images=None):
+    def frame_table(self, src, is_depth, intrinsics, cam2world, valid=None, weight=None, images=None, need_images=True):
         """The descriptor table of `integrate` for the list `src` of depth maps (is_depth) or pointmaps: (host table, device copy, T,
-        the tensors it points to).  integrate_table launches it; a table can be launched again as long as its tensors live."""
+        the tensors it points to).  integrate_table launches it; a table can be launched again as long as its tensors live.
+        need_images=False: the table is not for integrating (BrickTSDFVolume.allocate), so a volume with colours asks for no images."""
         T = len(src)
         depth = src if is_depth else None
         fk, w2c = camera_tables(intrinsics, cam2world, T)
@@ -164,7 +153,7 @@ class TSDFVolume:
         for name, m in maps.items():
             if m is not None and len(m) != T:
                 raise RuntimeError("integrate: mismatched lengths: %d frames, %d %s maps" % (T, len(m), name))
-        if self.rgb is not None and maps["images"] is None:
+        if need_images and self.rgb is not None and maps["images"] is None:
             raise ValueError("integrate: the volume has colours: pass images (or build it with color=False)")
         lib = L.load()
         st = L.stream_ptr()
@@ -201,78 +190,6 @@ class TSDFVolume:
             e.w2c[:] = w2c[i].tolist()
         table_d = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(self.device)
         return table, table_d, T, keep
-
-    def integrate_table(self, tbl):
-        """one sp3_tsdf_integrate launch of a frame_table"""
-        table, table_d, T, _ = tbl
-        lib, st = L.load(), L.stream_ptr()
-        nx, ny, nz = self.dims
-        L.check(lib.sp3_tsdf_integrate(table, table_d.data_ptr(), T, nx, ny, nz, self._origin_c, self.voxel_size, self.trunc,
-                                       self.tsdf.data_ptr(), self.weight.data_ptr(), L.ptr(self.rgb), st), "sp3_tsdf_integrate")
-        self.launches += 1
-        return self
-
-    def extract_raw(self, min_weight=1.0, max_vertices=None, max_faces=None):
-        """sp3_tsdf_extract as it is: -> (vertices fp32 [cap, 3], rgba int32 [cap], faces int32 [cap, 3], counts int32 [2] on the
-        device = the true V and F).  Nothing beyond the capacities is written; nothing synchronises."""
-        nx, ny, nz = self.dims
-        n = nx * ny * nz
-        lib = L.load()
-        cap_v = int(max_vertices) if max_vertices is not None else min(7 * n, max(4096, n // 4))
-        cap_f = int(max_faces) if max_faces is not None else min(12 * n, 2 * cap_v)
-        vertices = torch.empty((max(cap_v, 1), 3), dtype=torch.float32, device=self.device)
-        rgba = torch.empty(max(cap_v, 1), dtype=torch.int32, device=self.device)
-        faces = torch.empty((max(cap_f, 1), 3), dtype=torch.int32, device=self.device)
-        counts = torch.zeros(2, dtype=torch.int32, device=self.device)
-        ws = torch.empty(max(int(lib.sp3_tsdf_extract_ws_bytes(nx, ny, nz)), 16), dtype=torch.uint8, device=self.device)
-        L.check(lib.sp3_tsdf_extract(self.tsdf.data_ptr(), self.weight.data_ptr(), L.ptr(self.rgb), nx, ny, nz, self._origin_c, self.voxel_size,
-                                     float(min_weight), ws.data_ptr(), cap_v, cap_f, vertices.data_ptr(), rgba.data_ptr(), faces.data_ptr(),
-                                     counts.data_ptr(), L.stream_ptr()), "sp3_tsdf_extract")
-        return vertices[:cap_v], rgba[:cap_v], faces[:cap_f], counts
-
-    def extract_mesh(self, min_weight=1.0, scale=1.0, transform=None, min_component_faces=0, keep_largest=None, simplify_cell=None):
-        """The zero level as a welded mesh of the voxels seen with weight >= min_weight: dict(vertices fp32 [V, 3], colors uint8
-        [V, 4], faces int32 [F, 3], bounds float32 numpy [2, 3]), the shape of mesh.scene_mesh; positions are transform (scale x).
-        The counts are read once on the host; if the first guess of the capacities was too small the extraction runs once more with
-        the reported sizes.  Vertices that no face uses are dropped (mesh.compact_vertices).
-        min_component_faces > 0 or keep_largest = k: the floaters go (mesh.select_components, the rule of mesh.filter_components) --
-        only the faces of connected components with at least that many faces, and among the k largest, are kept, before the vertices
-        are compacted (once); the dict then also has components = dict(total, kept, faces_removed).  With the defaults nothing of
-        that runs.
-        simplify_cell = c (world units, before scale): the surface is simplified by vertex clustering (mesh.simplify) on the grid of
-        cell c from the volume's origin, after the component filter -- clustering can join a floater to the surface -- and before
-        the final compaction, which applies scale / transform; the result is mesh.simplify(extract_mesh(...), c, origin) and the
-        dict also has simplify = dict(cell, clusters, faces_in, faces_collapsed, faces_duplicate, faces_invalid).  None: nothing
-        of that runs."""
-        if not min_weight > 0:
-            raise ValueError("extract_mesh: min_weight must be > 0, got %r" % (min_weight,))
-        if simplify_cell is not None and not (simplify_cell > 0 and math.isfinite(simplify_cell)):
-            raise ValueError("extract_mesh: simplify_cell must be positive and finite, got %r" % (simplify_cell,))
-        if min_component_faces < 0 or (keep_largest is not None and keep_largest < 0):
-            raise ValueError("extract_mesh: min_component_faces %r and keep_largest %r must be >= 0" % (min_component_faces, keep_largest))
-        vertices, rgba, faces, counts = self.extract_raw(min_weight)
-        nv, nf = counts.cpu().tolist()
-        if nv > vertices.shape[0] or nf > faces.shape[0]:
-            vertices, rgba, faces, counts = self.extract_raw(min_weight, nv, nf)
-            nv2, nf2 = counts.cpu().tolist()
-            if (nv2, nf2) != (nv, nf):
-                raise RuntimeError("extract_mesh: the volume changed between two extractions (%d, %d) -> (%d, %d)" % (nv, nf, nv2, nf2))
-        faces = faces[:nf].contiguous()
-        stats = None
-        if min_component_faces > 0 or keep_largest is not None:
-            faces, stats = M.select_components(faces, nv, min_component_faces, keep_largest)
-        if simplify_cell is None:
-            pos, col, bounds = M.compact_vertices(vertices[:nv].contiguous(), rgba[:nv].contiguous(), faces=faces, scale=scale, transform=transform)
-        else:      # only the vertices the kept faces name enter a cluster: compact first, unscaled, then cluster, then scale / transform
-            pos, col, bounds = M.compact_vertices(vertices[:nv].contiguous(), rgba[:nv].contiguous(), faces=faces)
-        if pos.shape[0] == 0:
-            faces = faces[:0]
-        out = dict(vertices=pos, colors=col.contiguous().view(torch.uint8).reshape(-1, 4), faces=faces, bounds=bounds)
-        if simplify_cell is not None:
-            out = M.simplify(out, simplify_cell, origin=self.origin, scale=scale, transform=transform)
-        if stats is not None:
-            out["components"] = stats
-        return out
 
     def raycast(self, intrinsics, cam2world, size, near=0.0, far=math.inf, step_voxels=1.0, min_weight=1.0, vertices=True, normals=True,
                 colors=None):
@@ -327,7 +244,7 @@ class TSDFVolume:
         return table, table_d, T, out
 
     def raycast_table(self, tbl, step_voxels=1.0, min_weight=1.0):
-        """one sp3_tsdf_raycast launch of a view_table -> its maps"""
+        """one ray-cast launch of a view_table -> its maps"""
         table, table_d, T, out = tbl
         if not (step_voxels >= 0.25 and math.isfinite(step_voxels)):
             raise ValueError("raycast: step_voxels must be finite and >= 0.25, got %r" % (step_voxels,))
@@ -335,15 +252,119 @@ class TSDFVolume:
             raise ValueError("raycast: min_weight must be > 0, got %r" % (min_weight,))
         if T == 0:
             return out
-        nx, ny, nz = self.dims
         step = float(np.float32(np.float32(step_voxels) * np.float32(self.voxel_size)))
-        L.check(L.load().sp3_tsdf_raycast(table, table_d.data_ptr(), T, nx, ny, nz, self._origin_c, self.voxel_size, self.tsdf.data_ptr(),
-                                          self.weight.data_ptr(), L.ptr(self.rgb), float(min_weight), step, L.stream_ptr()), "sp3_tsdf_raycast")
+        self._raycast_launch(table, table_d, T, float(min_weight), step)
         self.raycasts += 1
         return out
 
+    def _mesh_buffers(self, n, max_vertices, max_faces):
+        """extract_raw's capacities for n voxels (the first guesses when None is given) and output buffers:
+        -> (cap_v, cap_f, vertices fp32 [cap, 3], rgba int32 [cap], faces int32 [cap, 3], counts int32 [2] zeroed)"""
+        cap_v = int(max_vertices) if max_vertices is not None else min(7 * n, max(4096, n // 4))
+        cap_f = int(max_faces) if max_faces is not None else min(12 * n, 2 * cap_v)
+        vertices = torch.empty((max(cap_v, 1), 3), dtype=torch.float32, device=self.device)
+        rgba = torch.empty(max(cap_v, 1), dtype=torch.int32, device=self.device)
+        faces = torch.empty((max(cap_f, 1), 3), dtype=torch.int32, device=self.device)
+        counts = torch.zeros(2, dtype=torch.int32, device=self.device)
+        return cap_v, cap_f, vertices, rgba, faces, counts
 
-class BrickTSDFVolume:
+    def extract_mesh(self, min_weight=1.0, scale=1.0, transform=None, min_component_faces=0, keep_largest=None, simplify_cell=None):
+        """The zero level as a welded mesh of the voxels seen with weight >= min_weight: dict(vertices fp32 [V, 3], colors uint8
+        [V, 4], faces int32 [F, 3], bounds float32 numpy [2, 3]), the shape of mesh.scene_mesh; positions are transform (scale x).
+        The counts are read once on the host; if the first guess of the capacities was too small the extraction runs once more with
+        the reported sizes.  Vertices that no face uses are dropped (mesh.compact_vertices).
+        min_component_faces > 0 or keep_largest = k: the floaters go (mesh.select_components, the rule of mesh.filter_components) --
+        only the faces of connected components with at least that many faces, and among the k largest, are kept, before the vertices
+        are compacted (once); the dict then also has components = dict(total, kept, faces_removed).  With the defaults nothing of
+        that runs.
+        simplify_cell = c (world units, before scale): the surface is simplified by vertex clustering (mesh.simplify) on the grid of
+        cell c from the volume's origin, after the component filter -- clustering can join a floater to the surface -- and before
+        the final compaction, which applies scale / transform; the result is mesh.simplify(extract_mesh(...), c, origin) and the
+        dict also has simplify = dict(cell, clusters, faces_in, faces_collapsed, faces_duplicate, faces_invalid).  None: nothing
+        of that runs."""
+        if not min_weight > 0:
+            raise ValueError("extract_mesh: min_weight must be > 0, got %r" % (min_weight,))
+        if simplify_cell is not None and not (simplify_cell > 0 and math.isfinite(simplify_cell)):
+            raise ValueError("extract_mesh: simplify_cell must be positive and finite, got %r" % (simplify_cell,))
+        if min_component_faces < 0 or (keep_largest is not None and keep_largest < 0):
+            raise ValueError("extract_mesh: min_component_faces %r and keep_largest %r must be >= 0" % (min_component_faces, keep_largest))
+        vertices, rgba, faces, counts = self.extract_raw(min_weight)
+        nv, nf = counts.cpu().tolist()
+        if nv > vertices.shape[0] or nf > faces.shape[0]:
+            vertices, rgba, faces, counts = self.extract_raw(min_weight, nv, nf)
+            nv2, nf2 = counts.cpu().tolist()
+            if (nv2, nf2) != (nv, nf):
+                raise RuntimeError("extract_mesh: the volume changed between two extractions (%d, %d) -> (%d, %d)" % (nv, nf, nv2, nf2))
+        faces = faces[:nf].contiguous()
+        stats = None
+        if min_component_faces > 0 or keep_largest is not None:
+            faces, stats = M.select_components(faces, nv, min_component_faces, keep_largest)
+        if simplify_cell is None:
+            pos, col, bounds = M.compact_vertices(vertices[:nv].contiguous(), rgba[:nv].contiguous(), faces=faces, scale=scale, transform=transform)
+        else:      # only the vertices the kept faces name enter a cluster: compact first, unscaled, then cluster, then scale / transform
+            pos, col, bounds = M.compact_vertices(vertices[:nv].contiguous(), rgba[:nv].contiguous(), faces=faces)
+        if pos.shape[0] == 0:
+            faces = faces[:0]
+        out = dict(vertices=pos, colors=col.contiguous().view(torch.uint8).reshape(-1, 4), faces=faces, bounds=bounds)
+        if simplify_cell is not None:
+            out = M.simplify(out, simplify_cell, origin=self.origin, scale=scale, transform=transform)
+        if stats is not None:
+            out["components"] = stats
+        return out
+
+
+class TSDFVolume(_Volume):
+    """A truncated signed distance volume on the device: tsdf fp32 [nz, ny, nx] (initial 1), weight (initial 0) and, with color,
+    rgb fp32 [nz, ny, nx, 3] in [0, 1].  Voxel (i, j, k) has its centre at origin + (i, j, k) * voxel_size.  trunc defaults to
+    3 voxels."""
+
+    def __init__(self, origin, voxel_size, dims, trunc=None, color=True, device="cuda"):
+        self.dims = _check_dims(dims)
+        self._set_lattice(origin, voxel_size, trunc, device)
+        nx, ny, nz = self.dims
+        self.tsdf = torch.empty((nz, ny, nx), dtype=torch.float32, device=self.device)
+        self.weight = torch.empty((nz, ny, nx), dtype=torch.float32, device=self.device)
+        self.rgb = torch.empty((nz, ny, nx, 3), dtype=torch.float32, device=self.device) if color else None
+        self.launches = 0                   # sp3_tsdf_integrate launches so far
+        self.raycasts = 0                   # sp3_tsdf_raycast launches so far
+        self.reset()
+
+    def reset(self):
+        self.tsdf.fill_(1.0)
+        self.weight.zero_()
+        if self.rgb is not None:
+            self.rgb.zero_()
+
+    def integrate_table(self, tbl):
+        """one sp3_tsdf_integrate launch of a frame_table"""
+        table, table_d, T, _ = tbl
+        lib, st = L.load(), L.stream_ptr()
+        nx, ny, nz = self.dims
+        L.check(lib.sp3_tsdf_integrate(table, table_d.data_ptr(), T, nx, ny, nz, self._origin_c, self.voxel_size, self.trunc,
+                                       self.tsdf.data_ptr(), self.weight.data_ptr(), L.ptr(self.rgb), st), "sp3_tsdf_integrate")
+        self.launches += 1
+        return self
+
+    def _raycast_launch(self, table, table_d, T, min_weight, step):
+        nx, ny, nz = self.dims
+        L.check(L.load().sp3_tsdf_raycast(table, table_d.data_ptr(), T, nx, ny, nz, self._origin_c, self.voxel_size, self.tsdf.data_ptr(),
+                                          self.weight.data_ptr(), L.ptr(self.rgb), min_weight, step, L.stream_ptr()), "sp3_tsdf_raycast")
+
+    def extract_raw(self, min_weight=1.0, max_vertices=None, max_faces=None):
+        """sp3_tsdf_extract as it is: -> (vertices fp32 [cap, 3], rgba int32 [cap], faces int32 [cap, 3], counts int32 [2] on the
+        device = the true V and F).  Nothing beyond the capacities is written; nothing synchronises."""
+        nx, ny, nz = self.dims
+        n = nx * ny * nz
+        lib = L.load()
+        cap_v, cap_f, vertices, rgba, faces, counts = self._mesh_buffers(n, max_vertices, max_faces)
+        ws = torch.empty(max(int(lib.sp3_tsdf_extract_ws_bytes(nx, ny, nz)), 16), dtype=torch.uint8, device=self.device)
+        L.check(lib.sp3_tsdf_extract(self.tsdf.data_ptr(), self.weight.data_ptr(), L.ptr(self.rgb), nx, ny, nz, self._origin_c, self.voxel_size,
+                                     float(min_weight), ws.data_ptr(), cap_v, cap_f, vertices.data_ptr(), rgba.data_ptr(), faces.data_ptr(),
+                                     counts.data_ptr(), L.stream_ptr()), "sp3_tsdf_extract")
+        return vertices[:cap_v], rgba[:cap_v], faces[:cap_f], counts
+
+
+class BrickTSDFVolume(_Volume):
     """The volume of TSDFVolume on two levels (include/spann3r_hip.h "Brick TSDF volume", csrc/bricks.hip): a virtual grid of `dims`
     voxels (rounded up to multiples of 8) whose 8 x 8 x 8 bricks are allocated where measurements land -- every brick within `band`
     (metric, default trunc, at most 8 voxels) of a measured point -- and a pool of `capacity` bricks that doubles when it runs out.
@@ -364,23 +385,10 @@ class BrickTSDFVolume:
             raise ValueError("BrickTSDFVolume: capacity must be >= 1, got %r" % (capacity,))
         if max(self.dims) >= 2 ** 20 or 2 * n_table + 256 >= 2 ** 31:
             raise ValueError("BrickTSDFVolume: dims %s over the index limit: %d bricks (bricks + capacity must stay below 2^31)" % (self.dims, n_table))
-        origin = np.asarray(origin, np.float64).reshape(-1)
-        if origin.shape != (3,) or not np.isfinite(origin).all():
-            raise ValueError("BrickTSDFVolume: origin must be three finite numbers")
-        self.voxel_size = float(np.float32(voxel_size))
-        if not (self.voxel_size > 0 and math.isfinite(self.voxel_size)):
-            raise ValueError("BrickTSDFVolume: voxel_size must be positive and finite, got %r" % (voxel_size,))
-        self.trunc = float(np.float32(3.0 * self.voxel_size if trunc is None else trunc))
-        if not (self.trunc > 0 and math.isfinite(self.trunc)):
-            raise ValueError("BrickTSDFVolume: trunc must be positive and finite, got %r" % (trunc,))
+        self._set_lattice(origin, voxel_size, trunc, device)
         self.band = float(np.float32(self.trunc if band is None else band))
         if not (0 < self.band <= float(np.float32(8.0) * np.float32(self.voxel_size))):
             raise ValueError("BrickTSDFVolume: band %r must lie in (0, 8 voxels = %g]" % (self.band, 8 * self.voxel_size))
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("BrickTSDFVolume: fusion runs on the GPU (HIP kernels); there is no CPU path")
-        self.origin = origin.astype(np.float32)
-        self._origin_c = (C.c_float * 3)(*self.origin.tolist())
         self.color = bool(color)
         dev = self.device
         self.table = torch.empty(max(n_table, 1), dtype=torch.int32, device=dev)[:n_table]
@@ -417,14 +425,9 @@ class BrickTSDFVolume:
         ts += [self._mesh_ws] if self._mesh_ws is not None else []
         return sum(t.numel() * t.element_size() for t in ts)
 
-    # the argument handling, the frame and view descriptors are TSDFVolume's own (they use self.rgb and self.device only)
-    integrate = TSDFVolume.integrate
-    raycast = TSDFVolume.raycast
-    view_table = TSDFVolume.view_table
-
-    def frame_table(self, src, is_depth, intrinsics, cam2world, valid=None, weight=None, images=None):
-        """TSDFVolume.frame_table plus, as a fifth entry, the device fp32 [T, 12] camera-to-world matrices `mark` reads for depth frames"""
-        tbl = TSDFVolume.frame_table(self, src, is_depth, intrinsics, cam2world, valid, weight, images)
+    def frame_table(self, src, is_depth, intrinsics, cam2world, valid=None, weight=None, images=None, need_images=True):
+        """the base's frame_table plus, as a fifth entry, the device fp32 [T, 12] camera-to-world matrices `mark` reads for depth frames"""
+        tbl = super().frame_table(src, is_depth, intrinsics, cam2world, valid, weight, images, need_images)
         P = _host_mats(cam2world, tbl[2], (4, 4), "cam2world")
         c2w = torch.from_numpy(np.ascontiguousarray(P[:, :3, :].reshape(tbl[2], 12).astype(np.float32))).to(self.device)
         return tbl + (c2w,)
@@ -439,12 +442,7 @@ class BrickTSDFVolume:
         src = _frames_list(depth, "depth", ()) if depth is not None else _frames_list(pts, "pts", (3,))
         if len(src) == 0:
             return self
-        rgb, self.rgb = self.rgb, None          # (no colour maps needed to mark)
-        try:
-            tbl = self.frame_table(src, depth is not None, intrinsics, cam2world, valid, weight, None)
-        finally:
-            self.rgb = rgb
-        return self.allocate_table(tbl)
+        return self.allocate_table(self.frame_table(src, depth is not None, intrinsics, cam2world, valid, weight, need_images=False))
 
     def allocate_table(self, tbl):
         table, table_d, T, _, c2w = tbl
@@ -481,22 +479,11 @@ class BrickTSDFVolume:
         self.launches += 1
         return self
 
-    def raycast_table(self, tbl, step_voxels=1.0, min_weight=1.0):
-        """one sp3_tsdf_brick_raycast launch of a view_table -> its maps"""
-        table, table_d, T, out = tbl
-        if not (step_voxels >= 0.25 and math.isfinite(step_voxels)):
-            raise ValueError("raycast: step_voxels must be finite and >= 0.25, got %r" % (step_voxels,))
-        if not min_weight > 0:
-            raise ValueError("raycast: min_weight must be > 0, got %r" % (min_weight,))
-        if T == 0:
-            return out
+    def _raycast_launch(self, table, table_d, T, min_weight, step):
         nx, ny, nz = self.dims
-        step = float(np.float32(np.float32(step_voxels) * np.float32(self.voxel_size)))
         L.check(L.load().sp3_tsdf_brick_raycast(table, table_d.data_ptr(), T, nx, ny, nz, self._origin_c, self.voxel_size, self.table.data_ptr(),
-                                                self.tsdf.data_ptr(), self.weight.data_ptr(), L.ptr(self.rgb), float(min_weight), step,
+                                                self.tsdf.data_ptr(), self.weight.data_ptr(), L.ptr(self.rgb), min_weight, step,
                                                 L.stream_ptr()), "sp3_tsdf_brick_raycast")
-        self.raycasts += 1
-        return out
 
     def brick_box(self):
         """(lo, size) in voxels of the bounding box of the allocated bricks; size 0 without any"""
@@ -534,14 +521,8 @@ class BrickTSDFVolume:
         if self.n_bricks > BRICK_MESH_LIMIT:
             raise ValueError("extract_raw: %d bricks over the index limit: 12 * 512 * n_bricks must stay below 2^31 (int32 vertex and face "
                              "indices), at most %d bricks" % (self.n_bricks, BRICK_MESH_LIMIT))
-        n = 512 * self.n_bricks
         lib = L.load()
-        cap_v = int(max_vertices) if max_vertices is not None else min(7 * n, max(4096, n // 4))
-        cap_f = int(max_faces) if max_faces is not None else min(12 * n, 2 * cap_v)
-        vertices = torch.empty((max(cap_v, 1), 3), dtype=torch.float32, device=self.device)
-        rgba = torch.empty(max(cap_v, 1), dtype=torch.int32, device=self.device)
-        faces = torch.empty((max(cap_f, 1), 3), dtype=torch.int32, device=self.device)
-        counts = torch.zeros(2, dtype=torch.int32, device=self.device)
+        cap_v, cap_f, vertices, rgba, faces, counts = self._mesh_buffers(512 * self.n_bricks, max_vertices, max_faces)
         if self._mesh_ws is None:
             self._mesh_ws = torch.empty(max(int(lib.sp3_tsdf_brick_extract_ws_bytes(min(self.capacity, BRICK_MESH_LIMIT))), 16), dtype=torch.uint8,
                                         device=self.device)
@@ -562,7 +543,7 @@ class BrickTSDFVolume:
         TSDFVolume.extract_mesh's, on both routes (the dense route clusters on the grid from the box's origin)."""
         if not direct:
             return self.to_dense(dims_limit=dims_limit).extract_mesh(min_weight, scale, transform, min_component_faces, keep_largest, simplify_cell)
-        return TSDFVolume.extract_mesh(self, min_weight, scale, transform, min_component_faces, keep_largest, simplify_cell)
+        return super().extract_mesh(min_weight, scale, transform, min_component_faces, keep_largest, simplify_cell)
 
 
 def _extent_box(extent):

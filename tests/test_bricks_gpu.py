@@ -242,6 +242,22 @@ def test_raycast_step_and_min_weight(frames, fused):
         assert _assert_same_maps(*fused, frames[4]["K"], frames[4]["cam2world"][None], **kw) > 0.2
 
 
+def test_raycast_of_a_colourless_volume_equals_the_dense_raycaster(frames):
+    """k_brick_raycast<false> against k_tsdf_raycast<false> directly: depth, vertices and normals of one scene camera, bit for bit"""
+    vol = _brick(color=False).integrate(**_args(frames, images=False))
+    dense = vol.to_dense(FULL)
+    assert vol.rgb is None and dense.rgb is None and vol.n_bricks == 376
+    fr = frames[2]
+    a, b = vol.raycast(fr["K"], fr["cam2world"][None], SIZE), dense.raycast(fr["K"], fr["cam2world"][None], SIZE)
+    assert sorted(a) == sorted(b) == ["depth", "normals", "vertices"]
+    for k in a:
+        x, y = a[k].contiguous(), b[k].contiguous()
+        assert x.shape == y.shape and torch.equal(x.view(torch.uint8), y.view(torch.uint8)), k
+    hit = float((a["depth"] != 0).float().mean())
+    print("hit share", hit)
+    assert hit >= 0.5                                                                             # (the main view: 72.9 % with colours)
+
+
 def test_track_frame_on_bricks_equals_track_frame_on_the_dense_volume(frames):
     from spann3r_amd import fusion as F
     vol = _brick(color=False).integrate(**_args(frames[:3], images=False))
