@@ -173,6 +173,11 @@ def main():
                     "the units of the pointmaps (mesh.simplify, on the device): with --fused the fused surface, after --min_component; with "
                     "--save_glb alone the per-frame sheets, which it welds into one vertex set; prints the faces before and after")
     ap.add_argument("--simplify_voxels", type=float, default=None, metavar="K", help="with --fused: --simplify with a cell of K voxels")
+    ap.add_argument("--eval_samples", type=int, default=None, metavar="N", help="with --fused --rgbd --eval: a second fused line from N points "
+                    "drawn by area from each fused surface with their exact face normals (evaluate.evaluate_meshes), next to the line "
+                    "that scores the mesh vertices")
+    ap.add_argument("--glb_normals", action="store_true", help="with --save_glb: write area-weighted vertex normals (mesh.vertex_normals, on "
+                    "the device) as the NORMAL attribute of the fused or per-frame mesh, so that viewers light it")
     ap.add_argument("--extent", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"), help="with --stream --fused "
                     "--bricks: the box the session may fuse in (default: a cube of +-4 units around the first camera)")
     ap.add_argument("--voxel_size", type=float, default=None, help="with --fused: voxel edge in the units of the pointmaps (default: the "
@@ -202,6 +207,14 @@ def main():
         ap.error("--simplify needs --fused or --save_glb (a mesh to simplify)")
     if args.simplify is not None and args.simplify_voxels is not None:
         ap.error("--simplify and --simplify_voxels exclude each other")
+    if args.eval_samples is not None and not (args.fused and args.rgbd and args.eval):
+        ap.error("--eval_samples needs --fused --rgbd --eval (two fused surfaces to sample)")
+    if args.eval_samples is not None and args.eval_samples <= 0:
+        ap.error("--eval_samples must be positive")
+    if args.glb_normals and not args.save_glb:
+        ap.error("--glb_normals needs --save_glb (a file to write them to)")
+    if args.glb_normals and args.as_pointcloud:
+        ap.error("--glb_normals needs a mesh: a point cloud (--as_pointcloud) has no faces to take normals from")
     for name in ("simplify", "simplify_voxels"):
         if getattr(args, name) is not None and not (getattr(args, name) > 0 and math.isfinite(getattr(args, name))):
             ap.error("--%s must be positive and finite" % name)
@@ -331,6 +344,11 @@ def main():
             print("Fused: Acc: %s, Comp: %s, NC1: %s, NC2: %s  (prediction %d vertices / %d faces, ground truth %d vertices / %d faces)" %
                   (rf["acc"], rf["comp"], rf["nc1"], rf["nc2"], pred_mesh["vertices"].shape[0], pred_mesh["faces"].shape[0],
                    gt_mesh["vertices"].shape[0], gt_mesh["faces"].shape[0]))
+            if args.eval_samples is not None:
+                from spann3r_amd.evaluate import evaluate_meshes
+                rs = evaluate_meshes(pred_mesh, gt_mesh, n_samples=args.eval_samples, threshold=0.1)
+                print("Fused (area-sampled, %d): Acc: %s, Comp: %s, NC1: %s, NC2: %s  (prediction area %.6g, ground truth area %.6g)" %
+                      (rs["samples"], rs["acc"], rs["comp"], rs["nc1"], rs["nc2"], rs["pred_area"], rs["gt_area"]))
     if args.save_ply:
         from spann3r_amd.postprocess import (estimate_focal_knowing_depth, confident_points, write_ply, estimate_poses,
                                              transforms_json, save_transforms)
@@ -396,7 +414,8 @@ def main():
                                    (args.min_component, " / --largest_component" if args.largest_component else "", fm["components"]["total"]))
             if fm["faces"].shape[0] == 0:
                 raise RuntimeError("--fused: the volume holds no surface (nothing passes conf_thresh %g with weight >= 1)" % args.conf_thresh)
-            size = mesh.write_glb(args.save_glb, fm["vertices"], fm["colors"], fm["faces"], bounds=fm["bounds"])
+            size = mesh.write_glb(args.save_glb, fm["vertices"], fm["colors"], fm["faces"], bounds=fm["bounds"],
+                                  normals=mesh.vertex_normals(fm) if args.glb_normals else None)
             info = dict(vertices=fm["vertices"].shape[0], faces=fm["faces"].shape[0], bytes=size)
         elif args.simplify is not None:                                           # the sheets welded: one vertex per cell of all frames
             scene = mesh.scene_mesh(*mesh.sequence_tensors(preds, batch), args.conf_thresh, args.as_pointcloud)
@@ -404,8 +423,16 @@ def main():
             report_simplify("per-frame sheets", scene)
             if scene["vertices"].shape[0] == 0:
                 raise RuntimeError("--simplify %g left nothing of the sheets to write" % args.simplify)
-            size = mesh.write_glb(args.save_glb, scene["vertices"], scene["colors"], scene["faces"], bounds=scene["bounds"])
+            size = mesh.write_glb(args.save_glb, scene["vertices"], scene["colors"], scene["faces"], bounds=scene["bounds"],
+                                  normals=mesh.vertex_normals(scene) if args.glb_normals else None)
             info = dict(vertices=scene["vertices"].shape[0], faces=0 if scene["faces"] is None else scene["faces"].shape[0], bytes=size)
+        elif args.glb_normals:                                                    # export_glb's mesh with its vertex normals
+            scene = mesh.scene_mesh(*mesh.sequence_tensors(preds, batch), args.conf_thresh)
+            if scene["faces"].shape[0] == 0:
+                raise RuntimeError("--glb_normals: nothing passes conf_thresh %g: no face to write" % args.conf_thresh)
+            size = mesh.write_glb(args.save_glb, scene["vertices"], scene["colors"], scene["faces"], bounds=scene["bounds"],
+                                  normals=mesh.vertex_normals(scene))
+            info = dict(vertices=scene["vertices"].shape[0], faces=scene["faces"].shape[0], bytes=size)
         else:
             info = mesh.export_glb(args.save_glb, preds, batch, conf_thresh=args.conf_thresh, as_pointcloud=args.as_pointcloud)
         print("wrote %d vertices, %d faces (%d bytes) to %s" % (info["vertices"], info["faces"], info["bytes"], args.save_glb))

@@ -1223,6 +1223,63 @@ int64_t sp3_mesh_cluster_faces_ws_bytes(int64_t nfaces, int table_log2);
 int sp3_mesh_cluster_faces(const int32_t* faces, int64_t nfaces, const int32_t* vertex_cluster, int64_t nverts, int dedup, int table_log2,
                            void* ws, int32_t* out_faces, int32_t* info, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh surface sampling and normals (spann3r_amd/mesh.py face_frames / sample_surface / vertex_normals and
+ * spann3r_amd/evaluate.py evaluate_meshes drive these; csrc/mesh_sample.hip): points drawn from the SURFACE of a mesh by area, each
+ * with its face's exact normal, and area-weighted vertex normals -- so that a fused surface is scored on what it is and not on
+ * where its tessellation put the vertices, and a viewer can light it.  tests/mesh_sample_ref.py restates the rule in numpy;
+ * Open3D's sample_points_uniformly / compute_vertex_normals and trimesh's sample_surface are not available to test against, so that
+ * restatement is the anchor (parity unpinned).  No entry point allocates, frees or synchronises; `ws` is caller-provided device
+ * scratch of the matching sp3_*_ws_bytes(), 8-byte aligned like cum and info.  Indices are int32: nverts and nfaces must stay below
+ * 2^31 - 1 (checked before anything is launched).  Every output is a function of the input alone: dmax is an integer maximum
+ * over the bits of non-negative doubles, the prefix sum and the vertex sums are integers, the random numbers are a function of
+ * (seed, sample index) -- two runs give the same bits, whatever the order of the atomics.  Every fp64 operation below is rounded
+ * on its own, in the order written (no FMA: the file is compiled under `#pragma clang fp contract(off)`).
+ *
+ * The rule.  vertices fp32 [V, 3], rgba uint32 [V] (nullable), faces int32 [F, 3].
+ *   1. Face frame.  A face is VALID when its three indices lie in 0..V-1; an invalid face is never dereferenced beyond that check.
+ *      For a valid face with corners A, B, C converted to fp64: e1 = B - A, e2 = C - A,
+ *      n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), d = sqrt(nx nx + ny ny + nz nz), summed left to right: twice
+ *      the area.  An invalid face, or one whose d is not finite (a NaN or infinite corner), has d = 0 and n = 0.  The unit face
+ *      normal is (float)(n / d) per component, (0, 0, 0) when d == 0.  dmax is the maximum d over all faces: the fp64 bits of
+ *      non-negative finite doubles, read as unsigned 64-bit integers, order as the doubles do, so one agent-scope 64-bit atomicMax
+ *      gives it exactly.
+ *   2. Sampling weight.  w_f = (uint64) floor(d_f / dmax * 4294967296.0), 0 when d_f == 0; w_f <= 2^32.  cum is the INCLUSIVE
+ *      prefix sum of w in face order, unsigned 64-bit; its total W stays below 2^63.  A face with w_f = 0 is never drawn: an
+ *      invalid or degenerate one, and also a face below 2^-32 of the largest one.  The total area is reported as
+ *      (double)W / 4294967296.0 * dmax / 2: the QUANTISED area, short of the sum of d / 2 by less than F dmax 2^-33.
+ *   3. Random numbers, counter-based and stateless: h(c) = splitmix64 of z = seed + (c + 1) * 0x9E3779B97F4A7C15 modulo 2^64:
+ *      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9, z = (z ^ (z >> 27)) * 0x94D049BB133111EB, h = z ^ (z >> 31).
+ *   4. Sample k uses the counters 3k, 3k + 1, 3k + 2.  Face: t = umulhi64(h(3k), W), face = the smallest f with cum[f] > t (an
+ *      upper-bound search; t < W, so it exists).  The draws are independent and identically distributed, as Open3D and trimesh
+ *      draw theirs: no stratification.  Barycentric coordinates: a = h(3k + 1) >> 40 and b = h(3k + 2) >> 40, 24-bit integers;
+ *      if a + b > 2^24 then a = 2^24 - a and b = 2^24 - b.  Point per axis: (float)((double)A + (a / 2^24 * e1 + b / 2^24 * e2)):
+ *      two products, one sum, one sum, one narrowing.  Colour per byte, alpha included:
+ *      (cA (2^24 - a - b) + cB a + cC b + 2^23) >> 24 in integers.  The normal of the sample is the unit face normal.
+ *   5. Vertex normals, area-weighted.  Per valid face and component q = llrint(n_c / dmax * 1073741824.0), round half to even,
+ *      |q| <= 2^30; q is added to each of the face's three vertices with agent-scope 64-bit integer atomic adds (two's complement
+ *      on unsigned 64-bit; one add per lane and sum, no aggregation in the wave).  normal = (float)(S_c / sqrt(Sx Sx + Sy Sy + Sz Sz))
+ *      with S converted to fp64, (0, 0, 0) when all three sums are 0 -- a vertex no valid face names, among others.
+ *
+ * sp3_mesh_face_frames : face_normals fp32 [F, 3] (nullable), cum uint64 [F], info uint64 [2] = (W, the bits of dmax).  5 launches:
+ *   clear info; frames (d, the normal, the atomicMax; the bits of d wait in cum); weights and the scan inside every 256-face
+ *   tile; one workgroup's scan of the tile totals; add-back.  ws: one uint64 per tile.  nfaces = 0 writes info = 0 and nothing else.
+ * sp3_mesh_sample : reads cum and info (as sp3_mesh_face_frames wrote them for the SAME vertices and faces) from the device, so
+ *   there is no host round trip between the two calls.  points, normals fp32 [N, 3], out_rgba uint32 [N] (null exactly when rgba
+ *   is null), face_index int32 [N].  One launch, one lane per sample; nsamples = 0 launches nothing.  W == 0 with nsamples > 0 must
+ *   not be launched (a launch then writes nothing): the caller reads info once, which also gives the area.  nsamples < 2^40.
+ * sp3_mesh_vertex_normals : info from sp3_mesh_face_frames of the same mesh; normals fp32 [V, 3].  3 launches (clear, accumulate,
+ *   finalise).  ws: 24 bytes of sums per vertex.  nverts = 0 launches nothing; nfaces = 0 gives zeros. */
+int64_t sp3_mesh_face_frames_ws_bytes(int64_t nfaces);
+int sp3_mesh_face_frames(const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, void* ws, float* face_normals,
+                         uint64_t* cum, uint64_t* info, void* stream);
+int sp3_mesh_sample(const float* vertices, const uint32_t* rgba, int64_t nverts, const int32_t* faces, int64_t nfaces, const uint64_t* cum,
+                    const uint64_t* info, int64_t nsamples, uint64_t seed, float* points, float* normals, uint32_t* out_rgba,
+                    int32_t* face_index, void* stream);
+int64_t sp3_mesh_vertex_normals_ws_bytes(int64_t nverts);
+int sp3_mesh_vertex_normals(const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, const uint64_t* info, void* ws,
+                            float* normals, void* stream);
+
 /* small utilities */
 /* n (1..8) contiguous device-to-device copies in one launch; every copy 16-byte aligned and a multiple of 16 bytes.
  * (The sequence loop's per-frame bookkeeping -- torch .clone() / slice assignments around spann3r/model.py:523-531.) */

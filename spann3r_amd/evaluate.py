@@ -334,6 +334,32 @@ def evaluate_reconstruction(pred_points, gt_points, threshold=0.1):
             "nc2_med": nc2_med, "transformation": T}
 
 
+def evaluate_meshes(pred_mesh, gt_mesh, n_samples=200_000, seed=0, threshold=0.1, icp=True):
+    """The metrics of evaluate_reconstruction for two SURFACES instead of two clouds, as NICE-SLAM-style eval_recon scripts take
+    them: n_samples points drawn by area from each mesh (mesh.sample_surface: the dicts of scene_mesh / extract_mesh / simplify,
+    the same seed for both), point-to-point ICP of the prediction's samples onto the ground truth's from identity unless
+    icp=False, the prediction's points moved by T and its normals rotated by T's rotation, then accuracy and completion with the
+    SAMPLED normals -- the exact unit normals of the faces drawn; no k-NN PCA.  The numbers no longer depend on where a
+    tessellation put its vertices.  -> the dict of evaluate_reconstruction plus pred_area, gt_area (the quantised areas) and
+    samples.  A mesh without area raises ValueError."""
+    from . import mesh as M
+    n = int(n_samples)
+    if n <= 0:
+        raise ValueError("evaluate_meshes: n_samples = %r, must be positive" % (n_samples,))
+    sp, sg = M.sample_surface(pred_mesh, n, seed=seed), M.sample_surface(gt_mesh, n, seed=seed)
+    pred, pred_n, gt, gt_n = sp["points"], sp["normals"], sg["points"], sg["normals"]
+    T = np.eye(4)
+    if icp:
+        T, _, _, _ = icp_point_to_point(pred, gt, threshold)
+        R = np.eye(4)
+        R[:3, :3] = T[:3, :3]
+        pred, pred_n = _transform(pred, T), _transform(pred_n, R)
+    acc, acc_med, nc1, nc1_med = accuracy(gt, pred, gt_n, pred_n)
+    comp, comp_med, nc2, nc2_med = completion(gt, pred, gt_n, pred_n)
+    return {"acc": acc, "comp": comp, "nc1": nc1, "nc2": nc2, "acc_med": acc_med, "comp_med": comp_med, "nc1_med": nc1_med,
+            "nc2_med": nc2_med, "transformation": T, "pred_area": sp["area"], "gt_area": sg["area"], "samples": n}
+
+
 def _align(views, preds, preds_all, clouds):
     from .loss import L21, Regr3D_t_ScaleShiftInv, _entries
     n = len(views)

@@ -325,6 +325,108 @@ def simplify(m, cell, origin=None, dedup=True, return_map=False, scale=1.0, tran
     return out
 
 
+def _check_mesh(m, what):
+    """(vertices fp32 [V, 3], rgba int32 [V] or None, faces int32 [F, 3]) of a mesh dict, contiguous on the device; a cloud raises"""
+    if m.get("faces") is None:
+        raise ValueError("%s: a point cloud has no faces (no surface to measure)" % what)
+    vertices, rgba = _check_vertices(m["vertices"], m.get("colors"), what)
+    faces = _dev(m["faces"], what + ": faces")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise RuntimeError("%s: faces must be int32 [F, 3], got %s %s" % (what, faces.dtype, tuple(faces.shape)))
+    if faces.shape[0] >= 2 ** 31 - 1:
+        raise ValueError("%s: %d faces: must stay below 2^31 - 1 (int32 indices)" % (what, faces.shape[0]))
+    return vertices, rgba, faces.contiguous()
+
+
+def _frames_raw(lib, vertices, faces, normals=True):
+    """sp3_mesh_face_frames, no host read: -> (face_normals fp32 [F, 3] or None, cum int64 [F] (the uint64 bits; W < 2^63), info int64 [2])"""
+    nv, nf, dev = vertices.shape[0], faces.shape[0], vertices.device
+    fn = torch.empty((nf, 3), dtype=torch.float32, device=dev) if normals else None
+    cum = torch.empty(nf, dtype=torch.int64, device=dev)
+    info = torch.empty(2, dtype=torch.int64, device=dev)
+    ws = _ws(lib.sp3_mesh_face_frames_ws_bytes(nf), dev)
+    L.check(lib.sp3_mesh_face_frames(L.ptr(vertices) if nv else 0, nv, L.ptr(faces) if nf else 0, nf, ws.data_ptr(), L.ptr(fn) if nf else 0,
+                                     cum.data_ptr() if nf else 0, info.data_ptr(), L.stream_ptr()), "sp3_mesh_face_frames")
+    return fn, cum, info
+
+
+def _read_info(info):
+    """the one 16-byte host read: -> (W, dmax, the quantised area W / 2^32 * dmax / 2)"""
+    host = info.cpu().numpy()
+    w, dmax = int(host[0]), float(host[1:].view(np.float64)[0])
+    return w, dmax, float(np.float64(w) / 4294967296.0 * np.float64(dmax) / 2.0)
+
+
+def face_frames(m):
+    """sp3_mesh_face_frames (include/spann3r_hip.h "Mesh surface sampling and normals") of the dict scene_mesh / extract_mesh /
+    simplify return: per face the cross product n of two edges in fp64 and its length d, twice the area.  -> dict(face_normals fp32
+    [F, 3] (zeros for a face that is invalid, not finite or without area), cum int64 [F] (the inclusive prefix sum of the integer
+    weights floor(d / dmax * 2^32)), info int64 [2] (W, the bits of dmax), on the device; W int, dmax float, area float = W / 2^32 *
+    dmax / 2, the QUANTISED area: a face below 2^-32 of the largest one counts as nothing).  The same bits every run.  One host read
+    of 16 bytes.  A cloud raises ValueError."""
+    vertices, _, faces = _check_mesh(m, "face_frames")
+    fn, cum, info = _frames_raw(L.load(), vertices, faces)
+    w, dmax, area = _read_info(info)
+    return dict(face_normals=fn, cum=cum, info=info, W=w, dmax=dmax, area=area)
+
+
+def surface_area(m):
+    """The quantised area of face_frames as a float.  A cloud raises ValueError."""
+    vertices, _, faces = _check_mesh(m, "surface_area")
+    return _read_info(_frames_raw(L.load(), vertices, faces, normals=False)[2])[2]
+
+
+def sample_surface(m, n, seed=0, return_faces=False):
+    """n points drawn independently and uniformly by area from the surface of a mesh dict (include/spann3r_hip.h "Mesh surface
+    sampling and normals"; sp3_mesh_face_frames + sp3_mesh_sample): sample k takes its face from the integer prefix sum of the face
+    weights and its place from two 24-bit barycentric coordinates, all three from a counter-based generator of (seed, k) -- the same
+    bits every run, and the first n of a longer draw are the shorter draw.  -> dict(points fp32 [n, 3], normals fp32 [n, 3] (the exact
+    unit normal of the face drawn), colors uint8 [n, 4] (the corners' colours mixed per byte; None when the mesh has none), area
+    (float, the quantised area) and, with return_faces, faces int32 [n]), tensors on the device.  One host read of 16 bytes between
+    the two calls: a mesh with no area to sample (no face, or every face invalid, non-finite or degenerate) with n > 0 raises
+    ValueError; n = 0 gives empty tensors.  A cloud raises ValueError."""
+    n, seed = int(n), int(seed)
+    if n < 0 or n >= 2 ** 40:
+        raise ValueError("sample_surface: n = %d must lie in 0 .. 2^40 - 1" % n)
+    vertices, rgba, faces = _check_mesh(m, "sample_surface")
+    dev, lib = vertices.device, L.load()
+    _, cum, info = _frames_raw(lib, vertices, faces, normals=False)
+    w, _, area = _read_info(info)
+    if n > 0 and w == 0:
+        raise ValueError("sample_surface: %d faces over %d vertices, none valid, finite and with an area: no area to sample" %
+                         (faces.shape[0], vertices.shape[0]))
+    points = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    normals = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    col = torch.empty(n, dtype=torch.int32, device=dev) if rgba is not None else None
+    fidx = torch.empty(n, dtype=torch.int32, device=dev)
+    if n > 0:
+        L.check(lib.sp3_mesh_sample(vertices.data_ptr(), L.ptr(rgba), vertices.shape[0], faces.data_ptr(), faces.shape[0], cum.data_ptr(),
+                                    info.data_ptr(), n, seed & (2 ** 64 - 1), points.data_ptr(), normals.data_ptr(), L.ptr(col), fidx.data_ptr(),
+                                    L.stream_ptr()), "sp3_mesh_sample")
+    out = dict(points=points, normals=normals, colors=None if col is None else col.view(torch.uint8).reshape(-1, 4), area=area)
+    if return_faces:
+        out["faces"] = fidx
+    return out
+
+
+def vertex_normals(m):
+    """Area-weighted unit vertex normals fp32 [V, 3] of a mesh dict, on the device (include/spann3r_hip.h "Mesh surface sampling and
+    normals"; sp3_mesh_face_frames + sp3_mesh_vertex_normals): every face adds its cross product, quantised to 2^-30 of the largest
+    one, to its three vertices in 64-bit integers -- the same bits every run and for any order of the faces.  A vertex no valid face
+    names, or whose faces cancel, gets (0, 0, 0).  No host read.  A cloud raises ValueError.  (Recompute after simplify: the
+    normals of a mesh do not survive it.)"""
+    vertices, _, faces = _check_mesh(m, "vertex_normals")
+    nv, nf, lib = vertices.shape[0], faces.shape[0], L.load()
+    out = torch.empty((nv, 3), dtype=torch.float32, device=vertices.device)
+    if nv == 0:
+        return out
+    _, _, info = _frames_raw(lib, vertices, faces, normals=False)
+    ws = _ws(lib.sp3_mesh_vertex_normals_ws_bytes(nv), vertices.device)
+    L.check(lib.sp3_mesh_vertex_normals(vertices.data_ptr(), nv, L.ptr(faces) if nf else 0, nf, info.data_ptr(), ws.data_ptr(), out.data_ptr(),
+                                        L.stream_ptr()), "sp3_mesh_vertex_normals")
+    return out
+
+
 def pts3d_to_mesh(img, pts3d, valid=None):
     """app.py:68-105 (pts3d_to_trimesh) for device tensors img, pts3d [h, w, 3] and valid bool [h, w]: dict(vertices [h w, 3],
     faces int64 [F, 3], face_colors [F, 3]) with the reference's order: four blocks (tl, tr, bl), (bl, tr, tl), (tr, bl, br), (br, bl, tr),
@@ -380,11 +482,12 @@ def _host(x):
     return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
 
 
-def write_glb(path, vertices, colors, faces=None, bounds=None):
+def write_glb(path, vertices, colors, faces=None, bounds=None, normals=None):
     """A glTF 2.0 binary file of one primitive: POSITION fp32 VEC3 (with min / max; `bounds` [2, 3] if already known), COLOR_0
     normalised unsigned byte VEC4 (uint8 [V, 3] gets alpha 255), and with faces [F, 3] uint32 indices, mode 4 (TRIANGLES) and a
-    doubleSided material; without faces mode 0 (POINTS).  One buffer, every chunk and buffer view 4-byte aligned.  Tensors are copied
-    to the host.  Returns the file length."""
+    doubleSided material; without faces mode 0 (POINTS).  With normals (fp32 [V, 3], finite: vertex_normals) a NORMAL fp32 VEC3
+    accessor is added, its buffer view appended after the others; without them the file is what it always was, byte for byte.
+    One buffer, every chunk and buffer view 4-byte aligned.  Tensors are copied to the host.  Returns the file length."""
     v = np.ascontiguousarray(_host(vertices), dtype="<f4")
     c = _host(colors)
     if v.ndim != 2 or v.shape[1] != 3 or v.shape[0] == 0:
@@ -418,6 +521,16 @@ def write_glb(path, vertices, colors, faces=None, bounds=None):
         chunks.append(f.tobytes())
         prim.update(indices=2, mode=4, material=0)
         doc["materials"] = [dict(doubleSided=True, pbrMetallicRoughness=dict(metallicFactor=0.0, roughnessFactor=1.0))]
+    if normals is not None:
+        nrm = np.ascontiguousarray(_host(normals), dtype="<f4")
+        if nrm.shape != v.shape:
+            raise ValueError("write_glb: normals %s must match the vertices %s" % (nrm.shape, v.shape))
+        if not np.isfinite(nrm).all():
+            raise ValueError("write_glb: non-finite vertex normal")
+        views.append(dict(buffer=0, byteOffset=sum(len(ch) for ch in chunks), byteLength=nrm.nbytes, target=34962))
+        accessors.append(dict(bufferView=len(views) - 1, componentType=5126, count=len(nrm), type="VEC3"))
+        chunks.append(nrm.tobytes())
+        prim["attributes"]["NORMAL"] = len(accessors) - 1
     binary = b"".join(chunks)                          # (12 V + 4 V + 12 F bytes: every view starts and ends on a multiple of 4)
     doc.update(meshes=[dict(primitives=[prim])], buffers=[dict(byteLength=len(binary))], bufferViews=views, accessors=accessors)
     text = json.dumps(doc, separators=(",", ":")).encode()
