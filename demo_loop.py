@@ -176,6 +176,9 @@ def main():
     ap.add_argument("--eval_samples", type=int, default=None, metavar="N", help="with --fused --rgbd --eval: a second fused line from N points "
                     "drawn by area from each fused surface with their exact face normals (evaluate.evaluate_meshes), next to the line "
                     "that scores the mesh vertices")
+    ap.add_argument("--eval_exact", action="store_true", help="with --eval_samples: a third fused line, the same samples measured against "
+                    "the other surface's triangles instead of its samples (evaluate.evaluate_meshes(exact=True): exact point-to-triangle "
+                    "distances, the normal of the face hit)")
     ap.add_argument("--glb_normals", action="store_true", help="with --save_glb: write area-weighted vertex normals (mesh.vertex_normals, on "
                     "the device) as the NORMAL attribute of the fused or per-frame mesh, so that viewers light it")
     ap.add_argument("--extent", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"), help="with --stream --fused "
@@ -211,6 +214,8 @@ def main():
         ap.error("--eval_samples needs --fused --rgbd --eval (two fused surfaces to sample)")
     if args.eval_samples is not None and args.eval_samples <= 0:
         ap.error("--eval_samples must be positive")
+    if args.eval_exact and args.eval_samples is None:
+        ap.error("--eval_exact needs --eval_samples (the samples it measures against the other surface's triangles)")
     if args.glb_normals and not args.save_glb:
         ap.error("--glb_normals needs --save_glb (a file to write them to)")
     if args.glb_normals and args.as_pointcloud:
@@ -349,6 +354,9 @@ def main():
                 rs = evaluate_meshes(pred_mesh, gt_mesh, n_samples=args.eval_samples, threshold=0.1)
                 print("Fused (area-sampled, %d): Acc: %s, Comp: %s, NC1: %s, NC2: %s  (prediction area %.6g, ground truth area %.6g)" %
                       (rs["samples"], rs["acc"], rs["comp"], rs["nc1"], rs["nc2"], rs["pred_area"], rs["gt_area"]))
+                if args.eval_exact:
+                    rx = evaluate_meshes(pred_mesh, gt_mesh, n_samples=args.eval_samples, threshold=0.1, exact=True)
+                    print("Fused (exact, %d): Acc: %s, Comp: %s, NC1: %s, NC2: %s" % (rx["samples"], rx["acc"], rx["comp"], rx["nc1"], rx["nc2"]))
     if args.save_ply:
         from spann3r_amd.postprocess import (estimate_focal_knowing_depth, confident_points, write_ply, estimate_poses,
                                              transforms_json, save_transforms)

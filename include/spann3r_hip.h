@@ -1280,6 +1280,72 @@ int64_t sp3_mesh_vertex_normals_ws_bytes(int64_t nverts);
 int sp3_mesh_vertex_normals(const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, const uint64_t* info, void* ws,
                             float* normals, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh distance (spann3r_amd/mesh.py TriangleGrid / point_mesh_distance and spann3r_amd/evaluate.py evaluate_meshes(exact=True)
+ * drive these; csrc/mesh_distance.hip): the exact unsigned distance from a point to the SURFACE of a triangle mesh, with the closest
+ * point, the face it lies on and the Voronoi region of that face -- so that a surface is scored against a surface and not against
+ * the nearest of its samples.  tests/mesh_distance_ref.py restates the rule in numpy and is itself checked against a second
+ * formulation in exact rationals; Open3D's RaycastingScene.compute_closest_points and trimesh's ProximityQuery are not available
+ * to test against (parity unpinned).  No entry point allocates, frees or synchronises; `ws` is caller-provided device scratch of
+ * sp3_mesh_dist_query_ws_bytes(nq), 16-byte aligned.  Indices are int32: nverts, nfaces and npairs stay below 2^31 - 1.  Every fp64
+ * operation below is rounded on its own, in the order written (no FMA: the file is compiled under `#pragma clang fp contract(off)`);
+ * dot(u, v) = (ux vx + uy vy) + uz vz.
+ *
+ * The rule.  vertices fp32 [V, 3], faces int32 [F, 3], a query p fp32 [3].
+ *   1. A face is USABLE when its three indices lie in 0..V-1 and the d of sp3_mesh_face_frames (rule 1 of "Mesh surface sampling and
+ *      normals": the length of the fp64 cross product of its two edges) is finite and > 0 -- which a NaN or infinite coordinate never
+ *      gives.  A face that is not usable is never dereferenced beyond that test and never wins.
+ *   2. Closest point c of a usable face (A, B, C) to p, everything converted to fp64 (Ericson, Real-Time Collision Detection 5.1.5):
+ *      ab = B - A, ac = C - A, ap = p - A, bp = p - B, cp = p - C; d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp),
+ *      d4 = dot(ac, bp), d5 = dot(ab, cp), d6 = dot(ac, cp); vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4 (two products,
+ *      one difference), e = d4 - d3, g = d5 - d6.  The FIRST of these tests that holds decides:
+ *        region 0 (A)      : d1 <= 0 and d2 <= 0                  c = A
+ *        region 1 (B)      : d3 >= 0 and d4 <= d3                 c = B
+ *        region 2 (edge AB): vc <= 0 and d1 >= 0 and d3 <= 0      t = d1 / (d1 - d3), c = A + t ab
+ *        region 3 (C)      : d6 >= 0 and d5 <= d6                 c = C
+ *        region 4 (edge AC): vb <= 0 and d2 >= 0 and d6 <= 0      t = d2 / (d2 - d6), c = A + t ac
+ *        region 5 (edge BC): va <= 0 and e >= 0 and g >= 0        t = e / (e + g), c = B + t (C - B)
+ *        region 6 (inside) : otherwise                            den = 1 / ((va + vb) + vc), s = vb den, t = vc den,
+ *                                                                 c = A + (ab s + ac t)
+ *      per axis.  d2(p, face) = (dx dx + dy dy) + dz dz of p - c.  (A comparison with a NaN is false: a NaN query ends in region 6
+ *      with d2 = NaN, which never wins.)
+ *   3. The result of a query is the minimum over the usable faces of the pair (d2, face index), compared lexicographically,
+ *      starting from (+inf, none) with a strict <: among equal d2 the smallest index wins, and a d2 that is NaN or +inf never
+ *      does.  It is a pure function of the inputs, whatever the grid, the order of the visits or the number of times a face is
+ *      evaluated.  Outputs: dist fp32 = (float)sqrt(d2); closest fp32 [3], the fp64 c rounded once; face int32; region uint8
+ *      (0..6).  No winner (no usable face, a non-finite query): +inf, the query itself, -1, 255.
+ *
+ * The grid of face references is an sp3_nn_grid as it is (origin, h, inv_h, slack, dims; its cell-of-x rule).
+ * sp3_mesh_tri_cell_count : counts int64 [F] = the number of cells the face is registered in: the cells cell(min - slack) ..
+ *   cell(max + slack) per axis of its fp32 bounding box (0 for a face that is not usable).  Registration is CONSERVATIVE: cell(x) --
+ *   an fp32 subtraction, product, floor and clamp -- is monotone in x, every point of the face has each coordinate between the
+ *   face's min and max, so under the very assignment the queries use it falls in a registered cell, whatever the rounding of the
+ *   inflation does (the slack only adds cells).  No tighter plane test is made.
+ * sp3_mesh_tri_cell_fill : offsets int64 [F] = the EXCLUSIVE prefix sum of counts (the host's), npairs their total; writes
+ *   (pair_cell, pair_face) int32 [npairs], a face's pairs in z, y, x order from offsets[f]; nothing is written at or past npairs.
+ *   The host sorts the pairs by cell (stable) and builds cell_start[cells + 1].
+ * sp3_mesh_dist_query : one lane per query, taken in q_order (nullable; sorted by home cell, clamped into the grid), results in
+ *   caller order.  Rings r = 0..max_ring around the home cell.  A face no cell of the visited block holds has, on one axis, all its
+ *   cells beyond one wall of the block, so it lies wholly behind that wall: the query is finished when sqrt of its best d2 is within
+ *   the distance to the nearest wall of the block that still has cells behind it, less the slack -- sp3_nn_query's rule.  Queries
+ *   left open go through the brute-force kernels.  pair_face [npairs] sorted by cell; indices read from it, from cell_start and from
+ *   faces are range-checked before use.  After the call the first 32 bytes of ws hold { int32 fallback queries, 3 x int32 pad,
+ *   uint64 cells visited, uint64 faces evaluated } (by the grid kernel).  nq = 0 launches nothing.
+ * sp3_mesh_dist_brute : the same result for every query with the faces staged through LDS in tiles of 512 (usability decided by
+ *   the loader), the face list split over workgroups; joined by a 64-bit integer atomicMin over the bits of d2, then, in a second pass
+ *   over the same tiles, an atomicMin of the face index among the faces with exactly that d2; a last launch recomputes the closest
+ *   point of the winner.  The fallback of sp3_mesh_dist_query, the route of a one-cell grid, and the on-device cross-check. */
+int sp3_mesh_tri_cell_count(const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, const sp3_nn_grid* g, int64_t* counts,
+                            void* stream);
+int sp3_mesh_tri_cell_fill(const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, const sp3_nn_grid* g, const int64_t* offsets,
+                           int64_t npairs, int32_t* pair_cell, int32_t* pair_face, void* stream);
+int64_t sp3_mesh_dist_query_ws_bytes(int64_t nq);
+int sp3_mesh_dist_query(const float* q, const int64_t* q_order, int64_t nq, const float* vertices, int64_t nverts, const int32_t* faces,
+                        int64_t nfaces, const int32_t* pair_face, int64_t npairs, const int32_t* cell_start, const sp3_nn_grid* g, int max_ring,
+                        void* ws, float* dist, float* closest, int32_t* face, uint8_t* region, void* stream);
+int sp3_mesh_dist_brute(const float* q, int64_t nq, const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, void* ws,
+                        float* dist, float* closest, int32_t* face, uint8_t* region, void* stream);
+
 /* small utilities */
 /* n (1..8) contiguous device-to-device copies in one launch; every copy 16-byte aligned and a multiple of 16 bytes.
  * (The sequence loop's per-frame bookkeeping -- torch .clone() / slice assignments around spann3r/model.py:523-531.) */

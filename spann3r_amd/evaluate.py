@@ -334,14 +334,31 @@ def evaluate_reconstruction(pred_points, gt_points, threshold=0.1):
             "nc2_med": nc2_med, "transformation": T}
 
 
-def evaluate_meshes(pred_mesh, gt_mesh, n_samples=200_000, seed=0, threshold=0.1, icp=True):
+def _exact_side(points, normals, target_mesh, face_normals):
+    """points (with their normals) against the TRIANGLES of target_mesh -> (mean, median of the distances, mean, median of
+    |n_point . n_face| with the unit normal of the face each closest point lies on)"""
+    from . import mesh as M
+    r = M.point_mesh_distance(points, target_mesh)
+    n = points.shape[0]
+    dots = torch.empty(n, dtype=torch.float32, device=points.device)
+    L.check(L.load().sp3_normal_dot(face_normals.data_ptr(), normals.data_ptr(), r["face"].data_ptr(), n, 1, dots.data_ptr(), L.stream_ptr()),
+            "sp3_normal_dot")
+    return _mean_median(r["dist"]) + _mean_median(dots)
+
+
+def evaluate_meshes(pred_mesh, gt_mesh, n_samples=200_000, seed=0, threshold=0.1, icp=True, exact=False):
     """The metrics of evaluate_reconstruction for two SURFACES instead of two clouds, as NICE-SLAM-style eval_recon scripts take
     them: n_samples points drawn by area from each mesh (mesh.sample_surface: the dicts of scene_mesh / extract_mesh / simplify,
     the same seed for both), point-to-point ICP of the prediction's samples onto the ground truth's from identity unless
     icp=False, the prediction's points moved by T and its normals rotated by T's rotation, then accuracy and completion with the
     SAMPLED normals -- the exact unit normals of the faces drawn; no k-NN PCA.  The numbers no longer depend on where a
     tessellation put its vertices.  -> the dict of evaluate_reconstruction plus pred_area, gt_area (the quantised areas) and
-    samples.  A mesh without area raises ValueError."""
+    samples.  A mesh without area raises ValueError.
+    exact=True measures every sample against the other mesh's TRIANGLES instead of against its samples (mesh.point_mesh_distance;
+    include/spann3r_hip.h "Mesh distance"): acc = the prediction's samples to the ground truth's faces, comp = the ground truth's
+    samples to the prediction's faces, its vertices moved by T; nc1 / nc2 = |n_sample . n_face| with the unit normal of the face
+    hit (mesh.face_frames; rotated by T's rotation for the prediction).  Sampling and ICP are unchanged.  The floor the sample
+    spacing puts under acc / comp is gone: two tessellations of one plane score 0.  The dict gains exact=True."""
     from . import mesh as M
     n = int(n_samples)
     if n <= 0:
@@ -349,15 +366,27 @@ def evaluate_meshes(pred_mesh, gt_mesh, n_samples=200_000, seed=0, threshold=0.1
     sp, sg = M.sample_surface(pred_mesh, n, seed=seed), M.sample_surface(gt_mesh, n, seed=seed)
     pred, pred_n, gt, gt_n = sp["points"], sp["normals"], sg["points"], sg["normals"]
     T = np.eye(4)
+    R = np.eye(4)
     if icp:
         T, _, _, _ = icp_point_to_point(pred, gt, threshold)
-        R = np.eye(4)
         R[:3, :3] = T[:3, :3]
         pred, pred_n = _transform(pred, T), _transform(pred_n, R)
-    acc, acc_med, nc1, nc1_med = accuracy(gt, pred, gt_n, pred_n)
-    comp, comp_med, nc2, nc2_med = completion(gt, pred, gt_n, pred_n)
-    return {"acc": acc, "comp": comp, "nc1": nc1, "nc2": nc2, "acc_med": acc_med, "comp_med": comp_med, "nc1_med": nc1_med,
-            "nc2_med": nc2_med, "transformation": T, "pred_area": sp["area"], "gt_area": sg["area"], "samples": n}
+    if exact:
+        pred_fn, gt_fn = M.face_frames(pred_mesh)["face_normals"], M.face_frames(gt_mesh)["face_normals"]
+        moved = pred_mesh
+        if icp:
+            moved = dict(vertices=_transform(pred_mesh["vertices"].contiguous().float(), T), faces=pred_mesh["faces"])
+            pred_fn = _transform(pred_fn, R)
+        acc, acc_med, nc1, nc1_med = _exact_side(pred, pred_n, gt_mesh, gt_fn)
+        comp, comp_med, nc2, nc2_med = _exact_side(gt, gt_n, moved, pred_fn)
+    else:
+        acc, acc_med, nc1, nc1_med = accuracy(gt, pred, gt_n, pred_n)
+        comp, comp_med, nc2, nc2_med = completion(gt, pred, gt_n, pred_n)
+    out = {"acc": acc, "comp": comp, "nc1": nc1, "nc2": nc2, "acc_med": acc_med, "comp_med": comp_med, "nc1_med": nc1_med,
+           "nc2_med": nc2_med, "transformation": T, "pred_area": sp["area"], "gt_area": sg["area"], "samples": n}
+    if exact:
+        out["exact"] = True
+    return out
 
 
 def _align(views, preds, preds_all, clouds):

@@ -282,6 +282,13 @@ _PROTOS = {
     "sp3_mesh_sample": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p,
                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "sp3_mesh_vertex_normals": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_mesh_tri_cell_count": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(NnGrid), C.c_void_p, C.c_void_p],
+    "sp3_mesh_tri_cell_fill": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(NnGrid), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                               C.c_void_p],
+    "sp3_mesh_dist_query": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                            C.POINTER(NnGrid), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_mesh_dist_brute": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                            C.c_void_p, C.c_void_p],
     "sp3_render_tris": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(RenderCam), C.c_int,
                         C.c_void_p, C.c_void_p, C.c_void_p],
     "sp3_ssi_align_stats": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -315,7 +322,7 @@ EXPORTS = sorted(list(_PROTOS) + ["sp3_last_error", "sp3_version", "sp3_conf_los
                                   "sp3_tsdf_extract_ws_bytes", "sp3_tsdf_track_accum_ws_bytes", "sp3_tsdf_brick_alloc_ws_bytes",
                                   "sp3_tsdf_brick_extract_ws_bytes", "sp3_mesh_components_ws_bytes", "sp3_mesh_select_faces_ws_bytes",
                                   "sp3_mesh_cluster_ws_bytes", "sp3_mesh_cluster_faces_ws_bytes", "sp3_mesh_face_frames_ws_bytes",
-                                  "sp3_mesh_vertex_normals_ws_bytes"])
+                                  "sp3_mesh_vertex_normals_ws_bytes", "sp3_mesh_dist_query_ws_bytes"])
 
 
 def load():
@@ -348,7 +355,7 @@ def load():
     lib.sp3_tsdf_brick_extract_ws_bytes.argtypes = [C.c_int]
     for name in ("sp3_nn_query_ws_bytes", "sp3_icp_accum_ws_bytes", "sp3_sum_count_ws_bytes", "sp3_mesh_vertices_ws_bytes", "sp3_eval_align_ws_bytes",
                  "sp3_tsdf_track_accum_ws_bytes", "sp3_mesh_components_ws_bytes", "sp3_mesh_select_faces_ws_bytes", "sp3_mesh_face_frames_ws_bytes",
-                 "sp3_mesh_vertex_normals_ws_bytes"):
+                 "sp3_mesh_vertex_normals_ws_bytes", "sp3_mesh_dist_query_ws_bytes"):
         getattr(lib, name).restype = C.c_int64
         getattr(lib, name).argtypes = [C.c_int64]
     for name in ("sp3_mesh_cluster_ws_bytes", "sp3_mesh_cluster_faces_ws_bytes"):

@@ -16,6 +16,7 @@ What this restates and what it does not:
 torch provides memory and the gather behind `face_colors`; trimesh, gradio and the ffmpeg frame extraction of app.py are not covered."""
 import ctypes as C
 import json
+import math
 import struct
 
 import numpy as np
@@ -424,6 +425,146 @@ def vertex_normals(m):
     ws = _ws(lib.sp3_mesh_vertex_normals_ws_bytes(nv), vertices.device)
     L.check(lib.sp3_mesh_vertex_normals(vertices.data_ptr(), nv, L.ptr(faces) if nf else 0, nf, info.data_ptr(), ws.data_ptr(), out.data_ptr(),
                                         L.stream_ptr()), "sp3_mesh_vertex_normals")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ mesh distance
+PAIRS_PER_FACE_CAP = 8          # (cell, face) references a TriangleGrid may hold per face before its cells are made larger
+FACES_PER_CELL = 0.5            # what evaluate.choose_grid aims the cell edge at: a surface leaves most cells of its box empty
+DIST_RING_BUDGET = 3            # rings walked before a query is handed to the brute-force kernels
+
+
+def _tri_cell_counts(lib, vertices, faces, g):
+    """sp3_mesh_tri_cell_count: -> int64 [F] on the device, the number of cells every face is registered in (0: not usable)"""
+    counts = torch.empty(faces.shape[0], dtype=torch.int64, device=faces.device)
+    L.check(lib.sp3_mesh_tri_cell_count(L.ptr(vertices) if vertices.shape[0] else 0, vertices.shape[0], L.ptr(faces) if faces.shape[0] else 0,
+                                        faces.shape[0], C.byref(g), L.ptr(counts) if faces.shape[0] else 0, L.stream_ptr()),
+            "sp3_mesh_tri_cell_count")
+    return counts
+
+
+class TriangleGrid:
+    """The faces of a mesh dict registered in a cell grid (include/spann3r_hip.h "Mesh distance"): built once, reused for any number
+    of query sets by point_mesh_distance.  The cell edge starts from evaluate.choose_grid on the box of the finite vertices with the
+    number of usable faces and grows by 1.25 while the (cell, face) references exceed PAIRS_PER_FACE_CAP per face; a grid of one cell
+    holds no references and is answered by the brute-force kernels.  Host reads: 8 bytes for the usable faces, 48 for the box, 8 per
+    try of h (one for near-uniform faces such as marching tetrahedra's).  h: start from this cell edge instead of choose_grid's.  A
+    mesh without a usable face raises ValueError; a cloud too.
+    Attributes: g (lib.NnGrid), dims, h, usable, pairs, tries, pair_face int32 [pairs], cell_start int32 [cells + 1]."""
+
+    def __init__(self, m, h=None):
+        from .evaluate import MAX_CELLS, choose_grid
+        lib = L.load()
+        self.vertices, _, self.faces = _check_mesh(m, "TriangleGrid")
+        v, f = self.vertices, self.faces
+        nf, dev = f.shape[0], v.device
+        one = L.NnGrid(0.0, 0.0, 0.0, 1.0, 1.0, 0.0, 1, 1, 1)
+        self.usable = int(_tri_cell_counts(lib, v, f, one).sum().item()) if nf else 0      # one cell: 1 per usable face
+        if self.usable == 0:
+            raise ValueError("TriangleGrid: %d faces over %d vertices, none valid, finite and with an area: no surface to measure against" %
+                             (nf, v.shape[0]))
+        fin = torch.isfinite(v)
+        inf = torch.tensor(math.inf, device=dev)
+        box = torch.stack((torch.where(fin, v, inf).amin(0), torch.where(fin, v, -inf).amax(0))).double().cpu().numpy()
+        box = np.where(np.isfinite(box), box, 0.0)
+        ext = box[1] - box[0]
+        if h is None:
+            h, dims = choose_grid(box[0], box[1], self.usable, occupancy=FACES_PER_CELL)
+        else:                                        # the caller's first cell edge (experiments; a huge one gives the one-cell grid)
+            h = float(h)
+            while True:
+                dims = tuple(int(math.floor(e / h)) + 1 for e in ext)
+                if dims[0] * dims[1] * dims[2] <= MAX_CELLS:
+                    break
+                h *= 1.25
+        maxabs = float(np.abs(box).max())
+        self.tries = 0
+        while True:
+            self.tries += 1
+            slack = 1e-6 * (maxabs + float(ext.max()) + h)
+            g = L.NnGrid(float(box[0, 0]), float(box[0, 1]), float(box[0, 2]), h, 1.0 / h, slack, *dims)
+            if dims == (1, 1, 1):
+                counts, pairs = None, 0
+                break
+            counts = _tri_cell_counts(lib, v, f, g)
+            pairs = int(counts.sum().item())
+            if pairs <= min(PAIRS_PER_FACE_CAP * nf, 2 ** 31 - 2):
+                break
+            h *= 1.25
+            dims = tuple(int(math.floor(e / h)) + 1 for e in ext)
+        self.g, self.h, self.dims, self.pairs = g, h, dims, pairs
+        self.pair_face = self.cell_start = None
+        if pairs:
+            offsets = torch.cumsum(counts, 0) - counts
+            cell = torch.empty(pairs, dtype=torch.int32, device=dev)
+            face = torch.empty(pairs, dtype=torch.int32, device=dev)
+            L.check(lib.sp3_mesh_tri_cell_fill(v.data_ptr(), v.shape[0], f.data_ptr(), nf, C.byref(g), offsets.data_ptr(), pairs, cell.data_ptr(),
+                                               face.data_ptr(), L.stream_ptr()), "sp3_mesh_tri_cell_fill")
+            sorted_cell, order = torch.sort(cell, stable=True)
+            self.pair_face = face[order].contiguous()
+            ncell = dims[0] * dims[1] * dims[2]
+            self.cell_start = torch.searchsorted(sorted_cell, torch.arange(ncell + 1, dtype=torch.int32, device=dev)).to(torch.int32)
+
+    def query_order(self, q):
+        """the queries sorted by the cell they fall in (clamped into the grid): the lanes of a wave then walk the same cells"""
+        ids = torch.empty(q.shape[0], dtype=torch.int32, device=q.device)
+        L.check(L.load().sp3_nn_cell_ids(q.data_ptr(), q.shape[0], C.byref(self.g), ids.data_ptr(), L.stream_ptr()), "sp3_nn_cell_ids")
+        return torch.sort(ids, stable=True)[1]
+
+
+def point_mesh_distance(points, m, grid=None, method="grid", return_stats=False, ring_budget=DIST_RING_BUDGET):
+    """The exact unsigned distance from every point fp32 [N, 3] (device) to the surface of a mesh dict (include/spann3r_hip.h "Mesh
+    distance"; sp3_mesh_dist_query / sp3_mesh_dist_brute) -> dict(dist fp32 [N], closest fp32 [N, 3], face int32 [N] (the face the
+    closest point lies on, the smallest index among equals), region uint8 [N] (0..6: A, B, edge AB, C, edge AC, edge BC, inside)),
+    tensors on the device.  A non-finite query gets +inf, itself, -1, 255.  The result is a function of the inputs alone: the same
+    bits for either method, for any grid and every run.
+    method: "grid" (a TriangleGrid -- pass one as `grid` to reuse it, it must have been built on this mesh -- walked ring by ring,
+    the brute-force kernels for what `ring_budget` rings leave open or when the grid is one cell) or "brute" (every query against
+    every face: the in-tree cross-check).  return_stats: also `stats` = dict(fallback_queries, cells_visited, faces_evaluated, grid,
+    h, pairs), one 32-byte host read.  A mesh without a usable face raises ValueError; N = 0 launches nothing."""
+    if method not in ("grid", "brute"):
+        raise ValueError("point_mesh_distance: method must be 'grid' or 'brute', got %r" % (method,))
+    lib = L.load()
+    q = _dev(points, "point_mesh_distance: points")
+    if q.dim() != 2 or q.shape[1] != 3 or q.dtype != torch.float32:
+        raise RuntimeError("point_mesh_distance: points must be fp32 [N, 3], got %s %s" % (q.dtype, tuple(q.shape)))
+    q = q.contiguous()
+    if grid is not None:
+        v, f, pairs = grid.vertices, grid.faces, grid.pairs
+    elif method == "brute":                         # no grid to build: only the count of usable faces, for the same ValueError
+        v, _, f = _check_mesh(m, "point_mesh_distance")
+        pairs = 0
+        one = L.NnGrid(0.0, 0.0, 0.0, 1.0, 1.0, 0.0, 1, 1, 1)
+        if f.shape[0] == 0 or int(_tri_cell_counts(lib, v, f, one).sum().item()) == 0:
+            raise ValueError("point_mesh_distance: %d faces over %d vertices, none valid, finite and with an area: no surface to measure against" %
+                             (f.shape[0], v.shape[0]))
+    else:
+        grid = TriangleGrid(m)
+        v, f, pairs = grid.vertices, grid.faces, grid.pairs
+    n, dev = q.shape[0], q.device
+    out = dict(dist=torch.empty(n, dtype=torch.float32, device=dev), closest=torch.empty((n, 3), dtype=torch.float32, device=dev),
+               face=torch.empty(n, dtype=torch.int32, device=dev), region=torch.empty(n, dtype=torch.uint8, device=dev))
+    stats = dict(fallback_queries=0, cells_visited=0, faces_evaluated=0, grid=(1, 1, 1) if grid is None else tuple(grid.dims),
+                 h=None if grid is None else grid.h, pairs=pairs)
+    if n > 0:
+        ws = _ws(lib.sp3_mesh_dist_query_ws_bytes(n), dev)
+        if method == "brute" or pairs == 0:
+            L.check(lib.sp3_mesh_dist_brute(q.data_ptr(), n, v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0], ws.data_ptr(),
+                                            out["dist"].data_ptr(), out["closest"].data_ptr(), out["face"].data_ptr(), out["region"].data_ptr(),
+                                            L.stream_ptr()), "sp3_mesh_dist_brute")
+            stats["fallback_queries"] = n
+        else:
+            order = grid.query_order(q)
+            L.check(lib.sp3_mesh_dist_query(q.data_ptr(), order.data_ptr(), n, v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0],
+                                            grid.pair_face.data_ptr(), grid.pairs, grid.cell_start.data_ptr(), C.byref(grid.g), int(ring_budget),
+                                            ws.data_ptr(), out["dist"].data_ptr(), out["closest"].data_ptr(), out["face"].data_ptr(),
+                                            out["region"].data_ptr(), L.stream_ptr()), "sp3_mesh_dist_query")
+            if return_stats:
+                head = ws[:32].cpu().numpy()
+                stats["fallback_queries"] = int(head[:4].view(np.int32)[0])
+                stats["cells_visited"], stats["faces_evaluated"] = (int(x) for x in head[16:32].view(np.uint64))
+    if return_stats:
+        out["stats"] = stats
     return out
 
 
