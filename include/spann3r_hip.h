@@ -40,6 +40,17 @@ enum { SP3_LOAD_PLAIN = 0, SP3_LOAD_CONV3X3 = 1, SP3_LOAD_SOFTMAX = 2 };
 const char* sp3_last_error(void);
 int sp3_version(void);
 
+/* Cache policy of the per-frame chain's once-read weight loads (process-wide):
+ *   0  every load uses the default policy
+ *   1  the library's table decides per kernel family and instance (the default)
+ *   2  every family that has a streaming variant streams (non-temporal weight loads): lean 196-row GEMMs, small-map and wide
+ *      3x3 convolutions, the q-projection attention
+ * Results are bit-identical under every mode; only the cache behaviour of the weight loads changes.  The mode is read at launch
+ * time (a captured graph keeps what it captured: set it before the first forward) and never changes what sp3_gemm_plan answers.
+ * Initialised from the environment variable SP3_W_STREAM (0 / 1 / 2).  sp3_weight_stream_set returns 0, or 1 for an unknown mode. */
+int sp3_weight_stream_set(int mode);
+int sp3_weight_stream_get(void);
+
 /* ------------------------------------------------------------------------------------------
  * sp3_gemm : C = epilogue( alpha * A[M,K] . W[N,K]^T )
  * Replaces every nn.Linear / 1x1 Conv2d / 3x3 Conv2d / ConvTranspose2d(k==stride) / einsum on the

@@ -365,13 +365,14 @@ __global__ __launch_bounds__(256) void attention_kernel(const typename AttnT<TT>
 // ------------------------------------------------------------------ bf16, fragment-order operands, prefetching
 struct KFrag { bf16x8 v[2]; };
 
-__device__ __forceinline__ KFrag load_frag(const __bf16* base, int row, int col, int K) {
+// WS: the streaming cache policy of a once-read weight (common.h ld_w16)
+template <bool WS = false> __device__ __forceinline__ KFrag load_frag(const __bf16* base, int row, int col, int K) {
   // lane (g, r) of a 16-row block reads its 16 elements (d = 16g .. 16g+15 of the head at `col`): two 16-byte halves,
   // one in each 1 KB piece of the fragment block
   const __bf16* p = base + packed_off(row, col, K, true);
   KFrag f;
-  f.v[0] = *reinterpret_cast<const bf16x8*>(p);
-  f.v[1] = *reinterpret_cast<const bf16x8*>(p + 64 * 8);
+  f.v[0] = ld_w16<WS>(p);
+  f.v[1] = ld_w16<WS>(p + 64 * 8);
   return f;
 }
 
@@ -392,7 +393,7 @@ struct QProjArgs {
   int group_imgs, img_tokens;
 };
 
-template <int NKB>
+template <int NKB, bool WS>
 __device__ __forceinline__ KFrag attn_qproj(const QProjArgs& qa, float* sh, int q0, int Nq, int h, int b, int lane, int wave, int g, int ql) {
   constexpr int D = NKB * 64, NL4 = NKB / 4, KW = NKB / 4, LD = 68;
   static_assert(NKB % 4 == 0 && NKB <= 16, "K over the 4 waves; LayerNorm partials: NKB / 4 float4 per lane of a 4-lane row team");
@@ -425,7 +426,7 @@ __device__ __forceinline__ KFrag attn_qproj(const QProjArgs& qa, float* sh, int 
     const int kb = wave + 4 * i;
     xf[i] = load_frag(X, xrow, kb * 64 + 16 * g, D);
 #pragma unroll
-    for (int t = 0; t < 4; ++t) wf[i][t] = load_frag(W, h * 64 + 16 * t + ql, kb * 64 + 16 * g, D);
+    for (int t = 0; t < 4; ++t) wf[i][t] = load_frag<WS>(W, h * 64 + 16 * t + ql, kb * 64 + 16 * g, D);
   }
   f32x4 acc[4];
 #pragma unroll
@@ -497,7 +498,7 @@ __device__ __forceinline__ KFrag attn_qproj(const QProjArgs& qa, float* sh, int 
 //     other resident waves cover the latency -- the explicit prefetch cost more registers than it hid).
 // 2 x 16 heads x 1024 tokens: 28.4 -> 21.5 us; 2 x 12 x 1024: 22.3 -> 16.7; 2 x 12 x 196: 4.26 -> 3.93.  Against the round-4 kernel the
 // outputs differ by <= 2.5e-4 of their maximum (the last bit of a probability before its bf16 rounding).
-template <int QB, int MINW, int QNKB = 0>
+template <int QB, int MINW, int QNKB = 0, bool WS = false>
 __global__ __launch_bounds__(256, MINW) void attention_packed_kernel(const __bf16* __restrict__ QP, int q_cols, int q_col0, int npad_q,
                                                                      const __bf16* __restrict__ KP, int k_cols, int k_col0, int npad_k,
                                                                      const __bf16* __restrict__ VTP, void* __restrict__ O, int64_t ldo,
@@ -557,7 +558,7 @@ __global__ __launch_bounds__(256, MINW) void attention_packed_kernel(const __bf1
     // round trip and the projection's operand round trip overlap
     static_assert(QB == 1, "the fused q projection serves one query block per workgroup");
     load_tile(wave < ntiles ? wave : ntiles - 1);
-    qf[0] = attn_qproj<QNKB>(qa, sh, q0, Nq, h, b, lane, wave, g, ql);
+    qf[0] = attn_qproj<QNKB, WS>(qa, sh, q0, Nq, h, b, lane, wave, g, ql);
   }
   if (wave < ntiles) {
     for (int tile = wave; tile < ntiles; tile += 4) {
@@ -852,15 +853,16 @@ void launch_rows(const void* q, int64_t sq, int64_t ldq, const void* k, int64_t 
                      scale, lse, G.xcd_map);
 }
 
-// fragment-order bf16 operands, QB query blocks per workgroup; QNKB > 0: q comes from the projection `qa` (qp unused)
-template <int QB, int MINW, int QNKB = 0>
+// fragment-order bf16 operands, QB query blocks per workgroup; QNKB > 0: q comes from the projection `qa` (qp unused), whose Wq
+// loads stream if WS
+template <int QB, int MINW, int QNKB = 0, bool WS = false>
 void launch_packed(const void* qp, int q_cols, int q_col0, int npad_q, const void* kp, int k_cols, int k_col0, int npad_k, const void* vtp,
                    void* out, int64_t ldo, int out_bf16, int out_packed, int B, int heads, int Nq, int Nk, float scale, int o_group,
                    int o_group_rows, const QProjArgs& qa, void* stream) {
   constexpr int lds = (4 * QB * 4 * 64 * 4 + 2 * 4 * QB * 64) * 4;       // the merge scratch: sh_o, sh_m, sh_l of the kernel
   static_assert(QNKB == 0 || lds >= 4 * 16 * 68 * 4, "the q projection's partial tiles fit the merge scratch");
   const AttnGrid G = attn_grid((Nq + 16 * QB - 1) / (16 * QB), heads, B);
-  hipLaunchKernelGGL((attention_packed_kernel<QB, MINW, QNKB>), G.grid, dim3(256), lds, reinterpret_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL((attention_packed_kernel<QB, MINW, QNKB, WS>), G.grid, dim3(256), lds, reinterpret_cast<hipStream_t>(stream),
                      static_cast<const __bf16*>(qp), q_cols, q_col0, npad_q, static_cast<const __bf16*>(kp), k_cols, k_col0, npad_k,
                      static_cast<const __bf16*>(vtp), out, ldo, out_bf16, out_packed, heads, Nq, Nk, scale, o_group, o_group_rows,
                      G.xcd_map, qa);
@@ -933,8 +935,9 @@ extern "C" int sp3_attention_packed_qproj(const sp3_attn_qproj_desc* dp, void* s
   qa.ln_s = d.ln_s; qa.bias = d.bias; qa.v_gs = d.vec_group_stride;
   qa.pos = d.pos; qa.cos = d.rope_cos; qa.sin = d.rope_sin;
   qa.eps = d.ln_eps; qa.group_imgs = d.o_group; qa.img_tokens = d.Nq;
-  launch_packed<1, 2, 12>(nullptr, 0, 0, 16, d.kp, d.k_cols, d.k_col0, d.npad_k, d.vtp, d.out, d.ldo, d.out_bf16, d.out_packed, d.B, d.heads,
-                          d.Nq, d.Nk, d.scale, d.o_group, d.o_group_rows, qa, stream);
+  const auto launch = sp3_weight_streams(SP3_WF_ATTN_QPROJ, 0) ? launch_packed<1, 2, 12, true> : launch_packed<1, 2, 12, false>;
+  launch(nullptr, 0, 0, 16, d.kp, d.k_cols, d.k_col0, d.npad_k, d.vtp, d.out, d.ldo, d.out_bf16, d.out_packed, d.B, d.heads, d.Nq, d.Nk, d.scale,
+         d.o_group, d.o_group_rows, qa, stream);
   SP3_LAUNCH_CHECK("sp3_attention_packed_qproj");
   return 0;
 }

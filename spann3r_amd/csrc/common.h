@@ -125,6 +125,23 @@ __device__ __forceinline__ void st_out(bf16x8* p, bf16x8 v) {
 template <typename T> __device__ __forceinline__ void st_out(T* p, T v) { *p = v; }
 #endif
 
+// Weight loads of the per-frame chain, by cache policy.  A 224 x 224 step reads ~650 MB of weights once each -- more than the 256 MB
+// MALL holds -- so every launch meets its weights cold, and a line it leaves behind in L2 / MALL is never hit again: it only evicts
+// what the step does re-read (the bank, activations, head maps).  The STREAM form marks such loads non-temporal
+// (global_load_dwordx4 ... nt; buffer loads and LDS DMA: aux = SP3_AUX_STREAM); the arithmetic does not change.  WS = false is the
+// plain load: the default-policy variant of a kernel is the code it had before the policy existed.  Which launches use which form
+// is a host decision per kernel family and instance (weight_stream.cpp); activation, bank, statistics and residual loads never do.
+enum { SP3_AUX_DEFAULT = 0, SP3_AUX_STREAM = 2 };      // aux of __builtin_amdgcn_raw_buffer_load_* / __builtin_amdgcn_global_load_lds
+template <bool WS> __device__ __forceinline__ bf16x8 ld_w16(const void* p) {
+  if constexpr (WS) return __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(p));
+  else return *reinterpret_cast<const bf16x8*>(p);
+}
+
+// The policy table (weight_stream.cpp).  family: SP3_WF_*; instance: the family's own id (lean GEMM / small-map conv: tile id; wide
+// conv: NF; q-projection attention: 0).  True if a launch issued now streams its weights.
+enum { SP3_WF_GEMM_SM = 0, SP3_WF_CONV_SM = 1, SP3_WF_ATTN_QPROJ = 2, SP3_WF_CONV_WIDE = 3, SP3_WF_COUNT = 4 };
+bool sp3_weight_streams(int family, int instance);
+
 // Bilinear x2 (align_corners=True) read of a half-resolution NHWC map at output pixel (oy, ox): the index clamps, scale factors and
 // association of sp3_upsample2x (csrc/dpt.hip), for epilogues that take the upsampled map as a residual without it existing in
 // memory.  p00..p11: pixel offsets (y * W + x) of the four taps in the H x W source.

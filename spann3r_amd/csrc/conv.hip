@@ -258,7 +258,8 @@ template <int NF> constexpr int lds_bytes() {                     // halo chunk,
 // from memory, 8 no epilogue (a dummy consumer keeps the MFMAs alive)
 // NF = 16-channel column blocks per workgroup: 4 (64 output channels), or 2 for maps whose grid of 64-channel tiles leaves most CUs idle
 // (batch-1 56 x 56: 112 workgroups) -- twice the workgroups, each with half the W stream, at twice the LDS reads per MFMA.
-template <typename TIN, int NF = 4, int ABL = 0>
+// WS: the weight queue's loads use the streaming cache policy (common.h SP3_AUX_STREAM); halo loads keep the default one
+template <typename TIN, int NF = 4, int ABL = 0, bool WS = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_wide_kernel(const ConvArgs a) {
   constexpr int BN = 16 * NF, SLAB_LD = BN + 4;
   // W units in flight per wave.  NF = 2 has the registers for a whole chunk (9 units x 2 fragments x 4): the queue slot is the tap, and
@@ -298,7 +299,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wide_kernel(const ConvArgs a) 
   auto w_load = [&](uint32_t o, bf16x8* dst) {
 #pragma unroll
     for (int n = 0; n < NF; ++n) {
-      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wlane, o + n * panel_bytes, 0);
+      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wlane, o + n * panel_bytes, WS ? SP3_AUX_STREAM : SP3_AUX_DEFAULT);
       dst[n] = *reinterpret_cast<const bf16x8*>(&v);
     }
   };
@@ -458,6 +459,22 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wide_kernel(const ConvArgs a) 
     }
   }
 }
+
+template <typename TIN, int NF, bool WS>
+int launch(dim3 grid, hipStream_t st, const ConvArgs& a) {
+  constexpr int lds = lds_bytes<NF>();
+  auto kern = conv3x3_wide_kernel<TIN, NF, 0, WS>;
+  if (lds > 64 * 1024) {
+    static bool raised = false;               // per instantiation: opt in to > 64 KiB of dynamic LDS once
+    if (!raised) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      if (e != hipSuccess) { sp3_set_error("sp3_conv3x3_tile: cannot raise dynamic LDS to %d: %s", lds, hipGetErrorString(e)); return 2; }
+      raised = true;
+    }
+  }
+  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
+  return 0;
+}
 }  // namespace wide
 
 }  // namespace
@@ -496,19 +513,12 @@ extern "C" int sp3_conv3x3_tile(const void* x, int in_bf16, const void* w_packed
       a.tiles_x = wtx; a.tiles_y = wty;
       dim3 grid(wtx * wty * B, Cout / (16 * nf));
       if (xcd_on) { a.xcd_nb = Cout / (16 * nf); grid = dim3((unsigned)(((wtx * wty * B + 7) / 8) * 8 * a.xcd_nb), 1); }
-      auto launch = [&](auto kern, int lds_bytes) -> int {
-        static bool raised = false;               // per instantiation: opt in to > 64 KiB of dynamic LDS once
-        if (!raised && lds_bytes > 64 * 1024) {
-          hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-          if (e != hipSuccess) { sp3_set_error("sp3_conv3x3_tile: cannot raise dynamic LDS to %d: %s", lds_bytes, hipGetErrorString(e)); return 2; }
-          raised = true;
-        }
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds_bytes, st, a);
-        return 0;
-      };
+      const bool ws = sp3_weight_streams(SP3_WF_CONV_WIDE, nf);
       int rc;
-      if (nf == 4) rc = in_bf16 ? launch(wide::conv3x3_wide_kernel<__bf16, 4>, wide::lds_bytes<4>()) : launch(wide::conv3x3_wide_kernel<float, 4>, wide::lds_bytes<4>());
-      else         rc = in_bf16 ? launch(wide::conv3x3_wide_kernel<__bf16, 2>, wide::lds_bytes<2>()) : launch(wide::conv3x3_wide_kernel<float, 2>, wide::lds_bytes<2>());
+      if (nf == 4) rc = in_bf16 ? (ws ? wide::launch<__bf16, 4, true>(grid, st, a) : wide::launch<__bf16, 4, false>(grid, st, a))
+                                : (ws ? wide::launch<float, 4, true>(grid, st, a) : wide::launch<float, 4, false>(grid, st, a));
+      else         rc = in_bf16 ? (ws ? wide::launch<__bf16, 2, true>(grid, st, a) : wide::launch<__bf16, 2, false>(grid, st, a))
+                                : (ws ? wide::launch<float, 2, true>(grid, st, a) : wide::launch<float, 2, false>(grid, st, a));
       if (rc) return rc;
       SP3_LAUNCH_CHECK("sp3_conv3x3_tile");
       return 0;

@@ -57,7 +57,8 @@ struct SmArgs {
 // grid = (8, mt, nz): linear workgroup id = x + 8 (y + mt z) -> XCD x; tile_m = y; z = group * ntz + zt, tile_n = 8 zt + x
 // SPLIT: A = [A | A2] along K (torch.cat(..., dim=-1) without the copy, spann3r/model.py:300): k-blocks [0, nkb1) come from A (a
 // fragment-order [M, 64 nkb1] matrix), the rest from A2 ([M, 64 (NKB - nkb1)])
-template <int MF, int NF, int WK, int NKB, int RING, int EPI, bool SPLIT = false>
+// WS: W goes through the streaming cache policy (common.h ld_w16); A and every epilogue operand keep the default one
+template <int MF, int NF, int WK, int NKB, int RING, int EPI, bool SPLIT = false, bool WS = false>
 __global__ __launch_bounds__(64 * WK) void sm_kernel(const SmArgs a) {
   constexpr int BM = MF * 16, BN = NF * 16, NT = 64 * WK;
   constexpr int NKW = NKB / WK;                               // k-blocks per wave
@@ -170,8 +171,8 @@ __global__ __launch_bounds__(64 * WK) void sm_kernel(const SmArgs a) {
   auto load = [&](int slot, int i) {
 #pragma unroll
     for (int n = 0; n < NF; ++n) {
-      wv[slot][n][0] = *reinterpret_cast<const bf16x8*>(wp[n] + (long)i * WK * 2048);
-      wv[slot][n][1] = *reinterpret_cast<const bf16x8*>(wp[n] + (long)i * WK * 2048 + 1024);
+      wv[slot][n][0] = ld_w16<WS>(wp[n] + (long)i * WK * 2048);
+      wv[slot][n][1] = ld_w16<WS>(wp[n] + (long)i * WK * 2048 + 1024);
     }
     const bool from2 = SPLIT && (wk + i * WK) >= nkb1;         // wave-uniform
 #pragma unroll
@@ -1339,7 +1340,7 @@ __device__ __forceinline__ void csm_store4(__bf16* p, const float (&v)[4]) {
 }
 
 // one workgroup's output tile (tile_m, tile_n).  Waves past WK (a level launch sized for a wider member) leave before the barrier.
-template <typename TM, int MF, int NF, int WK, int R>
+template <typename TM, int MF, int NF, int WK, int R, bool WS>
 __device__ __forceinline__ void conv_sm_body(const ConvSmArgs& a, const int tile_m, const int tile_n, float* smem) {
   constexpr int BM = MF * 16, BN = NF * 16, NT = 64 * WK, LD = BN + 4, CG = BN / 4;
   const int tid = threadIdx.x, lane = tid & 63, wk = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1384,8 +1385,8 @@ __device__ __forceinline__ void conv_sm_body(const ConvSmArgs& a, const int tile
   auto load = [&](int slot, int kb) {
 #pragma unroll
     for (int n = 0; n < NF; ++n) {
-      wv[slot][n][0] = *reinterpret_cast<const bf16x8*>(wp[n] + (long)kb * 2048);
-      wv[slot][n][1] = *reinterpret_cast<const bf16x8*>(wp[n] + (long)kb * 2048 + 1024);
+      wv[slot][n][0] = ld_w16<WS>(wp[n] + (long)kb * 2048);
+      wv[slot][n][1] = ld_w16<WS>(wp[n] + (long)kb * 2048 + 1024);
     }
     const int k0 = kb * 64 + g * 16;
     const int tap = (int)__umulhi((unsigned)k0, a.cin_magic), ci = k0 - tap * a.Cin;
@@ -1468,14 +1469,14 @@ __device__ __forceinline__ void conv_sm_body(const ConvSmArgs& a, const int tile
   }
 }
 
-template <typename TM, int MF, int NF, int WK, int R>
+template <typename TM, int MF, int NF, int WK, int R, bool WS>
 __global__ __launch_bounds__(64 * WK) void conv_sm_kernel(const ConvSmArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  conv_sm_body<TM, MF, NF, WK, R>(a, blockIdx.y, blockIdx.z * 8 + blockIdx.x, smem);
+  conv_sm_body<TM, MF, NF, WK, R, WS>(a, blockIdx.y, blockIdx.z * 8 + blockIdx.x, smem);
 }
 
 // workgroup w of a level launch -> (problem, tile_m, tile_n): within a problem the order of its own grid (8, mt, ntz), x fastest
-template <typename TM>
+template <typename TM, bool WS>
 __global__ __launch_bounds__(64 * 12) void conv_level_kernel(const ConvLevelArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int w = blockIdx.x;
@@ -1489,20 +1490,21 @@ __global__ __launch_bounds__(64 * 12) void conv_level_kernel(const ConvLevelArgs
     // K = 6912 a wave walks 9 k-blocks, i.e. 2 cold round trips (fp32: 3) instead of 3
     constexpr int R40 = sizeof(TM) == 2 ? 6 : 4;
     const int mt = (q.M + 15) / 16;
-    conv_sm_body<TM, 1, 1, 12, R40>(q, j % mt, (j / mt) * 8 + (local & 7), smem);
+    conv_sm_body<TM, 1, 1, 12, R40, WS>(q, j % mt, (j / mt) * 8 + (local & 7), smem);
   } else if constexpr (sizeof(TM) == 2) {       // (fp32 maps: the 32x32 body needs 240 registers, 12 waves leave 168 -- it stays in launches of its own)
     const int mt = (q.M + 31) / 32;
-    conv_sm_body<TM, 2, 2, 8, 3>(q, j % mt, (j / mt) * 8 + (local & 7), smem);
+    conv_sm_body<TM, 2, 2, 8, 3, WS>(q, j % mt, (j / mt) * 8 + (local & 7), smem);
   }
 }
 
 template <typename TM, int MF, int NF, int WK, int R>
-int conv_sm_launch(const ConvSmArgs& a, hipStream_t stream) {
+int conv_sm_launch(const ConvSmArgs& a, int tile, hipStream_t stream) {
   constexpr int BM = MF * 16, BN = NF * 16;
   constexpr size_t lds = (size_t)WK * BM * (BN + 4) * sizeof(float);
   static_assert(lds <= 64 * 1024, "partial tiles: default dynamic LDS limit");
   const int mt = (a.M + BM - 1) / BM, ntz = (a.N / BN + 7) / 8;
-  hipLaunchKernelGGL((conv_sm_kernel<TM, MF, NF, WK, R>), dim3(8, mt, ntz), dim3(64 * WK), lds, stream, a);
+  if (sp3_weight_streams(SP3_WF_CONV_SM, tile)) hipLaunchKernelGGL((conv_sm_kernel<TM, MF, NF, WK, R, true>), dim3(8, mt, ntz), dim3(64 * WK), lds, stream, a);
+  else hipLaunchKernelGGL((conv_sm_kernel<TM, MF, NF, WK, R, false>), dim3(8, mt, ntz), dim3(64 * WK), lds, stream, a);
   SP3_LAUNCH_CHECK("sp3_gemm (lean conv3x3)");
   return 0;
 }
@@ -1543,13 +1545,13 @@ ConvSmArgs conv_sm_args(const sp3_gemm_desc& d) {
 int conv_sm_dispatch(const sp3_gemm_desc& d, int tile, hipStream_t stream) {
   const ConvSmArgs a = conv_sm_args(d);
   if (d.a_bf16) {
-    if (tile == 40) return conv_sm_launch<__bf16, 1, 1, 12, 3>(a, stream);
+    if (tile == 40) return conv_sm_launch<__bf16, 1, 1, 12, 3>(a, tile, stream);
     // a single 32x32 launch has 8 waves, i.e. 256 registers: a ring of 5 (238, no scratch) holds all the k-blocks a wave walks at
     // K = 2304 -- one cold round trip instead of two.  (fp32 maps: 5 spills 188 registers, the ring stays at 3)
-    return conv_sm_launch<__bf16, 2, 2, 8, 5>(a, stream);
+    return conv_sm_launch<__bf16, 2, 2, 8, 5>(a, tile, stream);
   }
-  if (tile == 40) return conv_sm_launch<float, 1, 1, 12, 3>(a, stream);
-  return conv_sm_launch<float, 2, 2, 8, 3>(a, stream);
+  if (tile == 40) return conv_sm_launch<float, 1, 1, 12, 3>(a, tile, stream);
+  return conv_sm_launch<float, 2, 2, 8, 3>(a, tile, stream);
 }
 
 // Level launch: problems sorted by the k-blocks a wave walks (longest first: its workgroups are dispatched first); block size and
@@ -1579,8 +1581,16 @@ int conv_level_dispatch(const sp3_gemm_desc* ds, int n, hipStream_t stream) {
   for (int i = n; i < 4; ++i) { a.p[i] = a.p[0]; a.tile[i] = a.tile[0]; a.start[i + 1] = 0x7fffffff; }
   const int blocks = a.start[n];
   if (n < 4) a.start[n] = 0x7fffffff;
-  if (ds[0].a_bf16) hipLaunchKernelGGL(conv_level_kernel<__bf16>, dim3(blocks), dim3(threads), lds, stream, a);
-  else              hipLaunchKernelGGL(conv_level_kernel<float>, dim3(blocks), dim3(threads), lds, stream, a);
+  // one policy per launch: a level streams its weights if every member's instance does
+  bool ws = true;
+  for (int i = 0; i < n; ++i) ws = ws && sp3_weight_streams(SP3_WF_CONV_SM, a.tile[i]);
+  if (ds[0].a_bf16) {
+    if (ws) hipLaunchKernelGGL((conv_level_kernel<__bf16, true>), dim3(blocks), dim3(threads), lds, stream, a);
+    else    hipLaunchKernelGGL((conv_level_kernel<__bf16, false>), dim3(blocks), dim3(threads), lds, stream, a);
+  } else {
+    if (ws) hipLaunchKernelGGL((conv_level_kernel<float, true>), dim3(blocks), dim3(threads), lds, stream, a);
+    else    hipLaunchKernelGGL((conv_level_kernel<float, false>), dim3(blocks), dim3(threads), lds, stream, a);
+  }
   SP3_LAUNCH_CHECK("sp3_gemm_n (lean conv3x3 level)");
   return 0;
 }
@@ -1599,12 +1609,12 @@ struct SmInst {
   int tile_n() const { return bn ? bn : NF * 16; }
 };
 
-template <int MF, int NF, int WK, int NKB, int RING, int EPI, bool SPLIT = false>
+template <int MF, int NF, int WK, int NKB, int RING, int EPI, bool SPLIT = false, bool WS = false>
 int sm_launch(const SmArgs& a, int mt, int nz, hipStream_t stream) {
   constexpr int BM = MF * 16, BN = NF * 16;
   constexpr size_t lds = ((size_t)WK * BM * (BN + 4) + 2 * BM) * sizeof(float);
   static_assert(lds <= 160 * 1024, "partial tiles must fit the LDS");
-  auto kern = sm_kernel<MF, NF, WK, NKB, RING, EPI, SPLIT>;
+  auto kern = sm_kernel<MF, NF, WK, NKB, RING, EPI, SPLIT, WS>;
   if (lds > 64 * 1024) {
     static bool raised = false;
     if (!raised) {
@@ -1618,23 +1628,30 @@ int sm_launch(const SmArgs& a, int mt, int nz, hipStream_t stream) {
   return 0;
 }
 
+// the instance with the weight cache policy its tile id has in the table (weight_stream.cpp) when the launch is issued
+template <int TILE, int MF, int NF, int WK, int NKB, int RING, int EPI, bool SPLIT = false>
+int sm_launch_p(const SmArgs& a, int mt, int nz, hipStream_t stream) {
+  return sp3_weight_streams(SP3_WF_GEMM_SM, TILE) ? sm_launch<MF, NF, WK, NKB, RING, EPI, SPLIT, true>(a, mt, nz, stream)
+                                                  : sm_launch<MF, NF, WK, NKB, RING, EPI, SPLIT, false>(a, mt, nz, stream);
+}
+
 // The instances, chosen per shape from tools/ubench/gemm_sm.hip on MI355X (profiles/r04_gemm_small_m_tile_sweep.txt).
 // tile ids 30.. are what sp3_gemm_desc.tile / the profiles call them.
 const SmInst kInst[] = {
     // ROPE (q/k/v projections): BN % 32 == 0 (the RoPE partner column lies in the tile)
-    {30, SM_ROPE, 1024, 3, 4, 8, false, 0, 1 << 30, sm_launch<3, 4, 8, 16, 0, SM_ROPE>},      // val / enc-step qkv: 48x64, K over 8 waves
-    {31, SM_ROPE, 768, 2, 2, 4, false, 0, 1 << 30, sm_launch<2, 2, 4, 12, 0, SM_ROPE>},       // decoder qkv + ckv pair, cross q: 32x32 k4
+    {30, SM_ROPE, 1024, 3, 4, 8, false, 0, 1 << 30, sm_launch_p<30, 3, 4, 8, 16, 0, SM_ROPE>},      // val / enc-step qkv: 48x64, K over 8 waves
+    {31, SM_ROPE, 768, 2, 2, 4, false, 0, 1 << 30, sm_launch_p<31, 2, 2, 4, 12, 0, SM_ROPE>},       // decoder qkv + ckv pair, cross q: 32x32 k4
     // PACKED (fc1 + GELU, key MLP hidden)
-    {32, SM_PACKED, 1024, 4, 4, 8, false, 0, 1 << 30, sm_launch<4, 4, 8, 16, 0, SM_PACKED>},  // val fc1: 64x64 k8
-    {33, SM_PACKED, 768, 2, 4, 4, false, 0, 1 << 30, sm_launch<2, 4, 4, 12, 0, SM_PACKED>},   // dec fc1 x2: 32x64 k4
-    {42, SM_PACKED, 1792, 4, 2, 7, true, 0, 1 << 30, sm_launch<4, 2, 7, 28, 0, SM_PACKED, true>},   // key MLP hidden x2 (split A: feat | dec[-1]): 64x32 k7
+    {32, SM_PACKED, 1024, 4, 4, 8, false, 0, 1 << 30, sm_launch_p<32, 4, 4, 8, 16, 0, SM_PACKED>},  // val fc1: 64x64 k8
+    {33, SM_PACKED, 768, 2, 4, 4, false, 0, 1 << 30, sm_launch_p<33, 2, 4, 4, 12, 0, SM_PACKED>},   // dec fc1 x2: 32x64 k4
+    {42, SM_PACKED, 1792, 4, 2, 7, true, 0, 1 << 30, sm_launch_p<42, 4, 2, 7, 28, 0, SM_PACKED, true>},   // key MLP hidden x2 (split A: feat | dec[-1]): 64x32 k7
     // STREAM (output projections onto the residual stream)
-    {39, SM_STREAM, 1024, 3, 2, 8, false, 0, 768, sm_launch<3, 2, 8, 16, 0, SM_STREAM>},      // decoder_embed x2 (N = 768): 48x32 k8
-    {34, SM_STREAM, 1024, 2, 2, 8, false, 769, 1 << 30, sm_launch<2, 2, 8, 16, 0, SM_STREAM>},  // val proj, value_out: 32x32 k8
-    {35, SM_STREAM, 4096, 2, 2, 8, false, 0, 1 << 30, sm_launch<2, 2, 8, 64, 4, SM_STREAM>},   // val fc2: 32x32 k8, ring of 4
-    {36, SM_STREAM, 768, 3, 2, 6, false, 0, 1 << 30, sm_launch<3, 2, 6, 12, 0, SM_STREAM>},   // dec proj / cproj x2, pos patch embed: 48x32 k6
-    {37, SM_STREAM, 3072, 3, 2, 8, false, 0, 1 << 30, sm_launch<3, 2, 8, 48, 3, SM_STREAM>},  // dec fc2 x2: 48x32 k8, ring of 3
-    {38, SM_STREAM, 1792, 4, 2, 7, false, 0, 1 << 30, sm_launch<4, 2, 7, 28, 0, SM_STREAM>},  // key MLP out x2: 64x32 k7
+    {39, SM_STREAM, 1024, 3, 2, 8, false, 0, 768, sm_launch_p<39, 3, 2, 8, 16, 0, SM_STREAM>},      // decoder_embed x2 (N = 768): 48x32 k8
+    {34, SM_STREAM, 1024, 2, 2, 8, false, 769, 1 << 30, sm_launch_p<34, 2, 2, 8, 16, 0, SM_STREAM>},  // val proj, value_out: 32x32 k8
+    {35, SM_STREAM, 4096, 2, 2, 8, false, 0, 1 << 30, sm_launch_p<35, 2, 2, 8, 64, 4, SM_STREAM>},   // val fc2: 32x32 k8, ring of 4
+    {36, SM_STREAM, 768, 3, 2, 6, false, 0, 1 << 30, sm_launch_p<36, 3, 2, 6, 12, 0, SM_STREAM>},   // dec proj / cproj x2, pos patch embed: 48x32 k6
+    {37, SM_STREAM, 3072, 3, 2, 8, false, 0, 1 << 30, sm_launch_p<37, 3, 2, 8, 48, 3, SM_STREAM>},  // dec fc2 x2: 48x32 k8, ring of 3
+    {38, SM_STREAM, 1792, 4, 2, 7, false, 0, 1 << 30, sm_launch_p<38, 4, 2, 7, 28, 0, SM_STREAM>},  // key MLP out x2: 64x32 k7
     // SCORE (the memory read's S = LN_q(q) . K_hat^T / 32 with the softmax statistics of its 32-key groups; N = bank tokens, any multiple of 4)
     {43, SM_SCORE, 1024, 2, 2, 8, false, 0, 1 << 30, sm_launch<2, 2, 8, 16, 0, SM_SCORE>},
     // PROB (round 6: the long-bank read's score stage for > 256 query rows -- a 512 x 512 frame -- without a score matrix)

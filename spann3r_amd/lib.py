@@ -313,10 +313,11 @@ _PROTOS = {
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p],
     "sp3_tsdf_brick_to_dense": [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
                                 C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_weight_stream_set": [C.c_int],
     "sp3_tsdf_brick_extract": [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
 }
-EXPORTS = sorted(list(_PROTOS) + ["sp3_last_error", "sp3_version", "sp3_conf_loss_ws_bytes", "sp3_ssi_loss_ws_bytes", "sp3_sumsq_blocks", "sp3_colsum_rows_ws",
+EXPORTS = sorted(list(_PROTOS) + ["sp3_last_error", "sp3_version", "sp3_weight_stream_get", "sp3_conf_loss_ws_bytes", "sp3_ssi_loss_ws_bytes", "sp3_sumsq_blocks", "sp3_colsum_rows_ws",
                                   "sp3_nn_query_ws_bytes", "sp3_icp_accum_ws_bytes", "sp3_sum_count_ws_bytes",
                                   "sp3_mesh_faces_ws_bytes", "sp3_mesh_vertices_ws_bytes", "sp3_eval_align_ws_bytes",
                                   "sp3_tsdf_extract_ws_bytes", "sp3_tsdf_track_accum_ws_bytes", "sp3_tsdf_brick_alloc_ws_bytes",
@@ -337,6 +338,8 @@ def load():
     lib.sp3_last_error.restype = C.c_char_p
     lib.sp3_last_error.argtypes = []
     lib.sp3_version.restype = C.c_int
+    lib.sp3_weight_stream_get.restype = C.c_int
+    lib.sp3_weight_stream_get.argtypes = []
     lib.sp3_conf_loss_ws_bytes.restype = C.c_int64
     lib.sp3_conf_loss_ws_bytes.argtypes = [C.c_int, C.c_int]
     lib.sp3_ssi_loss_ws_bytes.restype = C.c_int64
