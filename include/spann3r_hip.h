@@ -663,6 +663,8 @@ int sp3_pnp_score(const float* pts, int F, int H, int W, float focal, float cx, 
  * sp3_nn_grid: a uniform cell grid over the reference cloud, chosen by the host: origin = the cloud's minimum corner, cell edge h,
  *   inv_h = 1 / h, dims nx * ny * nz (<= 2^24 cells); cell of x = clamp(floor((x - ox) * inv_h), 0, nx - 1), id = (cz * ny + cy) * nx + cx.
  *   slack: an upper bound of the fp32 rounding of cell assignment and wall positions, taken off every stopping bound.
+ *   csrc/cell_grid.h is the one statement of the grid's rule (cell of x, ring walk, stopping bound, workspace head), shared by
+ *   sp3_nn_query, sp3_knn_query and sp3_mesh_dist_query; spann3r_amd/cell_grid.py is the host half (h, dims, slack, cell_start).
  * sp3_nn_cell_ids     : ids[n] = cell id of every point (also used for the queries, clamped into the grid).
  * sp3_nn_pack_records : recs[i] = (x, y, z, bit pattern of s) of point s = order[i] (order null: s = i): 16-byte records.
  * sp3_nn_query : exact nearest neighbour of q[nq] among the m records sorted by cell id, cell_start[cells + 1] = first record of each
@@ -1338,7 +1340,8 @@ int sp3_mesh_vertex_normals(const float* vertices, int64_t nverts, const int32_t
  * sp3_mesh_dist_query : one lane per query, taken in q_order (nullable; sorted by home cell, clamped into the grid), results in
  *   caller order.  Rings r = 0..max_ring around the home cell.  A face no cell of the visited block holds has, on one axis, all its
  *   cells beyond one wall of the block, so it lies wholly behind that wall: the query is finished when sqrt of its best d2 is within
- *   the distance to the nearest wall of the block that still has cells behind it, less the slack -- sp3_nn_query's rule.  Queries
+ *   the distance to the nearest wall of the block that still has cells behind it, less the slack -- the walk and the bound of
+ *   csrc/cell_grid.h, the same code sp3_nn_query runs.  Queries
  *   left open go through the brute-force kernels.  pair_face [npairs] sorted by cell; indices read from it, from cell_start and from
  *   faces are range-checked before use.  After the call the first 32 bytes of ws hold { int32 fallback queries, 3 x int32 pad,
  *   uint64 cells visited, uint64 faces evaluated } (by the grid kernel).  nq = 0 launches nothing.

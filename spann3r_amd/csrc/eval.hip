@@ -1,23 +1,18 @@
 // Reconstruction metrics on the device (reference: eval.py:189-231, spann3r/tools/eval_recon.py): exact nearest-neighbour
 // search between two point clouds, k-NN / PCA normals, and the correspondence sums of point-to-point ICP.
 //
-//   * The reference cloud is binned into a uniform cell grid (host picks origin / edge h / dims, spann3r_amd/evaluate.py);
+//   * The reference cloud is binned into a uniform cell grid (host picks origin / edge h / dims, spann3r_amd/cell_grid.py);
 //     its points are stored sorted by cell as 16-byte records (x, y, z, original index) with a cell-start table.
-//   * A query walks the cells around its (clamped) home cell by Chebyshev ring r = 0, 1, ...  After ring r every unvisited
-//     point lies beyond a wall of the visited block, so the distance from the query to the nearest wall that still has cells
-//     behind it is a lower bound for everything unvisited (>= r*h for a query inside the box; sides with no cells behind
-//     them do not count, which is what makes it hold for queries outside the box too).  A query is finished when its best
-//     (k-th best) distance is within that bound, less a slack that covers the fp32 rounding of the cell assignment.
-//   * Queries still open after `max_ring` rings are compacted into a list; an LDS-tiled brute-force kernel serves them, the
-//     reference cloud split over workgroups and joined by a 64-bit integer atomicMin of (distance bits, index): the minimum
-//     does not depend on arrival order, so results are bit-reproducible.
-//   * Distances are direct differences, every operation rounded on its own (no FMA contraction): the squared distance is the
-//     same number a numpy fp32 restatement computes, whatever the compiler does.
+//   * A query walks the cells around its home cell ring by ring until its best (k-th best) distance is within the bound of
+//     the walked block: csrc/cell_grid.h states the walk, the bound and its slack, and why the result is exact.
+//   * Queries still open after `max_ring` rings go to an LDS-tiled brute-force kernel, the reference cloud split over workgroups
+//     and joined by a 64-bit integer atomicMin of (distance bits, index): order-free, so results are bit-reproducible.
+//   * Distances are direct differences.  dist2 uses the _rn intrinsics, which this compiler defines as plain operators: the sum is
+//     contracted into two FMAs, so d2 is within eval_ref.dist_bound but NOT bit-equal to a numpy fp32 restatement (unfusing moves bits).
 //   * Sums (ICP correspondences, metric means) are fp64 per workgroup into partial slabs, finished by a second kernel in a
 //     fixed order: no float atomics.
-#include "common.h"
+#include "cell_grid.h"
 #include "slab.h"
-#include <math.h>
 
 namespace {
 
@@ -34,23 +29,17 @@ __device__ __forceinline__ Rec ld_rec(const float4* p) {
   return r;
 }
 
-// (ax-bx)^2 + (ay-by)^2 + (az-bz)^2, each operation rounded to nearest on its own
+// (ax-bx)^2 + (ay-by)^2 + (az-bz)^2; the differences are rounded on their own, the sum compiles to a product and two FMAs (above)
 __device__ __forceinline__ float dist2(float ax, float ay, float az, float bx, float by, float bz) {
   const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by), dz = __fsub_rn(az, bz);
   return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
 }
 
-__device__ __forceinline__ int cell_axis(float x, float o, float inv_h, int n) {
-  const float t = floorf((x - o) * inv_h);
-  return (int)fminf(fmaxf(t, 0.f), (float)(n - 1));   // NaN -> 0: always a valid cell
-}
-
 __global__ __launch_bounds__(256) void cell_ids_kernel(const float* __restrict__ pts, int64_t n, sp3_nn_grid g, int* __restrict__ ids) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const int cx = cell_axis(pts[3 * i], g.ox, g.inv_h, g.nx), cy = cell_axis(pts[3 * i + 1], g.oy, g.inv_h, g.ny),
-            cz = cell_axis(pts[3 * i + 2], g.oz, g.inv_h, g.nz);
-  ids[i] = (cz * g.ny + cy) * g.nx + cx;
+  const Cell c = cell_of(g, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
+  ids[i] = cell_id(g, c.x, c.y, c.z);
 }
 
 __global__ __launch_bounds__(256) void pack_records_kernel(const float* __restrict__ pts, const int64_t* __restrict__ order, int64_t n,
@@ -61,104 +50,51 @@ __global__ __launch_bounds__(256) void pack_records_kernel(const float* __restri
   recs[i] = make_float4(pts[3 * s], pts[3 * s + 1], pts[3 * s + 2], __int_as_float((int)s));
 }
 
-// Lower bound of the distance from q to any point outside the cell block [c - r, c + r]^3 (clipped to the grid), less the slack.
-// +inf when the block covers the whole grid.
-__device__ __forceinline__ float ring_bound(const sp3_nn_grid& g, float qx, float qy, float qz, int cx, int cy, int cz, int r) {
-  float b = INFINITY;
-  if (cx - r > 0) b = fminf(b, qx - (g.ox + (float)(cx - r) * g.h));
-  if (cx + r < g.nx - 1) b = fminf(b, (g.ox + (float)(cx + r + 1) * g.h) - qx);
-  if (cy - r > 0) b = fminf(b, qy - (g.oy + (float)(cy - r) * g.h));
-  if (cy + r < g.ny - 1) b = fminf(b, (g.oy + (float)(cy + r + 1) * g.h) - qy);
-  if (cz - r > 0) b = fminf(b, qz - (g.oz + (float)(cz - r) * g.h));
-  if (cz + r < g.nz - 1) b = fminf(b, (g.oz + (float)(cz + r + 1) * g.h) - qz);
-  return b == INFINITY ? b : (b - g.slack) * 0.999999f;
-}
-
-// Visits the cells of Chebyshev ring r around (cx, cy, cz).  Cells of one x-row are contiguous in the sorted records, so a
-// row that lies wholly in the ring is one range; an inner row contributes its two end cells.  scan(first, last) sees record ranges.
-template <typename Scan>
-__device__ __forceinline__ void visit_ring(const sp3_nn_grid& g, const int* __restrict__ cell_start, int cx, int cy, int cz, int r,
-                                           int& cells, Scan scan) {
-  const int z0 = max(cz - r, 0), z1 = min(cz + r, g.nz - 1), y0 = max(cy - r, 0), y1 = min(cy + r, g.ny - 1);
-  const int x0 = max(cx - r, 0), x1 = min(cx + r, g.nx - 1);
-  for (int z = z0; z <= z1; ++z) {
-    for (int y = y0; y <= y1; ++y) {
-      const int base = (z * g.ny + y) * g.nx;
-      if (abs(z - cz) == r || abs(y - cy) == r) {
-        scan(cell_start[base + x0], cell_start[base + x1 + 1]);
-        cells += x1 - x0 + 1;
-      } else {
-        if (cx - r >= 0) { scan(cell_start[base + cx - r], cell_start[base + cx - r + 1]); ++cells; }
-        if (cx + r < g.nx) { scan(cell_start[base + cx + r], cell_start[base + cx + r + 1]); ++cells; }
-      }
-    }
-  }
-}
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// workspace head (sp3_nn_query): [0] fallback count (int), [2..3] as u64 at byte 16: cells visited, points visited
-struct NnHead { int fb_count; int pad[3]; unsigned long long cells, points; };
-
 // ---- exact 1-NN, one lane per query (queries sorted by home cell: the lanes of a wave walk the same cells)
 __global__ __launch_bounds__(256) void nn_grid_kernel(const float* __restrict__ q, const int64_t* __restrict__ order, int64_t nq,
                                                       const float4* __restrict__ recs, const int* __restrict__ cell_start, sp3_nn_grid g,
                                                       int max_ring, float max_dist, float* __restrict__ dist, int* __restrict__ idx,
-                                                      NnHead* head, unsigned long long* __restrict__ fb_key, int* __restrict__ fb_list) {
+                                                      GridHead* head, unsigned long long* __restrict__ fb_key, int* __restrict__ fb_list) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   int cells = 0, points = 0;
   if (t < nq) {
     const int64_t qi = order ? order[t] : t;
     const float qx = q[3 * qi], qy = q[3 * qi + 1], qz = q[3 * qi + 2];
-    const int cx = cell_axis(qx, g.ox, g.inv_h, g.nx), cy = cell_axis(qy, g.oy, g.inv_h, g.ny), cz = cell_axis(qz, g.oz, g.inv_h, g.nz);
     float best = INFINITY;
     int bi = -1;
-    bool done = false;
-    for (int r = 0; r <= max_ring; ++r) {
-      visit_ring(g, cell_start, cx, cy, cz, r, cells, [&](int s, int e) {
-        points += e - s;
-        for (int j = s; j < e; ++j) {
-          const Rec p = ld_rec(recs + j);
-          const float d2 = dist2(qx, qy, qz, p.x, p.y, p.z);
-          if (d2 < best) { best = d2; bi = p.i; }
-        }
-      });
-      const float b = ring_bound(g, qx, qy, qz, cx, cy, cz, r);
-      // finished: everything unvisited is farther than the best, or farther than max_dist (then the best decides alone)
-      if (b == INFINITY || (b > 0.f && (best <= b * b || b >= max_dist))) { done = true; break; }
-    }
-    if (done) {
+    const auto scan = [&](int s, int e) {
+      points += e - s;
+      for (int j = s; j < e; ++j) {
+        const Rec p = ld_rec(recs + j);
+        const float d2 = dist2(qx, qy, qz, p.x, p.y, p.z);
+        if (d2 < best) { best = d2; bi = p.i; }
+      }
+    };
+    // settled: everything unvisited is farther than the best, or farther than max_dist (then the best decides alone)
+    if (walk_rings(g, cell_start, qx, qy, qz, max_ring, cells, scan, [&](float b) { return best <= b * b || b >= max_dist; })) {
       const float d = __fsqrt_rn(best);
       const bool hit = bi >= 0 && d <= max_dist;
       dist[qi] = hit ? d : INFINITY;
       idx[qi] = hit ? bi : -1;
     } else {
-      const int slot = atomicAdd(&head->fb_count, 1);
-      fb_list[slot] = (int)qi;
-      fb_key[slot] = ~0ull;
+      head->open_slot(qi, fb_list, fb_key);
     }
   }
-  const unsigned long long c = wave_sum_u64((unsigned long long)cells), p = wave_sum_u64((unsigned long long)points);
-  if ((threadIdx.x & 63) == 0) { atomicAdd(&head->cells, c); atomicAdd(&head->points, p); }
+  head->count(cells, points);
 }
 
 // ---- brute force: a workgroup holds 256 queries in registers and streams its chunk of the reference cloud through LDS.
-// slots: the fallback list (list / count on the device) or every query (list == null).  key[slot] = min (d2 bits << 32 | index).
-__global__ __launch_bounds__(256) void nn_brute_kernel(const float* __restrict__ q, const int* __restrict__ list, const int* __restrict__ count,
-                                                       int64_t nq_all, const float4* __restrict__ recs, int64_t m, int64_t chunk,
-                                                       unsigned long long* __restrict__ key) {
+// slots: the fallback list or every query (cell_grid.h Slots).  key[slot] = min (d2 bits << 32 | index).
+__global__ __launch_bounds__(256) void nn_brute_kernel(const float* __restrict__ q, Slots slots, const float4* __restrict__ recs, int64_t m,
+                                                       int64_t chunk, unsigned long long* __restrict__ key) {
   __shared__ float4 tile[BRUTE_TILE];
-  const int64_t nq = count ? min((int64_t)*count, nq_all) : nq_all;
+  const int64_t nq = slots.size();
   const int64_t r0 = (int64_t)blockIdx.y * chunk, r1 = min(r0 + chunk, m);
   for (int64_t qb = (int64_t)blockIdx.x * 256; qb < nq; qb += (int64_t)gridDim.x * 256) {
     const int64_t slot = qb + threadIdx.x;
-    const bool active = slot < nq;
-    const int64_t qi = active ? (list ? (int64_t)list[slot] : slot) : 0;
-    const float qx = q[3 * qi], qy = q[3 * qi + 1], qz = q[3 * qi + 2];
+    const int64_t qi = slot < nq ? slots.query(slot) : -1;
+    const bool active = qi >= 0;
+    const float qx = active ? q[3 * qi] : 0.f, qy = active ? q[3 * qi + 1] : 0.f, qz = active ? q[3 * qi + 2] : 0.f;
     float best = INFINITY;
     int bi = 0x7fffffff;
     for (int64_t t0 = r0; t0 < r1; t0 += BRUTE_TILE) {
@@ -187,13 +123,13 @@ __global__ __launch_bounds__(256) void fill_u64_kernel(unsigned long long* p, in
   if (i < n) p[i] = ~0ull;
 }
 
-__global__ __launch_bounds__(256) void nn_brute_finish_kernel(const int* __restrict__ list, const int* __restrict__ count, int64_t nq_all,
-                                                              const unsigned long long* __restrict__ key, float max_dist,
+__global__ __launch_bounds__(256) void nn_brute_finish_kernel(Slots slots, const unsigned long long* __restrict__ key, float max_dist,
                                                               float* __restrict__ dist, int* __restrict__ idx) {
-  const int64_t nq = count ? min((int64_t)*count, nq_all) : nq_all;
+  const int64_t nq = slots.size();
   for (int64_t slot = (int64_t)blockIdx.x * 256 + threadIdx.x; slot < nq; slot += (int64_t)gridDim.x * 256) {
     const unsigned long long k = key[slot];
-    const int64_t qi = list ? (int64_t)list[slot] : slot;
+    const int64_t qi = slots.query(slot);
+    if (qi < 0) continue;
     const float d = __fsqrt_rn(__uint_as_float((unsigned)(k >> 32)));
     const bool hit = k != ~0ull && d <= max_dist;
     dist[qi] = hit ? d : INFINITY;
@@ -213,27 +149,23 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_grid_kernel(const float* __rest
   if (t >= nq) return;
   const int64_t qi = order ? order[t] : t;
   const float qx = q[3 * qi], qy = q[3 * qi + 1], qz = q[3 * qi + 2];
-  const int cx = cell_axis(qx, g.ox, g.inv_h, g.nx), cy = cell_axis(qy, g.oy, g.inv_h, g.ny), cz = cell_axis(qz, g.oz, g.inv_h, g.nz);
   for (int j = 0; j < k; ++j) { kd[j][l] = INFINITY; ki[j][l] = -1; }
   float kth = INFINITY;
   int cells = 0;
-  const int rmax = max(g.nx, max(g.ny, g.nz));
-  for (int r = 0; r < rmax; ++r) {
-    visit_ring(g, cell_start, cx, cy, cz, r, cells, [&](int s, int e) {
-      for (int j = s; j < e; ++j) {
-        const Rec p = ld_rec(recs + j);
-        const float d2 = dist2(qx, qy, qz, p.x, p.y, p.z);
-        if (d2 < kth) {
-          int u = k - 1;
-          while (u > 0 && kd[u - 1][l] > d2) { kd[u][l] = kd[u - 1][l]; ki[u][l] = ki[u - 1][l]; --u; }
-          kd[u][l] = d2; ki[u][l] = p.i;
-          kth = kd[k - 1][l];
-        }
+  const auto scan = [&](int s, int e) {
+    for (int j = s; j < e; ++j) {
+      const Rec p = ld_rec(recs + j);
+      const float d2 = dist2(qx, qy, qz, p.x, p.y, p.z);
+      if (d2 < kth) {
+        int u = k - 1;
+        while (u > 0 && kd[u - 1][l] > d2) { kd[u][l] = kd[u - 1][l]; ki[u][l] = ki[u - 1][l]; --u; }
+        kd[u][l] = d2; ki[u][l] = p.i;
+        kth = kd[k - 1][l];
       }
-    });
-    const float b = ring_bound(g, qx, qy, qz, cx, cy, cz, r);
-    if (b == INFINITY || (b > 0.f && kth <= b * b)) break;
-  }
+    }
+  };
+  // no ring budget: the block of ring max(dims) - 1 covers the whole grid
+  walk_rings(g, cell_start, qx, qy, qz, max(g.nx, max(g.ny, g.nz)) - 1, cells, scan, [&](float b) { return kth <= b * b; });
   for (int j = 0; j < k; ++j) {
     const float d = __fsqrt_rn(kd[j][l]);
     const bool hit = ki[j][l] >= 0 && d <= max_dist;
@@ -347,25 +279,14 @@ __global__ __launch_bounds__(256) void normal_dot_kernel(const float* __restrict
 }
 
 inline unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
-constexpr int64_t N_MAX = 0x7fffffff;   // indices travel as int32
-
-int check_grid(const sp3_nn_grid* g, const char* what) {
-  SP3_CHECK(g != nullptr, "%s: null grid", what);
-  SP3_CHECK(g->nx >= 1 && g->ny >= 1 && g->nz >= 1 && (int64_t)g->nx * g->ny * g->nz <= ((int64_t)1 << 24), "%s: grid dims %d x %d x %d", what,
-            g->nx, g->ny, g->nz);
-  SP3_CHECK(g->h > 0.f && g->inv_h > 0.f && g->slack >= 0.f, "%s: grid h / inv_h / slack must be positive", what);
-  return 0;
-}
 
 // the brute-force stage over `slots` queries (list / count nullable: every query)
 int launch_brute(const float* q, const int* list, const int* count, int64_t nq, const float4* recs, int64_t m, float max_dist,
                  unsigned long long* key, float* dist, int* idx, hipStream_t st) {
-  int64_t chunks = (m + 8191) / 8192;
-  chunks = chunks < 1 ? 1 : chunks > 256 ? 256 : chunks;
-  const int64_t chunk = ((m + chunks - 1) / chunks + BRUTE_TILE - 1) / BRUTE_TILE * BRUTE_TILE;
-  const unsigned qblocks = blocks256(nq) < 1024u ? blocks256(nq) : 1024u;
-  nn_brute_kernel<<<dim3(qblocks, (unsigned)((m + chunk - 1) / chunk)), 256, 0, st>>>(q, list, count, nq, recs, m, chunk, key);
-  nn_brute_finish_kernel<<<qblocks, 256, 0, st>>>(list, count, nq, key, max_dist, dist, idx);
+  const Slots slots = {list, count, nq};
+  const BruteLaunch l = size_brute(nq, m, 8192, BRUTE_TILE);
+  nn_brute_kernel<<<dim3(l.qblocks, l.chunks), 256, 0, st>>>(q, slots, recs, m, l.chunk, key);
+  nn_brute_finish_kernel<<<l.qblocks, 256, 0, st>>>(slots, key, max_dist, dist, idx);
   return 0;
 }
 
@@ -399,7 +320,7 @@ int sp3_nn_query(const float* q, const int64_t* q_order, int64_t nq, const float
   SP3_CHECK((((uintptr_t)recs | (uintptr_t)ws) & 15) == 0, "sp3_nn_query: records and workspace must be 16-byte aligned");
   if (check_grid(g, "sp3_nn_query")) return 1;
   hipStream_t st = (hipStream_t)stream;
-  NnHead* head = (NnHead*)ws;
+  GridHead* head = (GridHead*)ws;
   unsigned long long* key = (unsigned long long*)((char*)ws + 32);
   int* list = (int*)((char*)ws + 32 + nq * 8);
   if (hipMemsetAsync(ws, 0, 32, st) != hipSuccess) { sp3_set_error("sp3_nn_query: hipMemsetAsync failed"); return 2; }

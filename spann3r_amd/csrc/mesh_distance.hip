@@ -6,9 +6,9 @@
 //     a query is the lexicographic minimum of (d2, face index) over the usable faces: a pure function of the inputs, so a face may be
 //     evaluated in any order, any number of times, by either kernel.
 //   * Faces are registered in every cell of an sp3_nn_grid their bounding box touches (sp3_mesh_tri_cell_count / _fill; the host
-//     sorts the pairs by cell).  A query walks the cells around its home cell ring by ring, as sp3_nn_query does (csrc/eval.hip; the
-//     twenty lines of its ring walk and stopping bound are restated here): a face that no cell of the visited block holds has, on
-//     one axis, every one of its cells beyond a wall of the block, so it lies wholly behind that wall and the wall's distance bounds it.
+//     sorts the pairs by cell).  A query walks the cells around its home cell ring by ring, with the walk and the stopping bound of
+//     csrc/cell_grid.h, which sp3_nn_query shares: a face that no cell of the visited block holds has, on one axis, every one of
+//     its cells beyond a wall of the block, so it lies wholly behind that wall and the wall's distance bounds it.
 //   * The hot loops keep (d2, face) only; the closest point and the region of the winner are recomputed once at the end.
 //   * The brute-force kernel stages faces through LDS in tiles (corners and the usability verdict, one lane per face), the face list
 //     split over workgroups.  (d2, face) does not fit one 64-bit atomic, so the join is two passes over the same tiles: an integer
@@ -16,8 +16,8 @@
 //     that reach exactly that d2.  Both are order-free.
 //   * Every loop is bounded by max_ring, the grid dims, npairs or nfaces; nothing waits on another lane's store; what an atomic wrote
 //     is read by a LATER launch only.
-#include "common.h"
-#include <math.h>
+#include "cell_grid.h"
+#include "tri.h"
 
 #pragma clang fp contract(off)
 
@@ -27,39 +27,13 @@ typedef unsigned long long u64;
 
 constexpr int TB = 256;
 constexpr int TILE = 512;                      // faces per LDS tile of the brute-force kernel: 512 * 40 bytes
-constexpr int64_t N_MAX = 0x7fffffff;          // indices travel as int32
 constexpr int NO_FACE = 0x7fffffff;
 
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + TB - 1) / TB); }
 
 // ------------------------------------------------------------------------------------------------ a face
-// the nine coordinates of face f; false (nothing dereferenced beyond the three indices) when an index is outside 0..V-1
-__device__ __forceinline__ bool load_face(const float* __restrict__ verts, int nverts, const int* __restrict__ faces, int64_t f, float (&v)[9]) {
-  const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-  if (!((unsigned)a < (unsigned)nverts && (unsigned)b < (unsigned)nverts && (unsigned)c < (unsigned)nverts)) return false;
-  const float* pa = verts + 3 * (int64_t)a;
-  const float* pb = verts + 3 * (int64_t)b;
-  const float* pc = verts + 3 * (int64_t)c;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    v[k] = pa[k];
-    v[3 + k] = pb[k];
-    v[6 + k] = pc[k];
-  }
-  return true;
-}
-
-// the d > 0 of sp3_mesh_face_frames (csrc/mesh_sample.hip frame_of): the same operations in the same order
-__device__ __forceinline__ bool has_area(const float (&v)[9]) {
-  const double ax = (double)v[0], ay = (double)v[1], az = (double)v[2];
-  const double e1x = (double)v[3] - ax, e1y = (double)v[4] - ay, e1z = (double)v[5] - az;
-  const double e2x = (double)v[6] - ax, e2y = (double)v[7] - ay, e2z = (double)v[8] - az;
-  const double nx = e1y * e2z - e1z * e2y;
-  const double ny = e1z * e2x - e1x * e2z;
-  const double nz = e1x * e2y - e1y * e2x;
-  const double d = sqrt(nx * nx + ny * ny + nz * nz);
-  return d > 0.0 && d <= 1.7976931348623157e308;      // false for NaN and +inf
-}
+// usable: the d > 0 of sp3_mesh_face_frames, from the same edge_cross (csrc/tri.h)
+__device__ __forceinline__ bool has_area(const float (&v)[9]) { const double d = edge_cross(v).d; return d > 0.0 && is_finite(d); }
 
 __device__ __forceinline__ double dot3(double ax, double ay, double az, double bx, double by, double bz) {
   const double s = ax * bx + ay * by;
@@ -133,46 +107,7 @@ __device__ __forceinline__ void write_result(const float* __restrict__ verts, in
   region[qi] = (uint8_t)ro;
 }
 
-// ------------------------------------------------------------------------------------------------ the grid (csrc/eval.hip, restated)
-__device__ __forceinline__ int cell_axis(float x, float o, float inv_h, int n) {
-  const float t = floorf((x - o) * inv_h);
-  return (int)fminf(fmaxf(t, 0.f), (float)(n - 1));   // NaN -> 0: always a valid cell
-}
-
-// Lower bound of the distance from q to anything outside the cell block [c - r, c + r]^3 (clipped to the grid), less the slack.
-// +inf when the block covers the whole grid.
-__device__ __forceinline__ float ring_bound(const sp3_nn_grid& g, float qx, float qy, float qz, int cx, int cy, int cz, int r) {
-  float b = INFINITY;
-  if (cx - r > 0) b = fminf(b, qx - (g.ox + (float)(cx - r) * g.h));
-  if (cx + r < g.nx - 1) b = fminf(b, (g.ox + (float)(cx + r + 1) * g.h) - qx);
-  if (cy - r > 0) b = fminf(b, qy - (g.oy + (float)(cy - r) * g.h));
-  if (cy + r < g.ny - 1) b = fminf(b, (g.oy + (float)(cy + r + 1) * g.h) - qy);
-  if (cz - r > 0) b = fminf(b, qz - (g.oz + (float)(cz - r) * g.h));
-  if (cz + r < g.nz - 1) b = fminf(b, (g.oz + (float)(cz + r + 1) * g.h) - qz);
-  return b == INFINITY ? b : (b - g.slack) * 0.999999f;
-}
-
-// Visits the cells of Chebyshev ring r around (cx, cy, cz).  Cells of one x-row are contiguous in the sorted pairs, so a row that
-// lies wholly in the ring is one range; an inner row contributes its two end cells.  scan(first, last) sees pair ranges.
-template <typename Scan>
-__device__ __forceinline__ void visit_ring(const sp3_nn_grid& g, const int* __restrict__ cell_start, int cx, int cy, int cz, int r, int& cells,
-                                           Scan scan) {
-  const int z0 = max(cz - r, 0), z1 = min(cz + r, g.nz - 1), y0 = max(cy - r, 0), y1 = min(cy + r, g.ny - 1);
-  const int x0 = max(cx - r, 0), x1 = min(cx + r, g.nx - 1);
-  for (int z = z0; z <= z1; ++z) {
-    for (int y = y0; y <= y1; ++y) {
-      const int base = (z * g.ny + y) * g.nx;
-      if (abs(z - cz) == r || abs(y - cy) == r) {
-        scan(cell_start[base + x0], cell_start[base + x1 + 1]);
-        cells += x1 - x0 + 1;
-      } else {
-        if (cx - r >= 0) { scan(cell_start[base + cx - r], cell_start[base + cx - r + 1]); ++cells; }
-        if (cx + r < g.nx) { scan(cell_start[base + cx + r], cell_start[base + cx + r + 1]); ++cells; }
-      }
-    }
-  }
-}
-
+// ------------------------------------------------------------------------------------------------ faces in the grid (csrc/cell_grid.h)
 // the cells [x0, x1] x [y0, y1] x [z0, z1] of the face's bounding box pushed out by the slack; cell_axis is monotone in x, so every
 // point of the face falls in one of them whatever the fp32 rounding of the box does
 __device__ __forceinline__ void face_cells(const sp3_nn_grid& g, const float (&v)[9], int (&lo)[3], int (&hi)[3]) {
@@ -215,27 +150,18 @@ __global__ __launch_bounds__(TB) void k_md_cell_fill(const float* __restrict__ v
     for (int y = lo[1]; y <= hi[1]; ++y)
       for (int x = lo[0]; x <= hi[0]; ++x) {
         if (at >= npairs) return;      // offsets that do not belong to this grid: never past the arrays
-        pair_cell[at] = (z * g.ny + y) * g.nx + x;
+        pair_cell[at] = cell_id(g, x, y, z);
         pair_face[at] = (int)f;
         ++at;
       }
 }
-
-__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// workspace head: fallback count, pad, cells visited, faces evaluated (the layout of sp3_nn_query's)
-struct DistHead { int fb_count; int pad[3]; u64 cells, faces; };
 
 // ---- one lane per query (queries sorted by home cell: the lanes of a wave walk the same cells)
 __global__ __launch_bounds__(TB) void k_md_grid(const float* __restrict__ q, const int64_t* __restrict__ order, int64_t nq,
                                                  const float* __restrict__ verts, int nverts, const int* __restrict__ faces, int nfaces,
                                                  const int* __restrict__ pair_face, int npairs, const int* __restrict__ cell_start, sp3_nn_grid g,
                                                  int max_ring, float* __restrict__ dist, float* __restrict__ closest, int* __restrict__ face,
-                                                 uint8_t* __restrict__ region, DistHead* head, u64* __restrict__ fb_key, int* __restrict__ fb_face,
+                                                 uint8_t* __restrict__ region, GridHead* head, u64* __restrict__ fb_key, int* __restrict__ fb_face,
                                                  int* __restrict__ fb_list) {
   const int64_t t = (int64_t)blockIdx.x * TB + threadIdx.x;
   int cells = 0, evals = 0;
@@ -243,57 +169,45 @@ __global__ __launch_bounds__(TB) void k_md_grid(const float* __restrict__ q, con
     const int64_t qi = order ? order[t] : t;
     const float qx = q[3 * qi], qy = q[3 * qi + 1], qz = q[3 * qi + 2];
     const double px = (double)qx, py = (double)qy, pz = (double)qz;
-    const int cx = cell_axis(qx, g.ox, g.inv_h, g.nx), cy = cell_axis(qy, g.oy, g.inv_h, g.ny), cz = cell_axis(qz, g.oz, g.inv_h, g.nz);
     double best = INFINITY;
     int bf = -1;
-    bool done = false;
-    for (int r = 0; r <= max_ring; ++r) {
-      visit_ring(g, cell_start, cx, cy, cz, r, cells, [&](int s, int e) {
-        s = max(s, 0);
-        e = min(e, npairs);
-        for (int j = s; j < e; ++j) {
-          const int f = pair_face[j];
-          float v[9];
-          if (!((unsigned)f < (unsigned)nfaces && load_face(verts, nverts, faces, f, v))) continue;      // (the pairs hold usable faces only)
-          ++evals;
-          const double d2 = dist2_to_face(px, py, pz, v);
-          if (d2 < best || (d2 == best && f < bf)) { best = d2; bf = f; }
-        }
-      });
-      const float b = ring_bound(g, qx, qy, qz, cx, cy, cz, r);
-      // finished: everything unvisited lies behind a wall that is farther than the best
-      if (b == INFINITY || (b > 0.f && best <= (double)b * (double)b)) { done = true; break; }
-    }
-    if (done) {
+    const auto scan = [&](int s, int e) {
+      s = max(s, 0);
+      e = min(e, npairs);
+      for (int j = s; j < e; ++j) {
+        const int f = pair_face[j];
+        float v[9];
+        if (!((unsigned)f < (unsigned)nfaces && load_face(verts, nverts, faces, f, v))) continue;      // (the pairs hold usable faces only)
+        ++evals;
+        const double d2 = dist2_to_face(px, py, pz, v);
+        if (d2 < best || (d2 == best && f < bf)) { best = d2; bf = f; }
+      }
+    };
+    // settled: everything unvisited lies behind a wall that is farther than the best
+    if (walk_rings(g, cell_start, qx, qy, qz, max_ring, cells, scan, [&](float b) { return best <= (double)b * (double)b; })) {
       write_result(verts, nverts, faces, nfaces, qi, qx, qy, qz, bf < 0 ? NO_FACE : bf, dist, closest, face, region);
     } else {
-      const int slot = atomicAdd(&head->fb_count, 1);
-      fb_list[slot] = (int)qi;
-      fb_key[slot] = ~0ull;
-      fb_face[slot] = NO_FACE;
+      fb_face[head->open_slot(qi, fb_list, fb_key)] = NO_FACE;
     }
   }
-  const u64 c = wave_sum_u64((u64)cells), p = wave_sum_u64((u64)evals);
-  if ((threadIdx.x & 63) == 0) { atomicAdd(&head->cells, c); atomicAdd(&head->faces, p); }
+  head->count(cells, evals);
 }
 
 // ---- brute force: a workgroup holds 256 queries in registers and streams its chunk of the faces through LDS.
-// slots: the fallback list (list / count on the device) or every query (list == null).
+// slots: the fallback list or every query (cell_grid.h Slots).
 // PASS 0: key[slot] = min over the usable faces of the bits of d2.  PASS 1: fkey[slot] = min face index with d2 == key[slot].
 template <int PASS>
-__global__ __launch_bounds__(TB) void k_md_brute(const float* __restrict__ q, const int* __restrict__ list, const int* __restrict__ count,
-                                                  int64_t nq_all, const float* __restrict__ verts, int nverts, const int* __restrict__ faces,
-                                                  int64_t nfaces, int64_t chunk, u64* key, int* fkey) {
+__global__ __launch_bounds__(TB) void k_md_brute(const float* __restrict__ q, Slots slots, const float* __restrict__ verts, int nverts,
+                                                  const int* __restrict__ faces, int64_t nfaces, int64_t chunk, u64* key, int* fkey) {
   __shared__ float tv[TILE * 9];
   __shared__ int tf[TILE];      // the face index, -1 for a face that is not usable
-  const int64_t nq = count ? min((int64_t)*count, nq_all) : nq_all;
+  const int64_t nq = slots.size();
   const int64_t r0 = (int64_t)blockIdx.y * chunk, r1 = min(r0 + chunk, nfaces);
   for (int64_t qb = (int64_t)blockIdx.x * TB; qb < nq; qb += (int64_t)gridDim.x * TB) {
     const int64_t slot = qb + threadIdx.x;
-    const bool active = slot < nq;
-    const int64_t qi = active ? (list ? (int64_t)list[slot] : slot) : 0;
-    const bool qok = qi >= 0 && qi < nq_all;
-    const double px = qok ? (double)q[3 * qi] : 0.0, py = qok ? (double)q[3 * qi + 1] : 0.0, pz = qok ? (double)q[3 * qi + 2] : 0.0;
+    const int64_t qi = slot < nq ? slots.query(slot) : -1;
+    const bool active = qi >= 0;
+    const double px = active ? (double)q[3 * qi] : 0.0, py = active ? (double)q[3 * qi + 1] : 0.0, pz = active ? (double)q[3 * qi + 2] : 0.0;
     const double target = (PASS == 1 && active) ? __longlong_as_double((long long)key[slot]) : 0.0;      // NaN (all ones): nothing equals it
     double best = INFINITY;
     int bf = NO_FACE;
@@ -326,7 +240,7 @@ __global__ __launch_bounds__(TB) void k_md_brute(const float* __restrict__ q, co
         }
       }
     }
-    if (active && qok && r0 < r1) {
+    if (active && r0 < r1) {
       if (PASS == 0) {
         if (best < INFINITY) atomicMin(&key[slot], (u64)__double_as_longlong(best));      // d2 >= 0: bit order = value order
       } else {
@@ -341,33 +255,25 @@ __global__ __launch_bounds__(TB) void k_md_fill_keys(u64* __restrict__ key, int*
   if (i < n) { key[i] = ~0ull; fkey[i] = NO_FACE; }
 }
 
-__global__ __launch_bounds__(TB) void k_md_brute_finish(const float* __restrict__ q, const int* __restrict__ list, const int* __restrict__ count,
-                                                         int64_t nq_all, const float* __restrict__ verts, int nverts, const int* __restrict__ faces,
-                                                         int nfaces, const int* __restrict__ fkey, float* __restrict__ dist,
-                                                         float* __restrict__ closest, int* __restrict__ face, uint8_t* __restrict__ region) {
-  const int64_t nq = count ? min((int64_t)*count, nq_all) : nq_all;
+__global__ __launch_bounds__(TB) void k_md_brute_finish(const float* __restrict__ q, Slots slots, const float* __restrict__ verts, int nverts,
+                                                         const int* __restrict__ faces, int nfaces, const int* __restrict__ fkey,
+                                                         float* __restrict__ dist, float* __restrict__ closest, int* __restrict__ face,
+                                                         uint8_t* __restrict__ region) {
+  const int64_t nq = slots.size();
   for (int64_t slot = (int64_t)blockIdx.x * TB + threadIdx.x; slot < nq; slot += (int64_t)gridDim.x * TB) {
-    const int64_t qi = list ? (int64_t)list[slot] : slot;
-    if (qi < 0 || qi >= nq_all) continue;
+    const int64_t qi = slots.query(slot);
+    if (qi < 0) continue;
     write_result(verts, nverts, faces, nfaces, qi, q[3 * qi], q[3 * qi + 1], q[3 * qi + 2], fkey[slot], dist, closest, face, region);
   }
 }
 
-int check_grid(const sp3_nn_grid* g, const char* what) {
-  SP3_CHECK(g != nullptr, "%s: null grid", what);
-  SP3_CHECK(g->nx >= 1 && g->ny >= 1 && g->nz >= 1 && (int64_t)g->nx * g->ny * g->nz <= ((int64_t)1 << 24), "%s: grid dims %d x %d x %d", what,
-            g->nx, g->ny, g->nz);
-  SP3_CHECK(g->h > 0.f && g->inv_h > 0.f && g->slack >= 0.f, "%s: grid h / inv_h / slack must be positive", what);
-  return 0;
-}
-
 inline bool sizes_ok(int64_t nverts, int64_t nfaces) { return nverts >= 0 && nverts < N_MAX && nfaces >= 0 && nfaces < N_MAX; }
 
-struct Ws { DistHead* head; u64* key; int* fkey; int* list; };
+struct Ws { GridHead* head; u64* key; int* fkey; int* list; };
 inline int64_t round4(int64_t n) { return (n + 3) / 4 * 4; }
 inline Ws carve(void* ws, int64_t nq) {
   Ws w;
-  w.head = (DistHead*)ws;
+  w.head = (GridHead*)ws;
   w.key = (u64*)((char*)ws + 32);
   w.fkey = (int*)((char*)ws + 32 + round4(nq) * 8);
   w.list = w.fkey + round4(nq);
@@ -377,14 +283,12 @@ inline Ws carve(void* ws, int64_t nq) {
 // the brute-force stage over the listed queries (list / count null: every query): two passes and the finish
 void launch_brute(const float* q, const int* list, const int* count, int64_t nq, const float* verts, int nverts, const int* faces, int64_t nfaces,
                   const Ws& w, float* dist, float* closest, int* face, uint8_t* region, hipStream_t st) {
-  int64_t chunks = (nfaces + 4095) / 4096;
-  chunks = chunks < 1 ? 1 : chunks > 256 ? 256 : chunks;
-  const int64_t chunk = ((nfaces + chunks - 1) / chunks + TILE - 1) / TILE * TILE;
-  const unsigned qblocks = blocks_for(nq) < 1024u ? blocks_for(nq) : 1024u;
-  const dim3 grid(qblocks, (unsigned)((nfaces + chunk - 1) / chunk));
-  k_md_brute<0><<<grid, TB, 0, st>>>(q, list, count, nq, verts, nverts, faces, nfaces, chunk, w.key, w.fkey);
-  k_md_brute<1><<<grid, TB, 0, st>>>(q, list, count, nq, verts, nverts, faces, nfaces, chunk, w.key, w.fkey);
-  k_md_brute_finish<<<qblocks, TB, 0, st>>>(q, list, count, nq, verts, nverts, faces, (int)nfaces, w.fkey, dist, closest, face, region);
+  const Slots slots = {list, count, nq};
+  const BruteLaunch l = size_brute(nq, nfaces, 4096, TILE);
+  const dim3 grid(l.qblocks, l.chunks);
+  k_md_brute<0><<<grid, TB, 0, st>>>(q, slots, verts, nverts, faces, nfaces, l.chunk, w.key, w.fkey);
+  k_md_brute<1><<<grid, TB, 0, st>>>(q, slots, verts, nverts, faces, nfaces, l.chunk, w.key, w.fkey);
+  k_md_brute_finish<<<l.qblocks, TB, 0, st>>>(q, slots, verts, nverts, faces, (int)nfaces, w.fkey, dist, closest, face, region);
 }
 
 }  // namespace

@@ -14,6 +14,7 @@
 // (csrc/mesh_simplify.hip has the history).
 #include "common.h"
 #include "scan.h"
+#include "tri.h"
 #include <math.h>
 
 #pragma clang fp contract(off)
@@ -28,43 +29,18 @@ const int64_t kIndexLimit = 0x7fffffffLL;      // int32 indices; 256-element til
 
 // ------------------------------------------------------------------------------------------------ the rule of a face
 struct Frame {
-  double ax, ay, az, e1x, e1y, e1z, e2x, e2y, e2z;      // corner A and the two edges
-  double nx, ny, nz, d;                                 // e1 x e2 and its length; all zero for an invalid or non-finite face
-  int a, b, c;
-  bool valid;                                           // the three indices lie in 0..V-1 (nothing is dereferenced otherwise)
+  EdgeCross e;      // (csrc/tri.h) all zero for an invalid face; nx, ny, nz, d zero for a non-finite one
+  int abc[3];       // the face's three vertex indices
+  bool valid;       // they lie in 0..V-1 (nothing is dereferenced otherwise)
 };
 
 __device__ __forceinline__ Frame frame_of(const float* __restrict__ verts, int nverts, const int* __restrict__ faces, int64_t f) {
-  Frame r;
-  r.a = faces[3 * f];
-  r.b = faces[3 * f + 1];
-  r.c = faces[3 * f + 2];
-  r.valid = (unsigned)r.a < (unsigned)nverts && (unsigned)r.b < (unsigned)nverts && (unsigned)r.c < (unsigned)nverts;
-  r.ax = r.ay = r.az = r.e1x = r.e1y = r.e1z = r.e2x = r.e2y = r.e2z = 0.0;
-  r.nx = r.ny = r.nz = r.d = 0.0;
+  Frame r = {};
+  float v[9];
+  r.valid = load_face(verts, nverts, faces, f, v, r.abc);
   if (!r.valid) return r;
-  const float* pa = verts + 3 * (int64_t)r.a;
-  const float* pb = verts + 3 * (int64_t)r.b;
-  const float* pc = verts + 3 * (int64_t)r.c;
-  r.ax = (double)pa[0];
-  r.ay = (double)pa[1];
-  r.az = (double)pa[2];
-  r.e1x = (double)pb[0] - r.ax;
-  r.e1y = (double)pb[1] - r.ay;
-  r.e1z = (double)pb[2] - r.az;
-  r.e2x = (double)pc[0] - r.ax;
-  r.e2y = (double)pc[1] - r.ay;
-  r.e2z = (double)pc[2] - r.az;
-  const double nx = r.e1y * r.e2z - r.e1z * r.e2y;
-  const double ny = r.e1z * r.e2x - r.e1x * r.e2z;
-  const double nz = r.e1x * r.e2y - r.e1y * r.e2x;
-  const double d = sqrt(nx * nx + ny * ny + nz * nz);
-  if (d <= 1.7976931348623157e308) {      // finite (false for NaN and +inf)
-    r.nx = nx;
-    r.ny = ny;
-    r.nz = nz;
-    r.d = d;
-  }
+  r.e = edge_cross(v);
+  if (!is_finite(r.e.d)) r.e.nx = r.e.ny = r.e.nz = r.e.d = 0.0;
   return r;
 }
 
@@ -130,13 +106,13 @@ __global__ __launch_bounds__(MB) void k_sf_frames(const float* __restrict__ vert
   u64 bits = 0ull;
   if (f < nfaces) {
     const Frame r = frame_of(verts, nverts, faces, f);
-    bits = (u64)__double_as_longlong(r.d);
+    bits = (u64)__double_as_longlong(r.e.d);
     cum[f] = bits;
     if (face_normals != nullptr) {
-      const bool pos = r.d > 0.0;
-      face_normals[3 * f] = pos ? (float)(r.nx / r.d) : 0.f;
-      face_normals[3 * f + 1] = pos ? (float)(r.ny / r.d) : 0.f;
-      face_normals[3 * f + 2] = pos ? (float)(r.nz / r.d) : 0.f;
+      const bool pos = r.e.d > 0.0;
+      face_normals[3 * f] = pos ? (float)(r.e.nx / r.e.d) : 0.f;
+      face_normals[3 * f + 1] = pos ? (float)(r.e.ny / r.e.d) : 0.f;
+      face_normals[3 * f + 2] = pos ? (float)(r.e.nz / r.e.d) : 0.f;
     }
   }
   u64 m = bits;
@@ -233,15 +209,15 @@ __global__ __launch_bounds__(MB) void k_sf_sample(const float* __restrict__ vert
   // a drawn face has a weight, so it is valid and finite when cum belongs to these faces; frame_of checks the indices all the same
   const Frame r = frame_of(verts, nverts, faces, f);
   const double ua = (double)a / 16777216.0, ub = (double)b / 16777216.0;
-  points[3 * k] = place(r.ax, r.e1x, r.e2x, ua, ub);
-  points[3 * k + 1] = place(r.ay, r.e1y, r.e2y, ua, ub);
-  points[3 * k + 2] = place(r.az, r.e1z, r.e2z, ua, ub);
-  const bool pos = r.d > 0.0;
-  normals[3 * k] = pos ? (float)(r.nx / r.d) : 0.f;
-  normals[3 * k + 1] = pos ? (float)(r.ny / r.d) : 0.f;
-  normals[3 * k + 2] = pos ? (float)(r.nz / r.d) : 0.f;
+  points[3 * k] = place(r.e.ax, r.e.e1x, r.e.e2x, ua, ub);
+  points[3 * k + 1] = place(r.e.ay, r.e.e1y, r.e.e2y, ua, ub);
+  points[3 * k + 2] = place(r.e.az, r.e.e1z, r.e.e2z, ua, ub);
+  const bool pos = r.e.d > 0.0;
+  normals[3 * k] = pos ? (float)(r.e.nx / r.e.d) : 0.f;
+  normals[3 * k + 1] = pos ? (float)(r.e.ny / r.e.d) : 0.f;
+  normals[3 * k + 2] = pos ? (float)(r.e.nz / r.e.d) : 0.f;
   face_index[k] = f;
-  if (out_rgba != nullptr) out_rgba[k] = r.valid ? mix_bytes(rgba[r.a], rgba[r.b], rgba[r.c], (1u << 24) - a - b, a, b) : 0u;
+  if (out_rgba != nullptr) out_rgba[k] = r.valid ? mix_bytes(rgba[r.abc[0]], rgba[r.abc[1]], rgba[r.abc[2]], (1u << 24) - a - b, a, b) : 0u;
 }
 
 // ------------------------------------------------------------------------------------------------ vertex normals
@@ -255,12 +231,12 @@ __global__ __launch_bounds__(MB) void k_sf_vertex_accumulate(const float* __rest
   const int64_t f = (int64_t)blockIdx.x * MB + threadIdx.x;
   if (f >= nfaces) return;
   const Frame r = frame_of(verts, nverts, faces, f);
-  if (!(r.d > 0.0)) return;      // invalid, not finite or without area: q = 0
+  if (!(r.e.d > 0.0)) return;      // invalid, not finite or without area: q = 0
   const double dmax = __longlong_as_double((long long)info[1]);
-  const long long qx = llrint(r.nx / dmax * 1073741824.0);
-  const long long qy = llrint(r.ny / dmax * 1073741824.0);
-  const long long qz = llrint(r.nz / dmax * 1073741824.0);
-  const int v[3] = {r.a, r.b, r.c};
+  const long long qx = llrint(r.e.nx / dmax * 1073741824.0);
+  const long long qy = llrint(r.e.ny / dmax * 1073741824.0);
+  const long long qz = llrint(r.e.nz / dmax * 1073741824.0);
+  const int (&v)[3] = r.abc;
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
     u64* s = sums + 3 * (int64_t)v[j];

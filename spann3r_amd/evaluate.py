@@ -16,12 +16,13 @@ import math
 import numpy as np
 import torch
 
+from . import cell_grid
 from . import lib as L
+from .cell_grid import MAX_CELLS, choose_grid      # noqa: F401 -- re-exported: their public home was here
 
 KNN_MAX = 32
-MAX_CELLS = 1 << 22
-OCCUPANCY = 4.0          # mean points per cell the edge length aims for
 RING_BUDGET = 3          # rings walked before a query is handed to the brute-force kernel
+_read_counters = cell_grid.read_head      # tools/bench_eval_metrics.py reads the head through this name
 
 
 def _cloud(x, name):
@@ -37,34 +38,7 @@ def _cloud(x, name):
     return x.contiguous().float()
 
 
-def choose_grid(lo, hi, n, occupancy=OCCUPANCY, max_cells=MAX_CELLS):
-    """Cell edge and dims for n points in the box [lo, hi] (host, float64) -> (h, (nx, ny, nz)).
-    h aims at `occupancy` points per cell over the axes the cloud really extends along: an axis thinner than h holds one cell and
-    leaves the volume (planar, collinear and single-point clouds), every extent is floored, and h grows until the cell cap holds."""
-    ext = np.maximum(np.asarray(hi, np.float64) - np.asarray(lo, np.float64), 0.0)
-    emax = float(ext.max())
-    if not np.isfinite(emax) or emax <= 0.0:
-        return 1.0, (1, 1, 1)
-    floored = np.maximum(ext, 1e-6 * emax)
-    active = [0, 1, 2]
-    h = emax
-    while active:
-        h = float((np.prod(floored[active]) * occupancy / max(n, 1)) ** (1.0 / len(active)))
-        thin = [a for a in active if floored[a] < h]
-        if not thin:
-            break
-        active = [a for a in active if a not in thin]
-    if not active:
-        h = 2.0 * emax                               # fewer points than `occupancy`: one cell
-    h = max(h, 1e-30, emax * 2.0 ** -20)
-    while True:
-        dims = tuple(int(math.floor(e / h)) + 1 for e in ext)
-        if dims[0] * dims[1] * dims[2] <= max_cells:
-            return h, dims
-        h *= 1.25
-
-
-class CellGrid:
+class CellGrid(cell_grid.Grid):
     """The reference cloud binned for searching: records sorted by cell id, the cell-start table, the grid descriptor."""
 
     def __init__(self, ref, brute=False):
@@ -74,29 +48,17 @@ class CellGrid:
         dev = ref.device
         self.recs = torch.empty(m, 4, dtype=torch.float32, device=dev)
         if brute:                                    # one cell, records in caller order: what the brute-force kernels read
-            self.g = L.NnGrid(0.0, 0.0, 0.0, 1.0, 1.0, 0.0, 1, 1, 1)
+            self.g = cell_grid.one_cell()
             self.cell_start = torch.tensor([0, m], dtype=torch.int32, device=dev)
             L.check(lib.sp3_nn_pack_records(ref.data_ptr(), 0, m, self.recs.data_ptr(), L.stream_ptr()), "sp3_nn_pack_records")
             return
-        lo, hi = torch.aminmax(ref, dim=0)
-        box = torch.stack((lo, hi)).double().cpu().numpy()
-        box = np.where(np.isfinite(box), box, 0.0)
+        box = cell_grid.finite_box(*torch.aminmax(ref, dim=0))
         h, dims = choose_grid(box[0], box[1], m)
-        maxabs = float(np.abs(box).max())
-        slack = 1e-6 * (maxabs + float((box[1] - box[0]).max()) + h)
-        self.g = L.NnGrid(float(box[0, 0]), float(box[0, 1]), float(box[0, 2]), h, 1.0 / h, slack, *dims)
-        ncell = dims[0] * dims[1] * dims[2]
+        self.g = cell_grid.make_grid(box, h, dims)
         ids = torch.empty(m, dtype=torch.int32, device=dev)
         L.check(lib.sp3_nn_cell_ids(ref.data_ptr(), m, C.byref(self.g), ids.data_ptr(), L.stream_ptr()), "sp3_nn_cell_ids")
-        sorted_ids, order = torch.sort(ids, stable=True)
+        order, self.cell_start = cell_grid.cell_table(ids, dims[0] * dims[1] * dims[2])
         L.check(lib.sp3_nn_pack_records(ref.data_ptr(), order.data_ptr(), m, self.recs.data_ptr(), L.stream_ptr()), "sp3_nn_pack_records")
-        self.cell_start = torch.searchsorted(sorted_ids, torch.arange(ncell + 1, dtype=torch.int32, device=dev)).to(torch.int32)
-
-    def query_order(self, q):
-        """the queries sorted by the cell they fall in (clamped into the grid): the lanes of a wave then walk the same cells"""
-        ids = torch.empty(q.shape[0], dtype=torch.int32, device=q.device)
-        L.check(L.load().sp3_nn_cell_ids(q.data_ptr(), q.shape[0], C.byref(self.g), ids.data_ptr(), L.stream_ptr()), "sp3_nn_cell_ids")
-        return torch.sort(ids, stable=True)[1]
 
     def nn(self, q, max_dist=math.inf, ring_budget=RING_BUDGET, ws=None):
         """1-NN of q [N, 3] -> dist fp32 [N], idx int32 [N], ws (its first 32 bytes hold the counters of this call)"""
@@ -130,11 +92,6 @@ class CellGrid:
         L.check(lib.sp3_knn_query(q.data_ptr(), L.ptr(order), n, self.recs.data_ptr(), self.cell_start.data_ptr(), self.m, C.byref(self.g), int(k),
                                   float(max_dist), dist.data_ptr(), idx.data_ptr(), L.stream_ptr()), "sp3_knn_query")
         return dist, idx
-
-
-def _read_counters(ws):
-    head = ws[:32].cpu().numpy()
-    return int(head[:4].view(np.int32)[0]), int(head[16:24].view(np.uint64)[0]), int(head[24:32].view(np.uint64)[0])
 
 
 def nearest_neighbors(query, ref, k=1, max_dist=None, method="grid", return_stats=False, ring_budget=RING_BUDGET):

@@ -22,6 +22,7 @@ import struct
 import numpy as np
 import torch
 
+from . import cell_grid as G
 from . import lib as L
 
 SCALE = 10.0                                      # app.py:143
@@ -430,7 +431,7 @@ def vertex_normals(m):
 
 # ------------------------------------------------------------------------------------------------ mesh distance
 PAIRS_PER_FACE_CAP = 8          # (cell, face) references a TriangleGrid may hold per face before its cells are made larger
-FACES_PER_CELL = 0.5            # what evaluate.choose_grid aims the cell edge at: a surface leaves most cells of its box empty
+FACES_PER_CELL = 0.5            # what cell_grid.choose_grid aims the cell edge at: a surface leaves most cells of its box empty
 DIST_RING_BUDGET = 3            # rings walked before a query is handed to the brute-force kernels
 
 
@@ -443,9 +444,9 @@ def _tri_cell_counts(lib, vertices, faces, g):
     return counts
 
 
-class TriangleGrid:
+class TriangleGrid(G.Grid):
     """The faces of a mesh dict registered in a cell grid (include/spann3r_hip.h "Mesh distance"): built once, reused for any number
-    of query sets by point_mesh_distance.  The cell edge starts from evaluate.choose_grid on the box of the finite vertices with the
+    of query sets by point_mesh_distance.  The cell edge starts from cell_grid.choose_grid on the box of the finite vertices with the
     number of usable faces and grows by 1.25 while the (cell, face) references exceed PAIRS_PER_FACE_CAP per face; a grid of one cell
     holds no references and is answered by the brute-force kernels.  Host reads: 8 bytes for the usable faces, 48 for the box, 8 per
     try of h (one for near-uniform faces such as marching tetrahedra's).  h: start from this cell edge instead of choose_grid's.  A
@@ -453,36 +454,26 @@ class TriangleGrid:
     Attributes: g (lib.NnGrid), dims, h, usable, pairs, tries, pair_face int32 [pairs], cell_start int32 [cells + 1]."""
 
     def __init__(self, m, h=None):
-        from .evaluate import MAX_CELLS, choose_grid
         lib = L.load()
         self.vertices, _, self.faces = _check_mesh(m, "TriangleGrid")
         v, f = self.vertices, self.faces
         nf, dev = f.shape[0], v.device
-        one = L.NnGrid(0.0, 0.0, 0.0, 1.0, 1.0, 0.0, 1, 1, 1)
-        self.usable = int(_tri_cell_counts(lib, v, f, one).sum().item()) if nf else 0      # one cell: 1 per usable face
+        self.usable = int(_tri_cell_counts(lib, v, f, G.one_cell()).sum().item()) if nf else 0      # one cell: 1 per usable face
         if self.usable == 0:
             raise ValueError("TriangleGrid: %d faces over %d vertices, none valid, finite and with an area: no surface to measure against" %
                              (nf, v.shape[0]))
         fin = torch.isfinite(v)
         inf = torch.tensor(math.inf, device=dev)
-        box = torch.stack((torch.where(fin, v, inf).amin(0), torch.where(fin, v, -inf).amax(0))).double().cpu().numpy()
-        box = np.where(np.isfinite(box), box, 0.0)
+        box = G.finite_box(torch.where(fin, v, inf).amin(0), torch.where(fin, v, -inf).amax(0))
         ext = box[1] - box[0]
         if h is None:
-            h, dims = choose_grid(box[0], box[1], self.usable, occupancy=FACES_PER_CELL)
+            h, dims = G.choose_grid(box[0], box[1], self.usable, occupancy=FACES_PER_CELL)
         else:                                        # the caller's first cell edge (experiments; a huge one gives the one-cell grid)
-            h = float(h)
-            while True:
-                dims = tuple(int(math.floor(e / h)) + 1 for e in ext)
-                if dims[0] * dims[1] * dims[2] <= MAX_CELLS:
-                    break
-                h *= 1.25
-        maxabs = float(np.abs(box).max())
+            h, dims = G.grow_to_cap(ext, float(h))
         self.tries = 0
         while True:
             self.tries += 1
-            slack = 1e-6 * (maxabs + float(ext.max()) + h)
-            g = L.NnGrid(float(box[0, 0]), float(box[0, 1]), float(box[0, 2]), h, 1.0 / h, slack, *dims)
+            g = G.make_grid(box, h, dims)
             if dims == (1, 1, 1):
                 counts, pairs = None, 0
                 break
@@ -490,8 +481,7 @@ class TriangleGrid:
             pairs = int(counts.sum().item())
             if pairs <= min(PAIRS_PER_FACE_CAP * nf, 2 ** 31 - 2):
                 break
-            h *= 1.25
-            dims = tuple(int(math.floor(e / h)) + 1 for e in ext)
+            h, dims = G.grow_to_cap(ext, h * 1.25)
         self.g, self.h, self.dims, self.pairs = g, h, dims, pairs
         self.pair_face = self.cell_start = None
         if pairs:
@@ -500,16 +490,8 @@ class TriangleGrid:
             face = torch.empty(pairs, dtype=torch.int32, device=dev)
             L.check(lib.sp3_mesh_tri_cell_fill(v.data_ptr(), v.shape[0], f.data_ptr(), nf, C.byref(g), offsets.data_ptr(), pairs, cell.data_ptr(),
                                                face.data_ptr(), L.stream_ptr()), "sp3_mesh_tri_cell_fill")
-            sorted_cell, order = torch.sort(cell, stable=True)
+            order, self.cell_start = G.cell_table(cell, dims[0] * dims[1] * dims[2])
             self.pair_face = face[order].contiguous()
-            ncell = dims[0] * dims[1] * dims[2]
-            self.cell_start = torch.searchsorted(sorted_cell, torch.arange(ncell + 1, dtype=torch.int32, device=dev)).to(torch.int32)
-
-    def query_order(self, q):
-        """the queries sorted by the cell they fall in (clamped into the grid): the lanes of a wave then walk the same cells"""
-        ids = torch.empty(q.shape[0], dtype=torch.int32, device=q.device)
-        L.check(L.load().sp3_nn_cell_ids(q.data_ptr(), q.shape[0], C.byref(self.g), ids.data_ptr(), L.stream_ptr()), "sp3_nn_cell_ids")
-        return torch.sort(ids, stable=True)[1]
 
 
 def point_mesh_distance(points, m, grid=None, method="grid", return_stats=False, ring_budget=DIST_RING_BUDGET):
@@ -534,8 +516,7 @@ def point_mesh_distance(points, m, grid=None, method="grid", return_stats=False,
     elif method == "brute":                         # no grid to build: only the count of usable faces, for the same ValueError
         v, _, f = _check_mesh(m, "point_mesh_distance")
         pairs = 0
-        one = L.NnGrid(0.0, 0.0, 0.0, 1.0, 1.0, 0.0, 1, 1, 1)
-        if f.shape[0] == 0 or int(_tri_cell_counts(lib, v, f, one).sum().item()) == 0:
+        if f.shape[0] == 0 or int(_tri_cell_counts(lib, v, f, G.one_cell()).sum().item()) == 0:
             raise ValueError("point_mesh_distance: %d faces over %d vertices, none valid, finite and with an area: no surface to measure against" %
                              (f.shape[0], v.shape[0]))
     else:
@@ -560,9 +541,7 @@ def point_mesh_distance(points, m, grid=None, method="grid", return_stats=False,
                                             ws.data_ptr(), out["dist"].data_ptr(), out["closest"].data_ptr(), out["face"].data_ptr(),
                                             out["region"].data_ptr(), L.stream_ptr()), "sp3_mesh_dist_query")
             if return_stats:
-                head = ws[:32].cpu().numpy()
-                stats["fallback_queries"] = int(head[:4].view(np.int32)[0])
-                stats["cells_visited"], stats["faces_evaluated"] = (int(x) for x in head[16:32].view(np.uint64))
+                stats["fallback_queries"], stats["cells_visited"], stats["faces_evaluated"] = G.read_head(ws)
     if return_stats:
         out["stats"] = stats
     return out

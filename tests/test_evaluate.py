@@ -87,6 +87,19 @@ def test_choose_grid_handles_degenerate_boxes():
     assert dims[0] * dims[1] * dims[2] <= 2 * 4000
 
 
+def test_cell_table_keeps_the_order_inside_a_cell_and_spans_empty_cells():
+    from spann3r_amd.cell_grid import cell_table, grow_to_cap
+    ids = torch.tensor([4, 0, 1, 4, 0, 1, 0], dtype=torch.int32)        # 6 cells: 2 and 3 (in the middle) and 5 (at the end) are empty
+    order, start = cell_table(ids, 6)
+    assert order.tolist() == [1, 4, 6, 2, 5, 0, 3]                       # stable: the items of a cell keep their order
+    assert start.dtype == torch.int32 and start.tolist() == [0, 3, 5, 5, 5, 7, 7]
+    order, start = cell_table(torch.zeros(3, dtype=torch.int32), 1)      # the grid of one cell
+    assert order.tolist() == [0, 1, 2] and start.tolist() == [0, 3]
+    assert grow_to_cap([1.0, 1.0, 0.0], 0.25) == (0.25, (5, 5, 1))       # under the cap: h as given
+    h, dims = grow_to_cap([1.0, 1.0, 1.0], 0.125, max_cells=100)         # 9^3 > 100: h grows by 1.25 until the cap holds
+    assert dims[0] * dims[1] * dims[2] <= 100 and h == 0.125 * 1.25 ** 4 and dims == (4, 4, 4)
+
+
 # ------------------------------------------------------------------------------------------------ GPU: NN exactness
 @gpu
 @pytest.mark.parametrize("method", METHODS)
@@ -120,6 +133,32 @@ def test_nn_uniform_20k(fx, method):
     if method == "grid":
         assert stats["fallback_queries"] == 0
         assert stats["grid"][0] * stats["grid"][1] * stats["grid"][2] > 1000
+
+
+@gpu
+def test_nn_walk_without_a_ring_budget_on_a_flat_grid():
+    """The ring walk alone, to its end: a flat grid (nz = 1, nx != ny), queries inside the box and outside it on every side and
+    beyond every corner, out to 3 extents, and no ring budget, so that rings beyond the usual 3 and the exit taken when the walked
+    block covers the whole grid (bound +inf) give the answer instead of the brute-force stage."""
+    from spann3r_amd.evaluate import nearest_neighbors
+    rng = np.random.default_rng(11)
+    ext = np.array([4.0, 2.0, 0.0])
+    ref = (rng.uniform(0, 1, (600, 3)) * ext).astype(np.float32)
+    inside = rng.uniform(0, 1, (128, 3)) * ext
+    outside = np.empty((0, 3))
+    while len(outside) < 128:                        # uniform over the box pushed out by 3 extents (of x, for z), the box itself cut out
+        c = rng.uniform(-3, 4, (512, 3)) * np.array([4.0, 2.0, 4.0])
+        outside = np.concatenate([outside, c[((c[:, :2] < 0) | (c[:, :2] > ext[:2])).any(1)]])[:128]
+    side = np.sign(outside[:, :2] - ext[:2] / 2) * ((outside[:, :2] < 0) | (outside[:, :2] > ext[:2]))
+    assert len({tuple(s) for s in side.tolist()}) == 8                    # four sides, four corners
+    qry = np.concatenate([inside, outside]).astype(np.float32)
+    dist, idx, stats = nearest_neighbors(qry, ref, ring_budget=1 << 20, return_stats=True)
+    print(stats)
+    nx, ny, nz = stats["grid"]
+    assert nz == 1 and nx != ny and min(nx, ny) > 2 * 3 + 1               # a block of 3 rings cannot cover the grid
+    assert stats["fallback_queries"] == 0                                 # the walk alone answered
+    _check_nn(qry, ref, R.nn_brute(qry, ref)[0], dist, idx)
+    assert nearest_neighbors(qry, ref, return_stats=True)[2]["fallback_queries"] > 0      # and needed more than the usual 3 rings
 
 
 @gpu

@@ -132,6 +132,34 @@ def test_the_bumpy_sheet_grid_brute_and_restatement(sheet):
     assert all(torch.equal(again[k], got[k]) for k in ("dist", "closest", "face", "region"))
 
 
+def test_the_walk_without_a_ring_budget_answers_every_query():
+    """No ring budget: rings beyond the usual 3 and the exit taken when the walked block covers the whole grid (bound +inf) give the
+    answer, for queries near the surface, inside the box and outside it by up to 10 extents; nothing reaches the brute-force kernels."""
+    from spann3r_amd import mesh as M
+    verts, faces = _sheet(12)
+    assert len(faces) == 242
+    rng = np.random.default_rng(6)
+    f = faces[rng.integers(0, len(faces), 64)]
+    near = (verts[f] * rng.dirichlet((1, 1, 1), 64)[:, :, None]).sum(1) + rng.uniform(-0.005, 0.005, (64, 3))
+    lo, hi = verts.min(0), verts.max(0)
+    inside = rng.uniform(lo, hi, (64, 3))
+    direction = rng.normal(size=(64, 3))
+    direction /= np.linalg.norm(direction, axis=1, keepdims=True)
+    outside = (lo + hi) / 2 + direction * (hi - lo).max() * rng.uniform(1, 10, (64, 1))
+    q = np.concatenate([near, inside, outside]).astype(np.float32)
+    want = R.query(q, verts, faces)
+    m = _mesh(verts, faces)
+    grid = M.TriangleGrid(m)
+    print("grid", grid.dims, "h", grid.h, "pairs", grid.pairs)
+    assert max(grid.dims) > 2 * 3 + 1                                                  # a block of 3 rings cannot cover the grid
+    got = M.point_mesh_distance(_t(q), m, grid=grid, ring_budget=1 << 20, return_stats=True)
+    print(got["stats"])
+    assert got["stats"]["fallback_queries"] == 0                                       # the walk alone answered
+    _assert_same(got, want, "no ring budget")
+    _assert_same(got, M.point_mesh_distance(_t(q), m, method="brute"), "no ring budget against brute")
+    assert M.point_mesh_distance(_t(q), m, grid=grid, return_stats=True)["stats"]["fallback_queries"] > 0      # and needed more than 3 rings
+
+
 # ------------------------------------------------------------------------------------------------ 3. faces that must never win
 def test_unusable_faces_among_good_ones():
     from spann3r_amd import mesh as M
