@@ -179,6 +179,9 @@ def main():
     ap.add_argument("--eval_exact", action="store_true", help="with --eval_samples: a third fused line, the same samples measured against "
                     "the other surface's triangles instead of its samples (evaluate.evaluate_meshes(exact=True): exact point-to-triangle "
                     "distances, the normal of the face hit)")
+    ap.add_argument("--eval_depth", action="store_true", help="with --fused --rgbd --eval: one more fused line, the fused prediction's depth "
+                    "maps from the ground-truth cameras (mesh.render_depth_maps: rays against the mesh, on the device) scored against the "
+                    "RGB-D depth in image space: abs-rel, RMSE, delta < 1.25 and coverage (evaluate.evaluate_depth)")
     ap.add_argument("--glb_normals", action="store_true", help="with --save_glb: write area-weighted vertex normals (mesh.vertex_normals, on "
                     "the device) as the NORMAL attribute of the fused or per-frame mesh, so that viewers light it")
     ap.add_argument("--extent", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"), help="with --stream --fused "
@@ -216,6 +219,8 @@ def main():
         ap.error("--eval_samples must be positive")
     if args.eval_exact and args.eval_samples is None:
         ap.error("--eval_exact needs --eval_samples (the samples it measures against the other surface's triangles)")
+    if args.eval_depth and not (args.fused and args.rgbd and args.eval):
+        ap.error("--eval_depth needs --fused --rgbd --eval (a fused surface and ground-truth depth maps to score it against)")
     if args.glb_normals and not args.save_glb:
         ap.error("--glb_normals needs --save_glb (a file to write them to)")
     if args.glb_normals and args.as_pointcloud:
@@ -357,6 +362,11 @@ def main():
                 if args.eval_exact:
                     rx = evaluate_meshes(pred_mesh, gt_mesh, n_samples=args.eval_samples, threshold=0.1, exact=True)
                     print("Fused (exact, %d): Acc: %s, Comp: %s, NC1: %s, NC2: %s" % (rx["samples"], rx["acc"], rx["comp"], rx["nc1"], rx["nc2"]))
+            if args.eval_depth:
+                from spann3r_amd.evaluate import evaluate_depth
+                rd = evaluate_depth(pred_mesh, batch)
+                print("Fused (depth, %d views): AbsRel: %s, RMSE: %s, Delta1: %s, Coverage: %s  (%d pixels compared)" %
+                      (rd["views"], rd["abs_rel"], rd["rmse"], rd["delta1"], rd["coverage"], rd["pixels"]))
     if args.save_ply:
         from spann3r_amd.postprocess import (estimate_focal_knowing_depth, confident_points, write_ply, estimate_poses,
                                              transforms_json, save_transforms)

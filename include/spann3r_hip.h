@@ -1360,6 +1360,97 @@ int sp3_mesh_dist_query(const float* q, const int64_t* q_order, int64_t nq, cons
 int sp3_mesh_dist_brute(const float* q, int64_t nq, const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, void* ws,
                         float* dist, float* closest, int32_t* face, uint8_t* region, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh rays (spann3r_amd/mesh.py ray_mesh_intersect / render_depth_maps and spann3r_amd/evaluate.py evaluate_depth drive these;
+ * csrc/mesh_ray.hip): what a ray hits first on a triangle mesh -- the other geometric question next to "Mesh distance" -- and, from
+ * it, depth maps of a mesh seen from T cameras (spann3r/tools/render_dtu.py:54-80 render_depth_maps obtains them through pyrender and
+ * an OpenGL context; parity with pyrender is unpinned, it is not available to test against).  tests/mesh_ray_ref.py restates the
+ * rule in numpy and is itself checked against Moeller-Trumbore in exact rationals.  No entry point allocates, frees or synchronises;
+ * `ws` is caller-provided device scratch of sp3_mesh_ray_ws_bytes(nq) (32 bytes for sp3_mesh_ray_views), 16-byte aligned.  Indices
+ * are int32: nverts, nfaces and npairs stay below 2^31 - 1.  Every fp64 operation below is rounded on its own, in the order written
+ * (no FMA: the file is compiled under `#pragma clang fp contract(off)`).
+ *
+ * The rule.  vertices fp32 [V, 3], faces int32 [F, 3].
+ *   1. A RAY is o fp32 [3], d fp32 [3] (not normalised) and a range t_min <= t <= t_max with 0 <= t_min, doubles; o and d are
+ *      converted to fp64.  A ray with a non-finite component of o or d, or with d = 0, hits nothing.
+ *   2. A face is USABLE as in rule 1 of "Mesh distance" (indices in 0..V-1, the fp64 cross product of its edges finite and > 0); a
+ *      face that is not usable is never hit.
+ *   3. Intersection with a usable face (A, B, C) (Woop, Benthin, Wald: Watertight Ray/Triangle Intersection, JCGT 2013), in fp64:
+ *      kz = the axis of the largest |d|, the lowest axis among equals; kx = kz + 1, ky = kx + 1, cyclic; kx and ky are swapped when
+ *      d[kz] < 0.  Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz].  Per vertex P = vertex - o, X = P[kx] - Sx P[kz],
+ *      Y = P[ky] - Sy P[kz], Z = Sz P[kz].  U = Xc Yb - Yc Xb, V = Xa Yc - Ya Xc, W = Xb Ya - Yb Xa (two products, one difference).
+ *      A miss when one of U, V, W is < 0 and one is > 0.  det = (U + V) + W; a miss when det == 0.  T = (U Za + V Zb) + W Zc,
+ *      t = T / det, a zero t stored as +0.  A hit when t_min <= t <= t_max (a comparison with a NaN is false).
+ *      Watertight: the transformed vertex depends on the vertex and the ray only, and without FMA x y - z w = -(z w - x y) exactly, so
+ *      the edge function of an edge two faces share is for one the exact negative of the other's; a zero counts as inside for both.
+ *      No ray passes between two faces that share an edge; rule 4 decides which of them takes it.
+ *      SIDE: det > 0 exactly when the ray's origin lies on the side from which A, B, C appear counter-clockwise (the side the normal
+ *      (B - A) x (C - A) points to): side 0, the front.  det < 0: side 1, the back.  (Pinned on one triangle seen from both sides.)
+ *      cull: 0 keeps every hit, 1 ("back") drops the hits with side 1, 2 ("front") those with side 0, before the minimum.
+ *   4. The result of a ray is the minimum over the hits of the pair (t, face index), compared lexicographically, starting from
+ *      (+inf, none) with a strict <: among equal t the smallest index wins, and a t that is NaN or +inf never does.  It is a pure
+ *      function of the inputs, whatever the grid, the order of the visits or the number of times a face is evaluated.  Outputs:
+ *      t fp32 = the fp64 t rounded once; face int32; bary fp32 [3] = U / det, V / det, W / det, the weights of A, B, C;
+ *      point fp32 [3] = o + t d per axis, one fp64 product and one fp64 sum, rounded once; side uint8.  A miss: +inf, -1,
+ *      (0, 0, 0), o itself, 255.
+ *
+ * sp3_mesh_ray_query : one lane per ray, taken in q_order (nullable; a permutation of the rays, sorted by the cell of the origin),
+ *   results in caller order, over the grid of face references of sp3_mesh_tri_cell_count / _fill as it is (pair_face sorted by
+ *   cell, cell_start [cells + 1]; npairs >= 1).  The ray is clipped in fp64 against the box [origin - slack, wall(n) + slack] per axis
+ *   (wall(i) = fmaf(i, h, origin), as csrc/cell_grid.h computes it); an axis with d = 0 is a test of o against the two planes, never a
+ *   division.  A ray that misses the box, or whose clipped range is empty, evaluates nothing.  It starts at max(t_min, entry) in the
+ *   cell that the grid's own cell rule gives the entry point rounded to fp32 (clamped into the grid).  In every cell every referenced
+ *   face is evaluated and any hit kept, wherever it lies.  The exit parameter of the cell along an axis is (wall - o) / d with the
+ *   wall taken from the integer cell index at every step (no running sum: no drift); a cell on the rim of the grid has no wall on its
+ *   outer side and reaches to the box's exit.  The walk steps along the axis of the smallest exit (on a tie the lowest such axis: a
+ *   cell more is harmless) and ends when best t <= exit - 2 slack / |d[kz]|, when the exit is not before min(t_max, the box's exit),
+ *   or when no wall is left: at most nx + ny + nz cells, so there is no fallback list.
+ *   WHY NO HIT IS MISSED.  U, V, W of one sign make t a convex combination of Za, Zb, Zc, so the point o + t d of a hit lies in the
+ *   face's fp32 bounding box (to fp64 rounding).  Registration covers cell(min - slack) .. cell(max + slack) under the monotone fp32
+ *   cell rule, whose borders differ from the real-valued walls of the walk by less than half the slack (the subtraction, the product with
+ *   the rounded inv_h and the fmaf of a wall with the rounded h are under three fp32 ulps of the box's largest coordinate plus its
+ *   extent together; the host's slack, spann3r_amd/cell_grid.py make_grid, is 1e-6 of that: over eight).  The fp64 cell intervals of the walk tile
+ *   [start, exit] without a gap, each from the same integer-indexed walls, so the real-valued cell that holds the point of a hit with
+ *   t below the exit has been visited, and it or a neighbour within the slack of the point -- registered too -- is the cell the walk
+ *   was in.  The stopping margin is two slacks of travel along the dominant axis, a larger margin than registration's, and only
+ *   delays the stop; an entry cell that the fp32 rounding of the entry point puts one cell ahead skips less than half a slack of the
+ *   ray, which the registered neighbours cover, and one cell behind only adds a cell.  On an axis with d = 0 the fp32 cell of o is
+ *   exactly the cell registration gives that coordinate.
+ *   After the call the first 32 bytes of ws hold { int32 0, 3 x int32 pad, uint64 cells visited, uint64 faces evaluated }.
+ * sp3_mesh_ray_brute : the same result for every ray with the faces staged through LDS in tiles of 512 (usability decided by the
+ *   loader), the face list split over workgroups; joined by a 64-bit integer atomicMin over the bits of the non-negative t, then, in
+ *   a second pass over the same tiles, an atomicMin of the face index among the faces with exactly that t; a last launch recomputes
+ *   bary, point and side of the winner.  The route of a one-cell grid and the on-device cross-check.
+ * sp3_mesh_ray_views : the walk of sp3_mesh_ray_query (every face per ray when npairs == 0) for the rays of T cameras in ONE launch;
+ *   views_host and views_dev hold the same T descriptors, the host copy is validated and sizes the launch, the device copy is read,
+ *   never written, through scalar loads (a wave owns an 8 x 8 pixel tile of one view).  Pixel (u, v), centres at integer coordinates:
+ *   x = ((u + pixel_offset) - cu) / fu, y = ((v + pixel_offset) - cv) / fv in fp64 from the fp32 fields; d_i = fp32((R_i0 x + R_i1 y)
+ *   + R_i2), R_ij = c2w[4 i + j]; o_i = c2w[4 i + 3]; t_min = near, t_max = far, no culling.  The camera-frame direction has z = 1, so
+ *   t IS camera z.  depth[v * row_stride + u] = t, 0 for a miss (render_dtu.py's convention and sp3_tsdf_raycast's); face (nullable)
+ *   int32 and bary (nullable) fp32 [.., 3] likewise.  By construction equal to sp3_mesh_ray_query on the same rays, bit for bit.
+ *   T = 0 launches nothing; ws as above. */
+typedef struct {
+  float* depth;        /* [h, row_stride] */
+  int32_t* face;       /* [h, row_stride] or null */
+  float* bary;         /* [h, row_stride, 3] or null */
+  int64_t row_stride;  /* elements between rows, >= w */
+  int32_t w, h;
+  float fu, fv, cu, cv;
+  float c2w[12];       /* camera-to-world, row-major 3 x 4 */
+  float near, far;     /* 0 <= near <= far (+inf allowed), camera z */
+} sp3_mesh_ray_view;
+int64_t sp3_mesh_ray_ws_bytes(int64_t nq);
+int sp3_mesh_ray_query(const float* origins, const float* directions, const int64_t* q_order, int64_t nq, const float* vertices,
+                       int64_t nverts, const int32_t* faces, int64_t nfaces, const int32_t* pair_face, int64_t npairs,
+                       const int32_t* cell_start, const sp3_nn_grid* g, double t_min, double t_max, int cull, void* ws, float* t,
+                       int32_t* face, float* bary, float* point, uint8_t* side, void* stream);
+int sp3_mesh_ray_brute(const float* origins, const float* directions, int64_t nq, const float* vertices, int64_t nverts,
+                       const int32_t* faces, int64_t nfaces, double t_min, double t_max, int cull, void* ws, float* t, int32_t* face,
+                       float* bary, float* point, uint8_t* side, void* stream);
+int sp3_mesh_ray_views(const sp3_mesh_ray_view* views_host, const sp3_mesh_ray_view* views_dev, int T, float pixel_offset,
+                       const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, const int32_t* pair_face, int64_t npairs,
+                       const int32_t* cell_start, const sp3_nn_grid* g, void* ws, void* stream);
+
 /* small utilities */
 /* n (1..8) contiguous device-to-device copies in one launch; every copy 16-byte aligned and a multiple of 16 bytes.
  * (The sequence loop's per-frame bookkeeping -- torch .clone() / slice assignments around spann3r/model.py:523-531.) */

@@ -346,6 +346,39 @@ def evaluate_meshes(pred_mesh, gt_mesh, n_samples=200_000, seed=0, threshold=0.1
     return out
 
 
+def evaluate_depth(m, views, near=0.0, far=math.inf):
+    """A surface scored in image space against the depth of an RGB-D sequence, the usual companion of acc / comp: the mesh dict `m`
+    rendered from every view's `camera_intrinsics` / `camera_pose` at its `depthmap` size (mesh.render_depth_maps: rays against the
+    mesh on the device, all views in one launch; include/spann3r_hip.h "Mesh rays") and compared with `depthmap` on `valid_mask`.
+    -> dict(abs_rel = mean |p - g| / g, rmse = sqrt(mean (p - g)^2), delta1 = the share of pixels with max(p / g, g / p) < 1.25 --
+    all three over the valid_mask pixels the mesh hits -- coverage = the share of valid_mask pixels the mesh hits, its own number,
+    pixels = how many were compared, views).  The views of views.build_views, batch size 1 each or stacked; landscape views only,
+    as fusion.fuse_views.  Sums are fp64 reductions on the device; one host read.  No pixel to compare gives NaN errors."""
+    from . import mesh as M
+    if len(views) == 0:
+        raise ValueError("evaluate_depth: no views")
+    dev = m["vertices"].device
+    gt = torch.cat([v["depthmap"].to(dev) for v in views]).float()
+    valid = torch.cat([v["valid_mask"].to(dev) for v in views]).bool()
+    if gt.dim() != 3 or valid.shape != gt.shape:
+        raise RuntimeError("evaluate_depth: mismatched shapes: depthmap %s, valid_mask %s" % (tuple(gt.shape), tuple(valid.shape)))
+    K = torch.cat([v["camera_intrinsics"] for v in views]).double().cpu().numpy()
+    poses = torch.cat([v["camera_pose"] for v in views]).double().cpu().numpy()
+    pred = M.render_depth_maps(m, K, poses, gt.shape[1:], near=near, far=far)["depth"]
+    hit = valid & (pred > 0)
+    p, g = pred.double(), gt.double()
+    g = torch.where(hit, g, torch.ones_like(g))
+    p = torch.where(hit, p, torch.ones_like(p))
+    diff = p - g
+    ratio = torch.maximum(p / g, g / p)
+    sums = torch.stack([valid.sum().double(), hit.sum().double(), (diff.abs() / g).sum(), (diff * diff).sum(),
+                        (hit & (ratio < 1.25)).sum().double()]).cpu().tolist()
+    nv, nh = sums[0], sums[1]
+    nan = float("nan")
+    return dict(abs_rel=sums[2] / nh if nh else nan, rmse=math.sqrt(sums[3] / nh) if nh else nan, delta1=sums[4] / nh if nh else nan,
+                coverage=nh / nv if nv else nan, pixels=int(nh), views=int(gt.shape[0]))
+
+
 def _align(views, preds, preds_all, clouds):
     from .loss import L21, Regr3D_t_ScaleShiftInv, _entries
     n = len(views)

@@ -132,6 +132,13 @@ class TsdfFrame(C.Structure):
                 ("cv", C.c_float), ("w2c", C.c_float * 12)]
 
 
+class MeshRayView(C.Structure):
+    """sp3_mesh_ray_view (include/spann3r_hip.h)"""
+    _fields_ = [("depth", C.c_void_p), ("face", C.c_void_p), ("bary", C.c_void_p), ("row_stride", C.c_int64), ("w", C.c_int32), ("h", C.c_int32),
+                ("fu", C.c_float), ("fv", C.c_float), ("cu", C.c_float), ("cv", C.c_float), ("c2w", C.c_float * 12), ("near", C.c_float),
+                ("far", C.c_float)]
+
+
 class TsdfView(C.Structure):
     """sp3_tsdf_view (include/spann3r_hip.h)"""
     _fields_ = [("depth", C.c_void_p), ("vertex", C.c_void_p), ("normal", C.c_void_p), ("rgba", C.c_void_p), ("row_stride", C.c_int64),
@@ -289,6 +296,13 @@ _PROTOS = {
                             C.POINTER(NnGrid), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "sp3_mesh_dist_brute": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.c_void_p, C.c_void_p],
+    "sp3_mesh_ray_query": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                           C.c_void_p, C.POINTER(NnGrid), C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                           C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_mesh_ray_brute": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int,
+                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_mesh_ray_views": [C.POINTER(MeshRayView), C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                           C.c_int64, C.c_void_p, C.POINTER(NnGrid), C.c_void_p, C.c_void_p],
     "sp3_render_tris": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(RenderCam), C.c_int,
                         C.c_void_p, C.c_void_p, C.c_void_p],
     "sp3_ssi_align_stats": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -323,7 +337,7 @@ EXPORTS = sorted(list(_PROTOS) + ["sp3_last_error", "sp3_version", "sp3_weight_s
                                   "sp3_tsdf_extract_ws_bytes", "sp3_tsdf_track_accum_ws_bytes", "sp3_tsdf_brick_alloc_ws_bytes",
                                   "sp3_tsdf_brick_extract_ws_bytes", "sp3_mesh_components_ws_bytes", "sp3_mesh_select_faces_ws_bytes",
                                   "sp3_mesh_cluster_ws_bytes", "sp3_mesh_cluster_faces_ws_bytes", "sp3_mesh_face_frames_ws_bytes",
-                                  "sp3_mesh_vertex_normals_ws_bytes", "sp3_mesh_dist_query_ws_bytes"])
+                                  "sp3_mesh_vertex_normals_ws_bytes", "sp3_mesh_dist_query_ws_bytes", "sp3_mesh_ray_ws_bytes"])
 
 
 def load():
@@ -358,7 +372,7 @@ def load():
     lib.sp3_tsdf_brick_extract_ws_bytes.argtypes = [C.c_int]
     for name in ("sp3_nn_query_ws_bytes", "sp3_icp_accum_ws_bytes", "sp3_sum_count_ws_bytes", "sp3_mesh_vertices_ws_bytes", "sp3_eval_align_ws_bytes",
                  "sp3_tsdf_track_accum_ws_bytes", "sp3_mesh_components_ws_bytes", "sp3_mesh_select_faces_ws_bytes", "sp3_mesh_face_frames_ws_bytes",
-                 "sp3_mesh_vertex_normals_ws_bytes", "sp3_mesh_dist_query_ws_bytes"):
+                 "sp3_mesh_vertex_normals_ws_bytes", "sp3_mesh_dist_query_ws_bytes", "sp3_mesh_ray_ws_bytes"):
         getattr(lib, name).restype = C.c_int64
         getattr(lib, name).argtypes = [C.c_int64]
     for name in ("sp3_mesh_cluster_ws_bytes", "sp3_mesh_cluster_faces_ws_bytes"):

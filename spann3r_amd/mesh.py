@@ -547,6 +547,140 @@ def point_mesh_distance(points, m, grid=None, method="grid", return_stats=False,
     return out
 
 
+# ------------------------------------------------------------------------------------------------ mesh rays
+_CULL = {None: 0, "back": 1, "front": 2}
+
+
+def _ray_grid(m, grid, what, build=True):
+    """(vertices, faces, grid or None) for a ray call: the caller's TriangleGrid, a new one, or -- build False -- none, with
+    TriangleGrid's ValueError for a mesh without a usable face either way"""
+    if grid is not None:
+        return grid.vertices, grid.faces, grid
+    if build:
+        grid = TriangleGrid(m)
+        return grid.vertices, grid.faces, grid
+    v, _, f = _check_mesh(m, what)
+    if f.shape[0] == 0 or int(_tri_cell_counts(L.load(), v, f, G.one_cell()).sum().item()) == 0:
+        raise ValueError("%s: %d faces over %d vertices, none valid, finite and with an area: no surface to hit" % (what, f.shape[0], v.shape[0]))
+    return v, f, None
+
+
+def ray_mesh_intersect(origins, directions, m, grid=None, t_min=0.0, t_max=math.inf, cull=None, method="grid", return_stats=False):
+    """What every ray hits first on the surface of a mesh dict (include/spann3r_hip.h "Mesh rays"; sp3_mesh_ray_query /
+    sp3_mesh_ray_brute): origins, directions fp32 [N, 3] (device; directions need no normalising: t is in units of |d|) ->
+    dict(t fp32 [N] (+inf: a miss), face int32 [N] (-1; the smallest index among faces hit at the same t), bary fp32 [N, 3] (the
+    weights of the face's corners A, B, C), point fp32 [N, 3] (o + t d), side uint8 [N] (0: the ray's origin sees the face
+    counter-clockwise, 1: clockwise, 255: a miss)), tensors on the device.  Hits lie in t_min <= t <= t_max.  The test is watertight:
+    no ray passes between two faces that share an edge.  A ray with a non-finite component or d = 0 hits nothing.  The result is a
+    function of the inputs alone: the same bits for either method, for any grid and every run.
+    cull: None, "back" (hits with side 1 are ignored) or "front" (side 0).  method: "grid" (a TriangleGrid -- pass one as `grid` to
+    reuse it, it must have been built on this mesh -- walked cell by cell along the ray, rays served in the order of
+    grid.query_order(origins); the brute-force kernels when the grid is one cell) or "brute" (every ray against every face: the
+    in-tree cross-check).  return_stats: also `stats` = dict(cells_visited, faces_evaluated, grid, h, pairs), one 32-byte host read.
+    A mesh without a usable face raises ValueError; N = 0 launches nothing."""
+    if method not in ("grid", "brute"):
+        raise ValueError("ray_mesh_intersect: method must be 'grid' or 'brute', got %r" % (method,))
+    if cull not in _CULL:
+        raise ValueError("ray_mesh_intersect: cull must be None, 'back' or 'front', got %r" % (cull,))
+    t_min, t_max = float(t_min), float(t_max)
+    if not (0.0 <= t_min <= t_max):
+        raise ValueError("ray_mesh_intersect: 0 <= t_min <= t_max, got t_min %r, t_max %r" % (t_min, t_max))
+    lib = L.load()
+    o, d = _dev(origins, "ray_mesh_intersect: origins"), _dev(directions, "ray_mesh_intersect: directions")
+    for name, x in (("origins", o), ("directions", d)):
+        if x.dim() != 2 or x.shape[1] != 3 or x.dtype != torch.float32:
+            raise RuntimeError("ray_mesh_intersect: %s must be fp32 [N, 3], got %s %s" % (name, x.dtype, tuple(x.shape)))
+    if o.shape != d.shape:
+        raise RuntimeError("ray_mesh_intersect: %d origins and %d directions" % (o.shape[0], d.shape[0]))
+    o, d = o.contiguous(), d.contiguous()
+    v, f, grid = _ray_grid(m, grid, "ray_mesh_intersect", build=method == "grid")
+    pairs = 0 if grid is None else grid.pairs
+    n, dev = o.shape[0], o.device
+    out = dict(t=torch.empty(n, dtype=torch.float32, device=dev), face=torch.empty(n, dtype=torch.int32, device=dev),
+               bary=torch.empty((n, 3), dtype=torch.float32, device=dev), point=torch.empty((n, 3), dtype=torch.float32, device=dev),
+               side=torch.empty(n, dtype=torch.uint8, device=dev))
+    stats = dict(cells_visited=0, faces_evaluated=0, grid=(1, 1, 1) if grid is None else tuple(grid.dims), h=None if grid is None else grid.h,
+                 pairs=pairs)
+    if n > 0:
+        ws = _ws(lib.sp3_mesh_ray_ws_bytes(n), dev)
+        outs = (out["t"].data_ptr(), out["face"].data_ptr(), out["bary"].data_ptr(), out["point"].data_ptr(), out["side"].data_ptr())
+        if method == "brute" or pairs == 0:
+            L.check(lib.sp3_mesh_ray_brute(o.data_ptr(), d.data_ptr(), n, v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0], t_min, t_max,
+                                           _CULL[cull], ws.data_ptr(), *outs, L.stream_ptr()), "sp3_mesh_ray_brute")
+        else:
+            order = grid.query_order(o)
+            L.check(lib.sp3_mesh_ray_query(o.data_ptr(), d.data_ptr(), order.data_ptr(), n, v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0],
+                                           grid.pair_face.data_ptr(), grid.pairs, grid.cell_start.data_ptr(), C.byref(grid.g), t_min, t_max,
+                                           _CULL[cull], ws.data_ptr(), *outs, L.stream_ptr()), "sp3_mesh_ray_query")
+            if return_stats:
+                _, stats["cells_visited"], stats["faces_evaluated"] = G.read_head(ws)
+    if return_stats:
+        out["stats"] = stats
+    return out
+
+
+def render_depth_maps(m, intrinsics, cam2world, size, near=0.0, far=math.inf, grid=None, pixel_offset=0.0, opengl=False, return_faces=False,
+                      return_stats=False):
+    """Depth maps of a mesh dict seen from T cameras in ONE launch (include/spann3r_hip.h "Mesh rays"; sp3_mesh_ray_views) -- what
+    spann3r/tools/render_dtu.py:54-80 render_depth_maps obtains from pyrender: intrinsics [3, 3] or [T, 3, 3], cam2world [T, 4, 4] (or
+    one [4, 4]), size = (h, w) -> dict(depth fp32 [T, h, w]: camera z of the first surface along the ray of every pixel, 0 where
+    the ray hits nothing between near and far (camera z, held as fp32)), device tensors; return_faces: also face int32 [T, h, w] (-1: a miss) and
+    bary fp32 [T, h, w, 3].  Pixel centres lie at integer coordinates, the package's convention: the ray of pixel (u, v) has the
+    camera-frame direction ((u + pixel_offset - cx) / fx, (v + pixel_offset - cy) / fy, 1).  pyrender samples at pixel centres + 0.5,
+    so pixel_offset=0.5 reproduces its sampling (pyrender is not available to test against: that parity is unpinned).
+    opengl=True: the poses are the ones render_dtu.py hands to pyrender -- camera looking down -z, y up: columns 1 and 2 negated --
+    and that is undone here.  Both faces of the surface are seen.  grid: a TriangleGrid built on this mesh, to reuse it.  Skewed
+    intrinsics and non-finite or singular poses are refused as fusion.camera_tables refuses them.  return_stats: also `stats` as
+    ray_mesh_intersect's (one 32-byte host read); otherwise nothing synchronises beyond the grid's build."""
+    from .fusion import _host_array, camera_tables
+    h, w = (int(x) for x in size)
+    if h < 1 or w < 1:
+        raise ValueError("render_depth_maps: size %s must be (h, w) >= 1" % (size,))
+    near, far, pixel_offset = float(near), float(far), float(pixel_offset)
+    if not (0.0 <= near <= far):
+        raise ValueError("render_depth_maps: 0 <= near <= far, got near %r, far %r" % (near, far))
+    if not math.isfinite(pixel_offset):
+        raise ValueError("render_depth_maps: pixel_offset must be finite, got %r" % (pixel_offset,))
+    P = _host_array(cam2world)
+    P = P[None] if P.ndim == 2 else P.reshape(-1, 4, 4) if P.size == 0 else P
+    if P.ndim != 3 or P.shape[1:] != (4, 4):
+        raise ValueError("render_depth_maps: cam2world %s must be [4, 4] or [T, 4, 4]" % (P.shape,))
+    T = P.shape[0]
+    if opengl:
+        P = P * np.array([1.0, -1.0, -1.0, 1.0])
+    fk, _ = camera_tables(intrinsics, P, T)                      # (the inverse is only computed for its checks)
+    if not (fk[:, :2] != 0).all():
+        raise ValueError("render_depth_maps: intrinsics with a zero focal length")
+    v, f, grid = _ray_grid(m, grid, "render_depth_maps")
+    dev, lib = v.device, L.load()
+    out = dict(depth=torch.empty((T, h, w), dtype=torch.float32, device=dev))
+    if return_faces:
+        out["face"] = torch.empty((T, h, w), dtype=torch.int32, device=dev)
+        out["bary"] = torch.empty((T, h, w, 3), dtype=torch.float32, device=dev)
+    stats = dict(cells_visited=0, faces_evaluated=0, grid=tuple(grid.dims), h=grid.h, pairs=grid.pairs)
+    if T > 0:
+        table = (L.MeshRayView * T)()
+        for i in range(T):
+            e = table[i]
+            e.depth = out["depth"][i].data_ptr()
+            e.face = out["face"][i].data_ptr() if return_faces else None
+            e.bary = out["bary"][i].data_ptr() if return_faces else None
+            e.row_stride, e.w, e.h = w, w, h
+            e.fu, e.fv, e.cu, e.cv = (float(x) for x in fk[i])
+            e.c2w[:] = P[i, :3].reshape(12).astype(np.float32).tolist()
+            e.near, e.far = near, far
+        table_d = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+        ws = _ws(lib.sp3_mesh_ray_ws_bytes(0), dev)
+        L.check(lib.sp3_mesh_ray_views(table, table_d.data_ptr(), T, pixel_offset, v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0],
+                                       L.ptr(grid.pair_face), grid.pairs, L.ptr(grid.cell_start), C.byref(grid.g), ws.data_ptr(),
+                                       L.stream_ptr()), "sp3_mesh_ray_views")
+        if return_stats:
+            _, stats["cells_visited"], stats["faces_evaluated"] = G.read_head(ws)
+    if return_stats:
+        out["stats"] = stats
+    return out
+
+
 def pts3d_to_mesh(img, pts3d, valid=None):
     """app.py:68-105 (pts3d_to_trimesh) for device tensors img, pts3d [h, w, 3] and valid bool [h, w]: dict(vertices [h w, 3],
     faces int64 [F, 3], face_colors [F, 3]) with the reference's order: four blocks (tl, tr, bl), (bl, tr, tl), (tr, bl, br), (br, bl, tr),
