@@ -182,6 +182,9 @@ def main():
     ap.add_argument("--eval_depth", action="store_true", help="with --fused --rgbd --eval: one more fused line, the fused prediction's depth "
                     "maps from the ground-truth cameras (mesh.render_depth_maps: rays against the mesh, on the device) scored against the "
                     "RGB-D depth in image space: abs-rel, RMSE, delta < 1.25 and coverage (evaluate.evaluate_depth)")
+    ap.add_argument("--eval_bvh", action="store_true", help="with --eval_exact or --eval_depth: answer them over a bounding-volume hierarchy "
+                    "of the faces (mesh.TriangleBVH) instead of the uniform grid: the same numbers, at a cost that does not grow with the "
+                    "distance between prediction and ground truth")
     ap.add_argument("--glb_normals", action="store_true", help="with --save_glb: write area-weighted vertex normals (mesh.vertex_normals, on "
                     "the device) as the NORMAL attribute of the fused or per-frame mesh, so that viewers light it")
     ap.add_argument("--extent", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"), help="with --stream --fused "
@@ -219,6 +222,8 @@ def main():
         ap.error("--eval_samples must be positive")
     if args.eval_exact and args.eval_samples is None:
         ap.error("--eval_exact needs --eval_samples (the samples it measures against the other surface's triangles)")
+    if args.eval_bvh and not (args.eval_exact or args.eval_depth):
+        ap.error("--eval_bvh needs --eval_exact or --eval_depth (the evaluations that query the faces of a mesh)")
     if args.eval_depth and not (args.fused and args.rgbd and args.eval):
         ap.error("--eval_depth needs --fused --rgbd --eval (a fused surface and ground-truth depth maps to score it against)")
     if args.glb_normals and not args.save_glb:
@@ -360,11 +365,12 @@ def main():
                 print("Fused (area-sampled, %d): Acc: %s, Comp: %s, NC1: %s, NC2: %s  (prediction area %.6g, ground truth area %.6g)" %
                       (rs["samples"], rs["acc"], rs["comp"], rs["nc1"], rs["nc2"], rs["pred_area"], rs["gt_area"]))
                 if args.eval_exact:
-                    rx = evaluate_meshes(pred_mesh, gt_mesh, n_samples=args.eval_samples, threshold=0.1, exact=True)
+                    rx = evaluate_meshes(pred_mesh, gt_mesh, n_samples=args.eval_samples, threshold=0.1, exact=True,
+                                         accel="bvh" if args.eval_bvh else None)
                     print("Fused (exact, %d): Acc: %s, Comp: %s, NC1: %s, NC2: %s" % (rx["samples"], rx["acc"], rx["comp"], rx["nc1"], rx["nc2"]))
             if args.eval_depth:
                 from spann3r_amd.evaluate import evaluate_depth
-                rd = evaluate_depth(pred_mesh, batch)
+                rd = evaluate_depth(pred_mesh, batch, bvh=True if args.eval_bvh else None)
                 print("Fused (depth, %d views): AbsRel: %s, RMSE: %s, Delta1: %s, Coverage: %s  (%d pixels compared)" %
                       (rd["views"], rd["abs_rel"], rd["rmse"], rd["delta1"], rd["coverage"], rd["pixels"]))
     if args.save_ply:

@@ -1451,6 +1451,87 @@ int sp3_mesh_ray_views(const sp3_mesh_ray_view* views_host, const sp3_mesh_ray_v
                        const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, const int32_t* pair_face, int64_t npairs,
                        const int32_t* cell_start, const sp3_nn_grid* g, void* ws, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh BVH (spann3r_amd/mesh.py TriangleBVH and the bvh= keyword of point_mesh_distance / ray_mesh_intersect / render_depth_maps,
+ * spann3r_amd/evaluate.py evaluate_meshes(exact=True, accel="bvh") and evaluate_depth(bvh=...) drive these; csrc/mesh_bvh.hip): a
+ * bounding-volume hierarchy over the faces of a mesh that answers the questions of "Mesh distance" and "Mesh rays" BY THEIR OWN
+ * RULES at any range -- a query far from the surface, or a mesh whose faces differ wildly in size, costs a walk of the tree's depth
+ * where the uniform grid hands over to the brute-force kernels or grows its cells.  The faces of a leaf are evaluated by the very
+ * functions the grid and the brute-force kernels call (csrc/tri_dist.h, csrc/tri_ray.h) and the result is the same lexicographic
+ * minimum (rules 3 of "Mesh distance" and 4 of "Mesh rays"), so every output equals theirs bit for bit; tests/mesh_bvh_ref.py restates
+ * the structure and both walks in numpy.  No entry point allocates, frees or synchronises; `ws` is 32 bytes of caller-provided device
+ * scratch, 16-byte aligned.  Indices are int32: nverts and nfaces stay below 2^31 - 1.
+ *
+ * The structure.  LEAF = 4 faces per leaf node, ARITY = 4 children per node (named constants of csrc/mesh_bvh.hip and
+ * spann3r_amd/cell_grid.py).
+ *   1. KEYS.  A usable face (rule 1 of "Mesh distance") gets the 63-bit Morton key (x in bit 0, y in bit 1, z in bit 2 of every
+ *      triple) of the fp32 centre 0.5f min + 0.5f max of its fp32 bounding box, each axis quantised to 21 bits against the box of
+ *      the mesh's finite vertices: clamp(floor((c - lo) * scale), 0, 2^21 - 1), scale = fp32(2^21 / (hi - lo)), 0 for an axis of no
+ *      extent; a usable key is capped at 2^63 - 2 and a face that is not usable gets 2^63 - 1 (63 ones).  The host sorts the keys
+ *      (stable); `order` int32 [usable] is the usable faces in that order.  The key decides the QUALITY of the tree only: any
+ *      permutation of the usable faces gives a valid tree and the same results.
+ *   2. LEVELS.  Leaf node k holds order[k LEAF .. (k + 1) LEAF); node k of level l + 1 holds nodes k ARITY .. (k + 1) ARITY of
+ *      level l; levels are added until one holds a single node, the root: size(0) = ceil(usable / LEAF), size(l + 1) =
+ *      ceil(size(l) / ARITY), at most 16 levels.  Level l is stored at level_off[l] .. level_off[l + 1] of node_lo / node_hi fp32
+ *      [nodes, 3].  There are no child pointers, and a node exists iff its index is below its level's size: existence is decided
+ *      from counts, never from box values.  A node's box is the exact fp32 min / max of the vertices of the faces below it -- min
+ *      and max are exact and order-free, so the boxes have the same bits every run.
+ *   3. slack = 1e-6 (the largest |coordinate| of the box of the finite vertices + its largest extent): make_grid's without h.
+ * sp3_mesh_bvh_keys : keys int64 [n] of n faces, or -- faces null, n = nverts -- of n points (a non-finite point: 2^63 - 1); box =
+ *   6 floats ON THE HOST, lo then hi.  The point form gives the order queries are served in: neighbours descend together.
+ * sp3_mesh_bvh_build : one launch for the leaf level and one per level above it (at most 16), each reading only what an earlier
+ *   launch wrote.  No atomics, counters or flags.  The descriptor is validated by every entry point: 1 <= usable <= nfaces, leaves =
+ *   ceil(usable / LEAF), 1 <= levels <= 16, level_off[0] = 0, every level the ceiling quotient of the one below, the last of size 1.
+ *
+ * The walk: one lane per query, depth first, the stack in LDS laid out [entry][lane], (ARITY - 1) (levels - 1) + 1 entries of 4
+ * bytes (a popped node pushes at most ARITY nodes of the level below; 46 entries at 16 levels), no scratch memory.  A node is
+ * tested when it is pushed and again when it is popped; the children of a node are pushed farthest first, so the nearest is
+ * popped first.  Every node is pushed at most once, so the walk ends.  An entry is the node's index within its level under a
+ * marker bit at 30 - 2 level (LEAF = ARITY = 4): level l holds at most max(2^(29 - 2 l), 1) nodes for nfaces < 2^31 - 1, so the index
+ * stays below the marker up to the root of a 16-level tree (level 15, index 0: the word 1), and a descriptor with a larger level
+ * is refused.  Indices read from order, faces and q_order are range-checked; an entry of q_order outside 0 .. nq - 1 is skipped.
+ * sp3_mesh_bvh_dist_query : per axis g = max(max(lo - p, p - hi) - slack, 0) in fp64 from the node's fp32 box; lb = ((gx gx + gy gy)
+ *   + gz gz) (1 - 2^-30); a node is skipped iff lb > best d2 -- strictly, so a node that may hold an equal d2 with a smaller face
+ *   index is visited.  WHY NO FACE IS MISSED: the true distance to a box never exceeds the true distance to a face inside it; the
+ *   evaluated d2 of rule 2 differs from the true one by rounding (3.4e-13 relative measured against exact rationals in
+ *   tests/test_mesh_distance_cpu.py, larger for points within that of the surface, which the slack -- 1e-6 of the scene -- covers),
+ *   and the factor sits three orders above that; it only delays pruning.  This is an argument, not a proof: tests/test_mesh_bvh_cpu.py
+ *   checks the property lb(face's own box) <= evaluated d2 on thousands of pairs, slivers and near-contact included.  A non-finite
+ *   query never enters the tree: rule 3's no-winner outputs.  Outputs as sp3_mesh_dist_query; q_order nullable.
+ * sp3_mesh_bvh_ray_query : the ray is clipped in fp64 against the node's box pushed out by the slack, starting from [t_min, t_max],
+ *   with the slab test sp3_mesh_ray_query applies to the grid's box (an axis with d = 0 is a test of o, never a division).  A node is
+ *   skipped iff the clipped range is empty or its entry is > best t (strictly); children nearest entry first.
+ *   WHY NO HIT IS MISSED.  As for the grid: U, V, W of one sign make t a convex combination of Za, Zb, Zc, so the point o + t d of a
+ *   hit lies in the face's fp32 bounding box to fp64 rounding -- a few 1e-16 of the distances involved, against a slack of 1e-6 of
+ *   the scene.  The box of every ancestor contains the face's box exactly (min and max do not round).  So t lies in the clipped
+ *   range of the face's leaf and of every node above it, the entry of each of them is <= t, and none is skipped while best > t or
+ *   (best == t and the face's index is smaller): the face is evaluated.  Outputs as sp3_mesh_ray_query; q_order nullable.
+ * sp3_mesh_bvh_ray_views : the same walk for the rays of T cameras in ONE launch: the descriptors, the pixel rule and the outputs of
+ *   sp3_mesh_ray_views (a wave owns an 8 x 8 tile of one view; the device copy of the table is only read, through scalar loads).
+ * After a query the first 32 bytes of ws hold { int32 0, 3 x int32 pad, uint64 nodes visited, uint64 faces evaluated }.  nq = 0 and
+ * T = 0 launch nothing. */
+#define SP3_BVH_MAX_LEVELS 16
+typedef struct {
+  int32_t usable;                             /* entries of order: the usable faces */
+  int32_t leaves;                             /* ceil(usable / LEAF) */
+  int32_t levels;                             /* 1 .. SP3_BVH_MAX_LEVELS, the leaf level included */
+  int32_t level_off[SP3_BVH_MAX_LEVELS + 1];  /* level l: nodes level_off[l] .. level_off[l + 1] - 1; entries past `levels` unused */
+  float slack;
+} sp3_mesh_bvh;
+int sp3_mesh_bvh_keys(const float* vertices, int64_t nverts, const int32_t* faces, int64_t n, const float* box, int64_t* keys, void* stream);
+int sp3_mesh_bvh_build(const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, const int32_t* order, const sp3_mesh_bvh* b,
+                       float* node_lo, float* node_hi, void* stream);
+int sp3_mesh_bvh_dist_query(const float* q, const int64_t* q_order, int64_t nq, const float* vertices, int64_t nverts, const int32_t* faces,
+                            int64_t nfaces, const int32_t* order, const float* node_lo, const float* node_hi, const sp3_mesh_bvh* b, void* ws,
+                            float* dist, float* closest, int32_t* face, uint8_t* region, void* stream);
+int sp3_mesh_bvh_ray_query(const float* origins, const float* directions, const int64_t* q_order, int64_t nq, const float* vertices,
+                           int64_t nverts, const int32_t* faces, int64_t nfaces, const int32_t* order, const float* node_lo,
+                           const float* node_hi, const sp3_mesh_bvh* b, double t_min, double t_max, int cull, void* ws, float* t, int32_t* face,
+                           float* bary, float* point, uint8_t* side, void* stream);
+int sp3_mesh_bvh_ray_views(const sp3_mesh_ray_view* views_host, const sp3_mesh_ray_view* views_dev, int T, float pixel_offset,
+                           const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, const int32_t* order,
+                           const float* node_lo, const float* node_hi, const sp3_mesh_bvh* b, void* ws, void* stream);
+
 /* small utilities */
 /* n (1..8) contiguous device-to-device copies in one launch; every copy 16-byte aligned and a multiple of 16 bytes.
  * (The sequence loop's per-frame bookkeeping -- torch .clone() / slice assignments around spann3r/model.py:523-531.) */

@@ -62,6 +62,40 @@ def make_grid(box, h, dims):
     return L.NnGrid(float(box[0, 0]), float(box[0, 1]), float(box[0, 2]), h, 1.0 / h, slack, *dims)
 
 
+# ---- the implicit tree of mesh.TriangleBVH (include/spann3r_hip.h "Mesh BVH"; csrc/mesh_bvh.hip holds the same two constants)
+BVH_LEAF = 4             # faces per leaf node
+BVH_ARITY = 4            # children per node
+
+
+def bvh_levels(usable, leaf=BVH_LEAF, arity=BVH_ARITY):
+    """the level table of a tree over `usable` >= 1 faces -> (sizes, offsets): sizes[0] = ceil(usable / leaf) leaf nodes, every
+    level the ceiling quotient of the one below by `arity` until one node is left; level l is stored at offsets[l] .. offsets[l + 1]"""
+    if usable < 1:
+        raise ValueError("bvh_levels: %d faces: a tree needs one at least" % usable)
+    sizes = [-(-usable // leaf)]
+    while sizes[-1] > 1:
+        sizes.append(-(-sizes[-1] // arity))
+    offsets = [0]
+    for n in sizes:
+        offsets.append(offsets[-1] + n)
+    return sizes, offsets
+
+
+def bvh_slack(box):
+    """make_grid's slack without its h term: what the boxes of a tree are pushed out by"""
+    return 1e-6 * (float(np.abs(box).max()) + float((box[1] - box[0]).max()))
+
+
+def make_bvh(box, usable):
+    """the descriptor of the tree over `usable` faces in the box of the finite vertices"""
+    sizes, offsets = bvh_levels(usable)
+    if len(sizes) > L.MeshBvh.MAX_LEVELS:
+        raise ValueError("make_bvh: %d levels for %d faces: more than the %d the descriptor holds" % (len(sizes), usable, L.MeshBvh.MAX_LEVELS))
+    b = L.MeshBvh(usable=usable, leaves=sizes[0], levels=len(sizes), slack=bvh_slack(box))
+    b.level_off[:len(offsets)] = offsets
+    return b, sizes, offsets
+
+
 def cell_table(ids, ncell):
     """cell ids (any integer tensor, values in 0..ncell-1) -> (order, cell_start): the stable order that sorts the items by cell,
     and int32 [ncell + 1] with the sorted items of cell c at cell_start[c] .. cell_start[c + 1] - 1"""

@@ -1,8 +1,9 @@
 // Ray queries on a triangle mesh (include/spann3r_hip.h "Mesh rays"; spann3r_amd/mesh.py ray_mesh_intersect / render_depth_maps and
 // spann3r_amd/evaluate.py evaluate_depth drive these; tests/mesh_ray_ref.py restates the rule).
 //
-//   * The rule of one (ray, face) pair is Woop, Benthin and Wald's watertight test in fp64, every operation rounded on its own (the
-//     file-level pragma below) and in the order the header fixes.  The result of a ray is the lexicographic minimum of (t, face index)
+//   * The rule of one (ray, face) pair is Woop, Benthin and Wald's watertight test in fp64, every operation rounded on its own
+//     (csrc/tri_ray.h states it once, for this file and csrc/mesh_bvh.hip; the file-level pragma below covers the rest) and in the
+//     order the header fixes.  The result of a ray is the lexicographic minimum of (t, face index)
 //     over the hits: a pure function of the inputs, so a face may be evaluated in any order, any number of times, by any kernel.
 //   * The grid of face references is mesh.TriangleGrid's as it is (csrc/mesh_distance.hip registers the faces).  A ray is clipped
 //     against the grid's box pushed out by the slack and walks the cells it crosses one by one; the exit parameter of a cell is
@@ -18,7 +19,7 @@
 //   * Every loop is bounded by the grid dims, npairs or nfaces; nothing waits on another lane's store; what an atomic wrote is read
 //     by a LATER launch only.
 #include "cell_grid.h"
-#include "tri.h"
+#include "tri_ray.h"
 
 #pragma clang fp contract(off)
 
@@ -28,103 +29,9 @@ typedef unsigned long long u64;
 
 constexpr int TB = 256;
 constexpr int TILE = 512;                      // faces per LDS tile of the brute-force kernel: 512 * 40 bytes
-constexpr int NO_FACE = 0x7fffffff;
 constexpr int VIEW_TILE = 16;                  // a workgroup of sp3_mesh_ray_views: 16 x 16 pixels, four 8 x 8 wave tiles
-enum { CULL_NONE = 0, CULL_BACK = 1, CULL_FRONT = 2 };
 
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + TB - 1) / TB); }
-
-__device__ __forceinline__ bool has_area(const float (&v)[9]) { const double d = edge_cross(v).d; return d > 0.0 && is_finite(d); }
-
-// ------------------------------------------------------------------------------------------------ a ray and a face
-__device__ __forceinline__ float pick(float a, float b, float c, int k) { return k == 0 ? a : (k == 1 ? b : c); }
-__device__ __forceinline__ double pick(double a, double b, double c, int k) { return k == 0 ? a : (k == 1 ? b : c); }
-
-// the ray in the form the test wants it: the permuted origin and the shear (header, rule 3)
-struct Ray {
-  double okx, oky, okz, Sx, Sy, Sz;
-  int kx, ky, kz;
-  bool ok;      // finite and d != 0
-};
-
-__device__ __forceinline__ Ray make_ray(float ox, float oy, float oz, float dx, float dy, float dz) {
-  Ray r;
-  const double o0 = (double)ox, o1 = (double)oy, o2 = (double)oz, d0 = (double)dx, d1 = (double)dy, d2 = (double)dz;
-  r.ok = is_finite(fabs(o0)) && is_finite(fabs(o1)) && is_finite(fabs(o2)) && is_finite(fabs(d0)) && is_finite(fabs(d1)) && is_finite(fabs(d2)) &&
-         !(d0 == 0.0 && d1 == 0.0 && d2 == 0.0);
-  const double a0 = fabs(d0), a1 = fabs(d1), a2 = fabs(d2);
-  int kz = 0;
-  if (a1 > a0) kz = 1;
-  if (a2 > fmax(a0, a1)) kz = 2;
-  int kx = kz == 2 ? 0 : kz + 1, ky = kx == 2 ? 0 : kx + 1;
-  const double dkz = pick(d0, d1, d2, kz);
-  if (dkz < 0.0) { const int s = kx; kx = ky; ky = s; }
-  r.kx = kx; r.ky = ky; r.kz = kz;
-  r.okx = pick(o0, o1, o2, kx); r.oky = pick(o0, o1, o2, ky); r.okz = pick(o0, o1, o2, kz);
-  r.Sx = pick(d0, d1, d2, kx) / dkz;
-  r.Sy = pick(d0, d1, d2, ky) / dkz;
-  r.Sz = 1.0 / dkz;
-  return r;
-}
-
-struct Hit { double U, V, W, det, t; };
-
-// rule 3 for the face whose nine coordinates are at v; true for a hit inside [t_min, t_max] that the culling keeps
-__device__ __forceinline__ bool intersect(const Ray& r, const float* v, double t_min, double t_max, int cull, Hit& h) {
-  double X[3], Y[3], Z[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const float a = v[3 * i], b = v[3 * i + 1], c = v[3 * i + 2];
-    const double px = (double)pick(a, b, c, r.kx) - r.okx, py = (double)pick(a, b, c, r.ky) - r.oky, pz = (double)pick(a, b, c, r.kz) - r.okz;
-    X[i] = px - r.Sx * pz;
-    Y[i] = py - r.Sy * pz;
-    Z[i] = r.Sz * pz;
-  }
-  h.U = X[2] * Y[1] - Y[2] * X[1];
-  h.V = X[0] * Y[2] - Y[0] * X[2];
-  h.W = X[1] * Y[0] - Y[1] * X[0];
-  if ((h.U < 0.0 || h.V < 0.0 || h.W < 0.0) && (h.U > 0.0 || h.V > 0.0 || h.W > 0.0)) return false;
-  h.det = (h.U + h.V) + h.W;
-  if (h.det == 0.0) return false;
-  if ((cull == CULL_BACK && h.det < 0.0) || (cull == CULL_FRONT && h.det > 0.0)) return false;
-  const double T = (h.U * Z[0] + h.V * Z[1]) + h.W * Z[2];
-  double t = T / h.det;
-  if (t == 0.0) t = 0.0;      // -0 -> +0
-  h.t = t;
-  return t_min <= t && t <= t_max;      // (false for a NaN)
-}
-
-// what a ray reports of its winning face f (NO_FACE, -1 or anything that is no hit: the outputs of a miss)
-struct Result { float t, bary[3], point[3]; int face; int side; };
-
-__device__ __forceinline__ Result result_of(const float* __restrict__ verts, int nverts, const int* __restrict__ faces, int nfaces, const Ray& r,
-                                            float ox, float oy, float oz, float dx, float dy, float dz, double t_min, double t_max, int cull, int f) {
-  Result o;
-  o.t = INFINITY; o.face = -1; o.side = 255;
-  o.bary[0] = o.bary[1] = o.bary[2] = 0.f;
-  o.point[0] = ox; o.point[1] = oy; o.point[2] = oz;
-  float v[9];
-  Hit h;
-  if (r.ok && (unsigned)f < (unsigned)nfaces && load_face(verts, nverts, faces, f, v) && intersect(r, v, t_min, t_max, cull, h)) {
-    o.t = (float)h.t;
-    o.face = f;
-    o.side = h.det > 0.0 ? 0 : 1;
-    o.bary[0] = (float)(h.U / h.det); o.bary[1] = (float)(h.V / h.det); o.bary[2] = (float)(h.W / h.det);
-    const double mx = h.t * (double)dx, my = h.t * (double)dy, mz = h.t * (double)dz;
-    o.point[0] = (float)((double)ox + mx); o.point[1] = (float)((double)oy + my); o.point[2] = (float)((double)oz + mz);
-  }
-  return o;
-}
-
-struct RayOut { float* t; int* face; float* bary; float* point; uint8_t* side; };
-
-__device__ __forceinline__ void store(const RayOut& out, int64_t i, const Result& o) {
-  out.t[i] = o.t;
-  out.face[i] = o.face;
-  out.side[i] = (uint8_t)o.side;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { out.bary[3 * i + k] = o.bary[k]; out.point[3 * i + k] = o.point[k]; }
-}
 
 // ------------------------------------------------------------------------------------------------ the walk
 struct MeshRef {
@@ -142,20 +49,12 @@ __device__ __forceinline__ int walk_ray(const sp3_nn_grid& g, const MeshRef& m, 
   const float org[3] = {g.ox, g.oy, g.oz};
   const int n[3] = {g.nx, g.ny, g.nz};
   const double slack = (double)g.slack;
-  // the slab test against the box [origin - slack, wall(n) + slack]; a zero component is a test of the origin, not a division
-  double t0 = t_min, t1 = t_max;
+  // the slab test against the box [origin - slack, wall(n) + slack] (clip_box, csrc/tri_ray.h)
+  double lo[3], hi[3];
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double lo = (double)org[k] - slack, hi = (double)fmaf((float)n[k], g.h, org[k]) + slack;
-    if (d[k] == 0.0) {
-      if (!(o[k] >= lo && o[k] <= hi)) return -1;
-    } else {
-      const double a = (lo - o[k]) / d[k], b = (hi - o[k]) / d[k];
-      t0 = fmax(t0, fmin(a, b));
-      t1 = fmin(t1, fmax(a, b));
-    }
-  }
-  if (!(t0 <= t1)) return -1;
+  for (int k = 0; k < 3; ++k) { lo[k] = (double)org[k] - slack; hi[k] = (double)fmaf((float)n[k], g.h, org[k]) + slack; }
+  double t0 = t_min, t1 = t_max;
+  if (!clip_box(o, d, lo, hi, t0, t1)) return -1;
   // the entry cell, clamped into the grid by the cell rule itself
   int c[3];
 #pragma unroll
@@ -312,28 +211,16 @@ __global__ __launch_bounds__(VIEW_TILE * VIEW_TILE) void k_mr_views(const sp3_me
   const int py = blockIdx.y * VIEW_TILE + (wave >> 1) * 8 + (lane >> 3);
   int cells = 0, evals = 0;
   if (px < vw.w && py < vw.h) {
-    const double x = (((double)px + (double)pixel_offset) - (double)vw.cu) / (double)vw.fu;
-    const double y = (((double)py + (double)pixel_offset) - (double)vw.cv) / (double)vw.fv;
-    float dd[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const double a = (double)vw.c2w[4 * i] * x, b = (double)vw.c2w[4 * i + 1] * y;
-      dd[i] = (float)((a + b) + (double)vw.c2w[4 * i + 2]);
-    }
-    const float ox = vw.c2w[3], oy = vw.c2w[7], oz = vw.c2w[11];
+    float oo[3], dd[3];
+    pixel_ray(vw, px, py, pixel_offset, oo, dd);
+    const float ox = oo[0], oy = oo[1], oz = oo[2];
     const double t_min = (double)vw.near, t_max = (double)vw.far;
     const Ray r = make_ray(ox, oy, oz, dd[0], dd[1], dd[2]);
     int bf = -1;
     if (r.ok) bf = m.npairs > 0 ? walk_ray(g, m, r, ox, oy, oz, dd[0], dd[1], dd[2], t_min, t_max, CULL_NONE, cells, evals)
                                 : scan_all(m, r, t_min, t_max, CULL_NONE, evals);
     const Result o = result_of(m.verts, m.nverts, m.faces, m.nfaces, r, ox, oy, oz, dd[0], dd[1], dd[2], t_min, t_max, CULL_NONE, bf);
-    const int64_t p = (int64_t)py * vw.row_stride + px;
-    vw.depth[p] = o.face >= 0 ? o.t : 0.f;
-    if (vw.face != nullptr) vw.face[p] = o.face;
-    if (vw.bary != nullptr) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) vw.bary[3 * p + k] = o.bary[k];
-    }
+    store_pixel(vw, px, py, o);
   }
   head->count(cells, evals);
 }

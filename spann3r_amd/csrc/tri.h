@@ -1,11 +1,13 @@
 // One face of an indexed triangle mesh, per translation unit: its corners, and the cross product of two edges in fp64 with its
-// length (twice the area), which csrc/mesh_sample.hip weighs faces by and csrc/mesh_distance.hip calls a face usable by (> 0 and
-// finite).  Every fp64 operation is rounded on its own (the block-scope pragma in edge_cross), whatever the including file sets.
+// length (twice the area), which csrc/mesh_sample.hip weighs faces by and the searches over faces (csrc/mesh_distance.hip,
+// csrc/mesh_ray.hip, csrc/mesh_bvh.hip) call a face usable by (has_area: > 0 and finite).  Every fp64 operation is rounded on its own (the block-scope pragma in edge_cross), whatever the including file sets.
 #pragma once
 #include "common.h"
 #include <math.h>
 
 namespace {
+
+constexpr int NO_FACE = 0x7fffffff;      // "no winner yet" of the searches over faces (indices stay below it)
 
 // the three indices and the nine coordinates of face f; false (nothing dereferenced beyond the indices) when one is outside 0..V-1
 __device__ __forceinline__ bool load_face(const float* __restrict__ verts, int nverts, const int* __restrict__ faces, int64_t f, float (&v)[9],
@@ -39,5 +41,7 @@ __device__ __forceinline__ EdgeCross edge_cross(const float (&v)[9]) {
   return r;
 }
 __device__ __forceinline__ bool is_finite(double d) { return d <= 1.7976931348623157e308; }      // false for NaN and +inf
+// usable: the d > 0 of sp3_mesh_face_frames (rule 1 of "Mesh distance")
+__device__ __forceinline__ bool has_area(const float (&v)[9]) { const double d = edge_cross(v).d; return d > 0.0 && is_finite(d); }
 
 }  // namespace

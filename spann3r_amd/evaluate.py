@@ -291,11 +291,11 @@ def evaluate_reconstruction(pred_points, gt_points, threshold=0.1):
             "nc2_med": nc2_med, "transformation": T}
 
 
-def _exact_side(points, normals, target_mesh, face_normals):
+def _exact_side(points, normals, target_mesh, face_normals, bvh=None):
     """points (with their normals) against the TRIANGLES of target_mesh -> (mean, median of the distances, mean, median of
     |n_point . n_face| with the unit normal of the face each closest point lies on)"""
     from . import mesh as M
-    r = M.point_mesh_distance(points, target_mesh)
+    r = M.point_mesh_distance(points, target_mesh, bvh=bvh)
     n = points.shape[0]
     dots = torch.empty(n, dtype=torch.float32, device=points.device)
     L.check(L.load().sp3_normal_dot(face_normals.data_ptr(), normals.data_ptr(), r["face"].data_ptr(), n, 1, dots.data_ptr(), L.stream_ptr()),
@@ -303,7 +303,7 @@ def _exact_side(points, normals, target_mesh, face_normals):
     return _mean_median(r["dist"]) + _mean_median(dots)
 
 
-def evaluate_meshes(pred_mesh, gt_mesh, n_samples=200_000, seed=0, threshold=0.1, icp=True, exact=False):
+def evaluate_meshes(pred_mesh, gt_mesh, n_samples=200_000, seed=0, threshold=0.1, icp=True, exact=False, accel=None):
     """The metrics of evaluate_reconstruction for two SURFACES instead of two clouds, as NICE-SLAM-style eval_recon scripts take
     them: n_samples points drawn by area from each mesh (mesh.sample_surface: the dicts of scene_mesh / extract_mesh / simplify,
     the same seed for both), point-to-point ICP of the prediction's samples onto the ground truth's from identity unless
@@ -315,8 +315,16 @@ def evaluate_meshes(pred_mesh, gt_mesh, n_samples=200_000, seed=0, threshold=0.1
     include/spann3r_hip.h "Mesh distance"): acc = the prediction's samples to the ground truth's faces, comp = the ground truth's
     samples to the prediction's faces, its vertices moved by T; nc1 / nc2 = |n_sample . n_face| with the unit normal of the face
     hit (mesh.face_frames; rotated by T's rotation for the prediction).  Sampling and ICP are unchanged.  The floor the sample
-    spacing puts under acc / comp is gone: two tessellations of one plane score 0.  The dict gains exact=True."""
+    spacing puts under acc / comp is gone: two tessellations of one plane score 0.  The dict gains exact=True.
+    accel (with exact=True only): "grid" (the default: mesh.TriangleGrid, fastest when the prediction lies within a few cells of
+    the ground truth) or "bvh" (mesh.TriangleBVH: the same numbers bit for bit, at a cost that does not depend on how far apart
+    the two surfaces are -- the choice for a prediction that may be poor, and for meshes of wildly mixed face sizes)."""
     from . import mesh as M
+    if accel is not None and not exact:
+        raise ValueError("evaluate_meshes: accel=%r chooses the structure of the exact distance: pass exact=True" % (accel,))
+    if accel not in (None, "grid", "bvh"):
+        raise ValueError("evaluate_meshes: accel must be 'grid' or 'bvh', got %r" % (accel,))
+    bvh = True if accel == "bvh" else None
     n = int(n_samples)
     if n <= 0:
         raise ValueError("evaluate_meshes: n_samples = %r, must be positive" % (n_samples,))
@@ -334,8 +342,8 @@ def evaluate_meshes(pred_mesh, gt_mesh, n_samples=200_000, seed=0, threshold=0.1
         if icp:
             moved = dict(vertices=_transform(pred_mesh["vertices"].contiguous().float(), T), faces=pred_mesh["faces"])
             pred_fn = _transform(pred_fn, R)
-        acc, acc_med, nc1, nc1_med = _exact_side(pred, pred_n, gt_mesh, gt_fn)
-        comp, comp_med, nc2, nc2_med = _exact_side(gt, gt_n, moved, pred_fn)
+        acc, acc_med, nc1, nc1_med = _exact_side(pred, pred_n, gt_mesh, gt_fn, bvh)
+        comp, comp_med, nc2, nc2_med = _exact_side(gt, gt_n, moved, pred_fn, bvh)
     else:
         acc, acc_med, nc1, nc1_med = accuracy(gt, pred, gt_n, pred_n)
         comp, comp_med, nc2, nc2_med = completion(gt, pred, gt_n, pred_n)
@@ -346,14 +354,15 @@ def evaluate_meshes(pred_mesh, gt_mesh, n_samples=200_000, seed=0, threshold=0.1
     return out
 
 
-def evaluate_depth(m, views, near=0.0, far=math.inf):
+def evaluate_depth(m, views, near=0.0, far=math.inf, bvh=None):
     """A surface scored in image space against the depth of an RGB-D sequence, the usual companion of acc / comp: the mesh dict `m`
     rendered from every view's `camera_intrinsics` / `camera_pose` at its `depthmap` size (mesh.render_depth_maps: rays against the
     mesh on the device, all views in one launch; include/spann3r_hip.h "Mesh rays") and compared with `depthmap` on `valid_mask`.
     -> dict(abs_rel = mean |p - g| / g, rmse = sqrt(mean (p - g)^2), delta1 = the share of pixels with max(p / g, g / p) < 1.25 --
     all three over the valid_mask pixels the mesh hits -- coverage = the share of valid_mask pixels the mesh hits, its own number,
     pixels = how many were compared, views).  The views of views.build_views, batch size 1 each or stacked; landscape views only,
-    as fusion.fuse_views.  Sums are fp64 reductions on the device; one host read.  No pixel to compare gives NaN errors."""
+    as fusion.fuse_views.  Sums are fp64 reductions on the device; one host read.  No pixel to compare gives NaN errors.
+    bvh: a mesh.TriangleBVH built on `m`, or True to build one: the rays walk it instead of a TriangleGrid, the same depth maps."""
     from . import mesh as M
     if len(views) == 0:
         raise ValueError("evaluate_depth: no views")
@@ -364,7 +373,7 @@ def evaluate_depth(m, views, near=0.0, far=math.inf):
         raise RuntimeError("evaluate_depth: mismatched shapes: depthmap %s, valid_mask %s" % (tuple(gt.shape), tuple(valid.shape)))
     K = torch.cat([v["camera_intrinsics"] for v in views]).double().cpu().numpy()
     poses = torch.cat([v["camera_pose"] for v in views]).double().cpu().numpy()
-    pred = M.render_depth_maps(m, K, poses, gt.shape[1:], near=near, far=far)["depth"]
+    pred = M.render_depth_maps(m, K, poses, gt.shape[1:], near=near, far=far, bvh=bvh)["depth"]
     hit = valid & (pred > 0)
     p, g = pred.double(), gt.double()
     g = torch.where(hit, g, torch.ones_like(g))

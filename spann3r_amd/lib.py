@@ -139,6 +139,13 @@ class MeshRayView(C.Structure):
                 ("far", C.c_float)]
 
 
+class MeshBvh(C.Structure):
+    """sp3_mesh_bvh (include/spann3r_hip.h)"""
+    MAX_LEVELS = 16
+    _fields_ = [("usable", C.c_int32), ("leaves", C.c_int32), ("levels", C.c_int32), ("level_off", C.c_int32 * (MAX_LEVELS + 1)),
+                ("slack", C.c_float)]
+
+
 class TsdfView(C.Structure):
     """sp3_tsdf_view (include/spann3r_hip.h)"""
     _fields_ = [("depth", C.c_void_p), ("vertex", C.c_void_p), ("normal", C.c_void_p), ("rgba", C.c_void_p), ("row_stride", C.c_int64),
@@ -303,6 +310,15 @@ _PROTOS = {
                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "sp3_mesh_ray_views": [C.POINTER(MeshRayView), C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                            C.c_int64, C.c_void_p, C.POINTER(NnGrid), C.c_void_p, C.c_void_p],
+    "sp3_mesh_bvh_keys": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.c_void_p, C.c_void_p],
+    "sp3_mesh_bvh_build": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(MeshBvh), C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_mesh_bvh_dist_query": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.POINTER(MeshBvh), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_mesh_bvh_ray_query": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.POINTER(MeshBvh), C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_mesh_bvh_ray_views": [C.POINTER(MeshRayView), C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.POINTER(MeshBvh), C.c_void_p, C.c_void_p],
     "sp3_render_tris": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(RenderCam), C.c_int,
                         C.c_void_p, C.c_void_p, C.c_void_p],
     "sp3_ssi_align_stats": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],

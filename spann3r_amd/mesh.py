@@ -494,7 +494,73 @@ class TriangleGrid(G.Grid):
             self.pair_face = face[order].contiguous()
 
 
-def point_mesh_distance(points, m, grid=None, method="grid", return_stats=False, ring_budget=DIST_RING_BUDGET):
+_KEY_NONE = 2 ** 63 - 1          # sp3_mesh_bvh_keys: an item that is not usable
+
+
+class TriangleBVH:
+    """A bounding-volume hierarchy over the faces of a mesh dict (include/spann3r_hip.h "Mesh BVH"): built once, reused for any
+    number of query sets through the bvh= keyword of point_mesh_distance, ray_mesh_intersect and render_depth_maps, which then return
+    what they return with a TriangleGrid, bit for bit.  The usable faces are sorted by the Morton key of their box centres, cell_grid.
+    BVH_LEAF of them make a leaf and BVH_ARITY nodes a node of the level above (cell_grid.bvh_levels: no pointers, index arithmetic
+    and a table of level offsets); one launch builds each level.  Unlike the grid it has no cell edge to choose -- faces 64-fold
+    apart in size cost no retries -- and a query far from the surface costs a walk of the tree's depth instead of the brute-force
+    kernels.  Host reads: 8 bytes for the usable faces, 48 for the box.  A mesh without a usable face raises ValueError; a cloud too.
+    Attributes: vertices, faces, usable, order int32 [usable] (the usable faces in key order), levels, level_sizes, level_offsets,
+    node_lo / node_hi fp32 [nodes, 3] (level l at level_offsets[l] .. level_offsets[l + 1]), slack, b (lib.MeshBvh)."""
+
+    def __init__(self, m):
+        lib = L.load()
+        self.vertices, _, self.faces = _check_mesh(m, "TriangleBVH")
+        v, f = self.vertices, self.faces
+        nf, dev = f.shape[0], v.device
+        fin = torch.isfinite(v)
+        inf = torch.tensor(math.inf, device=dev)
+        box = G.finite_box(torch.where(fin, v, inf).amin(0), torch.where(fin, v, -inf).amax(0)) if v.shape[0] else np.zeros((2, 3))
+        self._box = (C.c_float * 6)(*box.astype(np.float32).reshape(6).tolist())      # (fp32 vertices: their box is exact in fp32)
+        keys = self._keys(lib, v, f, nf) if nf else None
+        self.usable = int((keys != _KEY_NONE).sum().item()) if nf else 0
+        if self.usable == 0:
+            raise ValueError("TriangleBVH: %d faces over %d vertices, none valid, finite and with an area: no surface to measure against" %
+                             (nf, v.shape[0]))
+        self.order = torch.sort(keys, stable=True)[1][:self.usable].to(torch.int32)
+        self.b, self.level_sizes, self.level_offsets = G.make_bvh(box, self.usable)
+        self.levels, self.slack = self.b.levels, float(self.b.slack)
+        self.node_lo = torch.empty((self.level_offsets[-1], 3), dtype=torch.float32, device=dev)
+        self.node_hi = torch.empty((self.level_offsets[-1], 3), dtype=torch.float32, device=dev)
+        L.check(lib.sp3_mesh_bvh_build(L.ptr(v), v.shape[0], f.data_ptr(), nf, self.order.data_ptr(), C.byref(self.b), self.node_lo.data_ptr(),
+                                       self.node_hi.data_ptr(), L.stream_ptr()), "sp3_mesh_bvh_build")
+
+    def _keys(self, lib, points, faces, n):
+        """sp3_mesh_bvh_keys of n faces, or (faces None) of the n points: int64 [n] on the device"""
+        keys = torch.empty(n, dtype=torch.int64, device=points.device)
+        L.check(lib.sp3_mesh_bvh_keys(L.ptr(points) if points.shape[0] else 0, points.shape[0], None if faces is None else L.ptr(faces) if n else 0,
+                                      n, self._box, L.ptr(keys) if n else 0, L.stream_ptr()), "sp3_mesh_bvh_keys")
+        return keys
+
+    def query_order(self, q):
+        """the queries sorted by their own Morton key in the tree's box: the lanes of a wave then descend through the same nodes"""
+        return torch.sort(self._keys(L.load(), q, None, q.shape[0]), stable=True)[1]
+
+    def tree_args(self):
+        """(order, node_lo, node_hi, descriptor) as the query entry points take them"""
+        return self.order.data_ptr(), self.node_lo.data_ptr(), self.node_hi.data_ptr(), C.byref(self.b)
+
+
+def _bvh_arg(bvh, m, grid, method, what):
+    """the TriangleBVH a call is to walk, or None: bvh = None, True (build one on m) or a TriangleBVH built on this mesh"""
+    if bvh is None or bvh is False:
+        return None
+    if grid is not None or method != "grid":
+        raise ValueError("%s: bvh= replaces the grid: leave grid=None and method at its default, got grid %s, method %r" %
+                         (what, "given" if grid is not None else "None", method))
+    if bvh is True:
+        return TriangleBVH(m)
+    if not isinstance(bvh, TriangleBVH):
+        raise ValueError("%s: bvh must be None, True or a TriangleBVH, got %s" % (what, type(bvh).__name__))
+    return bvh
+
+
+def point_mesh_distance(points, m, grid=None, method="grid", return_stats=False, ring_budget=DIST_RING_BUDGET, bvh=None):
     """The exact unsigned distance from every point fp32 [N, 3] (device) to the surface of a mesh dict (include/spann3r_hip.h "Mesh
     distance"; sp3_mesh_dist_query / sp3_mesh_dist_brute) -> dict(dist fp32 [N], closest fp32 [N, 3], face int32 [N] (the face the
     closest point lies on, the smallest index among equals), region uint8 [N] (0..6: A, B, edge AB, C, edge AC, edge BC, inside)),
@@ -503,15 +569,21 @@ def point_mesh_distance(points, m, grid=None, method="grid", return_stats=False,
     method: "grid" (a TriangleGrid -- pass one as `grid` to reuse it, it must have been built on this mesh -- walked ring by ring,
     the brute-force kernels for what `ring_budget` rings leave open or when the grid is one cell) or "brute" (every query against
     every face: the in-tree cross-check).  return_stats: also `stats` = dict(fallback_queries, cells_visited, faces_evaluated, grid,
-    h, pairs), one 32-byte host read.  A mesh without a usable face raises ValueError; N = 0 launches nothing."""
+    h, pairs), one 32-byte host read.  A mesh without a usable face raises ValueError; N = 0 launches nothing.
+    bvh: a TriangleBVH built on this mesh, or True to build one: the queries walk the tree instead (sp3_mesh_bvh_dist_query) and no
+    query falls back, however far from the surface it lies; `grid` must then be None and `method` its default, else ValueError.
+    stats gains nodes_visited, levels and nodes; fallback_queries and cells_visited are 0, grid (1, 1, 1)."""
     if method not in ("grid", "brute"):
         raise ValueError("point_mesh_distance: method must be 'grid' or 'brute', got %r" % (method,))
+    bvh = _bvh_arg(bvh, m, grid, method, "point_mesh_distance")
     lib = L.load()
     q = _dev(points, "point_mesh_distance: points")
     if q.dim() != 2 or q.shape[1] != 3 or q.dtype != torch.float32:
         raise RuntimeError("point_mesh_distance: points must be fp32 [N, 3], got %s %s" % (q.dtype, tuple(q.shape)))
     q = q.contiguous()
-    if grid is not None:
+    if bvh is not None:
+        v, f, pairs = bvh.vertices, bvh.faces, 0
+    elif grid is not None:
         v, f, pairs = grid.vertices, grid.faces, grid.pairs
     elif method == "brute":                         # no grid to build: only the count of usable faces, for the same ValueError
         v, _, f = _check_mesh(m, "point_mesh_distance")
@@ -527,9 +599,18 @@ def point_mesh_distance(points, m, grid=None, method="grid", return_stats=False,
                face=torch.empty(n, dtype=torch.int32, device=dev), region=torch.empty(n, dtype=torch.uint8, device=dev))
     stats = dict(fallback_queries=0, cells_visited=0, faces_evaluated=0, grid=(1, 1, 1) if grid is None else tuple(grid.dims),
                  h=None if grid is None else grid.h, pairs=pairs)
+    if bvh is not None:
+        stats.update(nodes_visited=0, levels=bvh.levels, nodes=bvh.level_offsets[-1])
     if n > 0:
-        ws = _ws(lib.sp3_mesh_dist_query_ws_bytes(n), dev)
-        if method == "brute" or pairs == 0:
+        ws = _ws(32 if bvh is not None else lib.sp3_mesh_dist_query_ws_bytes(n), dev)      # (the tree: the 32-byte head alone)
+        if bvh is not None:
+            order = bvh.query_order(q)
+            L.check(lib.sp3_mesh_bvh_dist_query(q.data_ptr(), order.data_ptr(), n, L.ptr(v), v.shape[0], f.data_ptr(), f.shape[0], *bvh.tree_args(),
+                                                ws.data_ptr(), out["dist"].data_ptr(), out["closest"].data_ptr(), out["face"].data_ptr(),
+                                                out["region"].data_ptr(), L.stream_ptr()), "sp3_mesh_bvh_dist_query")
+            if return_stats:
+                _, stats["nodes_visited"], stats["faces_evaluated"] = G.read_head(ws)
+        elif method == "brute" or pairs == 0:
             L.check(lib.sp3_mesh_dist_brute(q.data_ptr(), n, v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0], ws.data_ptr(),
                                             out["dist"].data_ptr(), out["closest"].data_ptr(), out["face"].data_ptr(), out["region"].data_ptr(),
                                             L.stream_ptr()), "sp3_mesh_dist_brute")
@@ -565,7 +646,7 @@ def _ray_grid(m, grid, what, build=True):
     return v, f, None
 
 
-def ray_mesh_intersect(origins, directions, m, grid=None, t_min=0.0, t_max=math.inf, cull=None, method="grid", return_stats=False):
+def ray_mesh_intersect(origins, directions, m, grid=None, t_min=0.0, t_max=math.inf, cull=None, method="grid", return_stats=False, bvh=None):
     """What every ray hits first on the surface of a mesh dict (include/spann3r_hip.h "Mesh rays"; sp3_mesh_ray_query /
     sp3_mesh_ray_brute): origins, directions fp32 [N, 3] (device; directions need no normalising: t is in units of |d|) ->
     dict(t fp32 [N] (+inf: a miss), face int32 [N] (-1; the smallest index among faces hit at the same t), bary fp32 [N, 3] (the
@@ -577,9 +658,13 @@ def ray_mesh_intersect(origins, directions, m, grid=None, t_min=0.0, t_max=math.
     reuse it, it must have been built on this mesh -- walked cell by cell along the ray, rays served in the order of
     grid.query_order(origins); the brute-force kernels when the grid is one cell) or "brute" (every ray against every face: the
     in-tree cross-check).  return_stats: also `stats` = dict(cells_visited, faces_evaluated, grid, h, pairs), one 32-byte host read.
-    A mesh without a usable face raises ValueError; N = 0 launches nothing."""
+    A mesh without a usable face raises ValueError; N = 0 launches nothing.
+    bvh: a TriangleBVH built on this mesh, or True to build one: the rays walk the tree instead (sp3_mesh_bvh_ray_query), served in
+    the order of bvh.query_order(origins); `grid` must then be None and `method` its default, else ValueError.  stats gains
+    nodes_visited, levels and nodes; cells_visited is 0, grid (1, 1, 1)."""
     if method not in ("grid", "brute"):
         raise ValueError("ray_mesh_intersect: method must be 'grid' or 'brute', got %r" % (method,))
+    bvh = _bvh_arg(bvh, m, grid, method, "ray_mesh_intersect")
     if cull not in _CULL:
         raise ValueError("ray_mesh_intersect: cull must be None, 'back' or 'front', got %r" % (cull,))
     t_min, t_max = float(t_min), float(t_max)
@@ -593,7 +678,7 @@ def ray_mesh_intersect(origins, directions, m, grid=None, t_min=0.0, t_max=math.
     if o.shape != d.shape:
         raise RuntimeError("ray_mesh_intersect: %d origins and %d directions" % (o.shape[0], d.shape[0]))
     o, d = o.contiguous(), d.contiguous()
-    v, f, grid = _ray_grid(m, grid, "ray_mesh_intersect", build=method == "grid")
+    v, f, grid = (bvh.vertices, bvh.faces, None) if bvh is not None else _ray_grid(m, grid, "ray_mesh_intersect", build=method == "grid")
     pairs = 0 if grid is None else grid.pairs
     n, dev = o.shape[0], o.device
     out = dict(t=torch.empty(n, dtype=torch.float32, device=dev), face=torch.empty(n, dtype=torch.int32, device=dev),
@@ -601,10 +686,19 @@ def ray_mesh_intersect(origins, directions, m, grid=None, t_min=0.0, t_max=math.
                side=torch.empty(n, dtype=torch.uint8, device=dev))
     stats = dict(cells_visited=0, faces_evaluated=0, grid=(1, 1, 1) if grid is None else tuple(grid.dims), h=None if grid is None else grid.h,
                  pairs=pairs)
+    if bvh is not None:
+        stats.update(nodes_visited=0, levels=bvh.levels, nodes=bvh.level_offsets[-1])
     if n > 0:
-        ws = _ws(lib.sp3_mesh_ray_ws_bytes(n), dev)
+        ws = _ws(32 if bvh is not None else lib.sp3_mesh_ray_ws_bytes(n), dev)
         outs = (out["t"].data_ptr(), out["face"].data_ptr(), out["bary"].data_ptr(), out["point"].data_ptr(), out["side"].data_ptr())
-        if method == "brute" or pairs == 0:
+        if bvh is not None:
+            order = bvh.query_order(o)
+            L.check(lib.sp3_mesh_bvh_ray_query(o.data_ptr(), d.data_ptr(), order.data_ptr(), n, L.ptr(v), v.shape[0], f.data_ptr(), f.shape[0],
+                                               *bvh.tree_args(), t_min, t_max, _CULL[cull], ws.data_ptr(), *outs, L.stream_ptr()),
+                    "sp3_mesh_bvh_ray_query")
+            if return_stats:
+                _, stats["nodes_visited"], stats["faces_evaluated"] = G.read_head(ws)
+        elif method == "brute" or pairs == 0:
             L.check(lib.sp3_mesh_ray_brute(o.data_ptr(), d.data_ptr(), n, v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0], t_min, t_max,
                                            _CULL[cull], ws.data_ptr(), *outs, L.stream_ptr()), "sp3_mesh_ray_brute")
         else:
@@ -620,7 +714,7 @@ def ray_mesh_intersect(origins, directions, m, grid=None, t_min=0.0, t_max=math.
 
 
 def render_depth_maps(m, intrinsics, cam2world, size, near=0.0, far=math.inf, grid=None, pixel_offset=0.0, opengl=False, return_faces=False,
-                      return_stats=False):
+                      return_stats=False, bvh=None):
     """Depth maps of a mesh dict seen from T cameras in ONE launch (include/spann3r_hip.h "Mesh rays"; sp3_mesh_ray_views) -- what
     spann3r/tools/render_dtu.py:54-80 render_depth_maps obtains from pyrender: intrinsics [3, 3] or [T, 3, 3], cam2world [T, 4, 4] (or
     one [4, 4]), size = (h, w) -> dict(depth fp32 [T, h, w]: camera z of the first surface along the ray of every pixel, 0 where
@@ -631,7 +725,9 @@ def render_depth_maps(m, intrinsics, cam2world, size, near=0.0, far=math.inf, gr
     opengl=True: the poses are the ones render_dtu.py hands to pyrender -- camera looking down -z, y up: columns 1 and 2 negated --
     and that is undone here.  Both faces of the surface are seen.  grid: a TriangleGrid built on this mesh, to reuse it.  Skewed
     intrinsics and non-finite or singular poses are refused as fusion.camera_tables refuses them.  return_stats: also `stats` as
-    ray_mesh_intersect's (one 32-byte host read); otherwise nothing synchronises beyond the grid's build."""
+    ray_mesh_intersect's (one 32-byte host read); otherwise nothing synchronises beyond the grid's build.
+    bvh: a TriangleBVH built on this mesh, or True to build one: the rays walk the tree instead (sp3_mesh_bvh_ray_views), the same
+    maps bit for bit; `grid` must then be None, else ValueError."""
     from .fusion import _host_array, camera_tables
     h, w = (int(x) for x in size)
     if h < 1 or w < 1:
@@ -651,13 +747,18 @@ def render_depth_maps(m, intrinsics, cam2world, size, near=0.0, far=math.inf, gr
     fk, _ = camera_tables(intrinsics, P, T)                      # (the inverse is only computed for its checks)
     if not (fk[:, :2] != 0).all():
         raise ValueError("render_depth_maps: intrinsics with a zero focal length")
-    v, f, grid = _ray_grid(m, grid, "render_depth_maps")
+    bvh = _bvh_arg(bvh, m, grid, "grid", "render_depth_maps")
+    v, f, grid = (bvh.vertices, bvh.faces, None) if bvh is not None else _ray_grid(m, grid, "render_depth_maps")
     dev, lib = v.device, L.load()
     out = dict(depth=torch.empty((T, h, w), dtype=torch.float32, device=dev))
     if return_faces:
         out["face"] = torch.empty((T, h, w), dtype=torch.int32, device=dev)
         out["bary"] = torch.empty((T, h, w, 3), dtype=torch.float32, device=dev)
-    stats = dict(cells_visited=0, faces_evaluated=0, grid=tuple(grid.dims), h=grid.h, pairs=grid.pairs)
+    if bvh is not None:
+        stats = dict(cells_visited=0, faces_evaluated=0, grid=(1, 1, 1), h=None, pairs=0, nodes_visited=0, levels=bvh.levels,
+                     nodes=bvh.level_offsets[-1])
+    else:
+        stats = dict(cells_visited=0, faces_evaluated=0, grid=tuple(grid.dims), h=grid.h, pairs=grid.pairs)
     if T > 0:
         table = (L.MeshRayView * T)()
         for i in range(T):
@@ -671,11 +772,15 @@ def render_depth_maps(m, intrinsics, cam2world, size, near=0.0, far=math.inf, gr
             e.near, e.far = near, far
         table_d = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
         ws = _ws(lib.sp3_mesh_ray_ws_bytes(0), dev)
-        L.check(lib.sp3_mesh_ray_views(table, table_d.data_ptr(), T, pixel_offset, v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0],
-                                       L.ptr(grid.pair_face), grid.pairs, L.ptr(grid.cell_start), C.byref(grid.g), ws.data_ptr(),
-                                       L.stream_ptr()), "sp3_mesh_ray_views")
+        if bvh is not None:
+            L.check(lib.sp3_mesh_bvh_ray_views(table, table_d.data_ptr(), T, pixel_offset, L.ptr(v), v.shape[0], f.data_ptr(), f.shape[0],
+                                               *bvh.tree_args(), ws.data_ptr(), L.stream_ptr()), "sp3_mesh_bvh_ray_views")
+        else:
+            L.check(lib.sp3_mesh_ray_views(table, table_d.data_ptr(), T, pixel_offset, v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0],
+                                           L.ptr(grid.pair_face), grid.pairs, L.ptr(grid.cell_start), C.byref(grid.g), ws.data_ptr(),
+                                           L.stream_ptr()), "sp3_mesh_ray_views")
         if return_stats:
-            _, stats["cells_visited"], stats["faces_evaluated"] = G.read_head(ws)
+            _, stats["nodes_visited" if bvh is not None else "cells_visited"], stats["faces_evaluated"] = G.read_head(ws)
     if return_stats:
         out["stats"] = stats
     return out
