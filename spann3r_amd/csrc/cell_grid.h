@@ -1,6 +1,8 @@
 // The uniform cell grid of the exact searches, shared by csrc/eval.hip (nearest points: sp3_nn_query, sp3_knn_query) and
 // csrc/mesh_distance.hip (nearest faces: sp3_mesh_dist_query).  This is the one statement of the rule; include/spann3r_hip.h
-// (sp3_nn_grid) describes what the host hands in.  Everything here is per translation unit (anonymous namespace).
+// (sp3_nn_grid) describes what the host hands in.  Everything here is per translation unit (anonymous namespace).  The last section
+// holds what the query entry points of the three searches over faces (csrc/mesh_distance.hip, csrc/mesh_ray.hip, csrc/mesh_bvh.hip)
+// share whatever their structure: the workgroup size, the lane's query index, the size checks and the workspace head.
 //   * The items (points, or the (cell, face) references of triangles) are stored sorted by cell id (z * ny + y) * nx + x with a
 //     cell-start table, so the cells of one x-row are one contiguous range.
 //   * A query walks the cells around its (clamped) home cell by Chebyshev ring r = 0, 1, ...  After ring r every unvisited item
@@ -128,6 +130,42 @@ inline BruteLaunch size_brute(int64_t nq, int64_t items, int per_chunk, int tile
   l.chunks = (unsigned)((items + l.chunk - 1) / l.chunk);
   l.qblocks = (unsigned)((nq + 255) / 256 < 1024 ? (nq + 255) / 256 : 1024);
   return l;
+}
+
+// ---- what the entry points of the searches over faces (csrc/mesh_distance.hip, csrc/mesh_ray.hip, csrc/mesh_bvh.hip) share
+typedef unsigned long long u64;
+constexpr int TB = 256;                        // lanes per workgroup of every kernel of those files
+inline unsigned blocks_for(int64_t n) { return (unsigned)((n + TB - 1) / TB); }
+inline int64_t round4(int64_t n) { return (n + 3) / 4 * 4; }
+
+// The query lane i serves, for every one-lane-per-query kernel of the three files (the grid kernels took order[i] unchecked before
+// this rule was shared; they now have the range check the tree kernels always had): -1 for a lane past the end and for an entry of
+// `order` that is no query (nothing is read or written for it).
+__device__ __forceinline__ int64_t query_of(const int64_t* __restrict__ order, int64_t i, int64_t nq) {
+  if (i >= nq) return -1;
+  const int64_t qi = order ? order[i] : i;
+  return (uint64_t)qi < (uint64_t)nq ? qi : -1;
+}
+
+// vertex and face counts that travel as int32; the registration of faces in cells (sp3_mesh_tri_cell_count / _fill) takes an empty
+// face list, a query needs one face at least
+inline bool sizes_ok_or_empty(int64_t nverts, int64_t nfaces) { return nverts >= 0 && nverts < N_MAX && nfaces >= 0 && nfaces < N_MAX; }
+inline bool sizes_ok(int64_t nverts, int64_t nfaces) { return sizes_ok_or_empty(nverts, nfaces) && nfaces >= 1; }
+inline int check_mesh_sizes(const char* what, int64_t nverts, int64_t nfaces) {
+  SP3_CHECK(sizes_ok(nverts, nfaces), "%s: nverts %lld or nfaces %lld out of range (1 face at least; both below 2^31 - 1)", what, (long long)nverts,
+            (long long)nfaces);
+  return 0;
+}
+inline int check_query_args(const char* what, int64_t nverts, int64_t nfaces, int64_t nq) {
+  if (check_mesh_sizes(what, nverts, nfaces)) return 1;
+  SP3_CHECK(nq >= 0 && nq <= N_MAX, "%s: nq = %lld out of range", what, (long long)nq);
+  return 0;
+}
+// the last host step before the first launch of a query: the workspace's alignment, and its head zeroed.  -> 0, or the entry point's return value
+inline int begin_query(void* ws, hipStream_t st, const char* what) {
+  SP3_CHECK(((uintptr_t)ws & 15) == 0, "%s: the workspace must be 16-byte aligned", what);
+  if (hipMemsetAsync(ws, 0, sizeof(GridHead), st) != hipSuccess) { sp3_set_error("%s: hipMemsetAsync failed", what); return 2; }
+  return 0;
 }
 
 }  // namespace

@@ -17,18 +17,21 @@
 //   * A node is skipped when its bound says that no face below it can win or tie: the bound is tested when the node is pushed and
 //     again when it is popped (the best has usually improved in between), and children are taken nearest first.
 //   * Indices read from `order`, `faces` and `q_order` are range-checked before use; the stack never grows past the size the host gave it.
+//   * The kernels that serve rays are the two front ends of csrc/ray_kernels.h (which csrc/mesh_ray.hip instantiates with the grid's
+//     walk) with the TreeWalker of this file; the distance kernel stays here, since unlike the grid's it has no fallback.  The lane's
+//     query index (query_of), the size checks and the workspace head (begin_query) are csrc/cell_grid.h's; the checks of ray
+//     arguments and of the table of views are csrc/ray_kernels.h's.  Nothing here sweeps every face: the two order-free passes of
+//     the brute-force kernels live in csrc/face_sweep.h.
 #include "cell_grid.h"
+#include "ray_kernels.h"
 #include "tri_dist.h"
-#include "tri_ray.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int TB = 256;                        // lanes per workgroup of every kernel here (the view kernel: 16 x 16 pixels)
 constexpr int LEAF = 4;                        // faces per leaf node
 constexpr int ARITY = 4;                       // children per node
-constexpr int VIEW_TILE = 16;
 constexpr int MAX_LEVELS = SP3_BVH_MAX_LEVELS;
 
 constexpr int log2_of(int x) { return x <= 1 ? 0 : 1 + log2_of(x / 2); }
@@ -48,8 +51,6 @@ static_assert((31 - LEAF_BITS + ARITY_BITS - 1) / ARITY_BITS + 1 <= MAX_LEVELS, 
 static_assert(level_cap(MAX_LEVELS - 1) == 1, "the last level of the table can only be a root");
 static_assert(entries_fit(MAX_LEVELS - 1), "every level of the table has a marker bit above its indices");
 static_assert(entry_bits(MAX_LEVELS - 1, 0) != 0u && entry_bits(0, (int)(level_cap(0) - 1)) < (1u << TOP_BIT) * 2u, "an entry is a non-zero 32-bit word");
-
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + TB - 1) / TB); }
 
 // ------------------------------------------------------------------------------------------------ keys
 // 21 bits -> every third bit of 63
@@ -274,13 +275,6 @@ __device__ __forceinline__ int walk_ray(const Tree& t, const int* s_off, const s
   return bf;
 }
 
-// the query lane i serves; -1 for a lane past the end and for an entry of q_order that is no query (nothing is read or written for it)
-__device__ __forceinline__ int64_t query_of(const int64_t* __restrict__ qorder, int64_t i, int64_t nq) {
-  if (i >= nq) return -1;
-  const int64_t qi = qorder ? qorder[i] : i;
-  return (uint64_t)qi < (uint64_t)nq ? qi : -1;
-}
-
 // ---- one lane per query, in the order of the queries' own Morton keys: the lanes of a wave descend through the same nodes
 __global__ __launch_bounds__(TB) void k_bvh_dist(const float* __restrict__ q, const int64_t* __restrict__ qorder, int64_t nq, Tree t, sp3_mesh_bvh b,
                                                   int cap, float* __restrict__ dist, float* __restrict__ closest, int* __restrict__ face,
@@ -288,9 +282,8 @@ __global__ __launch_bounds__(TB) void k_bvh_dist(const float* __restrict__ q, co
   extern __shared__ unsigned s_stack[];
   __shared__ int s_off[MAX_LEVELS + 1];
   stage_levels(b, s_off);
-  const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
   int nodes = 0, evals = 0;
-  const int64_t qi = query_of(qorder, i, nq);
+  const int64_t qi = query_of(qorder, (int64_t)blockIdx.x * TB + threadIdx.x, nq);
   if (qi >= 0) {
     const float qx = q[3 * qi], qy = q[3 * qi + 1], qz = q[3 * qi + 2];
     const int bf = walk_dist(t, s_off, b, s_stack + threadIdx.x, cap, qx, qy, qz, nodes, evals);
@@ -299,51 +292,27 @@ __global__ __launch_bounds__(TB) void k_bvh_dist(const float* __restrict__ q, co
   head->count(nodes, evals);
 }
 
-__global__ __launch_bounds__(TB) void k_bvh_ray(const float* __restrict__ org, const float* __restrict__ dir, const int64_t* __restrict__ qorder,
-                                                 int64_t nq, Tree t, sp3_mesh_bvh b, int cap, double t_min, double t_max, int cull, RayOut out,
-                                                 GridHead* head) {
-  extern __shared__ unsigned s_stack[];
-  __shared__ int s_off[MAX_LEVELS + 1];
-  stage_levels(b, s_off);
-  const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
-  int nodes = 0, evals = 0;
-  const int64_t qi = query_of(qorder, i, nq);
-  if (qi >= 0) {
-    const float ox = org[3 * qi], oy = org[3 * qi + 1], oz = org[3 * qi + 2], dx = dir[3 * qi], dy = dir[3 * qi + 1], dz = dir[3 * qi + 2];
-    const Ray r = make_ray(ox, oy, oz, dx, dy, dz);
-    const int bf = r.ok ? walk_ray(t, s_off, b, s_stack + threadIdx.x, cap, r, ox, oy, oz, dx, dy, dz, t_min, t_max, cull, nodes, evals) : -1;
-    store(out, qi, result_of(t.verts, t.nverts, t.faces, t.nfaces, r, ox, oy, oz, dx, dy, dz, t_min, t_max, cull, bf));
+// ---- the Walker of csrc/ray_kernels.h: the nodes a ray's slab test passes.  prepare: the level table in static LDS, this lane's
+// column of the stack in the launch's dynamic LDS.
+struct TreeWalker {
+  Tree m;
+  sp3_mesh_bvh b;
+  int cap;
+  const int* s_off;
+  unsigned* stack;
+  __device__ __forceinline__ void prepare(unsigned* lds) {
+    __shared__ int off[MAX_LEVELS + 1];
+    stage_levels(b, off);
+    s_off = off;
+    stack = lds + threadIdx.x;
   }
-  head->count(nodes, evals);
-}
-
-// ---- T cameras in one launch: a lane owns a pixel, a wave an 8 x 8 tile, a workgroup 16 x 16 pixels of view blockIdx.z
-__global__ __launch_bounds__(TB) void k_bvh_views(const sp3_mesh_ray_view* __restrict__ views, float pixel_offset, Tree t, sp3_mesh_bvh b, int cap,
-                                                   GridHead* head) {
-  extern __shared__ unsigned s_stack[];
-  __shared__ int s_off[MAX_LEVELS + 1];
-  stage_levels(b, s_off);
-  const sp3_mesh_ray_view& vw = views[blockIdx.z];      // (wave-uniform: the descriptor fields arrive by scalar loads)
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int px = blockIdx.x * VIEW_TILE + (wave & 1) * 8 + (lane & 7);
-  const int py = blockIdx.y * VIEW_TILE + (wave >> 1) * 8 + (lane >> 3);
-  int nodes = 0, evals = 0;
-  if (px < vw.w && py < vw.h) {
-    float oo[3], dd[3];
-    pixel_ray(vw, px, py, pixel_offset, oo, dd);
-    const double t_min = (double)vw.near, t_max = (double)vw.far;
-    const Ray r = make_ray(oo[0], oo[1], oo[2], dd[0], dd[1], dd[2]);
-    const int bf = r.ok ? walk_ray(t, s_off, b, s_stack + threadIdx.x, cap, r, oo[0], oo[1], oo[2], dd[0], dd[1], dd[2], t_min, t_max, CULL_NONE,
-                                   nodes, evals)
-                        : -1;
-    store_pixel(vw, px, py, result_of(t.verts, t.nverts, t.faces, t.nfaces, r, oo[0], oo[1], oo[2], dd[0], dd[1], dd[2], t_min, t_max, CULL_NONE, bf));
+  __device__ __forceinline__ int walk(const Ray& r, float ox, float oy, float oz, float dx, float dy, float dz, double t_min, double t_max, int cull,
+                                      int& nodes, int& evals) const {
+    return walk_ray(m, s_off, b, stack, cap, r, ox, oy, oz, dx, dy, dz, t_min, t_max, cull, nodes, evals);
   }
-  head->count(nodes, evals);
-}
+};
 
 // ------------------------------------------------------------------------------------------------ host
-static_assert(TB == VIEW_TILE * VIEW_TILE, "one stack stride for every kernel");
-
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // the level table the host built (spann3r_amd/cell_grid.py bvh_levels) against the counts it must follow from
@@ -369,12 +338,13 @@ int check_tree(const sp3_mesh_bvh* b, int64_t nfaces, const char* what) {
   return 0;
 }
 
-inline bool sizes_ok(int64_t nverts, int64_t nfaces) { return nverts >= 0 && nverts < N_MAX && nfaces >= 1 && nfaces < N_MAX; }
 inline int stack_cap(int levels) { return (ARITY - 1) * (levels - 1) + 1; }
+inline size_t stack_bytes(int cap) { return (size_t)cap * TB * sizeof(unsigned); }
 inline Tree tree_of(const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, const int32_t* order, const float* node_lo,
                     const float* node_hi) {
   return {vertices, (const int*)faces, (const int*)order, node_lo, node_hi, (int)nverts, (int)nfaces};
 }
+inline TreeWalker walker_of(const Tree& t, const sp3_mesh_bvh* b) { return {t, *b, stack_cap(b->levels), nullptr, nullptr}; }
 
 }  // namespace
 
@@ -403,8 +373,7 @@ extern "C" int sp3_mesh_bvh_keys(const float* vertices, int64_t nverts, const in
 
 extern "C" int sp3_mesh_bvh_build(const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, const int32_t* order,
                                   const sp3_mesh_bvh* b, float* node_lo, float* node_hi, void* stream) {
-  SP3_CHECK(sizes_ok(nverts, nfaces), "sp3_mesh_bvh_build: nverts %lld or nfaces %lld out of range (1 face at least; both below 2^31 - 1)",
-            (long long)nverts, (long long)nfaces);
+  if (check_mesh_sizes("sp3_mesh_bvh_build", nverts, nfaces)) return 1;
   if (check_tree(b, nfaces, "sp3_mesh_bvh_build")) return 1;
   SP3_CHECK(faces && order && node_lo && node_hi && (nverts == 0 || vertices), "sp3_mesh_bvh_build: null pointer");
   hipStream_t st = (hipStream_t)stream;
@@ -422,19 +391,15 @@ extern "C" int sp3_mesh_bvh_build(const float* vertices, int64_t nverts, const i
 extern "C" int sp3_mesh_bvh_dist_query(const float* q, const int64_t* q_order, int64_t nq, const float* vertices, int64_t nverts,
                                        const int32_t* faces, int64_t nfaces, const int32_t* order, const float* node_lo, const float* node_hi,
                                        const sp3_mesh_bvh* b, void* ws, float* dist, float* closest, int32_t* face, uint8_t* region, void* stream) {
-  SP3_CHECK(sizes_ok(nverts, nfaces), "sp3_mesh_bvh_dist_query: nverts %lld or nfaces %lld out of range (1 face at least; both below 2^31 - 1)",
-            (long long)nverts, (long long)nfaces);
-  SP3_CHECK(nq >= 0 && nq <= N_MAX, "sp3_mesh_bvh_dist_query: nq = %lld out of range", (long long)nq);
-  if (check_tree(b, nfaces, "sp3_mesh_bvh_dist_query")) return 1;
+  if (check_query_args("sp3_mesh_bvh_dist_query", nverts, nfaces, nq) || check_tree(b, nfaces, "sp3_mesh_bvh_dist_query")) return 1;
   if (nq == 0) return 0;
   SP3_CHECK(q && faces && order && node_lo && node_hi && ws && dist && closest && face && region && (nverts == 0 || vertices),
             "sp3_mesh_bvh_dist_query: null pointer");
-  SP3_CHECK(((uintptr_t)ws & 15) == 0, "sp3_mesh_bvh_dist_query: the workspace must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(ws, 0, 32, st) != hipSuccess) { sp3_set_error("sp3_mesh_bvh_dist_query: hipMemsetAsync failed"); return 2; }
+  if (const int e = begin_query(ws, st, "sp3_mesh_bvh_dist_query")) return e;
   const int cap = stack_cap(b->levels);
-  k_bvh_dist<<<blocks_for(nq), TB, (size_t)cap * TB * sizeof(unsigned), st>>>(q, q_order, nq, tree_of(vertices, nverts, faces, nfaces, order, node_lo, node_hi),
-                                                                             *b, cap, dist, closest, (int*)face, region, (GridHead*)ws);
+  k_bvh_dist<<<blocks_for(nq), TB, stack_bytes(cap), st>>>(q, q_order, nq, tree_of(vertices, nverts, faces, nfaces, order, node_lo, node_hi), *b, cap,
+                                                          dist, closest, (int*)face, region, (GridHead*)ws);
   SP3_LAUNCH_CHECK("sp3_mesh_bvh_dist_query");
   return 0;
 }
@@ -443,23 +408,15 @@ extern "C" int sp3_mesh_bvh_ray_query(const float* origins, const float* directi
                                       int64_t nverts, const int32_t* faces, int64_t nfaces, const int32_t* order, const float* node_lo,
                                       const float* node_hi, const sp3_mesh_bvh* b, double t_min, double t_max, int cull, void* ws, float* t,
                                       int32_t* face, float* bary, float* point, uint8_t* side, void* stream) {
-  SP3_CHECK(sizes_ok(nverts, nfaces), "sp3_mesh_bvh_ray_query: nverts %lld or nfaces %lld out of range (1 face at least; both below 2^31 - 1)",
-            (long long)nverts, (long long)nfaces);
-  SP3_CHECK(nq >= 0 && nq <= N_MAX, "sp3_mesh_bvh_ray_query: nq = %lld out of range", (long long)nq);
-  SP3_CHECK(t_min >= 0.0 && t_min <= t_max, "sp3_mesh_bvh_ray_query: 0 <= t_min <= t_max, got %g and %g", t_min, t_max);
-  SP3_CHECK(cull >= CULL_NONE && cull <= CULL_FRONT, "sp3_mesh_bvh_ray_query: cull %d must be 0 (none), 1 (back) or 2 (front)", cull);
-  if (check_tree(b, nfaces, "sp3_mesh_bvh_ray_query")) return 1;
+  if (check_mesh_args("sp3_mesh_bvh_ray_query", nverts, nfaces, nq, t_min, t_max, cull) || check_tree(b, nfaces, "sp3_mesh_bvh_ray_query")) return 1;
   if (nq == 0) return 0;
   SP3_CHECK(origins && directions && faces && order && node_lo && node_hi && ws && t && face && bary && point && side && (nverts == 0 || vertices),
             "sp3_mesh_bvh_ray_query: null pointer");
-  SP3_CHECK(((uintptr_t)ws & 15) == 0, "sp3_mesh_bvh_ray_query: the workspace must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(ws, 0, 32, st) != hipSuccess) { sp3_set_error("sp3_mesh_bvh_ray_query: hipMemsetAsync failed"); return 2; }
-  const int cap = stack_cap(b->levels);
+  if (const int e = begin_query(ws, st, "sp3_mesh_bvh_ray_query")) return e;
+  const TreeWalker w = walker_of(tree_of(vertices, nverts, faces, nfaces, order, node_lo, node_hi), b);
   const RayOut out = {t, (int*)face, bary, point, side};
-  k_bvh_ray<<<blocks_for(nq), TB, (size_t)cap * TB * sizeof(unsigned), st>>>(origins, directions, q_order, nq,
-                                                                            tree_of(vertices, nverts, faces, nfaces, order, node_lo, node_hi), *b, cap,
-                                                                            t_min, t_max, cull, out, (GridHead*)ws);
+  k_ray_query<<<blocks_for(nq), TB, stack_bytes(w.cap), st>>>(origins, directions, q_order, nq, w, t_min, t_max, cull, out, (GridHead*)ws);
   SP3_LAUNCH_CHECK("sp3_mesh_bvh_ray_query");
   return 0;
 }
@@ -467,34 +424,17 @@ extern "C" int sp3_mesh_bvh_ray_query(const float* origins, const float* directi
 extern "C" int sp3_mesh_bvh_ray_views(const sp3_mesh_ray_view* views_host, const sp3_mesh_ray_view* views_dev, int T, float pixel_offset,
                                       const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, const int32_t* order,
                                       const float* node_lo, const float* node_hi, const sp3_mesh_bvh* b, void* ws, void* stream) {
-  SP3_CHECK(sizes_ok(nverts, nfaces), "sp3_mesh_bvh_ray_views: nverts %lld or nfaces %lld out of range (1 face at least; both below 2^31 - 1)",
-            (long long)nverts, (long long)nfaces);
-  SP3_CHECK(T >= 0 && T <= 65535, "sp3_mesh_bvh_ray_views: T %d must be in 0 .. 65535", T);
-  SP3_CHECK(isfinite(pixel_offset), "sp3_mesh_bvh_ray_views: pixel_offset is not finite");
-  if (check_tree(b, nfaces, "sp3_mesh_bvh_ray_views")) return 1;
+  if (check_mesh_sizes("sp3_mesh_bvh_ray_views", nverts, nfaces) || check_view_args("sp3_mesh_bvh_ray_views", T, pixel_offset) ||
+      check_tree(b, nfaces, "sp3_mesh_bvh_ray_views"))
+    return 1;
   if (T == 0) return 0;
   SP3_CHECK(views_host && views_dev && faces && order && node_lo && node_hi && ws && (nverts == 0 || vertices), "sp3_mesh_bvh_ray_views: null pointer");
-  SP3_CHECK(((uintptr_t)ws & 15) == 0, "sp3_mesh_bvh_ray_views: the workspace must be 16-byte aligned");
-  int wmax = 0, hmax = 0;
-  for (int i = 0; i < T; ++i) {
-    const sp3_mesh_ray_view& v = views_host[i];
-    SP3_CHECK(v.w >= 1 && v.h >= 1 && v.w <= (1 << 24) && v.h <= (1 << 24) && v.row_stride >= v.w && (int64_t)v.h * v.row_stride < N_MAX / 3,
-              "sp3_mesh_bvh_ray_views: view %d: bad geometry: %d x %d, row stride %lld", i, v.w, v.h, (long long)v.row_stride);
-    SP3_CHECK(v.depth != nullptr, "sp3_mesh_bvh_ray_views: view %d: null depth map", i);
-    SP3_CHECK(isfinite(v.fu) && isfinite(v.fv) && isfinite(v.cu) && isfinite(v.cv) && v.fu != 0.f && v.fv != 0.f,
-              "sp3_mesh_bvh_ray_views: view %d: intrinsics must be finite with non-zero focal lengths", i);
-    SP3_CHECK((double)v.near >= 0.0 && v.near <= v.far, "sp3_mesh_bvh_ray_views: view %d: 0 <= near <= far, got %g and %g", i, (double)v.near,
-              (double)v.far);
-    wmax = v.w > wmax ? v.w : wmax;
-    hmax = v.h > hmax ? v.h : hmax;
-  }
-  const dim3 grid((wmax + VIEW_TILE - 1) / VIEW_TILE, (hmax + VIEW_TILE - 1) / VIEW_TILE, T);
-  SP3_CHECK(grid.y <= 65535, "sp3_mesh_bvh_ray_views: %d rows of pixels are more than one launch covers", hmax);
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(ws, 0, 32, st) != hipSuccess) { sp3_set_error("sp3_mesh_bvh_ray_views: hipMemsetAsync failed"); return 2; }
-  const int cap = stack_cap(b->levels);
-  k_bvh_views<<<grid, TB, (size_t)cap * TB * sizeof(unsigned), st>>>(views_dev, pixel_offset, tree_of(vertices, nverts, faces, nfaces, order, node_lo, node_hi),
-                                                                    *b, cap, (GridHead*)ws);
+  if (const int e = begin_query(ws, st, "sp3_mesh_bvh_ray_views")) return e;
+  dim3 grid;
+  if (check_views("sp3_mesh_bvh_ray_views", views_host, T, grid)) return 1;
+  const TreeWalker w = walker_of(tree_of(vertices, nverts, faces, nfaces, order, node_lo, node_hi), b);
+  k_ray_views<<<grid, TB, stack_bytes(w.cap), st>>>(views_dev, pixel_offset, w, (GridHead*)ws);
   SP3_LAUNCH_CHECK("sp3_mesh_bvh_ray_views");
   return 0;
 }

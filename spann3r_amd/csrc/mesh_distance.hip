@@ -11,25 +11,19 @@
 //     csrc/cell_grid.h, which sp3_nn_query shares: a face that no cell of the visited block holds has, on one axis, every one of
 //     its cells beyond a wall of the block, so it lies wholly behind that wall and the wall's distance bounds it.
 //   * The hot loops keep (d2, face) only; the closest point and the region of the winner are recomputed once at the end.
-//   * The brute-force kernel stages faces through LDS in tiles (corners and the usability verdict, one lane per face), the face list
-//     split over workgroups.  (d2, face) does not fit one 64-bit atomic, so the join is two passes over the same tiles: an integer
-//     atomicMin over the bits of d2 (non-negative doubles order as their bits do), then an atomicMin of the face index among the faces
-//     that reach exactly that d2.  Both are order-free.
+//   * Brute force -- every query, or the ones the walk left open -- is the face sweep of csrc/face_sweep.h (LDS tiles, the two
+//     order-free passes, the workspace carving) with the rule "key = d2, every usable face counts"; the finish kernel here turns the
+//     winning face into the four outputs.
+//   * The lane's query index (query_of), the size checks and the workspace head (begin_query) are csrc/cell_grid.h's, shared with
+//     csrc/mesh_ray.hip and csrc/mesh_bvh.hip.
 //   * Every loop is bounded by max_ring, the grid dims, npairs or nfaces; nothing waits on another lane's store; what an atomic wrote
 //     is read by a LATER launch only.
-#include "cell_grid.h"
+#include "face_sweep.h"
 #include "tri_dist.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-typedef unsigned long long u64;
-
-constexpr int TB = 256;
-constexpr int TILE = 512;                      // faces per LDS tile of the brute-force kernel: 512 * 40 bytes
-
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + TB - 1) / TB); }
 
 // ------------------------------------------------------------------------------------------------ faces in the grid (csrc/cell_grid.h)
 // the cells [x0, x1] x [y0, y1] x [z0, z1] of the face's bounding box pushed out by the slack; cell_axis is monotone in x, so every
@@ -87,10 +81,9 @@ __global__ __launch_bounds__(TB) void k_md_grid(const float* __restrict__ q, con
                                                  int max_ring, float* __restrict__ dist, float* __restrict__ closest, int* __restrict__ face,
                                                  uint8_t* __restrict__ region, GridHead* head, u64* __restrict__ fb_key, int* __restrict__ fb_face,
                                                  int* __restrict__ fb_list) {
-  const int64_t t = (int64_t)blockIdx.x * TB + threadIdx.x;
   int cells = 0, evals = 0;
-  if (t < nq) {
-    const int64_t qi = order ? order[t] : t;
+  const int64_t qi = query_of(order, (int64_t)blockIdx.x * TB + threadIdx.x, nq);
+  if (qi >= 0) {
     const float qx = q[3 * qi], qy = q[3 * qi + 1], qz = q[3 * qi + 2];
     const double px = (double)qx, py = (double)qy, pz = (double)qz;
     double best = INFINITY;
@@ -117,67 +110,18 @@ __global__ __launch_bounds__(TB) void k_md_grid(const float* __restrict__ q, con
   head->count(cells, evals);
 }
 
-// ---- brute force: a workgroup holds 256 queries in registers and streams its chunk of the faces through LDS.
-// slots: the fallback list or every query (cell_grid.h Slots).
-// PASS 0: key[slot] = min over the usable faces of the bits of d2.  PASS 1: fkey[slot] = min face index with d2 == key[slot].
-template <int PASS>
-__global__ __launch_bounds__(TB) void k_md_brute(const float* __restrict__ q, Slots slots, const float* __restrict__ verts, int nverts,
-                                                  const int* __restrict__ faces, int64_t nfaces, int64_t chunk, u64* key, int* fkey) {
-  __shared__ float tv[TILE * 9];
-  __shared__ int tf[TILE];      // the face index, -1 for a face that is not usable
-  const int64_t nq = slots.size();
-  const int64_t r0 = (int64_t)blockIdx.y * chunk, r1 = min(r0 + chunk, nfaces);
-  for (int64_t qb = (int64_t)blockIdx.x * TB; qb < nq; qb += (int64_t)gridDim.x * TB) {
-    const int64_t slot = qb + threadIdx.x;
-    const int64_t qi = slot < nq ? slots.query(slot) : -1;
+// ---- brute force (csrc/face_sweep.h): the key of a face is its squared distance, and every usable face counts
+struct DistRule {
+  const float* __restrict__ q;
+  double px, py, pz;
+  __device__ __forceinline__ bool load(int64_t qi) {
     const bool active = qi >= 0;
-    const double px = active ? (double)q[3 * qi] : 0.0, py = active ? (double)q[3 * qi + 1] : 0.0, pz = active ? (double)q[3 * qi + 2] : 0.0;
-    const double target = (PASS == 1 && active) ? __longlong_as_double((long long)key[slot]) : 0.0;      // NaN (all ones): nothing equals it
-    double best = INFINITY;
-    int bf = NO_FACE;
-    for (int64_t t0 = r0; t0 < r1; t0 += TILE) {
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < TILE / TB; ++k) {
-        const int i = threadIdx.x + k * TB;
-        const int64_t f = t0 + i;
-        if (f < r1) {
-          float v[9];
-          const bool ok = load_face(verts, nverts, faces, f, v) && has_area(v);
-          tf[i] = ok ? (int)f : -1;
-          if (ok) {
-#pragma unroll
-            for (int c = 0; c < 9; ++c) tv[i * 9 + c] = v[c];
-          }
-        }
-      }
-      __syncthreads();
-      const int cnt = (int)min((int64_t)TILE, r1 - t0);
-      for (int j = 0; j < cnt; ++j) {
-        const int f = tf[j];      // the same address in every lane: an LDS broadcast, and a uniform branch
-        if (f < 0) continue;
-        const double d2 = dist2_to_face(px, py, pz, tv + j * 9);
-        if (PASS == 0) {
-          if (d2 < best) best = d2;
-        } else {
-          if (d2 == target && f < bf) bf = f;
-        }
-      }
-    }
-    if (active && r0 < r1) {
-      if (PASS == 0) {
-        if (best < INFINITY) atomicMin(&key[slot], (u64)__double_as_longlong(best));      // d2 >= 0: bit order = value order
-      } else {
-        if (bf != NO_FACE) atomicMin(&fkey[slot], bf);
-      }
-    }
+    px = active ? (double)q[3 * qi] : 0.0; py = active ? (double)q[3 * qi + 1] : 0.0; pz = active ? (double)q[3 * qi + 2] : 0.0;
+    return active;
   }
-}
-
-__global__ __launch_bounds__(TB) void k_md_fill_keys(u64* __restrict__ key, int* __restrict__ fkey, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
-  if (i < n) { key[i] = ~0ull; fkey[i] = NO_FACE; }
-}
+  template <typename Take>
+  __device__ __forceinline__ void eval(const float* v, Take take) const { take(dist2_to_face(px, py, pz, v)); }
+};
 
 __global__ __launch_bounds__(TB) void k_md_brute_finish(const float* __restrict__ q, Slots slots, const float* __restrict__ verts, int nverts,
                                                          const int* __restrict__ faces, int nfaces, const int* __restrict__ fkey,
@@ -191,27 +135,11 @@ __global__ __launch_bounds__(TB) void k_md_brute_finish(const float* __restrict_
   }
 }
 
-inline bool sizes_ok(int64_t nverts, int64_t nfaces) { return nverts >= 0 && nverts < N_MAX && nfaces >= 0 && nfaces < N_MAX; }
-
-struct Ws { GridHead* head; u64* key; int* fkey; int* list; };
-inline int64_t round4(int64_t n) { return (n + 3) / 4 * 4; }
-inline Ws carve(void* ws, int64_t nq) {
-  Ws w;
-  w.head = (GridHead*)ws;
-  w.key = (u64*)((char*)ws + 32);
-  w.fkey = (int*)((char*)ws + 32 + round4(nq) * 8);
-  w.list = w.fkey + round4(nq);
-  return w;
-}
-
-// the brute-force stage over the listed queries (list / count null: every query): two passes and the finish
+// the brute-force stage over the listed queries (list / count null: every query): the two passes and the finish
 void launch_brute(const float* q, const int* list, const int* count, int64_t nq, const float* verts, int nverts, const int* faces, int64_t nfaces,
-                  const Ws& w, float* dist, float* closest, int* face, uint8_t* region, hipStream_t st) {
+                  const SweepWs& w, float* dist, float* closest, int* face, uint8_t* region, hipStream_t st) {
   const Slots slots = {list, count, nq};
-  const BruteLaunch l = size_brute(nq, nfaces, 4096, TILE);
-  const dim3 grid(l.qblocks, l.chunks);
-  k_md_brute<0><<<grid, TB, 0, st>>>(q, slots, verts, nverts, faces, nfaces, l.chunk, w.key, w.fkey);
-  k_md_brute<1><<<grid, TB, 0, st>>>(q, slots, verts, nverts, faces, nfaces, l.chunk, w.key, w.fkey);
+  const BruteLaunch l = sweep_faces(DistRule{q}, slots, verts, nverts, faces, nfaces, w, st);
   k_md_brute_finish<<<l.qblocks, TB, 0, st>>>(q, slots, verts, nverts, faces, (int)nfaces, w.fkey, dist, closest, face, region);
 }
 
@@ -219,7 +147,7 @@ void launch_brute(const float* q, const int* list, const int* count, int64_t nq,
 
 extern "C" int sp3_mesh_tri_cell_count(const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, const sp3_nn_grid* g,
                                        int64_t* counts, void* stream) {
-  SP3_CHECK(sizes_ok(nverts, nfaces), "sp3_mesh_tri_cell_count: nverts %lld or nfaces %lld out of range (int32 indices: both below 2^31 - 1)",
+  SP3_CHECK(sizes_ok_or_empty(nverts, nfaces), "sp3_mesh_tri_cell_count: nverts %lld or nfaces %lld out of range (int32 indices: both below 2^31 - 1)",
             (long long)nverts, (long long)nfaces);
   if (check_grid(g, "sp3_mesh_tri_cell_count")) return 1;
   if (nfaces == 0) return 0;
@@ -232,7 +160,7 @@ extern "C" int sp3_mesh_tri_cell_count(const float* vertices, int64_t nverts, co
 
 extern "C" int sp3_mesh_tri_cell_fill(const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, const sp3_nn_grid* g,
                                       const int64_t* offsets, int64_t npairs, int32_t* pair_cell, int32_t* pair_face, void* stream) {
-  SP3_CHECK(sizes_ok(nverts, nfaces), "sp3_mesh_tri_cell_fill: nverts %lld or nfaces %lld out of range (int32 indices: both below 2^31 - 1)",
+  SP3_CHECK(sizes_ok_or_empty(nverts, nfaces), "sp3_mesh_tri_cell_fill: nverts %lld or nfaces %lld out of range (int32 indices: both below 2^31 - 1)",
             (long long)nverts, (long long)nfaces);
   SP3_CHECK(npairs >= 0 && npairs < N_MAX, "sp3_mesh_tri_cell_fill: npairs %lld out of range (0 .. 2^31 - 2)", (long long)npairs);
   if (check_grid(g, "sp3_mesh_tri_cell_fill")) return 1;
@@ -251,8 +179,7 @@ extern "C" int64_t sp3_mesh_dist_query_ws_bytes(int64_t nq) { return nq < 0 || n
 extern "C" int sp3_mesh_dist_query(const float* q, const int64_t* q_order, int64_t nq, const float* vertices, int64_t nverts, const int32_t* faces,
                                    int64_t nfaces, const int32_t* pair_face, int64_t npairs, const int32_t* cell_start, const sp3_nn_grid* g,
                                    int max_ring, void* ws, float* dist, float* closest, int32_t* face, uint8_t* region, void* stream) {
-  SP3_CHECK(sizes_ok(nverts, nfaces) && nfaces >= 1, "sp3_mesh_dist_query: nverts %lld or nfaces %lld out of range (1 face at least; both below 2^31 - 1)",
-            (long long)nverts, (long long)nfaces);
+  if (check_mesh_sizes("sp3_mesh_dist_query", nverts, nfaces)) return 1;
   SP3_CHECK(nq >= 0 && nq <= N_MAX && npairs >= 0 && npairs < N_MAX, "sp3_mesh_dist_query: nq = %lld or npairs = %lld out of range", (long long)nq,
             (long long)npairs);
   SP3_CHECK(max_ring >= 0, "sp3_mesh_dist_query: max_ring must be non-negative");
@@ -260,10 +187,9 @@ extern "C" int sp3_mesh_dist_query(const float* q, const int64_t* q_order, int64
   if (nq == 0) return 0;
   SP3_CHECK(q && faces && cell_start && ws && dist && closest && face && region && (nverts == 0 || vertices) && (npairs == 0 || pair_face),
             "sp3_mesh_dist_query: null pointer");
-  SP3_CHECK(((uintptr_t)ws & 15) == 0, "sp3_mesh_dist_query: the workspace must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  const Ws w = carve(ws, nq);
-  if (hipMemsetAsync(ws, 0, 32, st) != hipSuccess) { sp3_set_error("sp3_mesh_dist_query: hipMemsetAsync failed"); return 2; }
+  if (const int e = begin_query(ws, st, "sp3_mesh_dist_query")) return e;
+  const SweepWs w = carve(ws, nq);
   k_md_grid<<<blocks_for(nq), TB, 0, st>>>(q, q_order, nq, vertices, (int)nverts, (const int*)faces, (int)nfaces, (const int*)pair_face, (int)npairs,
                                            (const int*)cell_start, *g, max_ring, dist, closest, (int*)face, region, w.head, w.key, w.fkey, w.list);
   launch_brute(q, w.list, &w.head->fb_count, nq, vertices, (int)nverts, (const int*)faces, nfaces, w, dist, closest, (int*)face, region, st);
@@ -273,16 +199,13 @@ extern "C" int sp3_mesh_dist_query(const float* q, const int64_t* q_order, int64
 
 extern "C" int sp3_mesh_dist_brute(const float* q, int64_t nq, const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, void* ws,
                                    float* dist, float* closest, int32_t* face, uint8_t* region, void* stream) {
-  SP3_CHECK(sizes_ok(nverts, nfaces) && nfaces >= 1, "sp3_mesh_dist_brute: nverts %lld or nfaces %lld out of range (1 face at least; both below 2^31 - 1)",
-            (long long)nverts, (long long)nfaces);
-  SP3_CHECK(nq >= 0 && nq <= N_MAX, "sp3_mesh_dist_brute: nq = %lld out of range", (long long)nq);
+  if (check_query_args("sp3_mesh_dist_brute", nverts, nfaces, nq)) return 1;
   if (nq == 0) return 0;
   SP3_CHECK(q && faces && ws && dist && closest && face && region && (nverts == 0 || vertices), "sp3_mesh_dist_brute: null pointer");
-  SP3_CHECK(((uintptr_t)ws & 15) == 0, "sp3_mesh_dist_brute: the workspace must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  const Ws w = carve(ws, nq);
-  if (hipMemsetAsync(ws, 0, 32, st) != hipSuccess) { sp3_set_error("sp3_mesh_dist_brute: hipMemsetAsync failed"); return 2; }
-  k_md_fill_keys<<<blocks_for(nq), TB, 0, st>>>(w.key, w.fkey, nq);
+  if (const int e = begin_query(ws, st, "sp3_mesh_dist_brute")) return e;
+  const SweepWs w = carve(ws, nq);
+  k_fill_keys<<<blocks_for(nq), TB, 0, st>>>(w.key, w.fkey, nq);
   launch_brute(q, nullptr, nullptr, nq, vertices, (int)nverts, (const int*)faces, nfaces, w, dist, closest, (int*)face, region, st);
   SP3_LAUNCH_CHECK("sp3_mesh_dist_brute");
   return 0;

@@ -11,27 +11,20 @@
 //     The walk ends when the best t lies before the exit of the current cell less a margin, when it leaves the grid or passes t_max:
 //     at most nx + ny + nz cells, so there is no fallback list.  The header says why no hit is missed.
 //   * The hot loops keep (t, face) only; bary, point and side of the winner are recomputed once at the end.
-//   * The brute-force kernel stages faces through LDS in tiles, the face list split over workgroups, and joins by the two order-free
-//     passes of csrc/mesh_distance.hip: an integer atomicMin over the bits of the non-negative t, then an atomicMin of the face index
-//     among the faces with exactly that t.
-//   * sp3_mesh_ray_views makes its rays from a read-only table of cameras (a wave owns an 8 x 8 pixel tile of one view, blockIdx.z:
-//     the descriptor arrives by scalar loads) and runs the same walk.
+//   * Brute force is the face sweep of csrc/face_sweep.h (LDS tiles, the two order-free passes, the workspace carving) with the rule
+//     "key = t of the hit, a missed face does not count"; the finish kernel here turns the winning face into the five outputs.
+//   * The kernels that serve rays are the two front ends of csrc/ray_kernels.h -- one lane per given ray, and one lane per pixel of a
+//     read-only table of cameras (sp3_mesh_ray_views) -- instantiated with the walk of this file; csrc/mesh_bvh.hip instantiates
+//     them with the tree's.  The host checks of the ray entry points and of the table of views are that header's too; the size
+//     checks and the workspace head (begin_query) are csrc/cell_grid.h's.
 //   * Every loop is bounded by the grid dims, npairs or nfaces; nothing waits on another lane's store; what an atomic wrote is read
 //     by a LATER launch only.
-#include "cell_grid.h"
-#include "tri_ray.h"
+#include "face_sweep.h"
+#include "ray_kernels.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-typedef unsigned long long u64;
-
-constexpr int TB = 256;
-constexpr int TILE = 512;                      // faces per LDS tile of the brute-force kernel: 512 * 40 bytes
-constexpr int VIEW_TILE = 16;                  // a workgroup of sp3_mesh_ray_views: 16 x 16 pixels, four 8 x 8 wave tiles
-
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + TB - 1) / TB); }
 
 // ------------------------------------------------------------------------------------------------ the walk
 struct MeshRef {
@@ -112,85 +105,38 @@ __device__ __forceinline__ int scan_all(const MeshRef& m, const Ray& r, double t
   return bf;
 }
 
-// ---- one lane per ray (rays sorted by the cell of their origin: the lanes of a wave start in the same cells)
-__global__ __launch_bounds__(TB) void k_mr_grid(const float* __restrict__ org, const float* __restrict__ dir, const int64_t* __restrict__ order,
-                                                 int64_t nq, MeshRef m, sp3_nn_grid g, double t_min, double t_max, int cull, RayOut out,
-                                                 GridHead* head) {
-  const int64_t t = (int64_t)blockIdx.x * TB + threadIdx.x;
-  int cells = 0, evals = 0;
-  if (t < nq) {
-    const int64_t qi = order ? order[t] : t;
-    const float ox = org[3 * qi], oy = org[3 * qi + 1], oz = org[3 * qi + 2], dx = dir[3 * qi], dy = dir[3 * qi + 1], dz = dir[3 * qi + 2];
-    const Ray r = make_ray(ox, oy, oz, dx, dy, dz);
-    const int bf = r.ok ? walk_ray(g, m, r, ox, oy, oz, dx, dy, dz, t_min, t_max, cull, cells, evals) : -1;
-    store(out, qi, result_of(m.verts, m.nverts, m.faces, m.nfaces, r, ox, oy, oz, dx, dy, dz, t_min, t_max, cull, bf));
+// ---- the Walker of csrc/ray_kernels.h: the cells along the ray.  VIEWS: a grid of one cell holds no references (sp3_mesh_ray_views
+// takes one; sp3_mesh_ray_query refuses it) and every face is scanned instead.  Nothing to prepare, no LDS.
+template <bool VIEWS>
+struct GridWalker {
+  MeshRef m;
+  sp3_nn_grid g;
+  __device__ __forceinline__ void prepare(unsigned*) {}
+  __device__ __forceinline__ int walk(const Ray& r, float ox, float oy, float oz, float dx, float dy, float dz, double t_min, double t_max, int cull,
+                                      int& cells, int& evals) const {
+    if (VIEWS && m.npairs <= 0) return scan_all(m, r, t_min, t_max, cull, evals);
+    return walk_ray(g, m, r, ox, oy, oz, dx, dy, dz, t_min, t_max, cull, cells, evals);
   }
-  head->count(cells, evals);
-}
+};
 
-// ---- brute force: a workgroup holds 256 rays in registers and streams its chunk of the faces through LDS.
-// PASS 0: key[slot] = min over the hits of the bits of t.  PASS 1: fkey[slot] = min face index with t == key[slot].
-template <int PASS>
-__global__ __launch_bounds__(TB) void k_mr_brute(const float* __restrict__ org, const float* __restrict__ dir, Slots slots,
-                                                  const float* __restrict__ verts, int nverts, const int* __restrict__ faces, int64_t nfaces,
-                                                  int64_t chunk, double t_min, double t_max, int cull, u64* key, int* fkey) {
-  __shared__ float tv[TILE * 9];
-  __shared__ int tf[TILE];      // the face index, -1 for a face that is not usable
-  const int64_t nq = slots.size();
-  const int64_t r0 = (int64_t)blockIdx.y * chunk, r1 = min(r0 + chunk, nfaces);
-  for (int64_t qb = (int64_t)blockIdx.x * TB; qb < nq; qb += (int64_t)gridDim.x * TB) {
-    const int64_t slot = qb + threadIdx.x;
-    const int64_t qi = slot < nq ? slots.query(slot) : -1;
-    Ray r = make_ray(0.f, 0.f, 0.f, 0.f, 0.f, 1.f);
+// ---- brute force (csrc/face_sweep.h): the key of a face is the t of its hit, and a face the ray misses does not count
+struct RayRule {
+  const float* __restrict__ org;
+  const float* __restrict__ dir;
+  double t_min, t_max;
+  int cull;
+  Ray r;
+  __device__ __forceinline__ bool load(int64_t qi) {
+    r = make_ray(0.f, 0.f, 0.f, 0.f, 0.f, 1.f);
     if (qi >= 0) r = make_ray(org[3 * qi], org[3 * qi + 1], org[3 * qi + 2], dir[3 * qi], dir[3 * qi + 1], dir[3 * qi + 2]);
-    const bool active = qi >= 0 && r.ok;
-    const double target = (PASS == 1 && active) ? __longlong_as_double((long long)key[slot]) : 0.0;      // NaN (all ones): nothing equals it
-    double best = INFINITY;
-    int bf = NO_FACE;
-    for (int64_t t0 = r0; t0 < r1; t0 += TILE) {
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < TILE / TB; ++k) {
-        const int i = threadIdx.x + k * TB;
-        const int64_t f = t0 + i;
-        if (f < r1) {
-          float v[9];
-          const bool ok = load_face(verts, nverts, faces, f, v) && has_area(v);
-          tf[i] = ok ? (int)f : -1;
-          if (ok) {
-#pragma unroll
-            for (int c = 0; c < 9; ++c) tv[i * 9 + c] = v[c];
-          }
-        }
-      }
-      __syncthreads();
-      const int cnt = (int)min((int64_t)TILE, r1 - t0);
-      for (int j = 0; j < cnt; ++j) {
-        const int f = tf[j];      // the same address in every lane: an LDS broadcast, and a uniform branch
-        if (f < 0) continue;
-        Hit h;
-        if (!intersect(r, tv + j * 9, t_min, t_max, cull, h)) continue;
-        if (PASS == 0) {
-          if (h.t < best) best = h.t;
-        } else {
-          if (h.t == target && f < bf) bf = f;
-        }
-      }
-    }
-    if (active && r0 < r1) {
-      if (PASS == 0) {
-        if (best < INFINITY) atomicMin(&key[slot], (u64)__double_as_longlong(best));      // t >= +0: bit order = value order
-      } else {
-        if (bf != NO_FACE) atomicMin(&fkey[slot], bf);
-      }
-    }
+    return qi >= 0 && r.ok;
   }
-}
-
-__global__ __launch_bounds__(TB) void k_mr_fill_keys(u64* __restrict__ key, int* __restrict__ fkey, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
-  if (i < n) { key[i] = ~0ull; fkey[i] = NO_FACE; }
-}
+  template <typename Take>
+  __device__ __forceinline__ void eval(const float* v, Take take) const {
+    Hit h;
+    if (intersect(r, v, t_min, t_max, cull, h)) take(h.t);
+  }
+};
 
 __global__ __launch_bounds__(TB) void k_mr_brute_finish(const float* __restrict__ org, const float* __restrict__ dir, int64_t nq,
                                                          const float* __restrict__ verts, int nverts, const int* __restrict__ faces, int nfaces,
@@ -202,40 +148,9 @@ __global__ __launch_bounds__(TB) void k_mr_brute_finish(const float* __restrict_
   }
 }
 
-// ---- T cameras in one launch: a lane owns a pixel, a wave an 8 x 8 tile, a workgroup 16 x 16 pixels of view blockIdx.z
-__global__ __launch_bounds__(VIEW_TILE * VIEW_TILE) void k_mr_views(const sp3_mesh_ray_view* __restrict__ views, float pixel_offset, MeshRef m,
-                                                                    sp3_nn_grid g, GridHead* head) {
-  const sp3_mesh_ray_view& vw = views[blockIdx.z];      // (wave-uniform: the descriptor fields arrive by scalar loads)
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int px = blockIdx.x * VIEW_TILE + (wave & 1) * 8 + (lane & 7);
-  const int py = blockIdx.y * VIEW_TILE + (wave >> 1) * 8 + (lane >> 3);
-  int cells = 0, evals = 0;
-  if (px < vw.w && py < vw.h) {
-    float oo[3], dd[3];
-    pixel_ray(vw, px, py, pixel_offset, oo, dd);
-    const float ox = oo[0], oy = oo[1], oz = oo[2];
-    const double t_min = (double)vw.near, t_max = (double)vw.far;
-    const Ray r = make_ray(ox, oy, oz, dd[0], dd[1], dd[2]);
-    int bf = -1;
-    if (r.ok) bf = m.npairs > 0 ? walk_ray(g, m, r, ox, oy, oz, dd[0], dd[1], dd[2], t_min, t_max, CULL_NONE, cells, evals)
-                                : scan_all(m, r, t_min, t_max, CULL_NONE, evals);
-    const Result o = result_of(m.verts, m.nverts, m.faces, m.nfaces, r, ox, oy, oz, dd[0], dd[1], dd[2], t_min, t_max, CULL_NONE, bf);
-    store_pixel(vw, px, py, o);
-  }
-  head->count(cells, evals);
-}
-
-inline bool sizes_ok(int64_t nverts, int64_t nfaces) { return nverts >= 0 && nverts < N_MAX && nfaces >= 1 && nfaces < N_MAX; }
-inline bool range_ok(double t_min, double t_max) { return t_min >= 0.0 && t_min <= t_max; }      // (false for a NaN)
-inline int64_t round4(int64_t n) { return (n + 3) / 4 * 4; }
-
-int check_mesh_args(const char* what, int64_t nverts, int64_t nfaces, int64_t nq, double t_min, double t_max, int cull) {
-  SP3_CHECK(sizes_ok(nverts, nfaces), "%s: nverts %lld or nfaces %lld out of range (1 face at least; both below 2^31 - 1)", what, (long long)nverts,
-            (long long)nfaces);
-  SP3_CHECK(nq >= 0 && nq <= N_MAX, "%s: nq = %lld out of range", what, (long long)nq);
-  SP3_CHECK(range_ok(t_min, t_max), "%s: 0 <= t_min <= t_max, got %g and %g", what, t_min, t_max);
-  SP3_CHECK(cull >= CULL_NONE && cull <= CULL_FRONT, "%s: cull %d must be 0 (none), 1 (back) or 2 (front)", what, cull);
-  return 0;
+inline MeshRef mesh_ref(const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, const int32_t* pair_face, int64_t npairs,
+                        const int32_t* cell_start) {
+  return {vertices, (const int*)faces, (const int*)pair_face, (const int*)cell_start, (int)nverts, (int)nfaces, (int)npairs};
 }
 
 }  // namespace
@@ -253,12 +168,11 @@ extern "C" int sp3_mesh_ray_query(const float* origins, const float* directions,
   if (nq == 0) return 0;
   SP3_CHECK(origins && directions && faces && pair_face && cell_start && ws && t && face && bary && point && side && (nverts == 0 || vertices),
             "sp3_mesh_ray_query: null pointer");
-  SP3_CHECK(((uintptr_t)ws & 15) == 0, "sp3_mesh_ray_query: the workspace must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(ws, 0, 32, st) != hipSuccess) { sp3_set_error("sp3_mesh_ray_query: hipMemsetAsync failed"); return 2; }
-  const MeshRef m = {vertices, (const int*)faces, (const int*)pair_face, (const int*)cell_start, (int)nverts, (int)nfaces, (int)npairs};
+  if (const int e = begin_query(ws, st, "sp3_mesh_ray_query")) return e;
+  const GridWalker<false> w = {mesh_ref(vertices, nverts, faces, nfaces, pair_face, npairs, cell_start), *g};
   const RayOut out = {t, (int*)face, bary, point, side};
-  k_mr_grid<<<blocks_for(nq), TB, 0, st>>>(origins, directions, q_order, nq, m, *g, t_min, t_max, cull, out, (GridHead*)ws);
+  k_ray_query<<<blocks_for(nq), TB, 0, st>>>(origins, directions, q_order, nq, w, t_min, t_max, cull, out, (GridHead*)ws);
   SP3_LAUNCH_CHECK("sp3_mesh_ray_query");
   return 0;
 }
@@ -270,20 +184,15 @@ extern "C" int sp3_mesh_ray_brute(const float* origins, const float* directions,
   if (nq == 0) return 0;
   SP3_CHECK(origins && directions && faces && ws && t && face && bary && point && side && (nverts == 0 || vertices),
             "sp3_mesh_ray_brute: null pointer");
-  SP3_CHECK(((uintptr_t)ws & 15) == 0, "sp3_mesh_ray_brute: the workspace must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(ws, 0, 32, st) != hipSuccess) { sp3_set_error("sp3_mesh_ray_brute: hipMemsetAsync failed"); return 2; }
-  u64* key = (u64*)((char*)ws + 32);
-  int* fkey = (int*)((char*)ws + 32 + round4(nq) * 8);
-  const Slots slots = {nullptr, nullptr, nq};
-  const BruteLaunch l = size_brute(nq, nfaces, 4096, TILE);
-  const dim3 grid(l.qblocks, l.chunks);
+  if (const int e = begin_query(ws, st, "sp3_mesh_ray_brute")) return e;
+  const SweepWs w = carve(ws, nq);      // (key and fkey; no fallback list)
   const RayOut out = {t, (int*)face, bary, point, side};
-  k_mr_fill_keys<<<blocks_for(nq), TB, 0, st>>>(key, fkey, nq);
-  k_mr_brute<0><<<grid, TB, 0, st>>>(origins, directions, slots, vertices, (int)nverts, (const int*)faces, nfaces, l.chunk, t_min, t_max, cull, key, fkey);
-  k_mr_brute<1><<<grid, TB, 0, st>>>(origins, directions, slots, vertices, (int)nverts, (const int*)faces, nfaces, l.chunk, t_min, t_max, cull, key, fkey);
+  k_fill_keys<<<blocks_for(nq), TB, 0, st>>>(w.key, w.fkey, nq);
+  const RayRule rule = {origins, directions, t_min, t_max, cull};
+  const BruteLaunch l = sweep_faces(rule, Slots{nullptr, nullptr, nq}, vertices, (int)nverts, (const int*)faces, nfaces, w, st);
   k_mr_brute_finish<<<l.qblocks, TB, 0, st>>>(origins, directions, nq, vertices, (int)nverts, (const int*)faces, (int)nfaces, t_min, t_max, cull,
-                                              fkey, out);
+                                              w.fkey, out);
   SP3_LAUNCH_CHECK("sp3_mesh_ray_brute");
   return 0;
 }
@@ -291,35 +200,18 @@ extern "C" int sp3_mesh_ray_brute(const float* origins, const float* directions,
 extern "C" int sp3_mesh_ray_views(const sp3_mesh_ray_view* views_host, const sp3_mesh_ray_view* views_dev, int T, float pixel_offset,
                                   const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, const int32_t* pair_face,
                                   int64_t npairs, const int32_t* cell_start, const sp3_nn_grid* g, void* ws, void* stream) {
-  SP3_CHECK(sizes_ok(nverts, nfaces), "sp3_mesh_ray_views: nverts %lld or nfaces %lld out of range (1 face at least; both below 2^31 - 1)",
-            (long long)nverts, (long long)nfaces);
+  if (check_mesh_sizes("sp3_mesh_ray_views", nverts, nfaces)) return 1;
   SP3_CHECK(npairs >= 0 && npairs < N_MAX, "sp3_mesh_ray_views: npairs = %lld out of range", (long long)npairs);
-  SP3_CHECK(T >= 0 && T <= 65535, "sp3_mesh_ray_views: T %d must be in 0 .. 65535", T);
-  SP3_CHECK(isfinite(pixel_offset), "sp3_mesh_ray_views: pixel_offset is not finite");
-  if (check_grid(g, "sp3_mesh_ray_views")) return 1;
+  if (check_view_args("sp3_mesh_ray_views", T, pixel_offset) || check_grid(g, "sp3_mesh_ray_views")) return 1;
   if (T == 0) return 0;
   SP3_CHECK(views_host && views_dev && faces && ws && (nverts == 0 || vertices) && (npairs == 0 || (pair_face && cell_start)),
             "sp3_mesh_ray_views: null pointer");
-  SP3_CHECK(((uintptr_t)ws & 15) == 0, "sp3_mesh_ray_views: the workspace must be 16-byte aligned");
-  int wmax = 0, hmax = 0;
-  for (int i = 0; i < T; ++i) {
-    const sp3_mesh_ray_view& v = views_host[i];
-    SP3_CHECK(v.w >= 1 && v.h >= 1 && v.w <= (1 << 24) && v.h <= (1 << 24) && v.row_stride >= v.w && (int64_t)v.h * v.row_stride < N_MAX / 3,
-              "sp3_mesh_ray_views: view %d: bad geometry: %d x %d, row stride %lld", i, v.w, v.h, (long long)v.row_stride);
-    SP3_CHECK(v.depth != nullptr, "sp3_mesh_ray_views: view %d: null depth map", i);
-    SP3_CHECK(isfinite(v.fu) && isfinite(v.fv) && isfinite(v.cu) && isfinite(v.cv) && v.fu != 0.f && v.fv != 0.f,
-              "sp3_mesh_ray_views: view %d: intrinsics must be finite with non-zero focal lengths", i);
-    SP3_CHECK(range_ok((double)v.near, (double)v.far), "sp3_mesh_ray_views: view %d: 0 <= near <= far, got %g and %g", i, (double)v.near,
-              (double)v.far);
-    wmax = v.w > wmax ? v.w : wmax;
-    hmax = v.h > hmax ? v.h : hmax;
-  }
-  const dim3 grid((wmax + VIEW_TILE - 1) / VIEW_TILE, (hmax + VIEW_TILE - 1) / VIEW_TILE, T);
-  SP3_CHECK(grid.y <= 65535, "sp3_mesh_ray_views: %d rows of pixels are more than one launch covers", hmax);
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(ws, 0, 32, st) != hipSuccess) { sp3_set_error("sp3_mesh_ray_views: hipMemsetAsync failed"); return 2; }
-  const MeshRef m = {vertices, (const int*)faces, (const int*)pair_face, (const int*)cell_start, (int)nverts, (int)nfaces, (int)npairs};
-  k_mr_views<<<grid, VIEW_TILE * VIEW_TILE, 0, st>>>(views_dev, pixel_offset, m, *g, (GridHead*)ws);
+  if (const int e = begin_query(ws, st, "sp3_mesh_ray_views")) return e;
+  dim3 grid;
+  if (check_views("sp3_mesh_ray_views", views_host, T, grid)) return 1;
+  const GridWalker<true> w = {mesh_ref(vertices, nverts, faces, nfaces, pair_face, npairs, cell_start), *g};
+  k_ray_views<<<grid, TB, 0, st>>>(views_dev, pixel_offset, w, (GridHead*)ws);
   SP3_LAUNCH_CHECK("sp3_mesh_ray_views");
   return 0;
 }

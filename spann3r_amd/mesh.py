@@ -444,6 +444,66 @@ def _tri_cell_counts(lib, vertices, faces, g):
     return counts
 
 
+def _usable_faces(lib, v, f, what, tail, count=None):
+    """the number of usable faces of a mesh -- `count`, or one per face registered in a grid of one cell (one 8-byte host read) --
+    or the ValueError of a mesh that has none"""
+    if count is None:
+        count = int(_tri_cell_counts(lib, v, f, G.one_cell()).sum().item()) if f.shape[0] else 0
+    if count == 0:
+        raise ValueError("%s: %d faces over %d vertices, none valid, finite and with an area: %s" % (what, f.shape[0], v.shape[0], tail))
+    return count
+
+
+def _finite_vertex_box(v):
+    """the box of the finite coordinates of v [V, 3] -> float64 numpy [2, 3] (one 48-byte host read); zeros without vertices"""
+    if v.shape[0] == 0:
+        return np.zeros((2, 3))
+    fin = torch.isfinite(v)
+    inf = torch.tensor(math.inf, device=v.device)
+    return G.finite_box(torch.where(fin, v, inf).amin(0), torch.where(fin, v, -inf).amax(0))
+
+
+def _ptrs(out, *keys):
+    return tuple(out[k].data_ptr() for k in keys)
+
+
+def _mesh_args(a):
+    """(vertices, nverts, faces, nfaces) of a structure as the query entry points take them"""
+    return L.ptr(a.vertices), a.vertices.shape[0], a.faces.data_ptr(), a.faces.shape[0]
+
+
+_DIST_OUT = ("dist", "closest", "face", "region")
+_RAY_OUT = ("t", "face", "bary", "point", "side")
+
+# What a query asks a mesh through -- TriangleGrid, TriangleBVH, _AllFaces -- has one surface: vertices, faces, query_order(q),
+# dist_query(q, out, ring_budget) and ray_query(o, d, t_min, t_max, cull, out) for n >= 1 queries, ray_views(table, table_d, T,
+# pixel_offset) for T >= 1 views, stats() (what the structure reports of itself) and read_stats(ws) (what a call counted: the one
+# 32-byte host read).  Every method owns its workspace and its one library call, and returns the workspace -- or None when the
+# call counted nothing worth reading (the brute-force kernels).
+
+
+class _AllFaces:
+    """method="brute": every query against every face (sp3_mesh_dist_brute / sp3_mesh_ray_brute), also what a TriangleGrid of one
+    cell answers point and ray queries with.  grid: the TriangleGrid whose dims, h and pairs stats() reports, if there is one."""
+
+    def __init__(self, vertices, faces, grid=None):
+        self.vertices, self.faces, self.grid = vertices, faces, grid
+
+    def stats(self):
+        return dict(grid=(1, 1, 1), h=None, pairs=0) if self.grid is None else self.grid.stats()
+
+    def dist_query(self, q, out, ring_budget=None):
+        lib, n = L.load(), q.shape[0]
+        ws = _ws(lib.sp3_mesh_dist_query_ws_bytes(n), q.device)
+        L.check(lib.sp3_mesh_dist_brute(q.data_ptr(), n, *_mesh_args(self), ws.data_ptr(), *_ptrs(out, *_DIST_OUT), L.stream_ptr()), "sp3_mesh_dist_brute")
+
+    def ray_query(self, o, d, t_min, t_max, cull, out):
+        lib, n = L.load(), o.shape[0]
+        ws = _ws(lib.sp3_mesh_ray_ws_bytes(n), o.device)
+        L.check(lib.sp3_mesh_ray_brute(o.data_ptr(), d.data_ptr(), n, *_mesh_args(self), t_min, t_max, cull, ws.data_ptr(), *_ptrs(out, *_RAY_OUT),
+                                       L.stream_ptr()), "sp3_mesh_ray_brute")
+
+
 class TriangleGrid(G.Grid):
     """The faces of a mesh dict registered in a cell grid (include/spann3r_hip.h "Mesh distance"): built once, reused for any number
     of query sets by point_mesh_distance.  The cell edge starts from cell_grid.choose_grid on the box of the finite vertices with the
@@ -458,13 +518,8 @@ class TriangleGrid(G.Grid):
         self.vertices, _, self.faces = _check_mesh(m, "TriangleGrid")
         v, f = self.vertices, self.faces
         nf, dev = f.shape[0], v.device
-        self.usable = int(_tri_cell_counts(lib, v, f, G.one_cell()).sum().item()) if nf else 0      # one cell: 1 per usable face
-        if self.usable == 0:
-            raise ValueError("TriangleGrid: %d faces over %d vertices, none valid, finite and with an area: no surface to measure against" %
-                             (nf, v.shape[0]))
-        fin = torch.isfinite(v)
-        inf = torch.tensor(math.inf, device=dev)
-        box = G.finite_box(torch.where(fin, v, inf).amin(0), torch.where(fin, v, -inf).amax(0))
+        self.usable = _usable_faces(lib, v, f, "TriangleGrid", "no surface to measure against")
+        box = _finite_vertex_box(v)
         ext = box[1] - box[0]
         if h is None:
             h, dims = G.choose_grid(box[0], box[1], self.usable, occupancy=FACES_PER_CELL)
@@ -493,6 +548,41 @@ class TriangleGrid(G.Grid):
             order, self.cell_start = G.cell_table(cell, dims[0] * dims[1] * dims[2])
             self.pair_face = face[order].contiguous()
 
+    def stats(self):
+        return dict(grid=tuple(self.dims), h=self.h, pairs=self.pairs)
+
+    def read_stats(self, ws):
+        return dict(zip(("fallback_queries", "cells_visited", "faces_evaluated"), G.read_head(ws)))
+
+    def _grid_args(self):
+        return L.ptr(self.pair_face), self.pairs, L.ptr(self.cell_start), C.byref(self.g)
+
+    def dist_query(self, q, out, ring_budget=DIST_RING_BUDGET):
+        if self.pairs == 0:
+            return _AllFaces(self.vertices, self.faces, self).dist_query(q, out)
+        lib, n = L.load(), q.shape[0]
+        ws = _ws(lib.sp3_mesh_dist_query_ws_bytes(n), q.device)
+        L.check(lib.sp3_mesh_dist_query(q.data_ptr(), self.query_order(q).data_ptr(), n, *_mesh_args(self), *self._grid_args(), int(ring_budget),
+                                        ws.data_ptr(), *_ptrs(out, *_DIST_OUT), L.stream_ptr()), "sp3_mesh_dist_query")
+        return ws
+
+    def ray_query(self, o, d, t_min, t_max, cull, out):
+        if self.pairs == 0:
+            return _AllFaces(self.vertices, self.faces, self).ray_query(o, d, t_min, t_max, cull, out)
+        lib, n = L.load(), o.shape[0]
+        ws = _ws(lib.sp3_mesh_ray_ws_bytes(n), o.device)
+        L.check(lib.sp3_mesh_ray_query(o.data_ptr(), d.data_ptr(), self.query_order(o).data_ptr(), n, *_mesh_args(self), *self._grid_args(), t_min,
+                                       t_max, cull, ws.data_ptr(), *_ptrs(out, *_RAY_OUT), L.stream_ptr()), "sp3_mesh_ray_query")
+        return ws
+
+    def ray_views(self, table, table_d, T, pixel_offset):
+        """(a grid of one cell goes to sp3_mesh_ray_views too: its kernel then scans every face)"""
+        lib = L.load()
+        ws = _ws(lib.sp3_mesh_ray_ws_bytes(0), table_d.device)
+        L.check(lib.sp3_mesh_ray_views(table, table_d.data_ptr(), T, pixel_offset, *_mesh_args(self), *self._grid_args(), ws.data_ptr(),
+                                       L.stream_ptr()), "sp3_mesh_ray_views")
+        return ws
+
 
 _KEY_NONE = 2 ** 63 - 1          # sp3_mesh_bvh_keys: an item that is not usable
 
@@ -513,15 +603,11 @@ class TriangleBVH:
         self.vertices, _, self.faces = _check_mesh(m, "TriangleBVH")
         v, f = self.vertices, self.faces
         nf, dev = f.shape[0], v.device
-        fin = torch.isfinite(v)
-        inf = torch.tensor(math.inf, device=dev)
-        box = G.finite_box(torch.where(fin, v, inf).amin(0), torch.where(fin, v, -inf).amax(0)) if v.shape[0] else np.zeros((2, 3))
+        box = _finite_vertex_box(v)
         self._box = (C.c_float * 6)(*box.astype(np.float32).reshape(6).tolist())      # (fp32 vertices: their box is exact in fp32)
         keys = self._keys(lib, v, f, nf) if nf else None
-        self.usable = int((keys != _KEY_NONE).sum().item()) if nf else 0
-        if self.usable == 0:
-            raise ValueError("TriangleBVH: %d faces over %d vertices, none valid, finite and with an area: no surface to measure against" %
-                             (nf, v.shape[0]))
+        self.usable = _usable_faces(lib, v, f, "TriangleBVH", "no surface to measure against",
+                                    count=int((keys != _KEY_NONE).sum().item()) if nf else 0)
         self.order = torch.sort(keys, stable=True)[1][:self.usable].to(torch.int32)
         self.b, self.level_sizes, self.level_offsets = G.make_bvh(box, self.usable)
         self.levels, self.slack = self.b.levels, float(self.b.slack)
@@ -545,19 +631,54 @@ class TriangleBVH:
         """(order, node_lo, node_hi, descriptor) as the query entry points take them"""
         return self.order.data_ptr(), self.node_lo.data_ptr(), self.node_hi.data_ptr(), C.byref(self.b)
 
+    def stats(self):
+        return dict(grid=(1, 1, 1), h=None, pairs=0, nodes_visited=0, levels=self.levels, nodes=self.level_offsets[-1])
 
-def _bvh_arg(bvh, m, grid, method, what):
-    """the TriangleBVH a call is to walk, or None: bvh = None, True (build one on m) or a TriangleBVH built on this mesh"""
-    if bvh is None or bvh is False:
-        return None
-    if grid is not None or method != "grid":
-        raise ValueError("%s: bvh= replaces the grid: leave grid=None and method at its default, got grid %s, method %r" %
-                         (what, "given" if grid is not None else "None", method))
-    if bvh is True:
-        return TriangleBVH(m)
-    if not isinstance(bvh, TriangleBVH):
-        raise ValueError("%s: bvh must be None, True or a TriangleBVH, got %s" % (what, type(bvh).__name__))
-    return bvh
+    def read_stats(self, ws):
+        _, nodes, faces = G.read_head(ws)
+        return dict(nodes_visited=nodes, faces_evaluated=faces)
+
+    def dist_query(self, q, out, ring_budget=None):
+        """(no ring budget: no query falls back)"""
+        ws = _ws(32, q.device)                       # the 32-byte head alone
+        L.check(L.load().sp3_mesh_bvh_dist_query(q.data_ptr(), self.query_order(q).data_ptr(), q.shape[0], *_mesh_args(self), *self.tree_args(),
+                                                 ws.data_ptr(), *_ptrs(out, *_DIST_OUT), L.stream_ptr()), "sp3_mesh_bvh_dist_query")
+        return ws
+
+    def ray_query(self, o, d, t_min, t_max, cull, out):
+        ws = _ws(32, o.device)
+        L.check(L.load().sp3_mesh_bvh_ray_query(o.data_ptr(), d.data_ptr(), self.query_order(o).data_ptr(), o.shape[0], *_mesh_args(self),
+                                                *self.tree_args(), t_min, t_max, cull, ws.data_ptr(), *_ptrs(out, *_RAY_OUT), L.stream_ptr()),
+                "sp3_mesh_bvh_ray_query")
+        return ws
+
+    def ray_views(self, table, table_d, T, pixel_offset):
+        lib = L.load()
+        ws = _ws(lib.sp3_mesh_ray_ws_bytes(0), table_d.device)
+        L.check(lib.sp3_mesh_bvh_ray_views(table, table_d.data_ptr(), T, pixel_offset, *_mesh_args(self), *self.tree_args(), ws.data_ptr(),
+                                           L.stream_ptr()), "sp3_mesh_bvh_ray_views")
+        return ws
+
+
+def _accel(m, grid, bvh, method, what, tail="no surface to hit"):
+    """What a call is to ask: a TriangleBVH (bvh = True: built on m, or one built on this mesh), else the caller's TriangleGrid, else
+    -- method "brute" -- every face, else a new TriangleGrid.  `tail` ends the ValueError of a mesh without a usable face."""
+    if bvh is not None and bvh is not False:
+        if grid is not None or method != "grid":
+            raise ValueError("%s: bvh= replaces the grid: leave grid=None and method at its default, got grid %s, method %r" %
+                             (what, "given" if grid is not None else "None", method))
+        if bvh is True:
+            return TriangleBVH(m)
+        if not isinstance(bvh, TriangleBVH):
+            raise ValueError("%s: bvh must be None, True or a TriangleBVH, got %s" % (what, type(bvh).__name__))
+        return bvh
+    if method == "brute":
+        if grid is not None:                         # its mesh, and its dims in the stats; none of its cells
+            return _AllFaces(grid.vertices, grid.faces, grid)
+        v, _, f = _check_mesh(m, what)               # no grid to build: only the count of usable faces, for the same ValueError
+        _usable_faces(L.load(), v, f, what, tail)
+        return _AllFaces(v, f)
+    return TriangleGrid(m) if grid is None else grid
 
 
 def point_mesh_distance(points, m, grid=None, method="grid", return_stats=False, ring_budget=DIST_RING_BUDGET, bvh=None):
@@ -575,54 +696,21 @@ def point_mesh_distance(points, m, grid=None, method="grid", return_stats=False,
     stats gains nodes_visited, levels and nodes; fallback_queries and cells_visited are 0, grid (1, 1, 1)."""
     if method not in ("grid", "brute"):
         raise ValueError("point_mesh_distance: method must be 'grid' or 'brute', got %r" % (method,))
-    bvh = _bvh_arg(bvh, m, grid, method, "point_mesh_distance")
-    lib = L.load()
     q = _dev(points, "point_mesh_distance: points")
     if q.dim() != 2 or q.shape[1] != 3 or q.dtype != torch.float32:
         raise RuntimeError("point_mesh_distance: points must be fp32 [N, 3], got %s %s" % (q.dtype, tuple(q.shape)))
     q = q.contiguous()
-    if bvh is not None:
-        v, f, pairs = bvh.vertices, bvh.faces, 0
-    elif grid is not None:
-        v, f, pairs = grid.vertices, grid.faces, grid.pairs
-    elif method == "brute":                         # no grid to build: only the count of usable faces, for the same ValueError
-        v, _, f = _check_mesh(m, "point_mesh_distance")
-        pairs = 0
-        if f.shape[0] == 0 or int(_tri_cell_counts(lib, v, f, G.one_cell()).sum().item()) == 0:
-            raise ValueError("point_mesh_distance: %d faces over %d vertices, none valid, finite and with an area: no surface to measure against" %
-                             (f.shape[0], v.shape[0]))
-    else:
-        grid = TriangleGrid(m)
-        v, f, pairs = grid.vertices, grid.faces, grid.pairs
+    acc = _accel(m, grid, bvh, method, "point_mesh_distance", "no surface to measure against")
     n, dev = q.shape[0], q.device
     out = dict(dist=torch.empty(n, dtype=torch.float32, device=dev), closest=torch.empty((n, 3), dtype=torch.float32, device=dev),
                face=torch.empty(n, dtype=torch.int32, device=dev), region=torch.empty(n, dtype=torch.uint8, device=dev))
-    stats = dict(fallback_queries=0, cells_visited=0, faces_evaluated=0, grid=(1, 1, 1) if grid is None else tuple(grid.dims),
-                 h=None if grid is None else grid.h, pairs=pairs)
-    if bvh is not None:
-        stats.update(nodes_visited=0, levels=bvh.levels, nodes=bvh.level_offsets[-1])
+    stats = dict(fallback_queries=0, cells_visited=0, faces_evaluated=0, **acc.stats())
     if n > 0:
-        ws = _ws(32 if bvh is not None else lib.sp3_mesh_dist_query_ws_bytes(n), dev)      # (the tree: the 32-byte head alone)
-        if bvh is not None:
-            order = bvh.query_order(q)
-            L.check(lib.sp3_mesh_bvh_dist_query(q.data_ptr(), order.data_ptr(), n, L.ptr(v), v.shape[0], f.data_ptr(), f.shape[0], *bvh.tree_args(),
-                                                ws.data_ptr(), out["dist"].data_ptr(), out["closest"].data_ptr(), out["face"].data_ptr(),
-                                                out["region"].data_ptr(), L.stream_ptr()), "sp3_mesh_bvh_dist_query")
-            if return_stats:
-                _, stats["nodes_visited"], stats["faces_evaluated"] = G.read_head(ws)
-        elif method == "brute" or pairs == 0:
-            L.check(lib.sp3_mesh_dist_brute(q.data_ptr(), n, v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0], ws.data_ptr(),
-                                            out["dist"].data_ptr(), out["closest"].data_ptr(), out["face"].data_ptr(), out["region"].data_ptr(),
-                                            L.stream_ptr()), "sp3_mesh_dist_brute")
+        ws = acc.dist_query(q, out, ring_budget)
+        if ws is None:                               # nothing counted: every query went to the brute-force kernels
             stats["fallback_queries"] = n
-        else:
-            order = grid.query_order(q)
-            L.check(lib.sp3_mesh_dist_query(q.data_ptr(), order.data_ptr(), n, v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0],
-                                            grid.pair_face.data_ptr(), grid.pairs, grid.cell_start.data_ptr(), C.byref(grid.g), int(ring_budget),
-                                            ws.data_ptr(), out["dist"].data_ptr(), out["closest"].data_ptr(), out["face"].data_ptr(),
-                                            out["region"].data_ptr(), L.stream_ptr()), "sp3_mesh_dist_query")
-            if return_stats:
-                stats["fallback_queries"], stats["cells_visited"], stats["faces_evaluated"] = G.read_head(ws)
+        elif return_stats:
+            stats.update(acc.read_stats(ws))
     if return_stats:
         out["stats"] = stats
     return out
@@ -630,20 +718,6 @@ def point_mesh_distance(points, m, grid=None, method="grid", return_stats=False,
 
 # ------------------------------------------------------------------------------------------------ mesh rays
 _CULL = {None: 0, "back": 1, "front": 2}
-
-
-def _ray_grid(m, grid, what, build=True):
-    """(vertices, faces, grid or None) for a ray call: the caller's TriangleGrid, a new one, or -- build False -- none, with
-    TriangleGrid's ValueError for a mesh without a usable face either way"""
-    if grid is not None:
-        return grid.vertices, grid.faces, grid
-    if build:
-        grid = TriangleGrid(m)
-        return grid.vertices, grid.faces, grid
-    v, _, f = _check_mesh(m, what)
-    if f.shape[0] == 0 or int(_tri_cell_counts(L.load(), v, f, G.one_cell()).sum().item()) == 0:
-        raise ValueError("%s: %d faces over %d vertices, none valid, finite and with an area: no surface to hit" % (what, f.shape[0], v.shape[0]))
-    return v, f, None
 
 
 def ray_mesh_intersect(origins, directions, m, grid=None, t_min=0.0, t_max=math.inf, cull=None, method="grid", return_stats=False, bvh=None):
@@ -664,13 +738,11 @@ def ray_mesh_intersect(origins, directions, m, grid=None, t_min=0.0, t_max=math.
     nodes_visited, levels and nodes; cells_visited is 0, grid (1, 1, 1)."""
     if method not in ("grid", "brute"):
         raise ValueError("ray_mesh_intersect: method must be 'grid' or 'brute', got %r" % (method,))
-    bvh = _bvh_arg(bvh, m, grid, method, "ray_mesh_intersect")
     if cull not in _CULL:
         raise ValueError("ray_mesh_intersect: cull must be None, 'back' or 'front', got %r" % (cull,))
     t_min, t_max = float(t_min), float(t_max)
     if not (0.0 <= t_min <= t_max):
         raise ValueError("ray_mesh_intersect: 0 <= t_min <= t_max, got t_min %r, t_max %r" % (t_min, t_max))
-    lib = L.load()
     o, d = _dev(origins, "ray_mesh_intersect: origins"), _dev(directions, "ray_mesh_intersect: directions")
     for name, x in (("origins", o), ("directions", d)):
         if x.dim() != 2 or x.shape[1] != 3 or x.dtype != torch.float32:
@@ -678,36 +750,16 @@ def ray_mesh_intersect(origins, directions, m, grid=None, t_min=0.0, t_max=math.
     if o.shape != d.shape:
         raise RuntimeError("ray_mesh_intersect: %d origins and %d directions" % (o.shape[0], d.shape[0]))
     o, d = o.contiguous(), d.contiguous()
-    v, f, grid = (bvh.vertices, bvh.faces, None) if bvh is not None else _ray_grid(m, grid, "ray_mesh_intersect", build=method == "grid")
-    pairs = 0 if grid is None else grid.pairs
+    acc = _accel(m, grid, bvh, method, "ray_mesh_intersect")
     n, dev = o.shape[0], o.device
     out = dict(t=torch.empty(n, dtype=torch.float32, device=dev), face=torch.empty(n, dtype=torch.int32, device=dev),
                bary=torch.empty((n, 3), dtype=torch.float32, device=dev), point=torch.empty((n, 3), dtype=torch.float32, device=dev),
                side=torch.empty(n, dtype=torch.uint8, device=dev))
-    stats = dict(cells_visited=0, faces_evaluated=0, grid=(1, 1, 1) if grid is None else tuple(grid.dims), h=None if grid is None else grid.h,
-                 pairs=pairs)
-    if bvh is not None:
-        stats.update(nodes_visited=0, levels=bvh.levels, nodes=bvh.level_offsets[-1])
+    stats = dict(cells_visited=0, faces_evaluated=0, **acc.stats())
     if n > 0:
-        ws = _ws(32 if bvh is not None else lib.sp3_mesh_ray_ws_bytes(n), dev)
-        outs = (out["t"].data_ptr(), out["face"].data_ptr(), out["bary"].data_ptr(), out["point"].data_ptr(), out["side"].data_ptr())
-        if bvh is not None:
-            order = bvh.query_order(o)
-            L.check(lib.sp3_mesh_bvh_ray_query(o.data_ptr(), d.data_ptr(), order.data_ptr(), n, L.ptr(v), v.shape[0], f.data_ptr(), f.shape[0],
-                                               *bvh.tree_args(), t_min, t_max, _CULL[cull], ws.data_ptr(), *outs, L.stream_ptr()),
-                    "sp3_mesh_bvh_ray_query")
-            if return_stats:
-                _, stats["nodes_visited"], stats["faces_evaluated"] = G.read_head(ws)
-        elif method == "brute" or pairs == 0:
-            L.check(lib.sp3_mesh_ray_brute(o.data_ptr(), d.data_ptr(), n, v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0], t_min, t_max,
-                                           _CULL[cull], ws.data_ptr(), *outs, L.stream_ptr()), "sp3_mesh_ray_brute")
-        else:
-            order = grid.query_order(o)
-            L.check(lib.sp3_mesh_ray_query(o.data_ptr(), d.data_ptr(), order.data_ptr(), n, v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0],
-                                           grid.pair_face.data_ptr(), grid.pairs, grid.cell_start.data_ptr(), C.byref(grid.g), t_min, t_max,
-                                           _CULL[cull], ws.data_ptr(), *outs, L.stream_ptr()), "sp3_mesh_ray_query")
-            if return_stats:
-                _, stats["cells_visited"], stats["faces_evaluated"] = G.read_head(ws)
+        ws = acc.ray_query(o, d, t_min, t_max, _CULL[cull], out)
+        if return_stats and ws is not None:
+            stats.update((k, x) for k, x in acc.read_stats(ws).items() if k in stats)      # (no ray falls back: that count is not reported)
     if return_stats:
         out["stats"] = stats
     return out
@@ -747,18 +799,13 @@ def render_depth_maps(m, intrinsics, cam2world, size, near=0.0, far=math.inf, gr
     fk, _ = camera_tables(intrinsics, P, T)                      # (the inverse is only computed for its checks)
     if not (fk[:, :2] != 0).all():
         raise ValueError("render_depth_maps: intrinsics with a zero focal length")
-    bvh = _bvh_arg(bvh, m, grid, "grid", "render_depth_maps")
-    v, f, grid = (bvh.vertices, bvh.faces, None) if bvh is not None else _ray_grid(m, grid, "render_depth_maps")
-    dev, lib = v.device, L.load()
+    acc = _accel(m, grid, bvh, "grid", "render_depth_maps")
+    dev = acc.vertices.device
     out = dict(depth=torch.empty((T, h, w), dtype=torch.float32, device=dev))
     if return_faces:
         out["face"] = torch.empty((T, h, w), dtype=torch.int32, device=dev)
         out["bary"] = torch.empty((T, h, w, 3), dtype=torch.float32, device=dev)
-    if bvh is not None:
-        stats = dict(cells_visited=0, faces_evaluated=0, grid=(1, 1, 1), h=None, pairs=0, nodes_visited=0, levels=bvh.levels,
-                     nodes=bvh.level_offsets[-1])
-    else:
-        stats = dict(cells_visited=0, faces_evaluated=0, grid=tuple(grid.dims), h=grid.h, pairs=grid.pairs)
+    stats = dict(cells_visited=0, faces_evaluated=0, **acc.stats())
     if T > 0:
         table = (L.MeshRayView * T)()
         for i in range(T):
@@ -771,16 +818,9 @@ def render_depth_maps(m, intrinsics, cam2world, size, near=0.0, far=math.inf, gr
             e.c2w[:] = P[i, :3].reshape(12).astype(np.float32).tolist()
             e.near, e.far = near, far
         table_d = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
-        ws = _ws(lib.sp3_mesh_ray_ws_bytes(0), dev)
-        if bvh is not None:
-            L.check(lib.sp3_mesh_bvh_ray_views(table, table_d.data_ptr(), T, pixel_offset, L.ptr(v), v.shape[0], f.data_ptr(), f.shape[0],
-                                               *bvh.tree_args(), ws.data_ptr(), L.stream_ptr()), "sp3_mesh_bvh_ray_views")
-        else:
-            L.check(lib.sp3_mesh_ray_views(table, table_d.data_ptr(), T, pixel_offset, v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0],
-                                           L.ptr(grid.pair_face), grid.pairs, L.ptr(grid.cell_start), C.byref(grid.g), ws.data_ptr(),
-                                           L.stream_ptr()), "sp3_mesh_ray_views")
+        ws = acc.ray_views(table, table_d, T, pixel_offset)
         if return_stats:
-            _, stats["nodes_visited" if bvh is not None else "cells_visited"], stats["faces_evaluated"] = G.read_head(ws)
+            stats.update((k, x) for k, x in acc.read_stats(ws).items() if k in stats)
     if return_stats:
         out["stats"] = stats
     return out
