@@ -179,6 +179,9 @@ def main():
     ap.add_argument("--eval_exact", action="store_true", help="with --eval_samples: a third fused line, the same samples measured against "
                     "the other surface's triangles instead of its samples (evaluate.evaluate_meshes(exact=True): exact point-to-triangle "
                     "distances, the normal of the face hit)")
+    ap.add_argument("--eval_cull", action="store_true", help="with --eval_samples: one more fused line, both fused surfaces first culled to "
+                    "what the input views could see (mesh.cull_to_views: shadow rays against each mesh, on the device; the cull_mesh step of "
+                    "NICE-SLAM-style protocols), then evaluate.evaluate_meshes; exact with --eval_exact, over a tree with --eval_bvh")
     ap.add_argument("--eval_depth", action="store_true", help="with --fused --rgbd --eval: one more fused line, the fused prediction's depth "
                     "maps from the ground-truth cameras (mesh.render_depth_maps: rays against the mesh, on the device) scored against the "
                     "RGB-D depth in image space: abs-rel, RMSE, delta < 1.25 and coverage (evaluate.evaluate_depth)")
@@ -222,6 +225,8 @@ def main():
         ap.error("--eval_samples must be positive")
     if args.eval_exact and args.eval_samples is None:
         ap.error("--eval_exact needs --eval_samples (the samples it measures against the other surface's triangles)")
+    if args.eval_cull and args.eval_samples is None:
+        ap.error("--eval_cull needs --eval_samples (the samples drawn from the culled surfaces)")
     if args.eval_bvh and not (args.eval_exact or args.eval_depth):
         ap.error("--eval_bvh needs --eval_exact or --eval_depth (the evaluations that query the faces of a mesh)")
     if args.eval_depth and not (args.fused and args.rgbd and args.eval):
@@ -368,6 +373,15 @@ def main():
                     rx = evaluate_meshes(pred_mesh, gt_mesh, n_samples=args.eval_samples, threshold=0.1, exact=True,
                                          accel="bvh" if args.eval_bvh else None)
                     print("Fused (exact, %d): Acc: %s, Comp: %s, NC1: %s, NC2: %s" % (rx["samples"], rx["acc"], rx["comp"], rx["nc1"], rx["nc2"]))
+                if args.eval_cull:                                                # both surfaces culled to what the input views observe
+                    h, w = batch[0]["depthmap"].shape[-2:]
+                    cams = dict(intrinsics=torch.cat([v["camera_intrinsics"] for v in batch]), cam2world=torch.cat([v["camera_pose"] for v in batch]),
+                                size=(h, w))
+                    rc = evaluate_meshes(pred_mesh, gt_mesh, n_samples=args.eval_samples, threshold=0.1, exact=args.eval_exact,
+                                         accel="bvh" if args.eval_exact and args.eval_bvh else None, cull_views=cams)
+                    print("Fused (culled to %d views, %d): Acc: %s, Comp: %s, NC1: %s, NC2: %s  (faces kept: prediction %d of %d, ground truth %d of %d)" %
+                          (len(batch), rc["samples"], rc["acc"], rc["comp"], rc["nc1"], rc["nc2"], rc["pred_faces_kept"], pred_mesh["faces"].shape[0],
+                           rc["gt_faces_kept"], gt_mesh["faces"].shape[0]))
             if args.eval_depth:
                 from spann3r_amd.evaluate import evaluate_depth
                 rd = evaluate_depth(pred_mesh, batch, bvh=True if args.eval_bvh else None)

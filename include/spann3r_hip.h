@@ -1532,6 +1532,80 @@ int sp3_mesh_bvh_ray_views(const sp3_mesh_ray_view* views_host, const sp3_mesh_r
                            const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, const int32_t* order,
                            const float* node_lo, const float* node_hi, const sp3_mesh_bvh* b, void* ws, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh visibility (spann3r_amd/mesh.py ray_mesh_occluded / point_visibility / vertex_visibility / cull_to_views and
+ * spann3r_amd/evaluate.py evaluate_meshes(cull_views=...) drive these; csrc/ray_kernels.h holds the two front ends, csrc/mesh_ray.hip
+ * and csrc/mesh_bvh.hip their entry points over the grid and over the tree, csrc/mesh_visibility.hip the face classes): which part of
+ * a mesh a set of cameras can see -- the cull_mesh step that NICE-SLAM-style evaluations apply to both meshes before accuracy and
+ * completion.  tests/mesh_visibility_ref.py restates the rule in numpy; Open3D, trimesh and the NICE-SLAM script are not available
+ * to test against, so that restatement and the closest-hit kernels of "Mesh rays" are the anchors (parity unpinned).  No entry
+ * point allocates, frees or synchronises; `ws` is 32 bytes of caller-provided device scratch, 16-byte aligned, whose head counts
+ * cells / nodes visited and faces evaluated as after sp3_mesh_ray_query.  Every fp64 operation below is rounded on its own, in the
+ * order written (no FMA).
+ *
+ * The rule.
+ *   1. OCCLUSION.  A ray (o, d, t_min, t_max, cull) of "Mesh rays" is OCCLUDED iff some usable face is a hit by rule 3 there: exactly
+ *      `face >= 0` of sp3_mesh_ray_query.  Whether a hit exists does not depend on which one a walk meets first, so the walks stop at
+ *      the first accepted hit (the grid's leaves its cell loop; the tree's sets its best key to -inf, below every node's entry, so
+ *      every later pop and push fails the test it already makes) and the answer is a pure function of the inputs whatever the
+ *      structure.  A miss walks exactly the path of the closest-hit walk.  A ray with a non-finite component or d = 0 is not
+ *      occluded; an empty range (t_min > t_max) occludes nothing.
+ *   2. VISIBILITY of a point p fp32 [3] from a view (w, h, fu, fv, cu, cv, near, far, c2w[12], w2c[12]; w2c is the fp64 inverse of
+ *      the pose rounded to fp32, fusion.camera_tables').  In fp64 from the fp32 fields:
+ *        x = ((W00 p0 + W01 p1) + W02 p2) + W03, y and z likewise from rows 1 and 2 of w2c;
+ *        IN RANGE: z > 0 and near <= z <= far;
+ *        u = (x / z) fu + cu, v = (y / z) fv + cv;
+ *        IN THE IMAGE: 0 <= (u - pixel_offset) + 0.5 < w and 0 <= (v - pixel_offset) + 0.5 < h (a pixel covers half a unit either
+ *        side of its centre, the pixel rule of sp3_mesh_ray_views);
+ *        the SHADOW RAY: o = the translation of c2w (as sp3_mesh_ray_views takes it), d_k = fp32((double)p_k - (double)o_k),
+ *        t_min = near / z, t_max = 1.0 - (double)bias, bias fp32 in [0, 1);
+ *      visible(p, view) = in range, in the image and the shadow ray not occluded.  A non-finite p is visible from nowhere.  Surfaces
+ *      in front of the near plane do not occlude (as they are not rendered by sp3_mesh_ray_views).  bias is a relative depth
+ *      tolerance: it drops the hit of a vertex on its own faces (t = 1 to the fp32 rounding of d); a convention, default 1e-3.
+ *   3. count int32 [N] = the number of views that see the point; mask uint8 [T, N] (nullable) = visible(p, view).
+ *   4. CULLING.  A vertex is SEEN iff count >= min_views.  The class of a face is -1 when one of its indices lies outside 0..V-1
+ *      (count is then never read for it), else 1 (keep) when -- mode 0, "any" -- one of its vertices is seen or -- mode 1, "all" --
+ *      all three are, else 0.  sp3_mesh_select_faces(face_component = the classes, ncomponents = 2, keep = {0, 1}) keeps the faces of
+ *      class 1 in their order and rotation, and sp3_mesh_compact_vertices drops the vertices nothing names.
+ *
+ * sp3_mesh_ray_occluded / sp3_mesh_bvh_ray_occluded : the arguments, host checks and workspace head of sp3_mesh_ray_query /
+ *   sp3_mesh_bvh_ray_query with one uint8 per ray (1: occluded) in place of the five outputs: one lane per ray in q_order, one byte
+ *   stored per ray and nothing else.
+ * sp3_mesh_point_views / sp3_mesh_bvh_point_views : one lane per (point, view) pair, the view in blockIdx.y (its descriptor is
+ *   wave-uniform and read through scalar loads), the points in q_order (nullable; the structure's own query order: the lanes of a
+ *   wave shoot from one origin at neighbouring targets).  The projection tests run first: a pair outside the frustum walks nothing.
+ *   A visible pair does one integer atomicAdd on count[p] (order-free: the same bits every run; the caller zeroes count) and every
+ *   pair stores mask[view * N + p] when mask is given.  views_host and views_dev hold the same T descriptors; the host copy is
+ *   validated as sp3_mesh_ray_views validates (1 <= w, h <= 2^24, finite intrinsics with non-zero focals, 0 <= near <= far,
+ *   T <= 65535), the device copy is only read.  bias must lie in [0, 1) and pixel_offset be finite.  The grid form takes
+ *   npairs = 0 (a grid of one cell: every face per ray).  T = 0 or N = 0 launches nothing.
+ * sp3_mesh_vis_face_class : cls int32 [F] of rule 4 from count int32 [V]; one lane per face.  F = 0 launches nothing. */
+typedef struct {
+  int32_t w, h;
+  float fu, fv, cu, cv;
+  float near, far;     /* 0 <= near <= far (+inf allowed), camera z */
+  float c2w[12];       /* camera-to-world, row-major 3 x 4: the origin of the shadow rays */
+  float w2c[12];       /* world-to-camera, row-major 3 x 4: the projection */
+} sp3_mesh_vis_view;
+int sp3_mesh_ray_occluded(const float* origins, const float* directions, const int64_t* q_order, int64_t nq, const float* vertices,
+                          int64_t nverts, const int32_t* faces, int64_t nfaces, const int32_t* pair_face, int64_t npairs,
+                          const int32_t* cell_start, const sp3_nn_grid* g, double t_min, double t_max, int cull, void* ws,
+                          uint8_t* occluded, void* stream);
+int sp3_mesh_bvh_ray_occluded(const float* origins, const float* directions, const int64_t* q_order, int64_t nq, const float* vertices,
+                              int64_t nverts, const int32_t* faces, int64_t nfaces, const int32_t* order, const float* node_lo,
+                              const float* node_hi, const sp3_mesh_bvh* b, double t_min, double t_max, int cull, void* ws,
+                              uint8_t* occluded, void* stream);
+int sp3_mesh_point_views(const sp3_mesh_vis_view* views_host, const sp3_mesh_vis_view* views_dev, int T, float pixel_offset, float bias,
+                         int cull, const float* points, const int64_t* q_order, int64_t npoints, const float* vertices, int64_t nverts,
+                         const int32_t* faces, int64_t nfaces, const int32_t* pair_face, int64_t npairs, const int32_t* cell_start,
+                         const sp3_nn_grid* g, void* ws, int32_t* count, uint8_t* mask, void* stream);
+int sp3_mesh_bvh_point_views(const sp3_mesh_vis_view* views_host, const sp3_mesh_vis_view* views_dev, int T, float pixel_offset,
+                             float bias, int cull, const float* points, const int64_t* q_order, int64_t npoints, const float* vertices,
+                             int64_t nverts, const int32_t* faces, int64_t nfaces, const int32_t* order, const float* node_lo,
+                             const float* node_hi, const sp3_mesh_bvh* b, void* ws, int32_t* count, uint8_t* mask, void* stream);
+int sp3_mesh_vis_face_class(const int32_t* faces, int64_t nfaces, int64_t nverts, const int32_t* count, int min_views, int mode,
+                            int32_t* cls, void* stream);
+
 /* small utilities */
 /* n (1..8) contiguous device-to-device copies in one launch; every copy 16-byte aligned and a multiple of 16 bytes.
  * (The sequence loop's per-frame bookkeeping -- torch .clone() / slice assignments around spann3r/model.py:523-531.) */

@@ -22,6 +22,8 @@
 //     query index (query_of), the size checks and the workspace head (begin_query) are csrc/cell_grid.h's; the checks of ray
 //     arguments and of the table of views are csrc/ray_kernels.h's.  Nothing here sweeps every face: the two order-free passes of
 //     the brute-force kernels live in csrc/face_sweep.h.
+//   * "Mesh visibility" (sp3_mesh_bvh_ray_occluded, sp3_mesh_bvh_point_views) asks the ray walk whether ANY face is a hit:
+//     walk_ray<true> drops best to -inf at the first accepted one, which ends the walk through the tests it already makes.
 #include "cell_grid.h"
 #include "ray_kernels.h"
 #include "tri_dist.h"
@@ -247,7 +249,10 @@ __device__ __forceinline__ int walk_dist(const Tree& t, const int* s_off, const 
   return bf;
 }
 
-// the winning face (-1: none) of the ray (o, d) in [t_min, t_max]
+// the winning face (-1: none) of the ray (o, d) in [t_min, t_max].  ANY ("Mesh visibility"): the first accepted hit puts best
+// below every node's entry (t0 >= t_min >= 0 > -inf), so every later pop and push fails the test walk_tree already makes: no new
+// control flow, and a ray that hits nothing walks what the closest-hit walk walks.
+template <bool ANY>
 __device__ __forceinline__ int walk_ray(const Tree& t, const int* s_off, const sp3_mesh_bvh& b, unsigned* stack, int cap, const Ray& r, float ox,
                                         float oy, float oz, float dx, float dy, float dz, double t_min, double t_max, int cull, int& nodes,
                                         int& evals) {
@@ -270,7 +275,9 @@ __device__ __forceinline__ int walk_ray(const Tree& t, const int* s_off, const s
             },
             [&](int f, const float (&v)[9]) {
               Hit h;
-              if (intersect(r, v, t_min, t_max, cull, h) && (h.t < best || (h.t == best && f < bf))) { best = h.t; bf = f; }
+              if (ANY) {
+                if (intersect(r, v, t_min, t_max, cull, h)) { best = -INFINITY; bf = f; }      // (the rest of this leaf is still evaluated)
+              } else if (intersect(r, v, t_min, t_max, cull, h) && (h.t < best || (h.t == best && f < bf))) { best = h.t; bf = f; }
             });
   return bf;
 }
@@ -306,9 +313,10 @@ struct TreeWalker {
     s_off = off;
     stack = lds + threadIdx.x;
   }
+  template <bool ANY = false>
   __device__ __forceinline__ int walk(const Ray& r, float ox, float oy, float oz, float dx, float dy, float dz, double t_min, double t_max, int cull,
                                       int& nodes, int& evals) const {
-    return walk_ray(m, s_off, b, stack, cap, r, ox, oy, oz, dx, dy, dz, t_min, t_max, cull, nodes, evals);
+    return walk_ray<ANY>(m, s_off, b, stack, cap, r, ox, oy, oz, dx, dy, dz, t_min, t_max, cull, nodes, evals);
   }
 };
 
@@ -436,5 +444,44 @@ extern "C" int sp3_mesh_bvh_ray_views(const sp3_mesh_ray_view* views_host, const
   const TreeWalker w = walker_of(tree_of(vertices, nverts, faces, nfaces, order, node_lo, node_hi), b);
   k_ray_views<<<grid, TB, stack_bytes(w.cap), st>>>(views_dev, pixel_offset, w, (GridHead*)ws);
   SP3_LAUNCH_CHECK("sp3_mesh_bvh_ray_views");
+  return 0;
+}
+
+// ---- "Mesh visibility" over the tree
+extern "C" int sp3_mesh_bvh_ray_occluded(const float* origins, const float* directions, const int64_t* q_order, int64_t nq, const float* vertices,
+                                         int64_t nverts, const int32_t* faces, int64_t nfaces, const int32_t* order, const float* node_lo,
+                                         const float* node_hi, const sp3_mesh_bvh* b, double t_min, double t_max, int cull, void* ws,
+                                         uint8_t* occluded, void* stream) {
+  if (check_mesh_args("sp3_mesh_bvh_ray_occluded", nverts, nfaces, nq, t_min, t_max, cull) || check_tree(b, nfaces, "sp3_mesh_bvh_ray_occluded"))
+    return 1;
+  if (nq == 0) return 0;
+  SP3_CHECK(origins && directions && faces && order && node_lo && node_hi && ws && occluded && (nverts == 0 || vertices),
+            "sp3_mesh_bvh_ray_occluded: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  if (const int e = begin_query(ws, st, "sp3_mesh_bvh_ray_occluded")) return e;
+  const TreeWalker w = walker_of(tree_of(vertices, nverts, faces, nfaces, order, node_lo, node_hi), b);
+  k_ray_occluded<<<blocks_for(nq), TB, stack_bytes(w.cap), st>>>(origins, directions, q_order, nq, w, t_min, t_max, cull, occluded, (GridHead*)ws);
+  SP3_LAUNCH_CHECK("sp3_mesh_bvh_ray_occluded");
+  return 0;
+}
+
+extern "C" int sp3_mesh_bvh_point_views(const sp3_mesh_vis_view* views_host, const sp3_mesh_vis_view* views_dev, int T, float pixel_offset,
+                                        float bias, int cull, const float* points, const int64_t* q_order, int64_t npoints,
+                                        const float* vertices, int64_t nverts, const int32_t* faces, int64_t nfaces, const int32_t* order,
+                                        const float* node_lo, const float* node_hi, const sp3_mesh_bvh* b, void* ws, int32_t* count,
+                                        uint8_t* mask, void* stream) {
+  if (check_vis_args("sp3_mesh_bvh_point_views", T, pixel_offset, bias, cull, nverts, nfaces, npoints) ||
+      check_tree(b, nfaces, "sp3_mesh_bvh_point_views"))
+    return 1;
+  if (T == 0 || npoints == 0) return 0;
+  SP3_CHECK(views_host && views_dev && points && count && faces && order && node_lo && node_hi && ws && (nverts == 0 || vertices),
+            "sp3_mesh_bvh_point_views: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  if (const int e = begin_query(ws, st, "sp3_mesh_bvh_point_views")) return e;
+  if (check_vis_views("sp3_mesh_bvh_point_views", views_host, T)) return 1;
+  const TreeWalker w = walker_of(tree_of(vertices, nverts, faces, nfaces, order, node_lo, node_hi), b);
+  k_point_views<<<point_views_grid(npoints, T), TB, stack_bytes(w.cap), st>>>(views_dev, pixel_offset, bias, cull, points, q_order, npoints, w,
+                                                                             (int*)count, mask, (GridHead*)ws);
+  SP3_LAUNCH_CHECK("sp3_mesh_bvh_point_views");
   return 0;
 }

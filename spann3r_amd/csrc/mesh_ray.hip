@@ -17,6 +17,9 @@
 //     read-only table of cameras (sp3_mesh_ray_views) -- instantiated with the walk of this file; csrc/mesh_bvh.hip instantiates
 //     them with the tree's.  The host checks of the ray entry points and of the table of views are that header's too; the size
 //     checks and the workspace head (begin_query) are csrc/cell_grid.h's.
+//   * "Mesh visibility" (sp3_mesh_ray_occluded, sp3_mesh_point_views) asks the same walk whether ANY face is a hit: walk_ray<true> and
+//     scan_all<true> return at the first accepted one; the <false> instantiations are the code they were.  Their front ends are
+//     csrc/ray_kernels.h's too.
 //   * Every loop is bounded by the grid dims, npairs or nfaces; nothing waits on another lane's store; what an atomic wrote is read
 //     by a LATER launch only.
 #include "face_sweep.h"
@@ -36,6 +39,8 @@ struct MeshRef {
 };
 
 // The winning face (-1: none) of the ray (o, d) in [t_min, t_max] by the walk of the header; cells / evals count what it did.
+// ANY ("Mesh visibility"): the first accepted hit ends the walk and is returned, whichever it is.
+template <bool ANY>
 __device__ __forceinline__ int walk_ray(const sp3_nn_grid& g, const MeshRef& m, const Ray& r, float ox, float oy, float oz, float dx, float dy,
                                         float dz, double t_min, double t_max, int cull, int& cells, int& evals) {
   const double o[3] = {(double)ox, (double)oy, (double)oz}, d[3] = {(double)dx, (double)dy, (double)dz};
@@ -69,7 +74,9 @@ __device__ __forceinline__ int walk_ray(const sp3_nn_grid& g, const MeshRef& m, 
       if (!((unsigned)f < (unsigned)m.nfaces && load_face(m.verts, m.nverts, m.faces, f, v))) continue;      // (the pairs hold usable faces only)
       ++evals;
       Hit h;
-      if (intersect(r, v, t_min, t_max, cull, h) && (h.t < best || (h.t == best && f < bf))) { best = h.t; bf = f; }
+      if (ANY) {
+        if (intersect(r, v, t_min, t_max, cull, h)) return f;
+      } else if (intersect(r, v, t_min, t_max, cull, h) && (h.t < best || (h.t == best && f < bf))) { best = h.t; bf = f; }
     }
     // the exit of this cell per axis, from the integer index; a cell on the rim of the grid reaches to the box's own exit
     double te = INFINITY;
@@ -92,6 +99,7 @@ __device__ __forceinline__ int walk_ray(const sp3_nn_grid& g, const MeshRef& m, 
 }
 
 // every face against the ray, for a grid of one cell (no references): usability decided here
+template <bool ANY>
 __device__ __forceinline__ int scan_all(const MeshRef& m, const Ray& r, double t_min, double t_max, int cull, int& evals) {
   double best = INFINITY;
   int bf = -1;
@@ -100,7 +108,9 @@ __device__ __forceinline__ int scan_all(const MeshRef& m, const Ray& r, double t
     if (!(load_face(m.verts, m.nverts, m.faces, f, v) && has_area(v))) continue;
     ++evals;
     Hit h;
-    if (intersect(r, v, t_min, t_max, cull, h) && h.t < best) { best = h.t; bf = f; }      // ascending f: the smallest index among equals
+    if (ANY) {
+      if (intersect(r, v, t_min, t_max, cull, h)) return f;
+    } else if (intersect(r, v, t_min, t_max, cull, h) && h.t < best) { best = h.t; bf = f; }      // ascending f: the smallest index among equals
   }
   return bf;
 }
@@ -112,10 +122,11 @@ struct GridWalker {
   MeshRef m;
   sp3_nn_grid g;
   __device__ __forceinline__ void prepare(unsigned*) {}
+  template <bool ANY = false>
   __device__ __forceinline__ int walk(const Ray& r, float ox, float oy, float oz, float dx, float dy, float dz, double t_min, double t_max, int cull,
                                       int& cells, int& evals) const {
-    if (VIEWS && m.npairs <= 0) return scan_all(m, r, t_min, t_max, cull, evals);
-    return walk_ray(g, m, r, ox, oy, oz, dx, dy, dz, t_min, t_max, cull, cells, evals);
+    if (VIEWS && m.npairs <= 0) return scan_all<ANY>(m, r, t_min, t_max, cull, evals);
+    return walk_ray<ANY>(g, m, r, ox, oy, oz, dx, dy, dz, t_min, t_max, cull, cells, evals);
   }
 };
 
@@ -213,5 +224,45 @@ extern "C" int sp3_mesh_ray_views(const sp3_mesh_ray_view* views_host, const sp3
   const GridWalker<true> w = {mesh_ref(vertices, nverts, faces, nfaces, pair_face, npairs, cell_start), *g};
   k_ray_views<<<grid, TB, 0, st>>>(views_dev, pixel_offset, w, (GridHead*)ws);
   SP3_LAUNCH_CHECK("sp3_mesh_ray_views");
+  return 0;
+}
+
+// ---- "Mesh visibility" over the grid
+extern "C" int sp3_mesh_ray_occluded(const float* origins, const float* directions, const int64_t* q_order, int64_t nq, const float* vertices,
+                                     int64_t nverts, const int32_t* faces, int64_t nfaces, const int32_t* pair_face, int64_t npairs,
+                                     const int32_t* cell_start, const sp3_nn_grid* g, double t_min, double t_max, int cull, void* ws,
+                                     uint8_t* occluded, void* stream) {
+  if (check_mesh_args("sp3_mesh_ray_occluded", nverts, nfaces, nq, t_min, t_max, cull)) return 1;
+  SP3_CHECK(npairs >= 1 && npairs < N_MAX, "sp3_mesh_ray_occluded: npairs = %lld out of range (a grid of one cell holds none: sp3_mesh_ray_brute)",
+            (long long)npairs);
+  if (check_grid(g, "sp3_mesh_ray_occluded")) return 1;
+  if (nq == 0) return 0;
+  SP3_CHECK(origins && directions && faces && pair_face && cell_start && ws && occluded && (nverts == 0 || vertices),
+            "sp3_mesh_ray_occluded: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  if (const int e = begin_query(ws, st, "sp3_mesh_ray_occluded")) return e;
+  const GridWalker<false> w = {mesh_ref(vertices, nverts, faces, nfaces, pair_face, npairs, cell_start), *g};
+  k_ray_occluded<<<blocks_for(nq), TB, 0, st>>>(origins, directions, q_order, nq, w, t_min, t_max, cull, occluded, (GridHead*)ws);
+  SP3_LAUNCH_CHECK("sp3_mesh_ray_occluded");
+  return 0;
+}
+
+extern "C" int sp3_mesh_point_views(const sp3_mesh_vis_view* views_host, const sp3_mesh_vis_view* views_dev, int T, float pixel_offset,
+                                    float bias, int cull, const float* points, const int64_t* q_order, int64_t npoints, const float* vertices,
+                                    int64_t nverts, const int32_t* faces, int64_t nfaces, const int32_t* pair_face, int64_t npairs,
+                                    const int32_t* cell_start, const sp3_nn_grid* g, void* ws, int32_t* count, uint8_t* mask, void* stream) {
+  if (check_vis_args("sp3_mesh_point_views", T, pixel_offset, bias, cull, nverts, nfaces, npoints)) return 1;
+  SP3_CHECK(npairs >= 0 && npairs < N_MAX, "sp3_mesh_point_views: npairs = %lld out of range", (long long)npairs);
+  if (check_grid(g, "sp3_mesh_point_views")) return 1;
+  if (T == 0 || npoints == 0) return 0;
+  SP3_CHECK(views_host && views_dev && points && count && faces && ws && (nverts == 0 || vertices) && (npairs == 0 || (pair_face && cell_start)),
+            "sp3_mesh_point_views: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  if (const int e = begin_query(ws, st, "sp3_mesh_point_views")) return e;
+  if (check_vis_views("sp3_mesh_point_views", views_host, T)) return 1;
+  const GridWalker<true> w = {mesh_ref(vertices, nverts, faces, nfaces, pair_face, npairs, cell_start), *g};
+  k_point_views<<<point_views_grid(npoints, T), TB, 0, st>>>(views_dev, pixel_offset, bias, cull, points, q_order, npoints, w, (int*)count, mask,
+                                                             (GridHead*)ws);
+  SP3_LAUNCH_CHECK("sp3_mesh_point_views");
   return 0;
 }

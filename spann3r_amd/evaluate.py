@@ -303,7 +303,7 @@ def _exact_side(points, normals, target_mesh, face_normals, bvh=None):
     return _mean_median(r["dist"]) + _mean_median(dots)
 
 
-def evaluate_meshes(pred_mesh, gt_mesh, n_samples=200_000, seed=0, threshold=0.1, icp=True, exact=False, accel=None):
+def evaluate_meshes(pred_mesh, gt_mesh, n_samples=200_000, seed=0, threshold=0.1, icp=True, exact=False, accel=None, cull_views=None):
     """The metrics of evaluate_reconstruction for two SURFACES instead of two clouds, as NICE-SLAM-style eval_recon scripts take
     them: n_samples points drawn by area from each mesh (mesh.sample_surface: the dicts of scene_mesh / extract_mesh / simplify,
     the same seed for both), point-to-point ICP of the prediction's samples onto the ground truth's from identity unless
@@ -318,7 +318,12 @@ def evaluate_meshes(pred_mesh, gt_mesh, n_samples=200_000, seed=0, threshold=0.1
     spacing puts under acc / comp is gone: two tessellations of one plane score 0.  The dict gains exact=True.
     accel (with exact=True only): "grid" (the default: mesh.TriangleGrid, fastest when the prediction lies within a few cells of
     the ground truth) or "bvh" (mesh.TriangleBVH: the same numbers bit for bit, at a cost that does not depend on how far apart
-    the two surfaces are -- the choice for a prediction that may be poor, and for meshes of wildly mixed face sizes)."""
+    the two surfaces are -- the choice for a prediction that may be poor, and for meshes of wildly mixed face sizes).
+    cull_views: a dict of the camera arguments of mesh.cull_to_views (intrinsics, cam2world, size and any of near, far, bias,
+    pixel_offset, opengl, cull, mode, min_views): both meshes are first culled to what those cameras could see, each against its
+    own surface (include/spann3r_hip.h "Mesh visibility") -- the cull_mesh step of NICE-SLAM-style protocols, without which rooms
+    the sequence never entered ruin comp and hallucinated back sides ruin acc.  The dict gains pred_faces_kept and gt_faces_kept.
+    With accel="bvh" the shadow rays walk a tree too.  None: nothing new runs."""
     from . import mesh as M
     if accel is not None and not exact:
         raise ValueError("evaluate_meshes: accel=%r chooses the structure of the exact distance: pass exact=True" % (accel,))
@@ -328,6 +333,10 @@ def evaluate_meshes(pred_mesh, gt_mesh, n_samples=200_000, seed=0, threshold=0.1
     n = int(n_samples)
     if n <= 0:
         raise ValueError("evaluate_meshes: n_samples = %r, must be positive" % (n_samples,))
+    kept = {}
+    if cull_views is not None:
+        pred_mesh, gt_mesh = (M.cull_to_views(x, bvh=bvh, **cull_views) for x in (pred_mesh, gt_mesh))
+        kept = dict(pred_faces_kept=pred_mesh["visibility"]["faces_kept"], gt_faces_kept=gt_mesh["visibility"]["faces_kept"])
     sp, sg = M.sample_surface(pred_mesh, n, seed=seed), M.sample_surface(gt_mesh, n, seed=seed)
     pred, pred_n, gt, gt_n = sp["points"], sp["normals"], sg["points"], sg["normals"]
     T = np.eye(4)
@@ -351,6 +360,7 @@ def evaluate_meshes(pred_mesh, gt_mesh, n_samples=200_000, seed=0, threshold=0.1
            "nc2_med": nc2_med, "transformation": T, "pred_area": sp["area"], "gt_area": sg["area"], "samples": n}
     if exact:
         out["exact"] = True
+    out.update(kept)
     return out
 
 

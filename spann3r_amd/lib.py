@@ -146,6 +146,12 @@ class MeshBvh(C.Structure):
                 ("slack", C.c_float)]
 
 
+class MeshVisView(C.Structure):
+    """sp3_mesh_vis_view (include/spann3r_hip.h)"""
+    _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("fu", C.c_float), ("fv", C.c_float), ("cu", C.c_float), ("cv", C.c_float),
+                ("near", C.c_float), ("far", C.c_float), ("c2w", C.c_float * 12), ("w2c", C.c_float * 12)]
+
+
 class TsdfView(C.Structure):
     """sp3_tsdf_view (include/spann3r_hip.h)"""
     _fields_ = [("depth", C.c_void_p), ("vertex", C.c_void_p), ("normal", C.c_void_p), ("rgba", C.c_void_p), ("row_stride", C.c_int64),
@@ -319,6 +325,17 @@ _PROTOS = {
                                C.c_void_p, C.c_void_p, C.c_void_p],
     "sp3_mesh_bvh_ray_views": [C.POINTER(MeshRayView), C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.POINTER(MeshBvh), C.c_void_p, C.c_void_p],
+    "sp3_mesh_ray_occluded": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                              C.c_void_p, C.POINTER(NnGrid), C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_mesh_bvh_ray_occluded": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.POINTER(MeshBvh), C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_mesh_point_views": [C.POINTER(MeshVisView), C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                             C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(NnGrid), C.c_void_p,
+                             C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_mesh_bvh_point_views": [C.POINTER(MeshVisView), C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                 C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MeshBvh), C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_mesh_vis_face_class": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
     "sp3_render_tris": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(RenderCam), C.c_int,
                         C.c_void_p, C.c_void_p, C.c_void_p],
     "sp3_ssi_align_stats": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],

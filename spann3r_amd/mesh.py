@@ -503,6 +503,15 @@ class _AllFaces:
         L.check(lib.sp3_mesh_ray_brute(o.data_ptr(), d.data_ptr(), n, *_mesh_args(self), t_min, t_max, cull, ws.data_ptr(), *_ptrs(out, *_RAY_OUT),
                                        L.stream_ptr()), "sp3_mesh_ray_brute")
 
+    def ray_occluded(self, o, d, t_min, t_max, cull, occluded):
+        """(no brute-force occlusion kernel: the closest hit of every ray, then face >= 0)"""
+        n, dev = o.shape[0], o.device
+        out = dict(t=torch.empty(n, dtype=torch.float32, device=dev), face=torch.empty(n, dtype=torch.int32, device=dev),
+                   bary=torch.empty((n, 3), dtype=torch.float32, device=dev), point=torch.empty((n, 3), dtype=torch.float32, device=dev),
+                   side=torch.empty(n, dtype=torch.uint8, device=dev))
+        self.ray_query(o, d, t_min, t_max, cull, out)
+        occluded.copy_(out["face"] >= 0)
+
 
 class TriangleGrid(G.Grid):
     """The faces of a mesh dict registered in a cell grid (include/spann3r_hip.h "Mesh distance"): built once, reused for any number
@@ -583,6 +592,23 @@ class TriangleGrid(G.Grid):
                                        L.stream_ptr()), "sp3_mesh_ray_views")
         return ws
 
+    def ray_occluded(self, o, d, t_min, t_max, cull, occluded):
+        if self.pairs == 0:
+            return _AllFaces(self.vertices, self.faces, self).ray_occluded(o, d, t_min, t_max, cull, occluded)
+        lib, n = L.load(), o.shape[0]
+        ws = _ws(32, o.device)
+        L.check(lib.sp3_mesh_ray_occluded(o.data_ptr(), d.data_ptr(), self.query_order(o).data_ptr(), n, *_mesh_args(self), *self._grid_args(), t_min,
+                                          t_max, cull, ws.data_ptr(), occluded.data_ptr(), L.stream_ptr()), "sp3_mesh_ray_occluded")
+        return ws
+
+    def point_views(self, table, table_d, T, pixel_offset, bias, cull, p, count, mask):
+        """(a grid of one cell goes to sp3_mesh_point_views too: its kernel then scans every face)"""
+        ws = _ws(32, p.device)
+        L.check(L.load().sp3_mesh_point_views(table, table_d.data_ptr(), T, pixel_offset, bias, cull, p.data_ptr(), self.query_order(p).data_ptr(),
+                                              p.shape[0], *_mesh_args(self), *self._grid_args(), ws.data_ptr(), count.data_ptr(), L.ptr(mask),
+                                              L.stream_ptr()), "sp3_mesh_point_views")
+        return ws
+
 
 _KEY_NONE = 2 ** 63 - 1          # sp3_mesh_bvh_keys: an item that is not usable
 
@@ -659,6 +685,20 @@ class TriangleBVH:
                                            L.stream_ptr()), "sp3_mesh_bvh_ray_views")
         return ws
 
+    def ray_occluded(self, o, d, t_min, t_max, cull, occluded):
+        ws = _ws(32, o.device)
+        L.check(L.load().sp3_mesh_bvh_ray_occluded(o.data_ptr(), d.data_ptr(), self.query_order(o).data_ptr(), o.shape[0], *_mesh_args(self),
+                                                   *self.tree_args(), t_min, t_max, cull, ws.data_ptr(), occluded.data_ptr(), L.stream_ptr()),
+                "sp3_mesh_bvh_ray_occluded")
+        return ws
+
+    def point_views(self, table, table_d, T, pixel_offset, bias, cull, p, count, mask):
+        ws = _ws(32, p.device)
+        L.check(L.load().sp3_mesh_bvh_point_views(table, table_d.data_ptr(), T, pixel_offset, bias, cull, p.data_ptr(),
+                                                  self.query_order(p).data_ptr(), p.shape[0], *_mesh_args(self), *self.tree_args(), ws.data_ptr(),
+                                                  count.data_ptr(), L.ptr(mask), L.stream_ptr()), "sp3_mesh_bvh_point_views")
+        return ws
+
 
 def _accel(m, grid, bvh, method, what, tail="no surface to hit"):
     """What a call is to ask: a TriangleBVH (bvh = True: built on m, or one built on this mesh), else the caller's TriangleGrid, else
@@ -720,6 +760,24 @@ def point_mesh_distance(points, m, grid=None, method="grid", return_stats=False,
 _CULL = {None: 0, "back": 1, "front": 2}
 
 
+def _ray_args(what, origins, directions, t_min, t_max, cull, method):
+    """the argument checks of ray_mesh_intersect and ray_mesh_occluded -> (origins, directions contiguous on the device, t_min, t_max floats)"""
+    if method not in ("grid", "brute"):
+        raise ValueError("%s: method must be 'grid' or 'brute', got %r" % (what, method))
+    if cull not in _CULL:
+        raise ValueError("%s: cull must be None, 'back' or 'front', got %r" % (what, cull))
+    t_min, t_max = float(t_min), float(t_max)
+    if not (0.0 <= t_min <= t_max):
+        raise ValueError("%s: 0 <= t_min <= t_max, got t_min %r, t_max %r" % (what, t_min, t_max))
+    o, d = _dev(origins, what + ": origins"), _dev(directions, what + ": directions")
+    for name, x in (("origins", o), ("directions", d)):
+        if x.dim() != 2 or x.shape[1] != 3 or x.dtype != torch.float32:
+            raise RuntimeError("%s: %s must be fp32 [N, 3], got %s %s" % (what, name, x.dtype, tuple(x.shape)))
+    if o.shape != d.shape:
+        raise RuntimeError("%s: %d origins and %d directions" % (what, o.shape[0], d.shape[0]))
+    return o.contiguous(), d.contiguous(), t_min, t_max
+
+
 def ray_mesh_intersect(origins, directions, m, grid=None, t_min=0.0, t_max=math.inf, cull=None, method="grid", return_stats=False, bvh=None):
     """What every ray hits first on the surface of a mesh dict (include/spann3r_hip.h "Mesh rays"; sp3_mesh_ray_query /
     sp3_mesh_ray_brute): origins, directions fp32 [N, 3] (device; directions need no normalising: t is in units of |d|) ->
@@ -736,20 +794,7 @@ def ray_mesh_intersect(origins, directions, m, grid=None, t_min=0.0, t_max=math.
     bvh: a TriangleBVH built on this mesh, or True to build one: the rays walk the tree instead (sp3_mesh_bvh_ray_query), served in
     the order of bvh.query_order(origins); `grid` must then be None and `method` its default, else ValueError.  stats gains
     nodes_visited, levels and nodes; cells_visited is 0, grid (1, 1, 1)."""
-    if method not in ("grid", "brute"):
-        raise ValueError("ray_mesh_intersect: method must be 'grid' or 'brute', got %r" % (method,))
-    if cull not in _CULL:
-        raise ValueError("ray_mesh_intersect: cull must be None, 'back' or 'front', got %r" % (cull,))
-    t_min, t_max = float(t_min), float(t_max)
-    if not (0.0 <= t_min <= t_max):
-        raise ValueError("ray_mesh_intersect: 0 <= t_min <= t_max, got t_min %r, t_max %r" % (t_min, t_max))
-    o, d = _dev(origins, "ray_mesh_intersect: origins"), _dev(directions, "ray_mesh_intersect: directions")
-    for name, x in (("origins", o), ("directions", d)):
-        if x.dim() != 2 or x.shape[1] != 3 or x.dtype != torch.float32:
-            raise RuntimeError("ray_mesh_intersect: %s must be fp32 [N, 3], got %s %s" % (name, x.dtype, tuple(x.shape)))
-    if o.shape != d.shape:
-        raise RuntimeError("ray_mesh_intersect: %d origins and %d directions" % (o.shape[0], d.shape[0]))
-    o, d = o.contiguous(), d.contiguous()
+    o, d, t_min, t_max = _ray_args("ray_mesh_intersect", origins, directions, t_min, t_max, cull, method)
     acc = _accel(m, grid, bvh, method, "ray_mesh_intersect")
     n, dev = o.shape[0], o.device
     out = dict(t=torch.empty(n, dtype=torch.float32, device=dev), face=torch.empty(n, dtype=torch.int32, device=dev),
@@ -763,6 +808,30 @@ def ray_mesh_intersect(origins, directions, m, grid=None, t_min=0.0, t_max=math.
     if return_stats:
         out["stats"] = stats
     return out
+
+
+def _camera_args(what, intrinsics, cam2world, size, near, far, pixel_offset, opengl):
+    """the camera arguments of render_depth_maps and point_visibility, checked -> (h, w, near, far, pixel_offset, cam2world float64
+    [T, 4, 4] with opengl undone, (fu, fv, cu, cv) float64 [T, 4], world-to-camera fp32 [T, 12]: fusion.camera_tables')"""
+    from .fusion import _host_array, camera_tables
+    h, w = (int(x) for x in size)
+    if h < 1 or w < 1:
+        raise ValueError("%s: size %s must be (h, w) >= 1" % (what, size))
+    near, far, pixel_offset = float(near), float(far), float(pixel_offset)
+    if not (0.0 <= near <= far):
+        raise ValueError("%s: 0 <= near <= far, got near %r, far %r" % (what, near, far))
+    if not math.isfinite(pixel_offset):
+        raise ValueError("%s: pixel_offset must be finite, got %r" % (what, pixel_offset))
+    P = _host_array(cam2world)
+    P = P[None] if P.ndim == 2 else P.reshape(-1, 4, 4) if P.size == 0 else P
+    if P.ndim != 3 or P.shape[1:] != (4, 4):
+        raise ValueError("%s: cam2world %s must be [4, 4] or [T, 4, 4]" % (what, P.shape))
+    if opengl:
+        P = P * np.array([1.0, -1.0, -1.0, 1.0])
+    fk, w2c = camera_tables(intrinsics, P, P.shape[0])
+    if not (fk[:, :2] != 0).all():
+        raise ValueError("%s: intrinsics with a zero focal length" % what)
+    return h, w, near, far, pixel_offset, P, fk, w2c
 
 
 def render_depth_maps(m, intrinsics, cam2world, size, near=0.0, far=math.inf, grid=None, pixel_offset=0.0, opengl=False, return_faces=False,
@@ -780,25 +849,8 @@ def render_depth_maps(m, intrinsics, cam2world, size, near=0.0, far=math.inf, gr
     ray_mesh_intersect's (one 32-byte host read); otherwise nothing synchronises beyond the grid's build.
     bvh: a TriangleBVH built on this mesh, or True to build one: the rays walk the tree instead (sp3_mesh_bvh_ray_views), the same
     maps bit for bit; `grid` must then be None, else ValueError."""
-    from .fusion import _host_array, camera_tables
-    h, w = (int(x) for x in size)
-    if h < 1 or w < 1:
-        raise ValueError("render_depth_maps: size %s must be (h, w) >= 1" % (size,))
-    near, far, pixel_offset = float(near), float(far), float(pixel_offset)
-    if not (0.0 <= near <= far):
-        raise ValueError("render_depth_maps: 0 <= near <= far, got near %r, far %r" % (near, far))
-    if not math.isfinite(pixel_offset):
-        raise ValueError("render_depth_maps: pixel_offset must be finite, got %r" % (pixel_offset,))
-    P = _host_array(cam2world)
-    P = P[None] if P.ndim == 2 else P.reshape(-1, 4, 4) if P.size == 0 else P
-    if P.ndim != 3 or P.shape[1:] != (4, 4):
-        raise ValueError("render_depth_maps: cam2world %s must be [4, 4] or [T, 4, 4]" % (P.shape,))
-    T = P.shape[0]
-    if opengl:
-        P = P * np.array([1.0, -1.0, -1.0, 1.0])
-    fk, _ = camera_tables(intrinsics, P, T)                      # (the inverse is only computed for its checks)
-    if not (fk[:, :2] != 0).all():
-        raise ValueError("render_depth_maps: intrinsics with a zero focal length")
+    h, w, near, far, pixel_offset, P, fk, _ = _camera_args("render_depth_maps", intrinsics, cam2world, size, near, far, pixel_offset, opengl)
+    T = P.shape[0]                                               # (the inverse is only computed for its checks)
     acc = _accel(m, grid, bvh, "grid", "render_depth_maps")
     dev = acc.vertices.device
     out = dict(depth=torch.empty((T, h, w), dtype=torch.float32, device=dev))
@@ -823,6 +875,129 @@ def render_depth_maps(m, intrinsics, cam2world, size, near=0.0, far=math.inf, gr
             stats.update((k, x) for k, x in acc.read_stats(ws).items() if k in stats)
     if return_stats:
         out["stats"] = stats
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ mesh visibility
+def ray_mesh_occluded(origins, directions, m, grid=None, t_min=0.0, t_max=math.inf, cull=None, method="grid", return_stats=False, bvh=None):
+    """Whether every ray hits ANYTHING on the surface of a mesh dict (include/spann3r_hip.h "Mesh visibility"; sp3_mesh_ray_occluded /
+    sp3_mesh_bvh_ray_occluded) -> bool [N] on the device, exactly ray_mesh_intersect(...)["face"] >= 0 for the same arguments -- a
+    pure function of the inputs -- at the cost of a walk that stops at the first hit and one byte per ray.  Arguments, their checks
+    and the choice of the structure are ray_mesh_intersect's; method="brute" (and a grid of one cell) IS ray_mesh_intersect's
+    brute-force route followed by the comparison.  return_stats: -> (the mask, stats as ray_mesh_intersect's).  A ray that hits
+    nothing walks what the closest-hit walk walks; only hits are cheaper."""
+    o, d, t_min, t_max = _ray_args("ray_mesh_occluded", origins, directions, t_min, t_max, cull, method)
+    acc = _accel(m, grid, bvh, method, "ray_mesh_occluded")
+    n = o.shape[0]
+    occluded = torch.empty(n, dtype=torch.bool, device=o.device)
+    stats = dict(cells_visited=0, faces_evaluated=0, **acc.stats())
+    if n > 0:
+        ws = acc.ray_occluded(o, d, t_min, t_max, _CULL[cull], occluded)
+        if return_stats and ws is not None:
+            stats.update((k, x) for k, x in acc.read_stats(ws).items() if k in stats)
+    return (occluded, stats) if return_stats else occluded
+
+
+def point_visibility(points, m, intrinsics, cam2world, size, near=0.0, far=math.inf, bias=1e-3, pixel_offset=0.0, opengl=False, cull=None,
+                     grid=None, bvh=None, return_mask=False, return_stats=False):
+    """How many of T cameras see every point fp32 [N, 3] (device) past the surface of a mesh dict, in ONE launch (include/
+    spann3r_hip.h "Mesh visibility"; sp3_mesh_point_views / sp3_mesh_bvh_point_views) -> dict(count int32 [N], views = T;
+    return_mask: mask bool [T, N]; return_stats: stats as ray_mesh_intersect's), device tensors.  A camera sees a point when the point lies in front
+    of it with near <= camera z <= far, projects into the image -- pixel centres at integer coordinates + pixel_offset, a pixel
+    reaching half a unit either side -- and the segment from the camera to the point hits no face between camera z = near and
+    (1 - bias) of the way.  bias is a RELATIVE DEPTH TOLERANCE, a convention and not an error bound: it drops the hit of a mesh's
+    vertex on its own faces (t = 1 to fp32 rounding); widen it for unwelded sheets that overlap within noise; it must lie in
+    [0, 1).  Surfaces in front of the near plane do not occlude, as render_depth_maps does not draw them.  A non-finite point is seen
+    by nobody.  Cameras (intrinsics, cam2world, size = (h, w), opengl) are render_depth_maps' and are refused as it refuses them.
+    cull: None, "back" or "front", which hits occlude (ray_mesh_intersect's).  grid / bvh: a TriangleGrid / TriangleBVH built on
+    this mesh (bvh=True builds one); the counts are the same bits either way.  For many views of a large mesh prefer bvh=: its walk
+    is the cheaper one per shadow ray (profiles/mesh_visibility.txt).  N = 0 or T = 0 launches nothing."""
+    h, w, near, far, pixel_offset, P, fk, w2c = _camera_args("point_visibility", intrinsics, cam2world, size, near, far, pixel_offset, opengl)
+    bias = float(bias)
+    if not (0.0 <= bias < 1.0) or not (0.0 <= float(np.float32(bias)) < 1.0):
+        raise ValueError("point_visibility: bias %r must lie in [0, 1)" % (bias,))
+    if cull not in _CULL:
+        raise ValueError("point_visibility: cull must be None, 'back' or 'front', got %r" % (cull,))
+    p = _dev(points, "point_visibility: points")
+    if p.dim() != 2 or p.shape[1] != 3 or p.dtype != torch.float32:
+        raise RuntimeError("point_visibility: points must be fp32 [N, 3], got %s %s" % (p.dtype, tuple(p.shape)))
+    p = p.contiguous()
+    acc = _accel(m, grid, bvh, "grid", "point_visibility", "no surface to hide behind")
+    T, n, dev = P.shape[0], p.shape[0], p.device
+    out = dict(count=torch.zeros(n, dtype=torch.int32, device=dev), views=T)
+    mask = torch.zeros((T, n), dtype=torch.uint8, device=dev) if return_mask else None
+    stats = dict(cells_visited=0, faces_evaluated=0, **acc.stats())
+    if T > 0 and n > 0:
+        table = (L.MeshVisView * T)()
+        for i in range(T):
+            e = table[i]
+            e.w, e.h = w, h
+            e.fu, e.fv, e.cu, e.cv = (float(x) for x in fk[i])
+            e.near, e.far = near, far
+            e.c2w[:] = P[i, :3].reshape(12).astype(np.float32).tolist()
+            e.w2c[:] = w2c[i].tolist()
+        table_d = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+        ws = acc.point_views(table, table_d, T, pixel_offset, bias, _CULL[cull], p, out["count"], mask)
+        if return_stats:
+            stats.update((k, x) for k, x in acc.read_stats(ws).items() if k in stats)
+    if return_mask:
+        out["mask"] = mask.bool()
+    if return_stats:
+        out["stats"] = stats
+    return out
+
+
+def vertex_visibility(m, intrinsics, cam2world, size, **kw):
+    """point_visibility of a mesh dict's own vertices against its own surface: count int32 [V] = the cameras that see each vertex"""
+    vertices, _, _ = _check_mesh(m, "vertex_visibility")
+    return point_visibility(vertices, m, intrinsics, cam2world, size, **kw)
+
+
+_VIS_MODE = {"any": 0, "all": 1}
+
+
+def cull_to_views(m, intrinsics, cam2world, size, near=0.0, far=math.inf, bias=1e-3, pixel_offset=0.0, opengl=False, cull=None, grid=None,
+                  bvh=None, mode="any", min_views=1, return_map=False):
+    """The part of a mesh that T cameras could see -- the cull_mesh step NICE-SLAM-style evaluations apply to both meshes before
+    accuracy and completion (include/spann3r_hip.h "Mesh visibility"): vertex_visibility, then a vertex is SEEN when at least
+    min_views cameras see it, and a face is kept when its indices are valid and (mode="any") one of its vertices or (mode="all") all
+    three are seen (sp3_mesh_vis_face_class, sp3_mesh_select_faces).  m is the dict scene_mesh / extract_mesh return; -> the same
+    kind of dict -- vertices, colors, faces, bounds recomputed (compact_vertices drops what no kept face names), everything else
+    carried as filter_components carries it -- plus visibility = dict(views, vertices_seen, faces_in, faces_kept); return_map: also
+    vertex_views int32 [V of the input] (the count per input vertex).  Kept faces and vertices stay in their order and rotation,
+    positions and colours bit for bit; everything culled gives an empty mesh, not an error; a cloud raises ValueError.  The camera
+    and structure arguments are point_visibility's.  Two host reads (the counts, compact_vertices' own) beyond the structure's."""
+    if mode not in _VIS_MODE:
+        raise ValueError("cull_to_views: mode must be 'any' or 'all', got %r" % (mode,))
+    min_views = int(min_views)
+    if min_views < 0:
+        raise ValueError("cull_to_views: min_views must be >= 0, got %r" % (min_views,))
+    vertices, rgba, faces = _check_mesh(m, "cull_to_views")
+    vis = point_visibility(vertices, m, intrinsics, cam2world, size, near=near, far=far, bias=bias, pixel_offset=pixel_offset, opengl=opengl,
+                           cull=cull, grid=grid, bvh=bvh)
+    count = vis["count"]
+    lib, nv, nf, dev = L.load(), vertices.shape[0], faces.shape[0], faces.device
+    cls = torch.empty(nf, dtype=torch.int32, device=dev)
+    L.check(lib.sp3_mesh_vis_face_class(faces.data_ptr(), nf, nv, L.ptr(count) if nv else 0, min_views, _VIS_MODE[mode], cls.data_ptr(),
+                                        L.stream_ptr()), "sp3_mesh_vis_face_class")
+    keep = torch.tensor([0, 1], dtype=torch.uint8, device=dev)
+    kept = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+    info = torch.zeros(2, dtype=torch.int32, device=dev)                  # [0]: faces kept, [1]: vertices seen
+    ws = _ws(lib.sp3_mesh_select_faces_ws_bytes(nf), dev)
+    L.check(lib.sp3_mesh_select_faces(faces.data_ptr(), cls.data_ptr(), nf, keep.data_ptr(), 2, ws.data_ptr(), kept.data_ptr(), info.data_ptr(),
+                                      L.stream_ptr()), "sp3_mesh_select_faces")
+    info[1] = (count >= min_views).sum()
+    nkept, seen = info.cpu().tolist()
+    kept = kept[:nkept]
+    # (`kept` is this function's own buffer, never the caller's faces: compact_vertices rewrites its indices in place)
+    pos, col, bounds = compact_vertices(vertices, rgba, faces=kept)
+    out = {k: v for k, v in m.items() if k not in ("vertices", "colors", "faces", "bounds", "visibility", "vertex_views")}
+    out.update(vertices=pos, faces=kept[:0] if pos.shape[0] == 0 else kept, bounds=bounds,
+               visibility=dict(views=vis["views"], vertices_seen=seen, faces_in=nf, faces_kept=nkept))
+    if "colors" in m:
+        out["colors"] = None if col is None else col.contiguous().view(torch.uint8).reshape(-1, 4)
+    if return_map:
+        out["vertex_views"] = count
     return out
 
 
