@@ -172,6 +172,11 @@ def main():
     ap.add_argument("--simplify", type=float, default=None, metavar="CELL", help="simplify the mesh by vertex clustering on a grid of CELL, in "
                     "the units of the pointmaps (mesh.simplify, on the device): with --fused the fused surface, after --min_component; with "
                     "--save_glb alone the per-frame sheets, which it welds into one vertex set; prints the faces before and after")
+    ap.add_argument("--smooth", type=int, default=0, metavar="N", help="with --fused: N rounds of Taubin's lambda|mu filter on the fused surface "
+                    "(mesh.smooth, on the device: boundary vertices fixed), after --min_component and before --simplify, --save_glb, --vis' "
+                    "fused.png and the fused --eval lines; --glb_normals are those of the smoothed positions")
+    ap.add_argument("--mesh_report", action="store_true", help="with --fused: print one line on the topology of every fused surface "
+                    "(mesh.topology, on the device): edges by class, Euler characteristic, closed or not")
     ap.add_argument("--simplify_voxels", type=float, default=None, metavar="K", help="with --fused: --simplify with a cell of K voxels")
     ap.add_argument("--eval_samples", type=int, default=None, metavar="N", help="with --fused --rgbd --eval: a second fused line from N points "
                     "drawn by area from each fused surface with their exact face normals (evaluate.evaluate_meshes), next to the line "
@@ -213,6 +218,10 @@ def main():
         ap.error("--min_component / --largest_component need --fused")
     if args.min_component < 0:
         ap.error("--min_component must be >= 0")
+    if (args.smooth or args.mesh_report) and not args.fused:
+        ap.error("--smooth / --mesh_report need --fused (a fused surface)")
+    if args.smooth < 0:
+        ap.error("--smooth must be >= 0")
     if args.simplify_voxels is not None and not args.fused:
         ap.error("--simplify_voxels needs --fused (a voxel size)")
     if args.simplify is not None and not (args.fused or args.save_glb):
@@ -298,7 +307,7 @@ def main():
               (end - start, len(batch) / (end - start), len(batch), it,
                ["eager warm-up", "hipGraph capture", "hipGraph replay"][min(it, 2)]))
     fuse_kw = dict(voxel_size=args.voxel_size, trunc_voxels=args.trunc_voxels, min_component_faces=args.min_component,
-                   keep_largest=1 if args.largest_component else None)
+                   keep_largest=1 if args.largest_component else None, smooth_iters=args.smooth)
     if args.simplify is not None:
         fuse_kw["simplify_cell"] = args.simplify
     elif args.simplify_voxels is not None and args.voxel_size:
@@ -310,6 +319,19 @@ def main():
             print("%s: simplified on a grid of %g: %d faces -> %d (%d collapsed, %d duplicate, %d invalid), %d clusters -> %d vertices" %
                   (what, s["cell"], s["faces_in"], 0 if fm["faces"] is None else fm["faces"].shape[0], s["faces_collapsed"], s["faces_duplicate"],
                    s["faces_invalid"], s["clusters"], fm["vertices"].shape[0]))
+
+    def report_topology(what, fm):
+        s = fm.get("smooth")
+        if s is not None:
+            print("%s: smoothed by %d rounds of lambda %g | mu %g, %d boundary vertices fixed" %
+                  (what, s["iterations"], s["lam"], s["mu"], s["fixed_vertices"]))
+        if args.mesh_report and fm.get("faces") is not None:
+            from spann3r_amd.mesh import topology
+            r = topology(fm).report
+            print("%s: %d edges (%d boundary, %d interior, %d inconsistent, %d non-manifold), %d usable faces (%d unusable), %d vertices "
+                  "referenced, Euler characteristic %d, %s" %
+                  (what, r["edges"], r["boundary"], r["interior"], r["inconsistent"], r["nonmanifold"], r["faces_usable"], r["faces_unusable"],
+                   r["vertices_referenced"], r["euler"], "closed" if r["closed"] else "open"))
 
     def report_components(what, fm):
         c = fm.get("components")
@@ -335,13 +357,15 @@ def main():
             fm, vol = fusion.fuse_sequence(preds, batch, focal=float(max(H, W)), poses=np.stack([np.eye(4)] * len(preds)), **kw)
         if args.simplify_voxels is not None and "simplify_cell" not in kw:      # no --voxel_size: the cell follows the volume's own voxel
             fm = dict(fm, **vol.extract_mesh(scale=kw.get("scale", 1.0), transform=kw.get("transform"), min_component_faces=args.min_component,
-                                             keep_largest=kw["keep_largest"], simplify_cell=args.simplify_voxels * vol.voxel_size))
+                                             keep_largest=kw["keep_largest"], simplify_cell=args.simplify_voxels * vol.voxel_size,
+                                             smooth_iters=args.smooth))
         if args.track:
             T = fm["corrections"][1:]
             ang = [math.degrees(math.acos(min(max((np.trace(t[:3, :3]) - 1) * 0.5, -1.0), 1.0))) for t in T]
             print("%d frames tracked of %d; largest correction %.3f degrees, %.3f voxels" %
                   (sum(fm["tracked"][1:]), len(T), max(ang, default=0.0), max((np.linalg.norm(t[:3, 3]) for t in T), default=0.0) / vol.voxel_size))
         report_components("fused surface", fm)
+        report_topology("fused surface", fm)
         report_simplify("fused surface", fm)
         return fm, vol
 
@@ -360,6 +384,8 @@ def main():
                                               torch.cat([v["camera_pose"] for v in batch]), a["masks_all"], a["images_all"], **fuse_kw)
             report_components("fused ground truth", gt_mesh)
             report_components("fused prediction", pred_mesh)
+            report_topology("fused ground truth", gt_mesh)
+            report_topology("fused prediction", pred_mesh)
             rf = evaluate_reconstruction(pred_mesh["vertices"], gt_mesh["vertices"], threshold=0.1)
             print("Fused: Acc: %s, Comp: %s, NC1: %s, NC2: %s  (prediction %d vertices / %d faces, ground truth %d vertices / %d faces)" %
                   (rf["acc"], rf["comp"], rf["nc1"], rf["nc2"], pred_mesh["vertices"].shape[0], pred_mesh["faces"].shape[0],

@@ -1606,6 +1606,72 @@ int sp3_mesh_bvh_point_views(const sp3_mesh_vis_view* views_host, const sp3_mesh
 int sp3_mesh_vis_face_class(const int32_t* faces, int64_t nfaces, int64_t nverts, const int32_t* count, int min_views, int mode,
                             int32_t* cls, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh topology and smoothing (spann3r_amd/mesh.py MeshTopology / topology / smooth drive these; csrc/mesh_topology.hip): the table
+ * of unique undirected edges of an indexed triangle mesh with their face incidences, the vertex adjacency derived from it, a
+ * manifold report, and Taubin's lambda|mu low-pass on top.  tests/mesh_topology_ref.py restates the rule in numpy; Open3D's
+ * filter_smooth_taubin is not available to test against (parity unpinned: the defaults 0.5 / -0.53 are its defaults).  No entry
+ * point allocates, frees or synchronises; `ws` is caller-provided device scratch of the matching sp3_*_ws_bytes(), 16-byte aligned.
+ * The two sorts between the entry points are the caller's (torch.sort(stable=True), as for TriangleGrid and TriangleBVH).  Every
+ * output is a pure function of the inputs: integer work, and fp64 sums in one fixed order.
+ *
+ * The rule.  Vertices 0..V-1, faces int32 [F, 3], V < 2^31 - 1, 3 F < 2^31.
+ *   Usable faces.  A face is USABLE when its three indices lie in 0..V-1 and are pairwise distinct (narrower than "Mesh components",
+ *     which accepts a == b: a self-edge has no meaning here).  An unusable face is never dereferenced.
+ *   Half-edges.  Usable face f has half-edges h = 3 f + c, c = 0, 1, 2, from a = face[c] to b = face[(c + 1) % 3]; lo = min(a, b),
+ *     hi = max(a, b); the half-edge is FORWARD when a < b.
+ *   Edge table.  The unique pairs (lo, hi) are the edges, numbered 0..E-1 in ascending (lo, hi) order.  Edge e has uses (its
+ *     half-edges), fwd (those that are forward) and the list of its half-edges in ascending h,
+ *     half_edges[edge_first[e] : edge_first[e + 1]]; its faces are h / 3.  edge_first[E] = 3 x the usable faces.
+ *   Edge class.  0 boundary: uses == 1.  1 interior: uses == 2 and fwd == 1.  2 inconsistent: uses == 2 and fwd is 0 or 2 (two faces
+ *     with the same winding along the edge; a duplicated face gives three).  3 non-manifold: uses > 2.
+ *   Vertex adjacency.  CSR: vertex_offsets int32 [V + 1], vertex_neighbors int32 [2 E]; row v holds the distinct vertices that share
+ *     an edge with v, ASCENDING.  vertex_boundary uint8 [V] = 1 iff v is an endpoint of a class-0 edge.
+ *   info int32 [16], ZERO on entry of sp3_mesh_edge_keys: [0] E, [1..4] the edges of class 0..3, [5] usable faces, [6] unusable faces,
+ *     [7] vertices with a non-empty row, [8] vertices with vertex_boundary = 1.  The report of mesh.py is one read of it:
+ *     euler = info[7] - E + info[5]; closed = (E > 0 and info[2] == E).
+ *   One smoothing pass with factor c (a double).  Vertex v with k > 0 neighbours n_0 < .. < n_{k-1} (its row) that is not fixed:
+ *     per component, in fp64, every operation rounded on its own (`#pragma clang fp contract(off)`, as csrc/tri_dist.h),
+ *       s = p[n_0];  s = s + p[n_1];  ..;  m = s / k;  out = fp32(p[v] + c * (m - p[v])).
+ *     A vertex with k = 0 or a fixed one (fixed uint8 [V], nullable: nothing fixed) copies its bits.  Positions between passes are
+ *     fp32 in ping-pong buffers: a pass never reads what it writes (out == positions is refused).  NaN and infinity propagate as
+ *     IEEE says; there are no special cases.  mesh.smooth: each of `iterations` rounds is pass(lam), then pass(mu) unless mu == 0.
+ * sp3_mesh_edge_keys : one lane per face writes keys int64 [3 F], keys[3 f + c] = ((lo << 31 | hi) << 1) | backward -- 63 bits -- or,
+ *   for an unusable face, three copies of 2^63 - 1, which lies above every real key; info[5] and info[6] are counted (integer adds
+ *   of wave popcounts).  The caller sorts the keys (stable) with the half-edge index as payload: equal pairs become one run, within
+ *   a run the forward entries come first, and equal keys keep ascending h.
+ * sp3_mesh_edge_table : keys / order int64 [nkeys] are the sorted keys and their payload (nkeys = 3 F).  Writes edges int32 [E, 2],
+ *   edge_first int32 [E + 1], edge_uses, edge_fwd int32 [E], edge_class uint8 [E], half_edges int32 [3 x usable], vertex_boundary
+ *   uint8 [V] and info[0..4], [7], [8]; every table has room for nkeys entries (edge_first: nkeys + 1), since E is not known to the
+ *   host.  With E = 0 nothing but vertex_boundary (zeros) and info is written.  Why each step is order-free:
+ *   - run heads (a real key whose key >> 1 differs from its predecessor's) are flagged, counted per 256-element tile, scanned by one
+ *     workgroup and scattered to offsets[tile] + rank: the head writes its pair and edge_first[e]; the last real element writes
+ *     edge_first[e + 1].  An element's edge is offsets[tile] + (heads of its tile up to and including itself) - 1, whether its
+ *     run began in its own tile or any number of tiles and scan chunks earlier: no lane walks a run.
+ *   - a later launch has one lane per edge: uses from edge_first, fwd by a binary search for the first backward entry of the run
+ *     (the sort put the forward ones first), the class, the class counts (integer adds of wave popcounts) and the flags of its two
+ *     vertices.  Several lanes may store to one flag; all store 1, and nothing reads a flag before the next launch.
+ *   - the sort leaves a run as two ascending lists of h, forward then backward.  A further launch, one lane per element, merges
+ *     them: an element's place is its place in its own list plus the entries of the other list below it (binary search), so that
+ *     the half-edges of an edge ascend.
+ *   - launch boundaries are the only hand-offs; no lane waits for another lane's store.  8 launches.
+ * sp3_mesh_adjacency_keys : one lane per edge writes keys int64 [2 E], (lo << 32) | hi and (hi << 32) | lo; 2 E < 2^31.  The caller
+ *   sorts them (they are distinct).
+ * sp3_mesh_adjacency_rows : lane i writes vertex_neighbors[i] = the low word of sorted key i and, for i <= V, vertex_offsets[i] =
+ *   the number of keys below i << 32 (binary search): rows ascend because the keys do.
+ * sp3_mesh_smooth_pass : one lane per vertex reads its two offsets and gathers its row in order; a row is never split over lanes,
+ *   which would change the order of the sum.  vertex_neighbors may be null when every row is empty. */
+int sp3_mesh_edge_keys(const int32_t* faces, int64_t nfaces, int64_t nverts, int64_t* keys, int32_t* info, void* stream);
+int64_t sp3_mesh_edge_table_ws_bytes(int64_t nkeys, int64_t nverts);
+int sp3_mesh_edge_table(const int64_t* keys, const int64_t* order, int64_t nkeys, int64_t nverts, void* ws, int32_t* edges,
+                        int32_t* edge_first, int32_t* edge_uses, int32_t* edge_fwd, uint8_t* edge_class, int32_t* half_edges,
+                        uint8_t* vertex_boundary, int32_t* info, void* stream);
+int sp3_mesh_adjacency_keys(const int32_t* edges, int64_t nedges, int64_t* keys, void* stream);
+int sp3_mesh_adjacency_rows(const int64_t* keys, int64_t nkeys, int64_t nverts, int32_t* vertex_offsets, int32_t* vertex_neighbors,
+                            void* stream);
+int sp3_mesh_smooth_pass(const float* positions, int64_t nverts, const int32_t* vertex_offsets, const int32_t* vertex_neighbors,
+                         const uint8_t* fixed, double factor, float* out, void* stream);
+
 /* small utilities */
 /* n (1..8) contiguous device-to-device copies in one launch; every copy 16-byte aligned and a multiple of 16 bytes.
  * (The sequence loop's per-frame bookkeeping -- torch .clone() / slice assignments around spann3r/model.py:523-531.) */

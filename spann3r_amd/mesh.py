@@ -429,6 +429,140 @@ def vertex_normals(m):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ mesh topology and smoothing
+_REPORT_KEYS = ("edges", "boundary", "interior", "inconsistent", "nonmanifold", "faces_usable", "faces_unusable", "vertices_referenced")
+_BOUNDARY_MODES = ("fixed", "free")
+
+
+class MeshTopology:
+    """The edge table and vertex adjacency of a mesh dict (include/spann3r_hip.h "Mesh topology and smoothing"): built once, reusable
+    while the faces do not change -- positions may move, which is what smooth(topology=) relies on.  A face is usable when its three
+    indices lie in 0..V-1 and are pairwise distinct; the unique pairs (lo, hi) of the usable faces' half-edges h = 3 f + c are the
+    edges, numbered in ascending (lo, hi) order.  Two stable sorts (the edge keys, the directed keys of the unique edges) and ten
+    launches; ONE host read, the 64 bytes behind `report`, between the two halves.  A cloud raises ValueError; F = 0, V = 0 or no
+    usable face give E = 0, empty tables, all-zero vertex_offsets and closed = False (F = 0 or V = 0 launch nothing).
+    Attributes, on the device: faces (the contiguous int32 [F, 3] it was built from), edges int32 [E, 2], edge_first int32 [E + 1],
+    half_edges int32 [3 x usable faces] (edge e: half_edges[edge_first[e] : edge_first[e + 1]], ascending; its faces are h // 3),
+    edge_uses, edge_fwd int32 [E], edge_class uint8 [E] (0 boundary, 1 interior, 2 inconsistent, 3 non-manifold), vertex_offsets
+    int32 [V + 1], vertex_neighbors int32 [2 E] (row v: the distinct neighbours of v, ascending), vertex_boundary uint8 [V].
+    On the host: n_vertices, n_faces, n_edges, boundary_vertices, report = dict(edges, boundary, interior, inconsistent,
+    nonmanifold, faces_usable, faces_unusable, vertices_referenced, euler = vertices_referenced - edges + faces_usable, closed =
+    every edge interior and E > 0)."""
+
+    def __init__(self, m):
+        vertices, _, faces = _check_mesh(m, "MeshTopology")
+        nv, nf, dev = vertices.shape[0], faces.shape[0], faces.device
+        if 3 * nf >= 2 ** 31:
+            raise ValueError("MeshTopology: %d faces: 3 F must stay below 2^31 (int32 half-edges)" % nf)
+        self.faces, self.n_vertices, self.n_faces = faces, nv, nf
+        i32 = dict(dtype=torch.int32, device=dev)
+        host = [0] * 9
+        host[6] = nf                                             # (V = 0: every face is unusable)
+        self.vertex_boundary = torch.zeros(nv, dtype=torch.uint8, device=dev)
+        if nf > 0 and nv > 0:
+            lib, n = L.load(), 3 * nf
+            keys = torch.empty(n, dtype=torch.int64, device=dev)
+            info = torch.zeros(16, **i32)
+            L.check(lib.sp3_mesh_edge_keys(faces.data_ptr(), nf, nv, keys.data_ptr(), info.data_ptr(), L.stream_ptr()), "sp3_mesh_edge_keys")
+            keys, order = torch.sort(keys, stable=True)
+            edges, first = torch.empty((n, 2), **i32), torch.empty(n + 1, **i32)
+            uses, fwd, half = torch.empty(n, **i32), torch.empty(n, **i32), torch.empty(n, **i32)
+            cls = torch.empty(n, dtype=torch.uint8, device=dev)
+            ws = _ws(lib.sp3_mesh_edge_table_ws_bytes(n, nv), dev)
+            L.check(lib.sp3_mesh_edge_table(keys.data_ptr(), order.data_ptr(), n, nv, ws.data_ptr(), edges.data_ptr(), first.data_ptr(),
+                                            uses.data_ptr(), fwd.data_ptr(), cls.data_ptr(), half.data_ptr(), self.vertex_boundary.data_ptr(),
+                                            info.data_ptr(), L.stream_ptr()), "sp3_mesh_edge_table")
+            host = info.cpu().tolist()[:9]                       # the one read
+        e, usable = host[0], host[5]
+        self.n_edges, self.boundary_vertices = e, host[8]
+        self.report = dict(zip(_REPORT_KEYS, host[:8]))
+        self.report.update(euler=host[7] - e + usable, closed=e > 0 and host[2] == e)
+        self.vertex_offsets = torch.zeros(nv + 1, **i32)
+        if e == 0:
+            self.edges, self.edge_first = torch.empty((0, 2), **i32), torch.zeros(1, **i32)
+            self.edge_uses, self.edge_fwd, self.half_edges, self.vertex_neighbors = (torch.empty(0, **i32) for _ in range(4))
+            self.edge_class = torch.empty(0, dtype=torch.uint8, device=dev)
+            return
+        if 2 * e >= 2 ** 31:
+            raise ValueError("MeshTopology: %d edges: 2 E must stay below 2^31 (int32 row offsets)" % e)
+        # (copies, so that the tables do not hold their 3 F capacity alive)
+        self.edges, self.edge_first, self.half_edges = edges[:e].clone(), first[:e + 1].clone(), half[:3 * usable].clone()
+        self.edge_uses, self.edge_fwd, self.edge_class = uses[:e].clone(), fwd[:e].clone(), cls[:e].clone()
+        dkeys = torch.empty(2 * e, dtype=torch.int64, device=dev)
+        L.check(lib.sp3_mesh_adjacency_keys(self.edges.data_ptr(), e, dkeys.data_ptr(), L.stream_ptr()), "sp3_mesh_adjacency_keys")
+        dkeys = torch.sort(dkeys, stable=True)[0]
+        self.vertex_neighbors = torch.empty(2 * e, **i32)
+        L.check(lib.sp3_mesh_adjacency_rows(dkeys.data_ptr(), 2 * e, nv, self.vertex_offsets.data_ptr(), self.vertex_neighbors.data_ptr(),
+                                            L.stream_ptr()), "sp3_mesh_adjacency_rows")
+
+    def matches(self, faces):
+        """True when this topology was built from exactly this face list (int32 [F, 3] on the device); compares the indices unless
+        it is the very tensor"""
+        if faces.shape != self.faces.shape or faces.device != self.faces.device:
+            return False
+        return faces.data_ptr() == self.faces.data_ptr() or bool(torch.equal(faces, self.faces))
+
+    def smooth_pass(self, positions, factor, fixed=None, out=None):
+        """sp3_mesh_smooth_pass: positions fp32 [V, 3] -> out (another buffer): every vertex with neighbours that `fixed` (uint8 [V] or
+        None) does not hold moves by factor x (mean of its row - itself), the row summed in its order in fp64.  No host read."""
+        if out is None:
+            out = torch.empty_like(positions)
+        if self.n_vertices > 0:
+            L.check(L.load().sp3_mesh_smooth_pass(positions.data_ptr(), self.n_vertices, self.vertex_offsets.data_ptr(),
+                                                  L.ptr(self.vertex_neighbors) if self.n_edges else 0, L.ptr(fixed), float(factor),
+                                                  out.data_ptr(), L.stream_ptr()), "sp3_mesh_smooth_pass")
+        return out
+
+
+def topology(m):
+    """MeshTopology(m): the edge table, the vertex adjacency and the manifold report of a mesh dict, on the device."""
+    return MeshTopology(m)
+
+
+def smooth(m, iterations=10, lam=0.5, mu=-0.53, boundary="fixed", topology=None):
+    """Taubin's lambda|mu low-pass on the vertices of a mesh dict (include/spann3r_hip.h "Mesh topology and smoothing"; Open3D's
+    filter_smooth_taubin has these defaults): each of `iterations` rounds is one pass with factor lam, then one with mu unless mu ==
+    0 (mu = 0: a plain Laplacian, which shrinks the surface; the negative step is what keeps its volume).  A pass moves every vertex
+    by factor x (the mean of its distinct neighbours - itself), uniform weights, summed in ascending neighbour order in fp64: the
+    same bits every run and for any order of the faces.  boundary="fixed" holds the end points of boundary edges where they are -- a
+    TSDF surface is open at the rim of what was observed, and the rim must not creep inward; "free" holds nothing.  Vertices no
+    usable face names do not move.  topology: a MeshTopology of these very faces (built when None); one built from another face
+    list raises ValueError.  -> the same kind of dict: colours, faces and every other key pass through, vertices are new (the
+    caller's are not written), bounds is recomputed, smooth = dict(iterations, lam, mu, boundary, fixed_vertices).  iterations = 0
+    returns the same bits.  Normals do not survive it: recompute vertex_normals.  Host reads: the topology's one, and the bounds.
+    A cloud raises ValueError."""
+    iterations, lam, mu = int(iterations), float(lam), float(mu)
+    if iterations < 0:
+        raise ValueError("smooth: iterations must be >= 0, got %d" % iterations)
+    if boundary not in _BOUNDARY_MODES:
+        raise ValueError("smooth: boundary must be one of %s, got %r" % (_BOUNDARY_MODES, boundary))
+    vertices, _, faces = _check_mesh(m, "smooth")
+    if topology is None:
+        topology = MeshTopology(dict(vertices=vertices, faces=faces))
+    elif not isinstance(topology, MeshTopology):
+        raise TypeError("smooth: topology must be a MeshTopology, got %s" % type(topology).__name__)
+    elif topology.n_vertices != vertices.shape[0] or topology.n_faces != faces.shape[0] or not topology.matches(faces):
+        raise ValueError("smooth: the topology was built from another mesh (%d vertices, %d faces; this one has %d, %d, or other indices)" %
+                         (topology.n_vertices, topology.n_faces, vertices.shape[0], faces.shape[0]))
+    fixed = topology.vertex_boundary if boundary == "fixed" else None
+    cur = vertices
+    if iterations > 0 and vertices.shape[0] > 0:
+        spare = [torch.empty_like(vertices), torch.empty_like(vertices)]      # ping-pong: the caller's buffer is only ever read
+        for factor in ([lam] if mu == 0.0 else [lam, mu]) * iterations:
+            cur = topology.smooth_pass(cur, factor, fixed, out=spare[0])
+            spare.reverse()
+    else:
+        cur = vertices.clone()
+    if cur.shape[0] > 0:
+        bounds = torch.stack([cur.amin(0), cur.amax(0)]).cpu().numpy().astype(np.float32)
+    else:
+        bounds = np.array([[np.inf] * 3, [-np.inf] * 3], np.float32)
+    out = {k: v for k, v in m.items() if k not in ("vertices", "bounds", "smooth")}
+    out.update(vertices=cur, bounds=bounds, smooth=dict(iterations=iterations, lam=lam, mu=mu, boundary=boundary,
+                                                        fixed_vertices=topology.boundary_vertices if fixed is not None else 0))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ mesh distance
 PAIRS_PER_FACE_CAP = 8          # (cell, face) references a TriangleGrid may hold per face before its cells are made larger
 FACES_PER_CELL = 0.5            # what cell_grid.choose_grid aims the cell edge at: a surface leaves most cells of its box empty
