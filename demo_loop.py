@@ -175,8 +175,12 @@ def main():
     ap.add_argument("--smooth", type=int, default=0, metavar="N", help="with --fused: N rounds of Taubin's lambda|mu filter on the fused surface "
                     "(mesh.smooth, on the device: boundary vertices fixed), after --min_component and before --simplify, --save_glb, --vis' "
                     "fused.png and the fused --eval lines; --glb_normals are those of the smoothed positions")
+    ap.add_argument("--fill_holes", type=int, default=0, metavar="N", help="with --fused: close every boundary loop of at most N >= 3 edges of the "
+                    "fused surface (mesh.fill_holes, on the device: a fan about the mean of the loop; the rim of what was observed is a long "
+                    "loop and stays open), after --min_component and before --smooth and --simplify")
     ap.add_argument("--mesh_report", action="store_true", help="with --fused: print one line on the topology of every fused surface "
-                    "(mesh.topology, on the device): edges by class, Euler characteristic, closed or not")
+                    "(mesh.topology, on the device): edges by class, Euler characteristic, closed or not; and one on its boundary loops "
+                    "(mesh.boundary_loops): loops, the longest, elements on open chains, irregular vertices")
     ap.add_argument("--simplify_voxels", type=float, default=None, metavar="K", help="with --fused: --simplify with a cell of K voxels")
     ap.add_argument("--eval_samples", type=int, default=None, metavar="N", help="with --fused --rgbd --eval: a second fused line from N points "
                     "drawn by area from each fused surface with their exact face normals (evaluate.evaluate_meshes), next to the line "
@@ -218,8 +222,10 @@ def main():
         ap.error("--min_component / --largest_component need --fused")
     if args.min_component < 0:
         ap.error("--min_component must be >= 0")
-    if (args.smooth or args.mesh_report) and not args.fused:
-        ap.error("--smooth / --mesh_report need --fused (a fused surface)")
+    if (args.smooth or args.mesh_report or args.fill_holes) and not args.fused:
+        ap.error("--smooth / --fill_holes / --mesh_report need --fused (a fused surface)")
+    if args.fill_holes != 0 and args.fill_holes < 3:
+        ap.error("--fill_holes must be 0 or >= 3 (the shortest loop)")
     if args.smooth < 0:
         ap.error("--smooth must be >= 0")
     if args.simplify_voxels is not None and not args.fused:
@@ -307,7 +313,7 @@ def main():
               (end - start, len(batch) / (end - start), len(batch), it,
                ["eager warm-up", "hipGraph capture", "hipGraph replay"][min(it, 2)]))
     fuse_kw = dict(voxel_size=args.voxel_size, trunc_voxels=args.trunc_voxels, min_component_faces=args.min_component,
-                   keep_largest=1 if args.largest_component else None, smooth_iters=args.smooth)
+                   keep_largest=1 if args.largest_component else None, smooth_iters=args.smooth, fill_holes=args.fill_holes)
     if args.simplify is not None:
         fuse_kw["simplify_cell"] = args.simplify
     elif args.simplify_voxels is not None and args.voxel_size:
@@ -321,17 +327,25 @@ def main():
                    s["faces_invalid"], s["clusters"], fm["vertices"].shape[0]))
 
     def report_topology(what, fm):
+        s = fm.get("fill")
+        if s is not None:
+            print("%s: %d of %d boundary loops of at most %d edges filled: %d vertices and %d faces added (%d boundary edges on open chains)" %
+                  (what, s["filled"], s["loops"], s["max_edges"], s["vertices_added"], s["faces_added"], s["open"]))
         s = fm.get("smooth")
         if s is not None:
             print("%s: smoothed by %d rounds of lambda %g | mu %g, %d boundary vertices fixed" %
                   (what, s["iterations"], s["lam"], s["mu"], s["fixed_vertices"]))
         if args.mesh_report and fm.get("faces") is not None:
-            from spann3r_amd.mesh import topology
-            r = topology(fm).report
+            from spann3r_amd.mesh import boundary_loops, topology
+            topo = topology(fm)
+            r = topo.report
             print("%s: %d edges (%d boundary, %d interior, %d inconsistent, %d non-manifold), %d usable faces (%d unusable), %d vertices "
                   "referenced, Euler characteristic %d, %s" %
                   (what, r["edges"], r["boundary"], r["interior"], r["inconsistent"], r["nonmanifold"], r["faces_usable"], r["faces_unusable"],
                    r["vertices_referenced"], r["euler"], "closed" if r["closed"] else "open"))
+            r = boundary_loops(fm, topo).report
+            print("%s: %d boundary edges in %d loops (the longest %d), %d on open chains, %d irregular boundary vertices" %
+                  (what, r["boundary"], r["loops"], r["longest"], r["open"], r["irregular_vertices"]))
 
     def report_components(what, fm):
         c = fm.get("components")
@@ -358,7 +372,7 @@ def main():
         if args.simplify_voxels is not None and "simplify_cell" not in kw:      # no --voxel_size: the cell follows the volume's own voxel
             fm = dict(fm, **vol.extract_mesh(scale=kw.get("scale", 1.0), transform=kw.get("transform"), min_component_faces=args.min_component,
                                              keep_largest=kw["keep_largest"], simplify_cell=args.simplify_voxels * vol.voxel_size,
-                                             smooth_iters=args.smooth))
+                                             smooth_iters=args.smooth, fill_holes=args.fill_holes))
         if args.track:
             T = fm["corrections"][1:]
             ang = [math.degrees(math.acos(min(max((np.trace(t[:3, :3]) - 1) * 0.5, -1.0), 1.0))) for t in T]

@@ -1672,6 +1672,86 @@ int sp3_mesh_adjacency_rows(const int64_t* keys, int64_t nkeys, int64_t nverts, 
 int sp3_mesh_smooth_pass(const float* positions, int64_t nverts, const int32_t* vertex_offsets, const int32_t* vertex_neighbors,
                          const uint8_t* fixed, double factor, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh boundary loops and hole filling (spann3r_amd/mesh.py BoundaryLoops / boundary_loops / fill_holes drive these;
+ * csrc/mesh_boundary.hip): the boundary edges of an edge table ("Mesh topology and smoothing") as ordered loops, and a fan over
+ * every loop of at most max_edges edges.  tests/mesh_boundary_ref.py restates the rule in numpy.  Unpinned: Open3D `fill_holes` /
+ * MeshLab are absent, nothing upstream fixes these numbers.  No entry point allocates, frees or synchronises; `ws` is
+ * caller-provided device scratch of the matching sp3_*_ws_bytes(), 16-byte aligned.  Integer work except the fp64 centroid sums;
+ * every output is a pure function of the inputs.
+ *
+ * The rule.  A mesh (vertices fp32 [V, 3], optional packed colours int32 [V], faces int32 [F, 3]) and the edge table of its faces.
+ *   Boundary elements.  The class-0 edges in ascending edge number are the elements j = 0..B-1, B = info[1] of the edge table (the
+ *     host has read it).  Element j has edge[j] = e, its one half-edge h[j] = half_edges[edge_first[e]], src[j] = faces[h / 3][h % 3]
+ *     and dst[j] = faces[h / 3][(h % 3 + 1) % 3]: the edge in the direction its face walks it.
+ *   Regular vertices, the successor.  A vertex is REGULAR when exactly one element leaves it (it is that element's src) and exactly
+ *     one enters it (dst).  next[j] = the element that leaves dst[j] if dst[j] is regular, else -1.  Bow-ties (two fans meeting in
+ *     one vertex), vertices on non-manifold edges and flipped windings are irregular; a chain ends there on purpose: nothing is
+ *     sorted by angle, nothing is guessed.
+ *   Cycles and chains.  next is injective on its domain -- next[j] = k makes dst[j] regular, so j is the only element entering
+ *     src[k] -- hence the elements fall into disjoint closed cycles and open simple chains; a chain never runs into a cycle.  A
+ *     closed cycle has at least 3 elements: a 1-cycle would be an edge from a vertex to itself (no usable face has one), a 2-cycle
+ *     two opposite half-edges on one vertex pair, which is one edge with two uses and so not of class 0.
+ *   Loops.  A closed cycle is a LOOP, its HEAD its smallest j; loops are numbered 0..L-1 by ascending head.  loop[j] = the number
+ *     of j's loop, rank[j] = the next-steps from the head to j; both -1 on an open chain.  CSR: loop_first int32 [L + 1],
+ *     loop_members int32 [loop_first[L]]; row l lists the loop's elements in walk order from the head.
+ *   info int32 [16], ZERO on entry of sp3_mesh_boundary_link: [0] B, [1] L, [2] elements on open chains, [3] irregular vertices (with
+ *     an element and not regular), [4] the longest loop (0 without one), [5] loop_first[L] = B - [2].
+ *   Filling with max_edges = n >= 3.  Every loop of length len <= n is filled, in loop order.  len == 3: one face (dst[m0], src[m0],
+ *     src[m2]) over its members m0, m1, m2 -- the boundary walk reversed, so the face is wound like its three neighbours -- and no
+ *     vertex.  len > 3: one new vertex c and len faces (dst[m], src[m], c) in member order.  New vertices follow V in loop order, new
+ *     faces follow F in (loop, rank) order; nothing that exists is rewritten.  Position of c per component, in fp64, every operation
+ *     rounded on its own (`#pragma clang fp contract(off)`, as sp3_mesh_smooth_pass):
+ *       s = p[src[m0]];  s = s + p[src[m1]];  ..;  c = fp32(s / len).
+ *     Colour of c, where there are colours, per byte channel in integers: (2 * sum + len) / (2 * len) (the mean, rounded half up).
+ *     Open chains and loops longer than n are never filled: that is how the observed rim of a fused surface stays open.
+ * sp3_mesh_boundary_elements : flags the class-0 edges, counts them per 256-element tile, scans, scatters (scan.h): writes edge /
+ *   half_edge / src / dst int32 [B], and per vertex vertex_out / vertex_in int32 [V] (the elements leaving / entering; integer
+ *   atomicAdds, order-free) and vertex_leave int32 [V] (an element that leaves it, -1 without one).  Several lanes may store to
+ *   vertex_leave[v] at an irregular vertex, with different values; the slot is only ever read where the counts say 1 and 1, where
+ *   one lane stored, and never before the next launch.  nboundary must be the table's info[1]; an element whose half-edge or
+ *   vertices are out of range (a table of another mesh) gets src = dst = -1 and links to nothing.  6 launches.
+ * sp3_mesh_boundary_link : one lane per element writes next; one lane per vertex counts the irregular ones into info[3].
+ * sp3_mesh_boundary_rounds : R = ceil(log2(max(B, 2))).
+ * sp3_mesh_boundary_rank : list ranking by pointer doubling.  state int32 [B, 4] per element: (ptr, label, steps, 0); after round k
+ *   ptr is the element 2^k steps ahead (-1: the chain ended within them), label the smallest element of the window of 2^k
+ *   elements that starts at j, steps the next-steps from j to the FIRST place the label stands at.  Round k reads one buffer and
+ *   writes the other (state and ws take turns so that round R - 1 lands in state): a round never reads what it writes.
+ *   new = (ptr[ptr], min label of the two windows, its steps (+ 2^k when it comes from the far window)); on EQUAL labels the near
+ *   window's steps stay -- once 2^k exceeds the length of a loop the window covers the head more than once, and rank needs the
+ *   first time.  After R rounds ptr == -1 exactly on open chains (no chain is longer than B <= 2^R) and label is the head on a
+ *   loop.  1 + R launches.
+ * sp3_mesh_boundary_loops : heads (label == j, ptr != -1) are flagged, counted, scanned (info[1] = L) and numbered; a loop's length
+ *   is steps + 1 of its head's successor next[head] -- no atomics, no walk; the lengths are scanned into loop_first (a grid of B + 1 lanes,
+ *   since L is not known to the host; info[5]); every element then writes loop, rank = (len - steps) % len and itself to
+ *   loop_members[loop_first[loop] + rank].  loop_first has room for B + 1 entries, loop_members for B.  7 launches.  The caller reads
+ *   info once afterwards and sizes the CSR.
+ * sp3_mesh_fill_count : one lane per loop decides len <= max_edges; two scans give vertex_at / face_at int32 [L] (the loop's new
+ *   vertex and first new face, counted from V and F; -1: none) and fill_info int32 [16], ZERO on entry: [0] vertices added, [1] faces
+ *   added, [2] loops filled.  4 launches.  The caller reads the totals and allocates.
+ * sp3_mesh_fill_emit : out_positions fp32 [V + added, 3], out_rgba int32 [V + added] (null with rgba null) and out_faces int32
+ *   [F + added, 3] already hold the mesh in front; one lane per loop with a centre adds its row in order (at most max_edges
+ *   members: the only sequential walk there is), one lane per member of a loop writes its face.  The caller's arrays are only read. */
+int64_t sp3_mesh_boundary_elements_ws_bytes(int64_t nedges);
+int sp3_mesh_boundary_elements(const int32_t* faces, int64_t nfaces, int64_t nverts, const uint8_t* edge_class, const int32_t* edge_first,
+                               const int32_t* half_edges, int64_t nedges, int64_t nboundary, void* ws, int32_t* edge, int32_t* half_edge,
+                               int32_t* src, int32_t* dst, int32_t* vertex_out, int32_t* vertex_in, int32_t* vertex_leave, void* stream);
+int sp3_mesh_boundary_link(const int32_t* dst, int64_t nboundary, const int32_t* vertex_out, const int32_t* vertex_in,
+                           const int32_t* vertex_leave, int64_t nverts, int32_t* next, int32_t* info, void* stream);
+int sp3_mesh_boundary_rounds(int64_t nboundary);
+int64_t sp3_mesh_boundary_rank_ws_bytes(int64_t nboundary);
+int sp3_mesh_boundary_rank(const int32_t* next, int64_t nboundary, void* ws, int32_t* state, void* stream);
+int64_t sp3_mesh_boundary_loops_ws_bytes(int64_t nboundary);
+int sp3_mesh_boundary_loops(const int32_t* next, const int32_t* state, int64_t nboundary, void* ws, int32_t* loop, int32_t* rank, int32_t* loop_first,
+                            int32_t* loop_members, int32_t* info, void* stream);
+int64_t sp3_mesh_fill_count_ws_bytes(int64_t nloops);
+int sp3_mesh_fill_count(const int32_t* loop_first, int64_t nloops, int64_t max_edges, void* ws, int32_t* vertex_at, int32_t* face_at,
+                        int32_t* info, void* stream);
+int sp3_mesh_fill_emit(const float* positions, const int32_t* rgba, int64_t nverts, int64_t nfaces, const int32_t* src, const int32_t* dst,
+                       const int32_t* loop, const int32_t* rank, const int32_t* loop_first, const int32_t* loop_members, int64_t nloops,
+                       int64_t nmembers, const int32_t* vertex_at, const int32_t* face_at, int64_t vertices_added, int64_t faces_added,
+                       float* out_positions, int32_t* out_rgba, int32_t* out_faces, void* stream);
+
 /* small utilities */
 /* n (1..8) contiguous device-to-device copies in one launch; every copy 16-byte aligned and a multiple of 16 bytes.
  * (The sequence loop's per-frame bookkeeping -- torch .clone() / slice assignments around spann3r/model.py:523-531.) */

@@ -269,7 +269,7 @@ class _Volume:
         return cap_v, cap_f, vertices, rgba, faces, counts
 
     def extract_mesh(self, min_weight=1.0, scale=1.0, transform=None, min_component_faces=0, keep_largest=None, simplify_cell=None,
-                     smooth_iters=0):
+                     smooth_iters=0, fill_holes=0):
         """The zero level as a welded mesh of the voxels seen with weight >= min_weight: dict(vertices fp32 [V, 3], colors uint8
         [V, 4], faces int32 [F, 3], bounds float32 numpy [2, 3]), the shape of mesh.scene_mesh; positions are transform (scale x).
         The counts are read once on the host; if the first guess of the capacities was too small the extraction runs once more with
@@ -287,7 +287,13 @@ class _Volume:
         unscaled vertices -- after the component filter, because a floater must not be smoothed into the surface, and before
         simplify_cell; scale / transform are applied afterwards, by simplify or by one more compaction.  With scale = 1 and no
         transform the result is mesh.smooth(extract_mesh(...), n); the dict also has smooth = dict(iterations, lam, mu, boundary,
-        fixed_vertices).  0: nothing of that runs."""
+        fixed_vertices).  0: nothing of that runs.
+        fill_holes = n >= 3: every boundary loop of at most n edges is closed (mesh.fill_holes: a fan about the mean of the loop, one
+        face for a loop of 3) -- after the component filter and the first compaction, and before smooth_iters, so that the filter
+        relaxes the fans (their centres are interior vertices: they move), and before simplify_cell; scale / transform are applied
+        afterwards, as for smooth_iters.  The rim of what was observed is a long loop and stays open.  With scale = 1 and no transform
+        the result is mesh.fill_holes(extract_mesh(...), n), then mesh.smooth, then mesh.simplify; the dict also has fill =
+        dict(max_edges, loops, filled, vertices_added, faces_added, open).  0: nothing of that runs."""
         if not min_weight > 0:
             raise ValueError("extract_mesh: min_weight must be > 0, got %r" % (min_weight,))
         if simplify_cell is not None and not (simplify_cell > 0 and math.isfinite(simplify_cell)):
@@ -296,6 +302,8 @@ class _Volume:
             raise ValueError("extract_mesh: min_component_faces %r and keep_largest %r must be >= 0" % (min_component_faces, keep_largest))
         if smooth_iters < 0:
             raise ValueError("extract_mesh: smooth_iters must be >= 0, got %r" % (smooth_iters,))
+        if fill_holes != 0 and fill_holes < 3:
+            raise ValueError("extract_mesh: fill_holes must be 0 or >= 3 (the shortest loop), got %r" % (fill_holes,))
         vertices, rgba, faces, counts = self.extract_raw(min_weight)
         nv, nf = counts.cpu().tolist()
         if nv > vertices.shape[0] or nf > faces.shape[0]:
@@ -307,18 +315,20 @@ class _Volume:
         stats = None
         if min_component_faces > 0 or keep_largest is not None:
             faces, stats = M.select_components(faces, nv, min_component_faces, keep_largest)
-        if simplify_cell is None and smooth_iters == 0:
+        if simplify_cell is None and smooth_iters == 0 and fill_holes == 0:
             pos, col, bounds = M.compact_vertices(vertices[:nv].contiguous(), rgba[:nv].contiguous(), faces=faces, scale=scale, transform=transform)
-        else:      # only the vertices the kept faces name enter a cluster or a row: compact first, unscaled, then smooth, cluster, scale / transform
+        else:      # only the vertices the kept faces name enter a cluster or a row: compact first, unscaled, then fill, smooth, cluster, scale / transform
             pos, col, bounds = M.compact_vertices(vertices[:nv].contiguous(), rgba[:nv].contiguous(), faces=faces)
         if pos.shape[0] == 0:
             faces = faces[:0]
         out = dict(vertices=pos, colors=col.contiguous().view(torch.uint8).reshape(-1, 4), faces=faces, bounds=bounds)
+        if fill_holes > 0:
+            out = M.fill_holes(out, fill_holes)
         if smooth_iters > 0:
             out = M.smooth(out, smooth_iters)
         if simplify_cell is not None:
             out = M.simplify(out, simplify_cell, origin=self.origin, scale=scale, transform=transform)
-        elif smooth_iters > 0 and (scale != 1.0 or transform is not None) and out["vertices"].shape[0] > 0:
+        elif (smooth_iters > 0 or fill_holes > 0) and (scale != 1.0 or transform is not None) and out["vertices"].shape[0] > 0:
             # (every vertex is named by a face: this compaction keeps them all, in order, and only applies scale / transform)
             pos, col, out["bounds"] = M.compact_vertices(out["vertices"], out["colors"].view(torch.int32).reshape(-1), faces=out["faces"].clone(),
                                                          scale=scale, transform=transform)
@@ -549,17 +559,17 @@ class BrickTSDFVolume(_Volume):
         return vertices[:cap_v], rgba[:cap_v], faces[:cap_f], counts
 
     def extract_mesh(self, min_weight=1.0, scale=1.0, transform=None, dims_limit=512, direct=False, min_component_faces=0,
-                     keep_largest=None, simplify_cell=None, smooth_iters=0):
+                     keep_largest=None, simplify_cell=None, smooth_iters=0, fill_holes=0):
         """direct=False: to_dense().extract_mesh(...), the surface of the allocated bricks' bounding box through the dense kernel (a box
         of more than dims_limit voxels on an axis raises).  direct=True: marching tetrahedra on the bricks themselves
         (sp3_tsdf_brick_extract) -- no dense intermediate, no limit on the extent, dims_limit ignored; the same surface as a set of
         triangles, its vertices and faces in pool-slot order and its positions from the virtual grid's own origin (the dense route
-        places them from the box's).  Capacities, the one retry, min_component_faces / keep_largest, simplify_cell, smooth_iters and the
-        dict are TSDFVolume.extract_mesh's, on both routes (the dense route clusters on the grid from the box's origin)."""
+        places them from the box's).  Capacities, the one retry, min_component_faces / keep_largest, simplify_cell, smooth_iters, fill_holes and
+        the dict are TSDFVolume.extract_mesh's, on both routes (the dense route clusters on the grid from the box's origin)."""
         if not direct:
             return self.to_dense(dims_limit=dims_limit).extract_mesh(min_weight, scale, transform, min_component_faces, keep_largest, simplify_cell,
-                                                                     smooth_iters)
-        return super().extract_mesh(min_weight, scale, transform, min_component_faces, keep_largest, simplify_cell, smooth_iters)
+                                                                     smooth_iters, fill_holes)
+        return super().extract_mesh(min_weight, scale, transform, min_component_faces, keep_largest, simplify_cell, smooth_iters, fill_holes)
 
 
 def _extent_box(extent):
@@ -763,17 +773,19 @@ class FusionSession:
         return self.volume.raycast(intrinsics, cam2world, size, **kw)
 
     def mesh(self, min_weight=1.0, scale=1.0, transform=None, dims_limit=512, direct=False, min_component_faces=0, keep_largest=None,
-             simplify_cell=None, smooth_iters=0):
+             simplify_cell=None, smooth_iters=0, fill_holes=0):
         """BrickTSDFVolume.extract_mesh of the model so far (direct=True: meshed on the bricks, whatever the extent;
         min_component_faces / keep_largest: without its floaters; simplify_cell: simplified by vertex clustering; smooth_iters:
-        smoothed by that many rounds of Taubin's filter before that)"""
+        smoothed by that many rounds of Taubin's filter before that; fill_holes: its boundary loops of at most that many edges closed
+        before that)"""
         return self.volume.extract_mesh(min_weight, scale, transform, dims_limit, direct, min_component_faces, keep_largest, simplify_cell,
-                                        smooth_iters)
+                                        smooth_iters, fill_holes)
 
 
 def fuse_sequence(preds, batch, conf_thresh=1e-3, voxel_size=None, dims_max=256, trunc_voxels=3.0, min_weight=1.0, scale=1.0,
                   transform=None, color=True, return_volume=False, focal=None, poses=None, track=False, return_poses=False, bricks=False,
-                  extent=None, direct_mesh=False, min_component_faces=0, keep_largest=None, simplify_cell=None, smooth_iters=0):
+                  extent=None, direct_mesh=False, min_component_faces=0, keep_largest=None, simplify_cell=None, smooth_iters=0,
+                  fill_holes=0):
     """The fused surface of a reconstruction from model.forward's `preds` and its `batch`: demo.py's own sequence -- the stacked
     pointmaps (mesh.sequence_tensors), the focal of frame 0 (estimate_focal_knowing_depth), one pose per frame (estimate_poses) --
     then the pointmaps of the pixels with (conf - 1) / conf > conf_thresh integrated through the `pts` path into a volume around
@@ -781,7 +793,7 @@ def fuse_sequence(preds, batch, conf_thresh=1e-3, voxel_size=None, dims_max=256,
     focal / poses (cam2world [t, 4, 4]) given: used instead of the estimates.  track / return_poses: as fuse_pointmaps (every frame
     after the first is registered to the model before it is integrated).  bricks / extent / direct_mesh: as fuse_pointmaps (a
     BrickTSDFVolume at voxel_size instead of the dense volume).  min_component_faces / keep_largest: as TSDFVolume.extract_mesh (the
-    floaters of the surface are dropped).  simplify_cell, smooth_iters: as TSDFVolume.extract_mesh.  Pointmaps without geometry (seeded random weights)
+    floaters of the surface are dropped).  simplify_cell, smooth_iters, fill_holes: as TSDFVolume.extract_mesh.  Pointmaps without geometry (seeded random weights)
     give a focal near 0: that raises rather than fusing through meaningless cameras."""
     from .postprocess import estimate_focal_knowing_depth, estimate_poses
     pts_all, images_all, conf_all = M.sequence_tensors(preds, batch)
@@ -802,12 +814,13 @@ def fuse_sequence(preds, batch, conf_thresh=1e-3, voxel_size=None, dims_max=256,
     return fuse_pointmaps(pts_all, K, np.asarray(poses, np.float64), valid, images_all, voxel_size, dims_max, trunc_voxels, min_weight, scale,
                           transform, color, return_volume, track, return_poses, bricks=bricks, extent=extent, direct_mesh=direct_mesh,
                           min_component_faces=min_component_faces, keep_largest=keep_largest, simplify_cell=simplify_cell,
-                          smooth_iters=smooth_iters)
+                          smooth_iters=smooth_iters, fill_holes=fill_holes)
 
 
 def fuse_pointmaps(pts_all, intrinsics, cam2world, valid, images=None, voxel_size=None, dims_max=256, trunc_voxels=3.0, min_weight=1.0,
                    scale=1.0, transform=None, color=True, return_volume=False, track=False, return_poses=False, track_args=None,
-                   bricks=False, extent=None, direct_mesh=False, min_component_faces=0, keep_largest=None, simplify_cell=None, smooth_iters=0):
+                   bricks=False, extent=None, direct_mesh=False, min_component_faces=0, keep_largest=None, simplify_cell=None, smooth_iters=0,
+                   fill_holes=0):
     """World pointmaps pts_all [t, h, w, 3] with their cameras, integrated through the `pts` path into a volume around the valid
     (and finite) points -> the mesh dict of TSDFVolume.extract_mesh (and the volume with return_volume).
     track=False: one integrate launch for all frames.  track=True: the KinectFusion sequence -- frame 0 is integrated; every later
@@ -820,7 +833,8 @@ def fuse_pointmaps(pts_all, intrinsics, cam2world, valid, images=None, voxel_siz
     extent = (lo, hi) when given -- the points are then not consulted at all, which is what a stream needs; the mesh comes from
     to_dense() of the allocated bricks' bounding box, which may have max(512, dims_max) voxels per axis, or with direct_mesh=True
     from the bricks themselves (BrickTSDFVolume.extract_mesh(direct=True): no such limit).
-    min_component_faces / keep_largest / simplify_cell / smooth_iters: as TSDFVolume.extract_mesh, whichever volume and route."""
+    min_component_faces / keep_largest / simplify_cell / smooth_iters / fill_holes: as TSDFVolume.extract_mesh, whichever volume and
+    route."""
     pts_all = _dev(pts_all, "fuse_pointmaps: pts_all").float()
     if pts_all.dim() != 4 or pts_all.shape[-1] != 3 or _dev(valid, "fuse_pointmaps: valid").shape != pts_all.shape[:3]:
         raise RuntimeError("fuse_pointmaps: mismatched shapes: pts_all %s must be [t, h, w, 3], valid %s [t, h, w]" %
@@ -858,19 +872,19 @@ def fuse_pointmaps(pts_all, intrinsics, cam2world, valid, images=None, voxel_siz
     if bricks:
         out = vol.extract_mesh(min_weight, scale, transform, dims_limit=max(512, dims_max), direct=direct_mesh,
                                min_component_faces=min_component_faces, keep_largest=keep_largest, simplify_cell=simplify_cell,
-                               smooth_iters=smooth_iters)
+                               smooth_iters=smooth_iters, fill_holes=fill_holes)
     else:
-        out = vol.extract_mesh(min_weight, scale, transform, min_component_faces, keep_largest, simplify_cell, smooth_iters)
+        out = vol.extract_mesh(min_weight, scale, transform, min_component_faces, keep_largest, simplify_cell, smooth_iters, fill_holes)
     if return_poses:
         out.update(poses=poses, corrections=corrections, tracked=tracked)
     return (out, vol) if return_volume else out
 
 
 def fuse_views(views, voxel_size=None, dims_max=256, trunc_voxels=3.0, min_weight=1.0, scale=1.0, transform=None, color=True,
-               return_volume=False, min_component_faces=0, keep_largest=None, simplify_cell=None, smooth_iters=0):
+               return_volume=False, min_component_faces=0, keep_largest=None, simplify_cell=None, smooth_iters=0, fill_holes=0):
     """The ground-truth surface of an RGB-D sequence: the views of views.build_views integrated through `depthmap`,
     `camera_intrinsics`, `camera_pose` and `valid_mask` into a volume around their valid `pts3d`.  -> as fuse_sequence
-    (min_component_faces / keep_largest / simplify_cell / smooth_iters: as TSDFVolume.extract_mesh).
+    (min_component_faces / keep_largest / simplify_cell / smooth_iters / fill_holes: as TSDFVolume.extract_mesh).
     Landscape views only: a portrait view rectified to landscape carries row-permuted intrinsics, which are refused as skewed."""
     if len(views) == 0:
         raise ValueError("fuse_views: no views")
@@ -890,5 +904,5 @@ def fuse_views(views, voxel_size=None, dims_max=256, trunc_voxels=3.0, min_weigh
             raise RuntimeError("fuse_views: img %s does not match depthmap %s" % (tuple(images.shape), tuple(depth.shape)))
     vol = volume_for_points(pts[valid], voxel_size, dims_max, trunc_voxels, color)
     vol.integrate(depth=depth, intrinsics=K, cam2world=poses, valid=valid, images=images)
-    out = vol.extract_mesh(min_weight, scale, transform, min_component_faces, keep_largest, simplify_cell, smooth_iters)
+    out = vol.extract_mesh(min_weight, scale, transform, min_component_faces, keep_largest, simplify_cell, smooth_iters, fill_holes)
     return (out, vol) if return_volume else out

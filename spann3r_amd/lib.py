@@ -342,6 +342,14 @@ _PROTOS = {
     "sp3_mesh_adjacency_keys": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
     "sp3_mesh_adjacency_rows": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     "sp3_mesh_smooth_pass": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p],
+    "sp3_mesh_boundary_elements": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_mesh_boundary_link": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_mesh_boundary_rank": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_mesh_boundary_loops": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_mesh_fill_count": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_mesh_fill_emit": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                           C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "sp3_render_tris": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(RenderCam), C.c_int,
                         C.c_void_p, C.c_void_p, C.c_void_p],
     "sp3_ssi_align_stats": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -377,7 +385,8 @@ EXPORTS = sorted(list(_PROTOS) + ["sp3_last_error", "sp3_version", "sp3_weight_s
                                   "sp3_tsdf_brick_extract_ws_bytes", "sp3_mesh_components_ws_bytes", "sp3_mesh_select_faces_ws_bytes",
                                   "sp3_mesh_cluster_ws_bytes", "sp3_mesh_cluster_faces_ws_bytes", "sp3_mesh_face_frames_ws_bytes",
                                   "sp3_mesh_vertex_normals_ws_bytes", "sp3_mesh_dist_query_ws_bytes", "sp3_mesh_ray_ws_bytes",
-                                  "sp3_mesh_edge_table_ws_bytes"])
+                                  "sp3_mesh_edge_table_ws_bytes", "sp3_mesh_boundary_elements_ws_bytes", "sp3_mesh_boundary_rounds",
+                                  "sp3_mesh_boundary_rank_ws_bytes", "sp3_mesh_boundary_loops_ws_bytes", "sp3_mesh_fill_count_ws_bytes"])
 
 
 def load():
@@ -412,7 +421,8 @@ def load():
     lib.sp3_tsdf_brick_extract_ws_bytes.argtypes = [C.c_int]
     for name in ("sp3_nn_query_ws_bytes", "sp3_icp_accum_ws_bytes", "sp3_sum_count_ws_bytes", "sp3_mesh_vertices_ws_bytes", "sp3_eval_align_ws_bytes",
                  "sp3_tsdf_track_accum_ws_bytes", "sp3_mesh_components_ws_bytes", "sp3_mesh_select_faces_ws_bytes", "sp3_mesh_face_frames_ws_bytes",
-                 "sp3_mesh_vertex_normals_ws_bytes", "sp3_mesh_dist_query_ws_bytes", "sp3_mesh_ray_ws_bytes"):
+                 "sp3_mesh_vertex_normals_ws_bytes", "sp3_mesh_dist_query_ws_bytes", "sp3_mesh_ray_ws_bytes", "sp3_mesh_boundary_elements_ws_bytes",
+                 "sp3_mesh_boundary_rank_ws_bytes", "sp3_mesh_boundary_loops_ws_bytes", "sp3_mesh_fill_count_ws_bytes"):
         getattr(lib, name).restype = C.c_int64
         getattr(lib, name).argtypes = [C.c_int64]
     for name in ("sp3_mesh_cluster_ws_bytes", "sp3_mesh_cluster_faces_ws_bytes"):
@@ -420,6 +430,8 @@ def load():
         getattr(lib, name).argtypes = [C.c_int64, C.c_int]
     lib.sp3_mesh_edge_table_ws_bytes.restype = C.c_int64
     lib.sp3_mesh_edge_table_ws_bytes.argtypes = [C.c_int64, C.c_int64]
+    lib.sp3_mesh_boundary_rounds.restype = C.c_int
+    lib.sp3_mesh_boundary_rounds.argtypes = [C.c_int64]
     for name, argtypes in _PROTOS.items():
         fn = getattr(lib, name)
         fn.restype = C.c_int

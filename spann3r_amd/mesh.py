@@ -519,6 +519,18 @@ def topology(m):
     return MeshTopology(m)
 
 
+def _own_topology(what, topology, vertices, faces):
+    """the MeshTopology of these very faces: built when None; one built from another face list raises ValueError"""
+    if topology is None:
+        return MeshTopology(dict(vertices=vertices, faces=faces))
+    if not isinstance(topology, MeshTopology):
+        raise TypeError("%s: topology must be a MeshTopology, got %s" % (what, type(topology).__name__))
+    if topology.n_vertices != vertices.shape[0] or topology.n_faces != faces.shape[0] or not topology.matches(faces):
+        raise ValueError("%s: the topology was built from another mesh (%d vertices, %d faces; this one has %d, %d, or other indices)" %
+                         (what, topology.n_vertices, topology.n_faces, vertices.shape[0], faces.shape[0]))
+    return topology
+
+
 def smooth(m, iterations=10, lam=0.5, mu=-0.53, boundary="fixed", topology=None):
     """Taubin's lambda|mu low-pass on the vertices of a mesh dict (include/spann3r_hip.h "Mesh topology and smoothing"; Open3D's
     filter_smooth_taubin has these defaults): each of `iterations` rounds is one pass with factor lam, then one with mu unless mu ==
@@ -537,13 +549,7 @@ def smooth(m, iterations=10, lam=0.5, mu=-0.53, boundary="fixed", topology=None)
     if boundary not in _BOUNDARY_MODES:
         raise ValueError("smooth: boundary must be one of %s, got %r" % (_BOUNDARY_MODES, boundary))
     vertices, _, faces = _check_mesh(m, "smooth")
-    if topology is None:
-        topology = MeshTopology(dict(vertices=vertices, faces=faces))
-    elif not isinstance(topology, MeshTopology):
-        raise TypeError("smooth: topology must be a MeshTopology, got %s" % type(topology).__name__)
-    elif topology.n_vertices != vertices.shape[0] or topology.n_faces != faces.shape[0] or not topology.matches(faces):
-        raise ValueError("smooth: the topology was built from another mesh (%d vertices, %d faces; this one has %d, %d, or other indices)" %
-                         (topology.n_vertices, topology.n_faces, vertices.shape[0], faces.shape[0]))
+    topology = _own_topology("smooth", topology, vertices, faces)
     fixed = topology.vertex_boundary if boundary == "fixed" else None
     cur = vertices
     if iterations > 0 and vertices.shape[0] > 0:
@@ -560,6 +566,123 @@ def smooth(m, iterations=10, lam=0.5, mu=-0.53, boundary="fixed", topology=None)
     out = {k: v for k, v in m.items() if k not in ("vertices", "bounds", "smooth")}
     out.update(vertices=cur, bounds=bounds, smooth=dict(iterations=iterations, lam=lam, mu=mu, boundary=boundary,
                                                         fixed_vertices=topology.boundary_vertices if fixed is not None else 0))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ mesh boundary loops and hole filling
+_LOOP_REPORT_KEYS = ("boundary", "loops", "open", "irregular_vertices", "longest")
+
+
+class BoundaryLoops:
+    """The boundary edges of a mesh dict as ordered loops (include/spann3r_hip.h "Mesh boundary loops and hole filling"): the class-0
+    edges of its MeshTopology (built when topology is None; a foreign one raises ValueError) are the elements 0..B-1 in ascending
+    edge number, each directed as its one face walks it; an element's successor is the element leaving its end vertex where exactly
+    one leaves and one enters, so bow-ties, non-manifold edges and flipped windings end a chain instead of being guessed through.
+    The closed cycles are the loops, numbered by their smallest element (the head); list ranking by pointer doubling,
+    ceil(log2(max(B, 2))) rounds of one launch each.  ONE host read after the last launch, the 64 bytes behind `report`; it sizes
+    the CSR.  B = 0 launches nothing and gives empty tables.  A cloud raises ValueError.
+    Attributes, on the device, int32: edge, half_edge, src, dst, next (-1: the chain ends), loop, rank (-1 on an open chain), all
+    [B]; loop_first [L + 1], loop_members [B - open] (row l: the elements of loop l in walk order from its head).  On the host:
+    topology, n_boundary, n_loops, rounds, report = dict(boundary, loops, open (elements on open chains), irregular_vertices,
+    longest (the longest loop, 0 without one))."""
+
+    def __init__(self, m, topology=None):
+        vertices, _, faces = _check_mesh(m, "BoundaryLoops")
+        topology = _own_topology("BoundaryLoops", topology, vertices, faces)
+        nv, nf, dev, b = vertices.shape[0], faces.shape[0], faces.device, topology.report["boundary"]
+        self.topology, self.n_boundary, self.rounds = topology, b, 0
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.edge, self.half_edge, self.src, self.dst, self.next, self.loop, self.rank = (torch.empty(b, **i32) for _ in range(7))
+        host = [0] * 5
+        if b > 0:
+            lib, e, st = L.load(), topology.n_edges, L.stream_ptr()
+            vout, vin, vleave = (torch.empty(nv, **i32) for _ in range(3))
+            info = torch.zeros(16, **i32)
+            ws = _ws(lib.sp3_mesh_boundary_elements_ws_bytes(e), dev)
+            L.check(lib.sp3_mesh_boundary_elements(faces.data_ptr(), nf, nv, topology.edge_class.data_ptr(), topology.edge_first.data_ptr(),
+                                                   topology.half_edges.data_ptr(), e, b, ws.data_ptr(), self.edge.data_ptr(),
+                                                   self.half_edge.data_ptr(), self.src.data_ptr(), self.dst.data_ptr(), vout.data_ptr(),
+                                                   vin.data_ptr(), vleave.data_ptr(), st), "sp3_mesh_boundary_elements")
+            L.check(lib.sp3_mesh_boundary_link(self.dst.data_ptr(), b, vout.data_ptr(), vin.data_ptr(), vleave.data_ptr(), nv,
+                                               self.next.data_ptr(), info.data_ptr(), st), "sp3_mesh_boundary_link")
+            self.rounds = int(lib.sp3_mesh_boundary_rounds(b))
+            state = torch.empty((b, 4), **i32)
+            ws_rank = _ws(lib.sp3_mesh_boundary_rank_ws_bytes(b), dev)
+            L.check(lib.sp3_mesh_boundary_rank(self.next.data_ptr(), b, ws_rank.data_ptr(), state.data_ptr(), st), "sp3_mesh_boundary_rank")
+            first, members = torch.empty(b + 1, **i32), torch.empty(b, **i32)
+            ws_loops = _ws(lib.sp3_mesh_boundary_loops_ws_bytes(b), dev)
+            L.check(lib.sp3_mesh_boundary_loops(self.next.data_ptr(), state.data_ptr(), b, ws_loops.data_ptr(), self.loop.data_ptr(), self.rank.data_ptr(),
+                                                first.data_ptr(), members.data_ptr(), info.data_ptr(), st), "sp3_mesh_boundary_loops")
+            host = info.cpu().tolist()[:6]                       # the one read
+            if host[0] != b or host[5] != b - host[2]:
+                raise RuntimeError("BoundaryLoops: %d elements, %d on open chains and %d on loops do not add up to B = %d" %
+                                   (host[0], host[2], host[5], b))
+            # (copies, so that the CSR does not hold its B + 1 capacity alive)
+            self.loop_first, self.loop_members = first[:host[1] + 1].clone(), members[:host[5]].clone()
+        else:
+            self.loop_first, self.loop_members = torch.zeros(1, **i32), torch.empty(0, **i32)
+        self.n_loops = host[1]
+        self.report = dict(zip(_LOOP_REPORT_KEYS, [b] + host[1:5]))
+
+
+def boundary_loops(m, topology=None):
+    """BoundaryLoops(m, topology): the boundary elements, their loops and the loop report of a mesh dict, on the device."""
+    return BoundaryLoops(m, topology)
+
+
+def fill_holes(m, max_edges, topology=None, loops=None):
+    """Closes every boundary loop of at most max_edges >= 3 edges of a mesh dict (include/spann3r_hip.h "Mesh boundary loops and hole
+    filling"): a loop of 3 gets one face, a longer one a new vertex at the mean of its vertices (summed in walk order in fp64; the
+    colour is the rounded integer mean per channel) and a fan of len faces, all wound like their neighbours.  New vertices follow the
+    old ones in loop order, new faces in (loop, rank) order.  Open chains (bow-ties, non-manifold or inconsistent neighbourhoods) and
+    longer loops stay open -- choose max_edges below the rim of what was observed.  loops: the BoundaryLoops of this mesh (built when
+    None, from `topology` when that is given); one of another face list raises ValueError.  -> the same kind of dict: vertices,
+    colors (when present) and faces are new tensors (the caller's are not written), bounds is unchanged (a mean lies inside the box
+    of its loop), normals are dropped (recompute vertex_normals), every other key passes through, fill = dict(max_edges, loops,
+    filled, vertices_added, faces_added, open).  With nothing to fill it returns equal bits.  Host reads: those of the topology and
+    the loops where they are built here, and one more of 64 bytes, the totals.  A cloud raises ValueError."""
+    max_edges = int(max_edges)
+    if max_edges < 3:
+        raise ValueError("fill_holes: max_edges must be >= 3 (the shortest loop), got %d" % max_edges)
+    vertices, rgba, faces = _check_mesh(m, "fill_holes")
+    if loops is None:
+        loops = BoundaryLoops(dict(vertices=vertices, faces=faces), topology)
+    elif not isinstance(loops, BoundaryLoops):
+        raise TypeError("fill_holes: loops must be a BoundaryLoops, got %s" % type(loops).__name__)
+    else:
+        _own_topology("fill_holes", loops.topology, vertices, faces)
+        if topology is not None and topology is not loops.topology:
+            _own_topology("fill_holes", topology, vertices, faces)
+    nv, nf, nl, dev = vertices.shape[0], faces.shape[0], loops.n_loops, faces.device
+    added_v = added_f = filled = 0
+    if nl > 0:
+        lib, st = L.load(), L.stream_ptr()
+        vertex_at, face_at = torch.empty(nl, dtype=torch.int32, device=dev), torch.empty(nl, dtype=torch.int32, device=dev)
+        info = torch.zeros(16, dtype=torch.int32, device=dev)
+        ws = _ws(lib.sp3_mesh_fill_count_ws_bytes(nl), dev)
+        L.check(lib.sp3_mesh_fill_count(loops.loop_first.data_ptr(), nl, min(max_edges, 2 ** 31 - 1), ws.data_ptr(), vertex_at.data_ptr(),
+                                        face_at.data_ptr(), info.data_ptr(), st), "sp3_mesh_fill_count")
+        added_v, added_f, filled = info.cpu().tolist()[:3]       # the one read
+    if nv + added_v >= 2 ** 31 - 1 or 3 * (nf + added_f) >= 2 ** 31:
+        raise ValueError("fill_holes: %d + %d vertices, %d + %d faces: the filled mesh must keep int32 indices and half-edges" %
+                         (nv, added_v, nf, added_f))
+    new_v = torch.empty((nv + added_v, 3), dtype=torch.float32, device=dev)
+    new_f = torch.empty((nf + added_f, 3), dtype=torch.int32, device=dev)
+    new_c = torch.empty(nv + added_v, dtype=torch.int32, device=dev) if rgba is not None else None
+    new_v[:nv].copy_(vertices)
+    new_f[:nf].copy_(faces)
+    if new_c is not None:
+        new_c[:nv].copy_(rgba)
+    if added_f > 0:
+        L.check(lib.sp3_mesh_fill_emit(vertices.data_ptr(), L.ptr(rgba), nv, nf, loops.src.data_ptr(), loops.dst.data_ptr(),
+                                       loops.loop.data_ptr(), loops.rank.data_ptr(), loops.loop_first.data_ptr(), loops.loop_members.data_ptr(),
+                                       nl, loops.loop_members.shape[0], vertex_at.data_ptr(), face_at.data_ptr(), added_v, added_f,
+                                       new_v.data_ptr(), L.ptr(new_c), new_f.data_ptr(), st), "sp3_mesh_fill_emit")
+    out = {k: v for k, v in m.items() if k not in ("vertices", "colors", "faces", "normals", "fill")}
+    out.update(vertices=new_v, faces=new_f)
+    if "colors" in m:
+        out["colors"] = None if new_c is None else new_c.view(torch.uint8).reshape(-1, 4)
+    out["fill"] = dict(max_edges=max_edges, loops=nl, filled=filled, vertices_added=added_v, faces_added=added_f, open=loops.report["open"])
     return out
 
 
