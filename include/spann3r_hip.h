@@ -282,6 +282,9 @@ int sp3_rope_2d(void* tokens, int dtype, int B, int N, int H, int D, int64_t sB,
  *                    the model: 16 mantissa bits per product, fp32 softmax and accumulation) |
  *   SP3_ATTN_F16X3 = fp32 operands with every product through three fp16 MFMAs of a split x = h + l * 2^-11 (the "f16x3" precision:
  *                    22 operand bits, every product exact in fp32; operands must stay below fp16's 65504).
+ * Pads: q rows beyond Nq and k rows beyond Nk inside the allocation are never read and may hold anything.  vt columns
+ * [Nk, Nk rounded up to 64) are read and multiplied by probabilities that are exactly zero: they may hold anything FINITE
+ * (0 * NaN and 0 * inf are NaN); columns beyond that up to vt_ld are never read.  Any scale, of either sign, is served.
  */
 int sp3_attention(const void* q, int64_t sq, int64_t ldq, const void* k, int64_t sk, int64_t ldk,
                   const void* vt, int64_t vt_ld, void* out, int64_t ldo, int out_bf16,
@@ -296,7 +299,12 @@ int sp3_attention_ex(const void* q, int64_t sq, int64_t ldq, const void* k, int6
  * matrices, head h of q at columns q_col0 + 64h (k: k_col0 + 64h); vtp as described at qkv_packed (vt_ld = npad_k).
  * out: fp32/bf16 row-major [B*Nq, ldo] or fragment order (out_packed).  o_group > 0: every o_group consecutive images form
  * one problem of a grouped launch whose output rows start at a multiple of o_group_rows (image b -> row
- * (b / o_group) * o_group_rows + (b % o_group) * Nq), so each problem's packed rows stay 16-aligned; 0: rows b * Nq. */
+ * (b / o_group) * o_group_rows + (b % o_group) * Nq), so each problem's packed rows stay 16-aligned; 0: rows b * Nq.
+ * Pads: q rows [Nq, npad_q) and k rows [Nk, npad_k) of an image may hold anything, NaN included -- a padded query's results are
+ * dropped, a padded key is taken out of the softmax by a select.  V of keys [Nk, Nk rounded up to 64) is multiplied by
+ * probabilities that are exactly zero and may hold anything FINITE (0 * NaN is NaN); V beyond that is never read.  Output rows
+ * other than the B * Nq defined ones (the rows [o_group * Nq, o_group_rows) of a group among them) are not written.
+ * scale > 0 is required: the kernel takes the tile maximum of the raw scores before it scales them. */
 int sp3_attention_packed(const void* qp, int q_cols, int q_col0, int npad_q, const void* kp, int k_cols, int k_col0, int npad_k,
                          const void* vtp, void* out, int64_t ldo, int out_bf16, int out_packed,
                          int B, int heads, int Nq, int Nk, float scale, int o_group, int o_group_rows, void* stream);
@@ -307,7 +315,8 @@ int sp3_attention_packed(const void* qp, int q_cols, int q_col0, int npad_q, con
  * bf16 copy of x, the producer's LayerNorm partials (folded norm2: ln_s = column sums of gamma (.) Wq, bias = bq + Wq beta) and the
  * fragment-order weight.  Images come in groups (the two decoder sides of a grouped launch): image b belongs to group b / o_group;
  * its rows are (b % o_group) * Nq + token inside the group's x / statistics / positions; the *_group_stride fields step from group
- * to group (elements of bf16, floats).  k / v / out arguments as sp3_attention_packed.  D = 768 (12 heads), Nq < 512. */
+ * to group (elements of bf16, floats).  k / v / out arguments as sp3_attention_packed, pads and scale > 0 included; rows of
+ * x_packed / ln_stats / pos beyond a group's o_group * Nq are never read.  D = 768 (12 heads), Nq < 512. */
 typedef struct sp3_attn_qproj_desc {
   const void* x_packed; int64_t x_group_stride;
   const float* ln_stats; int64_t stats_group_stride;   /* [rows][D / 32][2] */

@@ -901,6 +901,7 @@ extern "C" int sp3_attention_packed(const void* qp, int q_cols, int q_col0, int 
                                     int heads, int Nq, int Nk, float scale, int o_group, int o_group_rows, void* stream) {
   SP3_CHECK(qp && kp && vtp && out, "sp3_attention_packed: null pointer");
   SP3_CHECK(B > 0 && heads > 0 && Nq > 0 && Nk > 0, "sp3_attention_packed: bad shape");
+  SP3_CHECK(scale > 0.f, "sp3_attention_packed: scale=%g must be positive (the kernel takes the tile maximum of the raw scores)", (double)scale);
   SP3_CHECK(npad_q % 16 == 0 && npad_q >= ((Nq + 15) / 16) * 16 && npad_k % 64 == 0 && npad_k >= ((Nk + 63) / 64) * 64,
             "sp3_attention_packed: npad_q=%d / npad_k=%d do not cover Nq=%d / Nk=%d", npad_q, npad_k, Nq, Nk);
   SP3_CHECK(q_cols % 64 == 0 && k_cols % 64 == 0 && q_col0 % 64 == 0 && k_col0 % 64 == 0, "sp3_attention_packed: column geometry");
@@ -921,6 +922,7 @@ extern "C" int sp3_attention_packed_qproj(const sp3_attn_qproj_desc* dp, void* s
             "sp3_attention_packed_qproj: null pointer");
   SP3_CHECK(d.D == 768 && d.heads * 64 == d.D, "sp3_attention_packed_qproj: the decoder width (D = 768 = heads x 64) only, got D=%d heads=%d", d.D, d.heads);
   SP3_CHECK(d.B > 0 && d.Nq > 0 && d.Nk > 0 && d.Nq < 512, "sp3_attention_packed_qproj: bad shape (one query block per workgroup: Nq < 512)");
+  SP3_CHECK(d.scale > 0.f, "sp3_attention_packed_qproj: scale=%g must be positive (the kernel takes the tile maximum of the raw scores)", (double)d.scale);
   SP3_CHECK(d.npad_k % 64 == 0 && d.npad_k >= ((d.Nk + 63) / 64) * 64 && d.k_cols % 64 == 0 && d.k_col0 % 64 == 0, "sp3_attention_packed_qproj: key geometry");
   SP3_CHECK(d.out_packed || d.ldo % 4 == 0, "sp3_attention_packed_qproj: ldo");
   SP3_CHECK(d.o_group > 0 && d.B % d.o_group == 0 && d.o_group_rows >= d.o_group * d.Nq, "sp3_attention_packed_qproj: groups (images per decoder side)");

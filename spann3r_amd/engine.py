@@ -300,7 +300,11 @@ class Engine:
         cos, sin = rope_tab or (self.cos, self.sin)
         ln = ops.LnFold(st, C, w[pre + "qkv.s"], 1e-6)
         if self.packed_attn:
-            # fragment-order q/k (+ PV-order V) straight from the projection epilogue; zero pad rows are never written
+            # fragment-order q/k (+ PV-order V) straight from the projection epilogue, which never writes the pad rows.  zero=True
+            # clears a workspace when it is first allocated, not per call: the key is (name, shape, dtype), the shape is in npad, so
+            # a geometry with the same batch and npad (196 tokens, then 195) finds the previous one's rows in its pads.  That is
+            # within what the kernels allow (include/spann3r_hip.h, sp3_attention_packed: q / k pads may hold anything, V pads
+            # anything FINITE, which is what the first clearing is for); tests/test_attention_forms_gpu.py holds both ends.
             qkp = self.ws("qkp" + tag, ops.packed_shape(B * npad, 2 * A, self.wdt), self.wdt, zero=True)
             vtp = self.ws("vtp" + tag, (B * heads * npad * 64,), self.wdt, zero=True)
             ops.proj_rope_vt(xp, w[pre + "qkv.w"], w[pre + "qkv.b"], qkp, 0, vtp, npad, M=R, N=3 * A, K=C, lda=C,
