@@ -180,7 +180,11 @@ typedef struct sp3_gemm_desc {
    *   [B, res2_up_H, res2_up_W, N] and the residual added is its bilinear x2 (align_corners, the arithmetic of sp3_upsample2x), cropped to
    *   conv_OH x conv_OW (<= 2 res2_up_H x 2 res2_up_W) and rounded to the map dtype as the stored upsampled map would have been:
    *   FeatureFusionBlock's interpolate -> next block's `output + res` (croco/models/dpt_block.py:205-218) without the upsampled map in
-   *   memory.  sp3_gemm_plan answers -1 for any other kernel family. */
+   *   memory.  sp3_gemm_plan answers -1 for any other kernel family.
+   *   Rounding: the bilinear x2 is computed in fp32 (csrc/common.h up2x_taps / up2x_mix: the one arithmetic of every upsample kernel) and
+   *   rounded to the map dtype BEFORE it is added, so the residual is bit-equal to what sp3_upsample2x_bf16 would have stored; r1 + r2
+   *   are then added in fp32 and the sum is rounded once, at the store.  Against a float64 interpolation rounded to bf16 a fraction of a
+   *   per cent of the residual's elements therefore sit on the other bf16 neighbour (tests/gemm_desc_ref.py takes either). */
   int32_t res2_up_H, res2_up_W;
 } sp3_gemm_desc;
 int sp3_gemm(const sp3_gemm_desc* desc_host, void* stream);

@@ -54,32 +54,27 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const T* __restrict__ i
   pix /= outW;
   const int oy = (int)(pix % outH);
   const int b = (int)(pix / outH);
-  const int OH = 2 * H, OW = 2 * W;
-  const float sh = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
-  const float sw = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
-  const float fy = sh * (float)oy, fx = sw * (float)ox;
-  int y0 = (int)fy, x0 = (int)fx;
-  y0 = y0 < H - 1 ? y0 : H - 1;
-  x0 = x0 < W - 1 ? x0 : W - 1;
-  const int y1 = y0 < H - 1 ? y0 + 1 : y0, x1 = x0 < W - 1 ? x0 + 1 : x0;
-  const float ly = fy - (float)y0, lx = fx - (float)x0;
-  const float hy = 1.f - ly, hx = 1.f - lx;
+  // index clamps, weights and the association of the mix are spelled out once (common.h up2x_taps / up2x_mix: ATen's
+  // hy*(hx*v00 + lx*v01) + ly*(hx*v10 + lx*v11) with its fma contractions fixed), so that this kernel, the 16-byte bf16 kernel below and
+  // the epilogues that take the upsampled map as a residual give the same bits.  Left to the compiler, the contraction differed between
+  // the kernels and between the four channels of a thread (fma(hx, v00, lx*v01) here, fma(lx, v01, hx*v00) there): a last-bit
+  // difference in fp32 that a bf16 store turns into a whole step once in some 10^4 elements.
+  const Up2xTaps t = up2x_taps(H, W, oy, ox);
   const T* base = in + (int64_t)b * H * W * C;
-  const float4 v00 = ld4(base + (((int64_t)y0 * W + x0) * c4 + cc) * 4);
-  const float4 v01 = ld4(base + (((int64_t)y0 * W + x1) * c4 + cc) * 4);
-  const float4 v10 = ld4(base + (((int64_t)y1 * W + x0) * c4 + cc) * 4);
-  const float4 v11 = ld4(base + (((int64_t)y1 * W + x1) * c4 + cc) * 4);
+  const float4 v00 = ld4(base + ((int64_t)t.p00 * c4 + cc) * 4);
+  const float4 v01 = ld4(base + ((int64_t)t.p01 * c4 + cc) * 4);
+  const float4 v10 = ld4(base + ((int64_t)t.p10 * c4 + cc) * 4);
+  const float4 v11 = ld4(base + ((int64_t)t.p11 * c4 + cc) * 4);
   float4 o;
-  // same association as ATen's upsample_bilinear2d: hy*(hx*v00 + lx*v01) + ly*(hx*v10 + lx*v11)
-  o.x = hy * (hx * v00.x + lx * v01.x) + ly * (hx * v10.x + lx * v11.x);
-  o.y = hy * (hx * v00.y + lx * v01.y) + ly * (hx * v10.y + lx * v11.y);
-  o.z = hy * (hx * v00.z + lx * v01.z) + ly * (hx * v10.z + lx * v11.z);
-  o.w = hy * (hx * v00.w + lx * v01.w) + ly * (hx * v10.w + lx * v11.w);
+  o.x = up2x_mix(t, v00.x, v01.x, v10.x, v11.x);
+  o.y = up2x_mix(t, v00.y, v01.y, v10.y, v11.y);
+  o.z = up2x_mix(t, v00.z, v01.z, v10.z, v11.z);
+  o.w = up2x_mix(t, v00.w, v01.w, v10.w, v11.w);
   st4(out + idx * 4, o);
 }
 
 // bf16 maps with C % 8 == 0 (every map of the DPT heads): 8 channels = 16 bytes per thread, one output row per blockIdx.y (no
-// per-thread divisions by the image size), the same fp32 arithmetic per element as above (bit-identical results).  A pure
+// per-thread divisions by the image size), the same fp32 arithmetic per element as above (up2x_taps / up2x_mix: bit-identical results).  A pure
 // bandwidth kernel in front of a convolution: 224 x 224 x 128 went from 11.2 us (8-byte accesses) to the time below.
 __global__ __launch_bounds__(256) void upsample2x_bf16x8_kernel(const __bf16* __restrict__ in, __bf16* __restrict__ out, int H, int W,
                                                                 int C, int outH, int outW) {
@@ -88,25 +83,15 @@ __global__ __launch_bounds__(256) void upsample2x_bf16x8_kernel(const __bf16* __
   if (t >= outW * c8) return;
   const int ox = t / c8, cg = t - ox * c8;
   const int oy = blockIdx.y, b = blockIdx.z;
-  const int OH = 2 * H, OW = 2 * W;
-  const float sh = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
-  const float sw = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
-  const float fy = sh * (float)oy, fx = sw * (float)ox;
-  int y0 = (int)fy, x0 = (int)fx;
-  y0 = y0 < H - 1 ? y0 : H - 1;
-  x0 = x0 < W - 1 ? x0 : W - 1;
-  const int y1 = y0 < H - 1 ? y0 + 1 : y0, x1 = x0 < W - 1 ? x0 + 1 : x0;
-  const float ly = fy - (float)y0, lx = fx - (float)x0;
-  const float hy = 1.f - ly, hx = 1.f - lx;
+  const Up2xTaps tp = up2x_taps(H, W, oy, ox);
   const __bf16* base = in + (int64_t)b * H * W * C + cg * 8;
-  const bf16x8 v00 = *reinterpret_cast<const bf16x8*>(base + ((int64_t)y0 * W + x0) * C);
-  const bf16x8 v01 = *reinterpret_cast<const bf16x8*>(base + ((int64_t)y0 * W + x1) * C);
-  const bf16x8 v10 = *reinterpret_cast<const bf16x8*>(base + ((int64_t)y1 * W + x0) * C);
-  const bf16x8 v11 = *reinterpret_cast<const bf16x8*>(base + ((int64_t)y1 * W + x1) * C);
+  const bf16x8 v00 = *reinterpret_cast<const bf16x8*>(base + (int64_t)tp.p00 * C);
+  const bf16x8 v01 = *reinterpret_cast<const bf16x8*>(base + (int64_t)tp.p01 * C);
+  const bf16x8 v10 = *reinterpret_cast<const bf16x8*>(base + (int64_t)tp.p10 * C);
+  const bf16x8 v11 = *reinterpret_cast<const bf16x8*>(base + (int64_t)tp.p11 * C);
   bf16x8 o;
 #pragma unroll
-  for (int e = 0; e < 8; ++e)
-    o[e] = (__bf16)(hy * (hx * (float)v00[e] + lx * (float)v01[e]) + ly * (hx * (float)v10[e] + lx * (float)v11[e]));
+  for (int e = 0; e < 8; ++e) o[e] = (__bf16)up2x_mix(tp, (float)v00[e], (float)v01[e], (float)v10[e], (float)v11[e]);
   st_out(reinterpret_cast<bf16x8*>(out + (((int64_t)b * outH + oy) * outW + ox) * C + cg * 8), o);
 }
 

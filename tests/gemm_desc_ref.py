@@ -459,6 +459,13 @@ class Case:
                 B["res2"].body.copy_(r.reshape(-1))
                 up = upsample2x(r.double(), g("conv_OH"), g("conv_OW"))
                 self.res[2] = bf(up.float()).double().reshape(1, M, N)          # rounded to the map dtype as the stored map would be
+                # the kernel interpolates in fp32 and then rounds: where the float64 value lies within the fp32 interpolation bound of a
+                # bf16 rounding boundary its residual may be either neighbour.  res2_alt: what to add to expected() for the other
+                # candidates (zero on every one-candidate element); res2_two: the share of two-candidate elements
+                import conv_ref
+                lo, hi, two = conv_ref.bf16_candidates(up, conv_ref.upsample_bound(r, g("conv_OH"), g("conv_OW")))
+                self.res2_alt = [(c.double().reshape(1, M, N) - self.res[2]) for c in (lo, hi)]
+                self.res2_two = float(two.float().mean())
             else:
                 ld = g("ldr%d" % i)
                 r = (rnd(G, M, N) * 2 + 0.3 * i).to(rdt)
@@ -709,10 +716,10 @@ ZOUT_BOUNDS = (("kept mass", 1e-5), ("row max", 1e-6), ("1/Z", 1e-5))      # tes
                                                                           # because the builder keeps every probability clear of the threshold
 
 
-def bf16_excess(got, ref, width=32):
+def bf16_excess_map(got, ref, width=32):
     """a bf16-stored output against the unrounded reference, element by element: a correctly rounded store of an fp32-accumulated value
-    lies within half a bf16 step of the reference plus 2e-5 of its 32-column group's largest value.  Returns the worst
-    |got - ref| / bound (pass: <= 1), so small elements are held as tightly as large ones."""
+    lies within half a bf16 step of the reference plus 2e-5 of its 32-column group's largest value.  Returns |got - ref| / bound per
+    element (pass: <= 1), so small elements are held as tightly as large ones."""
     got, ref = got.double().reshape(-1, got.shape[-1]), ref.double().reshape(-1, ref.shape[-1])
     n = ref.shape[1]
     nt = (n + width - 1) // width
@@ -720,7 +727,21 @@ def bf16_excess(got, ref, width=32):
     slack = 2e-5 * gmax.repeat_interleave(width)[:n][None]
     mag = (ref.abs() + slack).clamp_min(1e-38)
     half_step = torch.exp2(torch.floor(torch.log2(mag)) - 8)
-    return float(((got - ref).abs() / (half_step + slack)).max())
+    return (got - ref).abs() / (half_step + slack)
+
+
+def bf16_excess(got, ref, width=32):
+    """the worst element of bf16_excess_map"""
+    return float(bf16_excess_map(got, ref, width).max())
+
+
+def conv_bf16_excess(case, z, got, ref):
+    """bf16_excess of a convolution output; with a half-resolution res2 every element takes the smaller error over the candidates of its
+    upsampled residual (Case.res2_alt)"""
+    ex = bf16_excess_map(got, ref)
+    for alt in getattr(case, "res2_alt", ()):
+        ex = torch.minimum(ex, bf16_excess_map(got, ref + alt[z]))
+    return float(ex.max())
 
 
 def block_errors(got, ref, width=32):
@@ -762,11 +783,19 @@ def compare(case):
             note(name, blk)
             if not (blk < tol and allv < tol):
                 fails.append("%s[%d]: per 32-column group %.3e, whole %.3e (bound %.1e)" % (name, z, blk, allv, tol))
-            if o.dtype == BF and case.loader != LOAD_SOFTMAX:
-                # reported, not asserted: on the device five small-map convolution rows with bf16 residual maps (table lines 21, 25, 45,
-                # 75, 183; tiles 40 / 41) sit 7 .. 49 x outside this elementwise bound while inside the family's 4e-3 -- an open
-                # question about the rounding point of the residual sum, recorded by SP3_CENSUS_REPORT until it is answered
-                note(name + " bf16 steps", bf16_excess(o, e))
+            if o.dtype == BF and case.loader == LOAD_CONV3X3 and name == "C":
+                # asserted.  Five small-map rows with a half-resolution res2 (table lines 21, 25, 45, 75, 183; tiles 40 / 41) used to sit
+                # 7 .. 49 x outside this bound.  The cause was in this reference, not in the kernel: conv_sm_body adds r1 + r2 in fp32 and
+                # rounds once at the store, but it interpolates the half-resolution residual in fp32 and rounds THAT to bf16 (bit-equal to
+                # sp3_upsample2x_bf16 into memory), where the reference interpolated in float64 and rounded -- a fraction of a per cent of
+                # the elements land on the other bf16 neighbour, a whole step of the residual (tests/test_conv_ref_cpu.py reproduces it).
+                # Such elements now have two candidates: conv_bf16_excess.
+                ex = conv_bf16_excess(case, z, o, e)
+                note(name + " bf16 steps", ex)
+                if not ex <= 1.0:
+                    fails.append("%s[%d]: %.2f x the elementwise bf16 bound" % (name, z, ex))
+            elif o.dtype == BF and case.loader != LOAD_SOFTMAX:
+                note(name + " bf16 steps", bf16_excess(o, e))                     # reported (SP3_CENSUS_REPORT), not asserted
         # outputs derived from the finished C: the fragment-order copy bit for bit, the statistics from the stored values
         cf = cg.double()
         if "c2" in got and not torch.equal(got["c2"][z], cg.to(case.wdt)):
@@ -787,5 +816,9 @@ def compare(case):
             note("sm_stats_out", max(e0, e1))
             if not (e0 < 1e-6 and e1 < 1e-5):
                 fails.append("sm_stats_out: max %.3e, sum exp %.3e" % (e0, e1))
+    if hasattr(case, "res2_two"):
+        errs["res2_up two-candidate share"] = case.res2_two
+        if not case.res2_two <= 0.01:
+            fails.append("res2_up: %.4f of the elements have two candidates (cap 1 %%)" % case.res2_two)
     fails += ["sentinel: " + s for s in case.sentinel_faults()]
     return fails, errs

@@ -1,7 +1,9 @@
 """Replay of the launch census: every row of tests/golden/gemm_plan_table.jsonl -- every distinct auto-tile GEMM launch the model
 issues -- is built by tests/gemm_desc_ref.py (guard bands, poisoned slack, non-minimal strides), launched with tile = -1 through
 sp3_gemm / sp3_gemm_n, and every output compared with the float64 reference of the descriptor: whole-output max norm AND per problem
-and 32-column group.  The plan of the real descriptor must still be the recorded tile.  Rows recorded with the lean instances off run
+and 32-column group; a bf16 convolution output also per element, within half a bf16 step (gemm_desc_ref.conv_bf16_excess: a half-resolution
+res2 may round to either bf16 neighbour where its float64 value lies within the fp32 interpolation bound of a rounding boundary, on at
+most 1 % of a row).  The plan of the real descriptor must still be the recorded tile.  Rows recorded with the lean instances off run
 in one child process (SP3_LEAN_GEMM is read once per process).  test_census_is_current keeps the table honest: a model launch that is
 not a row of it fails there."""
 import ctypes as C

@@ -328,3 +328,49 @@ def test_compare_holds_each_softmax_row_quantity_and_each_bf16_element():
     assert R.bf16_excess(o, e) <= 1.0 and R.block_errors(o, e)[0] < 4e-3
     o[7, 40] = (o[7, 40].float() * (1 + 2.0 ** -7)).to(BF)                            # one step, in a small element of a small group
     assert R.bf16_excess(o, e) > 1.5 and R.block_errors(o, e)[1] < 4e-3
+
+
+UP_ROWS = [(ln, r) for ln, r in ROWS if r["descs"][0].get("res2_up_H")]
+
+
+def test_res2_up_rows_are_the_five():
+    assert [ln for ln, _ in UP_ROWS] == [21, 25, 45, 75, 183]
+    assert all(r["descs"][0].get("loader") == R.LOAD_CONV3X3 and r["descs"][0].get("out_bf16") and r["descs"][0].get("res_bf16") for _, r in UP_ROWS)
+
+
+@pytest.mark.parametrize("line,row", UP_ROWS, ids=["L%d" % ln for ln, _ in UP_ROWS])
+def test_res2_up_row_takes_either_rounding_of_the_upsampled_residual(line, row):
+    """the answer to the census's open question, without a GPU.  An output built the way the kernel builds it -- the half-resolution
+    residual interpolated in fp32 (conv_ref.emulate_upsample: sp3_upsample2x's arithmetic) and rounded to bf16, everything else exact,
+    one rounding at the store -- is several times outside the elementwise bf16 bound against the float64-interpolated residual alone,
+    and inside it once an element within the fp32 interpolation bound of a rounding boundary may take either neighbour.  At most 1 %
+    of a row's elements have two candidates."""
+    import conv_ref as CR
+    c = R.row_cases(row, line)[0].materialize("cpu")
+    f = c.f
+    r = c.bufs["res2"].body.view(c.cB, f["res2_up_H"], f["res2_up_W"], c.N)
+    kernel_res2 = CR.emulate_upsample(r, f["conv_OH"], f["conv_OW"]).to(BF).double().reshape(c.M, c.N)
+    exp = c.expected()["C"][0]
+    out = (exp - c.res[2][0] + kernel_res2).float().to(BF)
+    c.got()["C"][0].copy_(out)
+    flips = int((kernel_res2 != c.res[2][0]).sum())
+    alone = R.bf16_excess(out, exp)
+    fails, errs = R.compare(c)
+    print("line %d: %d of %d residual elements on the other neighbour; alone %.1f x the bound, with candidates %.3f x; two-candidate share %.4f"
+          % (line, flips, out.numel(), alone, errs["C bf16 steps"], c.res2_two))
+    assert flips > 0 and alone > 3.0
+    assert fails == [] and errs["C bf16 steps"] <= 1.0 and 0 < c.res2_two <= 0.01
+    # the candidate rule is no licence: the residual's NEXT neighbour on a two-candidate element, or the other neighbour on a
+    # one-candidate element, still fails
+    lo, hi = (c.res[2] + c.res2_alt[0])[0], (c.res[2] + c.res2_alt[1])[0]
+    i = int(((hi - lo) / (exp.abs() + 1e-3)).reshape(-1).argmax())         # (a two-candidate element whose residual step is large next to the output)
+    bad = out.clone().reshape(-1)
+    step = float(hi.reshape(-1)[i] - lo.reshape(-1)[i])
+    bad[i] = (exp.reshape(-1)[i] - c.res[2][0].reshape(-1)[i] + hi.reshape(-1)[i] + step).float().to(BF)
+    c.got()["C"][0].copy_(bad.view_as(out))
+    assert any("elementwise bf16 bound" in s for s in R.compare(c)[0])
+    j = int(((lo == hi) & (exp.abs() > 0.5)).reshape(-1).nonzero()[0])
+    bad = out.clone().reshape(-1)
+    bad[j] = (bad[j].float() * (1 + 2.0 ** -7)).to(BF)
+    c.got()["C"][0].copy_(bad.view_as(out))
+    assert any("elementwise bf16 bound" in s for s in R.compare(c)[0])
