@@ -7,8 +7,14 @@
 // masked K tail path, epilogues that branch on a dozen options.  Here everything a shape fixes is a template constant:
 //   * K (k-blocks), tile and wave count are compile-time; the grid is 3-D (x = XCD, y = M-tile, z = group x N-tile / 8), so the
 //     tile map needs no division and the M-tiles that share a weight panel still land on one XCD, adjacent in dispatch order;
-//   * K is split over ALL waves of the workgroup (4..16) and a wave requests every operand byte it will ever need before its
-//     first MFMA (or keeps a RING of k-blocks in flight when K is long): one cold round trip per launch;
+//   * K is split over ALL waves of the workgroup (4..16) and a wave is MEANT to request every operand byte it will ever need before
+//     its first MFMA: one cold round trip per launch.  The source order alone does not give that -- the compiler's scheduler sinks
+//     the loads between the MFMAs to save registers (tools/issue_order.py shows what a build holds in flight;
+//     profiles/sm_issue_order.txt).  The 8-wave instances that run one workgroup per CU pin the order with scheduling fences and
+//     plan for 2 waves per SIMD (WD / AD below): tiles 35 / 37 (K = 4096 / 3072) keep the wave's whole W walk and an A ring of 3
+//     k-blocks in flight, 44 / 42 loads, A ring queued first; tiles 30 / 32 queue both k-blocks of A, then of W.  The other
+//     instances are left to the scheduler (14-19 of 22-36 loads ahead of the first MFMA): the 4-wave ones need 3-7 workgroups per CU
+//     and lose more to the registers than they gain (profiles/sm_issue_order_ab.txt);
 //   * the tile is chosen per shape so that the launch is ONE round of <= ~2 workgroups per CU with the fewest operand bytes
 //     through the CUs' vector caches (the K loop is bound by L2 -> CU bytes at ~35 B/clk/CU, not by HBM or the MFMAs);
 //   * every epilogue operand (bias, LayerNorm column sums and row statistics, residual rows, RoPE positions and table rows)
@@ -58,8 +64,14 @@ struct SmArgs {
 // SPLIT: A = [A | A2] along K (torch.cat(..., dim=-1) without the copy, spann3r/model.py:300): k-blocks [0, nkb1) come from A (a
 // fragment-order [M, 64 nkb1] matrix), the rest from A2 ([M, 64 (NKB - nkb1)])
 // WS: W goes through the streaming cache policy (common.h ld_w16); A and every epilogue operand keep the default one
-template <int MF, int NF, int WK, int NKB, int RING, int EPI, bool SPLIT = false, bool WS = false>
-__global__ __launch_bounds__(64 * WK) void sm_kernel(const SmArgs a) {
+// WD / AD > 0 (instances that run one 8-wave workgroup per CU): separate depths for the two operands -- WD k-blocks of W (cold, read
+// once; WD >= k-blocks per wave: the whole walk) and a ring of AD k-blocks of A (L2-warm: written by the launch before), with the
+// issue order pinned by scheduling fences and the occupancy the compiler plans for fixed at WK / 4 waves per SIMD (one workgroup per
+// CU).  Same addresses, same MFMA order per accumulator as WD = 0: every output bit stays.
+// WD = 0: RING k-blocks of both operands, the order left to the compiler's scheduler.
+template <int MF, int NF, int WK, int NKB, int RING, int EPI, bool SPLIT = false, bool WS = false, int WD = 0, int AD = 0>
+__global__ __launch_bounds__(64 * WK) __attribute__((amdgpu_waves_per_eu(WD > 0 ? WK / 4 : 0, WD > 0 ? WK / 4 : 0)))
+void sm_kernel(const SmArgs a) {
   constexpr int BM = MF * 16, BN = NF * 16, NT = 64 * WK;
   constexpr int NKW = NKB / WK;                               // k-blocks per wave
   constexpr int R = (RING == 0 || RING > NKW) ? NKW : RING;   // k-blocks in flight per wave
@@ -167,39 +179,85 @@ __global__ __launch_bounds__(64 * WK) void sm_kernel(const SmArgs a) {
       wp[n] = W + ((long)nb * NKB + wk) * 2048 + lane * 16;
     }
   }
-  bf16x8 av[R][MF][2], wv[R][NF][2];
-  auto load = [&](int slot, int i) {
-#pragma unroll
-    for (int n = 0; n < NF; ++n) {
-      wv[slot][n][0] = ld_w16<WS>(wp[n] + (long)i * WK * 2048);
-      wv[slot][n][1] = ld_w16<WS>(wp[n] + (long)i * WK * 2048 + 1024);
-    }
-    const bool from2 = SPLIT && (wk + i * WK) >= nkb1;         // wave-uniform
-#pragma unroll
-    for (int m = 0; m < MF; ++m) {
-      const char* q = (SPLIT && from2 ? ap2[m] : ap[m]) + (long)i * WK * 2048;
-      av[slot][m][0] = *reinterpret_cast<const bf16x8*>(q);
-      av[slot][m][1] = *reinterpret_cast<const bf16x8*>(q + 1024);
-    }
-  };
   f32x4 acc[MF][NF];
 #pragma unroll
   for (int m = 0; m < MF; ++m)
 #pragma unroll
     for (int n = 0; n < NF; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int i = 0; i < R; ++i) load(i, i);
-#pragma unroll
-  for (int i = 0; i < NKW; ++i) {
-    const int s = i % R;
-#pragma unroll
-    for (int m = 0; m < MF; ++m)
+  if constexpr (WD == 0) {
+    bf16x8 av[R][MF][2], wv[R][NF][2];
+    auto load = [&](int slot, int i) {
 #pragma unroll
       for (int n = 0; n < NF; ++n) {
-        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[s][m][0], wv[s][n][0], acc[m][n], 0, 0, 0);
-        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[s][m][1], wv[s][n][1], acc[m][n], 0, 0, 0);
+        wv[slot][n][0] = ld_w16<WS>(wp[n] + (long)i * WK * 2048);
+        wv[slot][n][1] = ld_w16<WS>(wp[n] + (long)i * WK * 2048 + 1024);
       }
-    if (i + R < NKW) load(s, i + R);
+      const bool from2 = SPLIT && (wk + i * WK) >= nkb1;         // wave-uniform
+#pragma unroll
+      for (int m = 0; m < MF; ++m) {
+        const char* q = (SPLIT && from2 ? ap2[m] : ap[m]) + (long)i * WK * 2048;
+        av[slot][m][0] = *reinterpret_cast<const bf16x8*>(q);
+        av[slot][m][1] = *reinterpret_cast<const bf16x8*>(q + 1024);
+      }
+    };
+#pragma unroll
+    for (int i = 0; i < R; ++i) load(i, i);
+#pragma unroll
+    for (int i = 0; i < NKW; ++i) {
+      const int s = i % R;
+#pragma unroll
+      for (int m = 0; m < MF; ++m)
+#pragma unroll
+        for (int n = 0; n < NF; ++n) {
+          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[s][m][0], wv[s][n][0], acc[m][n], 0, 0, 0);
+          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[s][m][1], wv[s][n][1], acc[m][n], 0, 0, 0);
+        }
+      if (i + R < NKW) load(s, i + R);
+    }
+  } else {
+    // vmcnt retires loads in the order they were queued.  The A ring goes first: k-block 0 then waits for its own W only, and the
+    // A refills land behind W blocks that the MFMAs wait for anyway (W first: 1-2 % slower per launch on cold weights; interleaved
+    // by k-block: 3-4 % slower -- profiles/sm_issue_order_ab.txt).
+    constexpr int RW = WD < NKW ? WD : NKW, RA = AD < NKW ? AD : NKW;
+    static_assert(!SPLIT && AD > 0, "separate depths: one A source");
+    static_assert(2 * (RW * NF + RA * MF) + 16 <= 63, "vmcnt is a 6-bit count (16: more than any epilogue requests ahead of the K loop)");
+    bf16x8 av[RA][MF][2], wv[RW][NF][2];
+    auto load_w = [&](int slot, int i) {
+#pragma unroll
+      for (int n = 0; n < NF; ++n) {
+        wv[slot][n][0] = ld_w16<WS>(wp[n] + (long)i * WK * 2048);
+        wv[slot][n][1] = ld_w16<WS>(wp[n] + (long)i * WK * 2048 + 1024);
+      }
+    };
+    auto load_a = [&](int slot, int i) {
+#pragma unroll
+      for (int m = 0; m < MF; ++m) {
+        av[slot][m][0] = *reinterpret_cast<const bf16x8*>(ap[m] + (long)i * WK * 2048);
+        av[slot][m][1] = *reinterpret_cast<const bf16x8*>(ap[m] + (long)i * WK * 2048 + 1024);
+      }
+    };
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < RA; ++i) load_a(i, i);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < RW; ++i) load_w(i, i);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < NKW; ++i) {
+      const int sa = i % RA, sw = i % RW;
+#pragma unroll
+      for (int m = 0; m < MF; ++m)
+#pragma unroll
+        for (int n = 0; n < NF; ++n) {
+          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[sa][m][0], wv[sw][n][0], acc[m][n], 0, 0, 0);
+          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[sa][m][1], wv[sw][n][1], acc[m][n], 0, 0, 0);
+        }
+      __builtin_amdgcn_sched_barrier(0);
+      if (i + RW < NKW) load_w(sw, i + RW);
+      if (i + RA < NKW) load_a(sa, i + RA);
+      __builtin_amdgcn_sched_barrier(0);
+    }
   }
 
   // ---- partial tiles -> LDS (C layout: col = lane & 15, row = 4 (lane >> 4) + reg); folded LayerNorm: mean / rstd of the rows
@@ -1609,12 +1667,12 @@ struct SmInst {
   int tile_n() const { return bn ? bn : NF * 16; }
 };
 
-template <int MF, int NF, int WK, int NKB, int RING, int EPI, bool SPLIT = false, bool WS = false>
+template <int MF, int NF, int WK, int NKB, int RING, int EPI, bool SPLIT = false, bool WS = false, int WD = 0, int AD = 0>
 int sm_launch(const SmArgs& a, int mt, int nz, hipStream_t stream) {
   constexpr int BM = MF * 16, BN = NF * 16;
   constexpr size_t lds = ((size_t)WK * BM * (BN + 4) + 2 * BM) * sizeof(float);
   static_assert(lds <= 160 * 1024, "partial tiles must fit the LDS");
-  auto kern = sm_kernel<MF, NF, WK, NKB, RING, EPI, SPLIT, WS>;
+  auto kern = sm_kernel<MF, NF, WK, NKB, RING, EPI, SPLIT, WS, WD, AD>;
   if (lds > 64 * 1024) {
     static bool raised = false;
     if (!raised) {
@@ -1629,28 +1687,28 @@ int sm_launch(const SmArgs& a, int mt, int nz, hipStream_t stream) {
 }
 
 // the instance with the weight cache policy its tile id has in the table (weight_stream.cpp) when the launch is issued
-template <int TILE, int MF, int NF, int WK, int NKB, int RING, int EPI, bool SPLIT = false>
+template <int TILE, int MF, int NF, int WK, int NKB, int RING, int EPI, bool SPLIT = false, int WD = 0, int AD = 0>
 int sm_launch_p(const SmArgs& a, int mt, int nz, hipStream_t stream) {
-  return sp3_weight_streams(SP3_WF_GEMM_SM, TILE) ? sm_launch<MF, NF, WK, NKB, RING, EPI, SPLIT, true>(a, mt, nz, stream)
-                                                  : sm_launch<MF, NF, WK, NKB, RING, EPI, SPLIT, false>(a, mt, nz, stream);
+  return sp3_weight_streams(SP3_WF_GEMM_SM, TILE) ? sm_launch<MF, NF, WK, NKB, RING, EPI, SPLIT, true, WD, AD>(a, mt, nz, stream)
+                                                  : sm_launch<MF, NF, WK, NKB, RING, EPI, SPLIT, false, WD, AD>(a, mt, nz, stream);
 }
 
 // The instances, chosen per shape from tools/ubench/gemm_sm.hip on MI355X (profiles/r04_gemm_small_m_tile_sweep.txt).
 // tile ids 30.. are what sp3_gemm_desc.tile / the profiles call them.
 const SmInst kInst[] = {
     // ROPE (q/k/v projections): BN % 32 == 0 (the RoPE partner column lies in the tile)
-    {30, SM_ROPE, 1024, 3, 4, 8, false, 0, 1 << 30, sm_launch_p<30, 3, 4, 8, 16, 0, SM_ROPE>},      // val / enc-step qkv: 48x64, K over 8 waves
+    {30, SM_ROPE, 1024, 3, 4, 8, false, 0, 1 << 30, sm_launch_p<30, 3, 4, 8, 16, 0, SM_ROPE, false, 2, 2>},      // val / enc-step qkv: 48x64, K over 8 waves, both k-blocks pinned up front
     {31, SM_ROPE, 768, 2, 2, 4, false, 0, 1 << 30, sm_launch_p<31, 2, 2, 4, 12, 0, SM_ROPE>},       // decoder qkv + ckv pair, cross q: 32x32 k4
     // PACKED (fc1 + GELU, key MLP hidden)
-    {32, SM_PACKED, 1024, 4, 4, 8, false, 0, 1 << 30, sm_launch_p<32, 4, 4, 8, 16, 0, SM_PACKED>},  // val fc1: 64x64 k8
+    {32, SM_PACKED, 1024, 4, 4, 8, false, 0, 1 << 30, sm_launch_p<32, 4, 4, 8, 16, 0, SM_PACKED, false, 2, 2>},  // val fc1: 64x64 k8, both k-blocks pinned up front
     {33, SM_PACKED, 768, 2, 4, 4, false, 0, 1 << 30, sm_launch_p<33, 2, 4, 4, 12, 0, SM_PACKED>},   // dec fc1 x2: 32x64 k4
     {42, SM_PACKED, 1792, 4, 2, 7, true, 0, 1 << 30, sm_launch_p<42, 4, 2, 7, 28, 0, SM_PACKED, true>},   // key MLP hidden x2 (split A: feat | dec[-1]): 64x32 k7
     // STREAM (output projections onto the residual stream)
     {39, SM_STREAM, 1024, 3, 2, 8, false, 0, 768, sm_launch_p<39, 3, 2, 8, 16, 0, SM_STREAM>},      // decoder_embed x2 (N = 768): 48x32 k8
     {34, SM_STREAM, 1024, 2, 2, 8, false, 769, 1 << 30, sm_launch_p<34, 2, 2, 8, 16, 0, SM_STREAM>},  // val proj, value_out: 32x32 k8
-    {35, SM_STREAM, 4096, 2, 2, 8, false, 0, 1 << 30, sm_launch_p<35, 2, 2, 8, 64, 4, SM_STREAM>},   // val fc2: 32x32 k8, ring of 4
+    {35, SM_STREAM, 4096, 2, 2, 8, false, 0, 1 << 30, sm_launch_p<35, 2, 2, 8, 64, 4, SM_STREAM, false, 8, 3>},   // val fc2: 32x32 k8, all of W + an A ring of 3
     {36, SM_STREAM, 768, 3, 2, 6, false, 0, 1 << 30, sm_launch_p<36, 3, 2, 6, 12, 0, SM_STREAM>},   // dec proj / cproj x2, pos patch embed: 48x32 k6
-    {37, SM_STREAM, 3072, 3, 2, 8, false, 0, 1 << 30, sm_launch_p<37, 3, 2, 8, 48, 3, SM_STREAM>},  // dec fc2 x2: 48x32 k8, ring of 3
+    {37, SM_STREAM, 3072, 3, 2, 8, false, 0, 1 << 30, sm_launch_p<37, 3, 2, 8, 48, 3, SM_STREAM, false, 6, 3>},  // dec fc2 x2: 48x32 k8, all of W + an A ring of 3
     {38, SM_STREAM, 1792, 4, 2, 7, false, 0, 1 << 30, sm_launch_p<38, 4, 2, 7, 28, 0, SM_STREAM>},  // key MLP out x2: 64x32 k7
     // SCORE (the memory read's S = LN_q(q) . K_hat^T / 32 with the softmax statistics of its 32-key groups; N = bank tokens, any multiple of 4)
     {43, SM_SCORE, 1024, 2, 2, 8, false, 0, 1 << 30, sm_launch<2, 2, 8, 16, 0, SM_SCORE>},

@@ -8,7 +8,7 @@ ends and meets its weights cold in HBM, as in the model.  Reported: us per launc
 under mode 0 (default policy) and mode 2 (every streaming variant), per kernel family.  A guide for the table, not its judge: the
 table is decided in the model.
 
-  python tools/probe_cold_chain.py [--mb 544] [--reps 5] [--only gemm,conv,wide,qproj]"""
+  python tools/probe_cold_chain.py [--mb 544] [--reps 5] [--only gemm,conv,wide,qproj] [--tiles 35,37]"""
 import argparse
 import ctypes as C
 import json
@@ -75,6 +75,8 @@ def gemm_rows(a):
         t = row["tiles"][0]
         conv = t in (40, 41)
         if row["lean"] != 1 or "bf16_224" not in row["from"] or t not in NAMES or t in seen or conv != (a.family == "conv"):
+            continue
+        if a.tiles and t not in a.tiles:
             continue
         if any(d["M"] > (2048 if conv else 392) or d.get("dyn_n") for d in row["descs"]):
             continue
@@ -158,7 +160,9 @@ def main():
     ap.add_argument("--mb", type=float, default=544.0, help="MB of distinct weight copies per chain (> 512: twice the MALL)")
     ap.add_argument("--reps", type=int, default=5, help="timed replays of a chain")
     ap.add_argument("--only", default="gemm,conv,wide,qproj")
+    ap.add_argument("--tiles", default="", help="gemm / conv chains: only these tile ids (comma separated)")
     a = ap.parse_args()
+    a.tiles = {int(t) for t in a.tiles.split(",") if t}
     assert torch.cuda.is_available(), "needs an MI355X"
     print("cold-weight chains, %.0f MB of weight copies each, %d timed replays; us per launch, mode 0 (default) vs mode 2 (stream)" % (a.mb, a.reps))
     for fam in a.only.split(","):
