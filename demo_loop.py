@@ -204,6 +204,14 @@ def main():
     ap.add_argument("--voxel_size", type=float, default=None, help="with --fused: voxel edge in the units of the pointmaps (default: the "
                     "longest side of the confident points' box takes 256 voxels)")
     ap.add_argument("--trunc_voxels", type=float, default=3.0, help="with --fused: truncation distance in voxels")
+    ap.add_argument("--clean", type=float, default=None, metavar="TOL", help="clean the confidences across the frames before anything reads "
+                    "them (spann3r_amd.multiview.clean_sequence, on the device: DUSt3R's clean_pointcloud rule): a pixel that floats in "
+                    "front of what a more confident frame measured, by more than the relative depth tolerance TOL, gets confidence 0 and "
+                    "so leaves --save_ply, --save_glb, --vis, --fused and --eval; prints the pixels clipped per frame and in total")
+    ap.add_argument("--clean_order", default="sequence", choices=["parallel", "sequence"], help="with --clean: judge every frame against "
+                    "the original confidences (parallel, one launch) or frame by frame against the already cleaned ones (sequence)")
+    ap.add_argument("--min_agree", type=int, default=0, metavar="K", help="with --clean: also drop every pixel that fewer than K other frames "
+                    "agree with or that any frame looks through (multiview.support_mask); 0: off")
     ap.add_argument("--rgbd", default=None, metavar="DIR", help="folder of *.npz frames (rgb uint8 [H,W,3], depth uint16 or float32 [H,W], "
                     "K [3,3], pose [4,4] cam2world; tools/make_rgbd_folder.py writes one): views with ground truth built on the GPU "
                     "(spann3r_amd.views.build_views) instead of synthetic frames")
@@ -246,6 +254,10 @@ def main():
         ap.error("--eval_bvh needs --eval_exact or --eval_depth (the evaluations that query the faces of a mesh)")
     if args.eval_depth and not (args.fused and args.rgbd and args.eval):
         ap.error("--eval_depth needs --fused --rgbd --eval (a fused surface and ground-truth depth maps to score it against)")
+    if args.min_agree < 0 or (args.min_agree and args.clean is None):
+        ap.error("--min_agree must be >= 0 and needs --clean (its depth tolerance)")
+    if args.clean is not None and not 0.0 <= args.clean < 1.0:
+        ap.error("--clean must lie in [0, 1)")
     if args.glb_normals and not args.save_glb:
         ap.error("--glb_normals needs --save_glb (a file to write them to)")
     if args.glb_normals and args.as_pointcloud:
@@ -312,6 +324,28 @@ def main():
         print("Time: %.4f s, FPS: %.1f  (%d frames, call %d: %s)" %
               (end - start, len(batch) / (end - start), len(batch), it,
                ["eager warm-up", "hipGraph capture", "hipGraph replay"][min(it, 2)]))
+    if args.clean is not None:                                                    # once, in front of every consumer of the confidences
+        import numpy as np
+        from spann3r_amd import multiview
+        kw = dict(tol=args.clean, order=args.clean_order)
+        try:
+            pts_c, _, conf_c, info = multiview.clean_sequence(preds, batch, **kw)
+        except RuntimeError as e:
+            if "degenerate pointmaps" not in str(e):
+                raise
+            _, H, W, _ = preds[0]["pts3d"].shape
+            print("%s: cleaning through nominal cameras (focal %d, identity poses)" % (e, max(H, W)))
+            pts_c, _, conf_c, info = multiview.clean_sequence(preds, batch, focal=float(max(H, W)), poses=np.stack([np.eye(4)] * len(preds)), **kw)
+        print("cleaned confidences (tol %g, %s order): pixels clipped per frame %s, %d of %d in total" %
+              (args.clean, args.clean_order, info["cleaned"], sum(info["cleaned"]), conf_c.numel()))
+        if args.min_agree:
+            _, H, W, _ = pts_c.shape
+            K = np.array([[info["focal"], 0, W / 2], [0, info["focal"], H / 2], [0, 0, 1]], np.float64)
+            keep = multiview.support_mask(multiview.view_consistency(pts_c, K, info["poses"], conf=conf_c, tol=args.clean), args.min_agree)
+            print("support: %d of %d pixels have at least %d agreeing frames and none looking through them" %
+                  (int(keep.sum()), keep.numel(), args.min_agree))
+            conf_c = torch.where(keep, conf_c, torch.zeros_like(conf_c))
+        preds = [dict(p, conf=conf_c[j:j + 1].to(p["conf"].dtype)) for j, p in enumerate(preds)]
     fuse_kw = dict(voxel_size=args.voxel_size, trunc_voxels=args.trunc_voxels, min_component_faces=args.min_component,
                    keep_largest=1 if args.largest_component else None, smooth_iters=args.smooth, fill_holes=args.fill_holes)
     if args.simplify is not None:

@@ -1765,6 +1765,62 @@ int sp3_mesh_fill_emit(const float* positions, const int32_t* rgba, int64_t nver
                        int64_t nmembers, const int32_t* vertex_at, const int32_t* face_at, int64_t vertices_added, int64_t faces_added,
                        float* out_positions, int32_t* out_rgba, int32_t* out_faces, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Multi-view consistency (spann3r_amd/multiview.py drives these; csrc/multiview.hip).  Every frame of a reconstruction has a
+ * pointmap in one world frame and a confidence; a flying pixel at a depth discontinuity survives a per-frame confidence test
+ * although other cameras look straight through it.  Here every pixel's point is looked up in every OTHER frame: it is counted as
+ * seen, in agreement, in front of or behind what that frame measured there, and its confidence is clipped where it floats in front
+ * of a more confident measurement.  The rule is that of DUSt3R's BasePCOptimizer.clean_pointcloud (dust3r/cloud_opt/base_opt.py),
+ * with these differences: the pixel is floor(u + 0.5) instead of torch.round (they differ only at exact halves); the projection is
+ * fu * xc / zc + cu instead of a matrix product followed by a division; the depth of frame j at a pixel is the camera z of j's own
+ * pointmap there, not an optimised depth map; there is a `valid` mask, which that method lacks.  Parity with that method is
+ * UNPINNED (dust3r.cloud_opt cannot be imported where this is built); tests/multiview_ref.py restates the rule below in numpy and
+ * the kernel is checked against that bit for bit.  No entry point allocates device memory, frees or synchronises.  Every fp32
+ * operation is rounded on its own (`#pragma clang fp contract(off)`) and sums run left to right as written.
+ *
+ * Frames are sp3_tsdf_frame descriptors exactly as sp3_tsdf_integrate takes them (frames_host and frames_dev hold the same T
+ *   descriptors; the host copy is only read for the checks).  Every frame must have pts; a frame with depth is refused.
+ *   pixel_weight carries the confidence (nullable), valid is nullable, rgba is ignored.  Frames may differ in w, h and row_stride.
+ * Lookup of a world point X = (x, y, z) in frame j (descriptor fr, m = fr.w2c), the steps of sp3_tsdf_integrate in its order:
+ *     zc = ((m8 x + m9 y) + m10 z) + m11;  skip unless zc > 0;  xc (m0..m3) and yc (m4..m7) likewise;
+ *     u = fu * xc / zc + cu, v = fv * yc / zc + cv;  px = floor(u + 0.5), py = floor(v + 0.5);
+ *     skip unless 0 <= px < w and 0 <= py < h (compared in fp32, a NaN fails);  p = py * row_stride + px;  skip if valid[p] == 0;
+ *     d = ((m8 X' + m9 Y') + m10 Z') + m11 of pts[p] = (X', Y', Z');  skip unless d is finite and > 0.
+ *   A lookup that is not skipped is SEEN.
+ * Classes, with lo = (1.0f - tol) * d and hi = (1.0f + tol) * d:  FRONT: zc < lo (the point floats in front of what j measured
+ *   there, a free-space violation);  BEHIND: not front and zc > hi (occluded in j, which says nothing);  AGREE: otherwise;
+ *   STRONGER: front, both frames have pixel_weight, and conf_i[q] < conf_j[p] (a NaN on either side fails).
+ * Counts of pixel q of frame i, X = pts_i[q]: all four 0 if valid_i[q] == 0; otherwise every j != i is visited in table order (a
+ *   non-finite X is skipped by every lookup on its own).  counts[q] = (seen, agree, front, stronger) as int32; behind is
+ *   seen - agree - front.  They are integers of a pure per-pair predicate: the same bits on every run.
+ * Cleaning: pixel q of frame i is BAD iff some j is front for it and conf_i[q] < c_j[p], with conf_i the ORIGINAL confidence of
+ *   frame i and c_j the state of frame j.  Parallel order: c_j is j's original confidence, so bad == (stronger > 0).  Sequence order
+ *   (that method's in-place loop): frames are processed i = 0 .. T - 1; c_j is the cleaned confidence of j when j < i and the
+ *   original when j > i.  (The original conf_i suffices: before its first clip a pixel holds its original value, and a clip is
+ *   idempotent.)  conf_out[q] = (conf < max_bad_conf ? conf : max_bad_conf) for a bad pixel and the input bits otherwise; a NaN
+ *   confidence is never bad and passes through.
+ *
+ * out_host / out_dev: T descriptors sp3_multiview_out, one per frame: counts int32 [h, row_stride, 4] (nullable, 16-byte aligned),
+ *   conf_out fp32 [h, row_stride] (nullable), max_bad_conf (not NaN).  Only pixels inside w x h are written.
+ * sp3_multiview_counts: ONE launch over all (frame, 16 x 16 pixel block): a lane owns a pixel, a wave an 8 x 8 tile; the descriptor
+ *   tables are read by scalar loads only.  Writes counts and, where conf_out is set, the parallel-order cleaning.  0 <= tol < 1;
+ *   with any conf_out set every frame needs pixel_weight.  T <= 65535.  T = 0 is a no-op; T = 1 writes zeros and passes the
+ *   confidence through.
+ * sp3_multiview_clean: the sequence order as T launches of the same kernel; launch i covers frame i only, reads out[j].conf_out
+ *   for j < i (written by the earlier launches) and frames[j].pixel_weight for j > i; the launch boundaries are the only hand-offs.
+ *   Every conf_out must be non-null.  counts, where set, are the counts against the ORIGINAL confidences, those of the counts call.
+ * Both refuse a conf_out that equals a pixel_weight or another conf_out (pointer equality); that the buffers do not overlap in any
+ *   other way is the caller's contract. */
+typedef struct sp3_multiview_out {
+  int32_t* counts;             /* device int32 [h, row_stride, 4]: seen, agree, front, stronger; nullable */
+  float* conf_out;             /* device fp32 [h, row_stride]; nullable */
+  float max_bad_conf;
+} sp3_multiview_out;
+int sp3_multiview_counts(const sp3_tsdf_frame* frames_host, const sp3_tsdf_frame* frames_dev, int T, float tol,
+                         const sp3_multiview_out* out_host, const sp3_multiview_out* out_dev, void* stream);
+int sp3_multiview_clean(const sp3_tsdf_frame* frames_host, const sp3_tsdf_frame* frames_dev, int T, float tol,
+                        const sp3_multiview_out* out_host, const sp3_multiview_out* out_dev, void* stream);
+
 /* small utilities */
 /* n (1..8) contiguous device-to-device copies in one launch; every copy 16-byte aligned and a multiple of 16 bytes.
  * (The sequence loop's per-frame bookkeeping -- torch .clone() / slice assignments around spann3r/model.py:523-531.) */

@@ -785,7 +785,7 @@ class FusionSession:
 def fuse_sequence(preds, batch, conf_thresh=1e-3, voxel_size=None, dims_max=256, trunc_voxels=3.0, min_weight=1.0, scale=1.0,
                   transform=None, color=True, return_volume=False, focal=None, poses=None, track=False, return_poses=False, bricks=False,
                   extent=None, direct_mesh=False, min_component_faces=0, keep_largest=None, simplify_cell=None, smooth_iters=0,
-                  fill_holes=0):
+                  fill_holes=0, clean_tol=None, clean_order="sequence"):
     """The fused surface of a reconstruction from model.forward's `preds` and its `batch`: demo.py's own sequence -- the stacked
     pointmaps (mesh.sequence_tensors), the focal of frame 0 (estimate_focal_knowing_depth), one pose per frame (estimate_poses) --
     then the pointmaps of the pixels with (conf - 1) / conf > conf_thresh integrated through the `pts` path into a volume around
@@ -793,7 +793,9 @@ def fuse_sequence(preds, batch, conf_thresh=1e-3, voxel_size=None, dims_max=256,
     focal / poses (cam2world [t, 4, 4]) given: used instead of the estimates.  track / return_poses: as fuse_pointmaps (every frame
     after the first is registered to the model before it is integrated).  bricks / extent / direct_mesh: as fuse_pointmaps (a
     BrickTSDFVolume at voxel_size instead of the dense volume).  min_component_faces / keep_largest: as TSDFVolume.extract_mesh (the
-    floaters of the surface are dropped).  simplify_cell, smooth_iters, fill_holes: as TSDFVolume.extract_mesh.  Pointmaps without geometry (seeded random weights)
+    floaters of the surface are dropped).  simplify_cell, smooth_iters, fill_holes: as TSDFVolume.extract_mesh.  clean_tol = t: the confidences are cleaned across the frames first
+    (multiview.clean_confidence with tol t and clean_order, through the same focal and poses), so a pixel that floats in front of what a
+    more confident frame measured does not pass conf_thresh; None: nothing of that runs.  Pointmaps without geometry (seeded random weights)
     give a focal near 0: that raises rather than fusing through meaningless cameras."""
     from .postprocess import estimate_focal_knowing_depth, estimate_poses
     pts_all, images_all, conf_all = M.sequence_tensors(preds, batch)
@@ -809,8 +811,11 @@ def fuse_sequence(preds, batch, conf_thresh=1e-3, voxel_size=None, dims_max=256,
         raise ValueError("fuse_sequence: focal must be positive and finite, got %r" % focal)
     if poses is None:
         poses, _ = estimate_poses(pts_all, focal, pp)
-    valid = (conf_all - 1) / conf_all > conf_thresh
     K = np.array([[focal, 0, pp[0]], [0, focal, pp[1]], [0, 0, 1]], np.float64)
+    if clean_tol is not None:
+        from .multiview import clean_confidence
+        conf_all = clean_confidence(pts_all, conf_all, K, np.asarray(poses, np.float64), tol=clean_tol, order=clean_order)
+    valid = (conf_all - 1) / conf_all > conf_thresh
     return fuse_pointmaps(pts_all, K, np.asarray(poses, np.float64), valid, images_all, voxel_size, dims_max, trunc_voxels, min_weight, scale,
                           transform, color, return_volume, track, return_poses, bricks=bricks, extent=extent, direct_mesh=direct_mesh,
                           min_component_faces=min_component_faces, keep_largest=keep_largest, simplify_cell=simplify_cell,

@@ -132,6 +132,11 @@ class TsdfFrame(C.Structure):
                 ("cv", C.c_float), ("w2c", C.c_float * 12)]
 
 
+class MultiviewOut(C.Structure):
+    """sp3_multiview_out (include/spann3r_hip.h)"""
+    _fields_ = [("counts", C.c_void_p), ("conf_out", C.c_void_p), ("max_bad_conf", C.c_float)]
+
+
 class MeshRayView(C.Structure):
     """sp3_mesh_ray_view (include/spann3r_hip.h)"""
     _fields_ = [("depth", C.c_void_p), ("face", C.c_void_p), ("bary", C.c_void_p), ("row_stride", C.c_int64), ("w", C.c_int32), ("h", C.c_int32),
@@ -374,6 +379,8 @@ _PROTOS = {
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p],
     "sp3_tsdf_brick_to_dense": [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
                                 C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sp3_multiview_counts": [C.POINTER(TsdfFrame), C.c_void_p, C.c_int, C.c_float, C.POINTER(MultiviewOut), C.c_void_p, C.c_void_p],
+    "sp3_multiview_clean": [C.POINTER(TsdfFrame), C.c_void_p, C.c_int, C.c_float, C.POINTER(MultiviewOut), C.c_void_p, C.c_void_p],
     "sp3_weight_stream_set": [C.c_int],
     "sp3_tsdf_brick_extract": [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
