@@ -212,6 +212,13 @@ def main():
                     "the original confidences (parallel, one launch) or frame by frame against the already cleaned ones (sequence)")
     ap.add_argument("--min_agree", type=int, default=0, metavar="K", help="with --clean: also drop every pixel that fewer than K other frames "
                     "agree with or that any frame looks through (multiview.support_mask); 0: off")
+    ap.add_argument("--global_align", action="store_true", help="DUSt3R's global alignment (spann3r_amd.align.GlobalAligner, on the device): "
+                    "the DUSt3R pair graph of the frames is aligned into one set of poses, focals and depth maps, and the aligned pointmaps "
+                    "(in the first camera's frame), its confidences, poses and focals replace forward's prediction for --save_ply, --save_glb, "
+                    "--vis, --fused and --clean; prints edges, initial loss, final loss, iterations")
+    ap.add_argument("--align_iters", type=int, default=300, metavar="N", help="with --global_align: iterations of the optimiser")
+    ap.add_argument("--align_graph", default="complete", metavar="GRAPH", help="with --global_align: the pair graph, make_pairs' scene_graph "
+                    "(complete, swin-K, oneref-K, ...)")
     ap.add_argument("--rgbd", default=None, metavar="DIR", help="folder of *.npz frames (rgb uint8 [H,W,3], depth uint16 or float32 [H,W], "
                     "K [3,3], pose [4,4] cam2world; tools/make_rgbd_folder.py writes one): views with ground truth built on the GPU "
                     "(spann3r_amd.views.build_views) instead of synthetic frames")
@@ -260,6 +267,8 @@ def main():
         ap.error("--clean must lie in [0, 1)")
     if args.glb_normals and not args.save_glb:
         ap.error("--glb_normals needs --save_glb (a file to write them to)")
+    if args.global_align and (args.stream or args.offline or args.align_iters < 1):
+        ap.error("--global_align aligns forward's frames: not with --stream or --offline, and --align_iters must be >= 1")
     if args.glb_normals and args.as_pointcloud:
         ap.error("--glb_normals needs a mesh: a point cloud (--as_pointcloud) has no faces to take normals from")
     for name in ("simplify", "simplify_voxels"):
@@ -324,12 +333,40 @@ def main():
         print("Time: %.4f s, FPS: %.1f  (%d frames, call %d: %s)" %
               (end - start, len(batch) / (end - start), len(batch), it,
                ["eager warm-up", "hipGraph capture", "hipGraph replay"][min(it, 2)]))
+    aligned = None
+    if args.global_align:                                                         # once, in front of every consumer of the prediction
+        from spann3r_amd.align import GlobalAligner
+        from spann3r_amd.runner import pair_graph
+        with torch.no_grad():
+            graph = pair_graph(model.dust3r, batch, scene_graph=args.align_graph)
+        torch.cuda.synchronize()
+        start = time.time()
+        scene = GlobalAligner(graph)
+        final = scene.compute_global_alignment(init="mst", niter=args.align_iters)
+        torch.cuda.synchronize()
+        print("global alignment: %d edges, initial loss %.6g, final loss %.6g, %d iterations (%.3f s)" %
+              (scene.n_edges, scene.losses[0], final, len(scene.losses), time.time() - start))
+        with torch.no_grad():                                                     # everything in the first camera's frame, as forward gives it
+            poses = scene.get_im_poses().double().cpu()
+            to_first = torch.linalg.inv(poses[0])
+            poses = (to_first @ poses).numpy()
+            R0, t0 = to_first[:3, :3].float().to(device), to_first[:3, 3].float().to(device)
+            aligned = dict(poses=poses, K=scene.get_intrinsics().double().cpu().numpy())
+            preds = [{("pts3d" if j == 0 else "pts3d_in_other_view"): (p @ R0.T + t0)[None].to(preds[j]["conf"].dtype),
+                      "conf": c[None].to(preds[j]["conf"].dtype)} for j, (p, c) in enumerate(zip(scene.get_pts3d(), scene.im_conf))]
     if args.clean is not None:                                                    # once, in front of every consumer of the confidences
         import numpy as np
         from spann3r_amd import multiview
         kw = dict(tol=args.clean, order=args.clean_order)
         try:
-            pts_c, _, conf_c, info = multiview.clean_sequence(preds, batch, **kw)
+            if aligned is not None:                                               # the aligned cameras: every image's own intrinsics
+                from spann3r_amd import mesh as M
+                pts_c, _, conf_all = M.sequence_tensors(preds, batch)
+                conf_c = multiview.clean_confidence(pts_c, conf_all, aligned["K"], aligned["poses"], **kw)
+                info = dict(poses=aligned["poses"], K=aligned["K"],
+                            cleaned=(conf_c.view(torch.int32) != conf_all.contiguous().view(torch.int32)).flatten(1).sum(1).cpu().tolist())
+            else:
+                pts_c, _, conf_c, info = multiview.clean_sequence(preds, batch, **kw)
         except RuntimeError as e:
             if "degenerate pointmaps" not in str(e):
                 raise
@@ -340,7 +377,7 @@ def main():
               (args.clean, args.clean_order, info["cleaned"], sum(info["cleaned"]), conf_c.numel()))
         if args.min_agree:
             _, H, W, _ = pts_c.shape
-            K = np.array([[info["focal"], 0, W / 2], [0, info["focal"], H / 2], [0, 0, 1]], np.float64)
+            K = info["K"] if "K" in info else np.array([[info["focal"], 0, W / 2], [0, info["focal"], H / 2], [0, 0, 1]], np.float64)
             keep = multiview.support_mask(multiview.view_consistency(pts_c, K, info["poses"], conf=conf_c, tol=args.clean), args.min_agree)
             print("support: %d of %d pixels have at least %d agreeing frames and none looking through them" %
                   (int(keep.sum()), keep.numel(), args.min_agree))
@@ -396,7 +433,13 @@ def main():
         kw = dict(conf_thresh=args.conf_thresh, return_volume=True, track=args.track, return_poses=args.track, bricks=args.bricks,
                   direct_mesh=args.direct_mesh, **fuse_kw, **kw)
         try:
-            fm, vol = fusion.fuse_sequence(preds, batch, **kw)
+            if aligned is not None:                                               # the aligned cameras, not estimates from the pointmaps
+                from spann3r_amd import mesh as M
+                pts_all, images_all, conf_all = M.sequence_tensors(preds, batch)
+                fm, vol = fusion.fuse_pointmaps(pts_all, aligned["K"], aligned["poses"], (conf_all - 1) / conf_all > args.conf_thresh, images_all,
+                                                **{k: v for k, v in kw.items() if k != "conf_thresh"})
+            else:
+                fm, vol = fusion.fuse_sequence(preds, batch, **kw)
         except RuntimeError as e:
             if "degenerate pointmaps" not in str(e):
                 raise

@@ -1821,6 +1821,81 @@ int sp3_multiview_counts(const sp3_tsdf_frame* frames_host, const sp3_tsdf_frame
 int sp3_multiview_clean(const sp3_tsdf_frame* frames_host, const sp3_tsdf_frame* frames_dev, int T, float tol,
                         const sp3_multiview_out* out_host, const sp3_multiview_out* out_dev, void* stream);
 
+/* ---- Global alignment (csrc/align.hip; spann3r_amd/align.py) --------------------------------------------------------------
+ * A pair graph gives, for every ordered pair e = (i_e, j_e), two pointmaps in i's camera frame and two confidences.  Global
+ * alignment looks for ONE set of camera poses, focals and depth maps that explains all pairs at once: the loss below is the
+ * confidence-weighted distance between the E pairwise pointmaps, each moved by its own similarity, and the N unprojected depth
+ * maps.  It follows PointCloudOptimizer.forward (dust3r/cloud_opt/optimizer.py) with dist = "l1".  Parity with that class is
+ * UNPINNED (dust3r.cloud_opt cannot be imported where this is built); tests/align_ref.py restates the rule below in numpy, and a
+ * float64 torch statement of the reference's formulas, from its parametrisation down, is the second anchor.  The kernel sees only
+ * GEOMETRIC parameters: a log, an exp or a quaternion on the device would not round like numpy, so the parametrisation stays in
+ * torch (spann3r_amd/align.py).  No entry point allocates device memory, frees or synchronises.  Every fp32 operation is rounded
+ * on its own (`#pragma clang fp contract(off)`), dot products run left to right as written, division and square root are IEEE.
+ *
+ * Image n (sp3_align_image): depth d fp32 [h, row_stride] (the positive depth itself), c2w = C (row-major 3 x 4), f, (cx, cy),
+ *   grad_depth fp32 [h, row_stride] (output, nullable).  Edge e (sp3_align_edge): img = (i_e, j_e); per side s the pointmap
+ *   pts[s] fp32 [h, row_stride[s], 3] and the weight[s] fp32 [h, row_stride[s]] of image img[s] (the already transformed
+ *   confidence, e.g. log conf); M (row-major 3 x 4, already s_e [R_e | t_e]); a = (axy, axy, az).
+ * Items: an item is (e, s); the items of image n are those with img[s] == n, listed as CSR item_first[N + 1], item_edge[2 E],
+ *   item_side[2 E].  Every (e, s) must be listed exactly once, under its image.
+ * Pixel (u, v) of image n, integer pixel centres, all fp32:
+ *     ux = u - cx, vy = v - cy;  rx = ux / f, ry = vy / f;  xc = (d ux) / f, yc = (d vy) / f;  hx = xc / f, hy = yc / f, df = d / f;
+ *     X_r = ((C_r0 xc + C_r1 yc) + C_r2 d) + C_r3.
+ *   For every item of n, in CSR order, with P, W the item's pointmap and weight at (u, v):
+ *     q = a (.) P;  Y_r = ((M_r0 qx + M_r1 qy) + M_r2 qz) + M_r3;  r = X - Y;  rho = sqrt((r0^2 + r1^2) + r2^2);  term = W rho;
+ *     g = (W / rho) r, and g = 0 where rho == 0 (torch.norm's backward);  gc_c = (g0 C_0c + g1 C_1c) + g2 C_2c (c = 0..2);
+ *     gm_c = (g0 M_0c + g1 M_1c) + g2 M_2c.
+ * Loss: L = S_0 / A_0 + S_1 / A_1;  S_s = the fp64 sum of the fp32 terms of side s;  A_s = the pixel count of side s over all
+ *   edges (total_area_i / total_area_j of the reference).
+ * Outputs, all gradients of L:
+ *   grad_depth[u, v] = the fp32 sum over the items of n, in order, of ((gc_0 rx + gc_1 ry) + gc_2) / (float)A_s; stored once.
+ *   img_sums fp64 [N, 15]: 0..11 dL/dC (g_r * (xc, yc, d, 1)_c at 4 r + c), 12 dL/df (-(gc_0 hx + gc_1 hy)), 13 / 14
+ *     dL/dcx, dL/dcy (-(gc_0 df), -(gc_1 df)).  The products g_r * x_c are taken in fp64 (exact), the rest in fp32 and converted;
+ *     every addend is then multiplied by 1.0 / A_s in fp64.
+ *   edge_sums fp64 [E, 15], over both items of the edge: 0..11 dL/dM (-(g_r * (qx, qy, qz, 1)_c)), 12..14 dL/da per component
+ *     (-(gm_c * P_c)); products in fp64, times 1.0 / A_s.  (a has two free values: dL/daxy = [12] + [13].)
+ *   loss3 fp64 [3]: S_0, S_1, L = S_0 * (1 / A_0) + S_1 * (1 / A_1).
+ *   All fp64 sums run in a fixed order: in the wave, the four waves in order, one row per (image | edge-side, 16 x 16 block) in ws,
+ *   then a second launch adds the rows in index order (the scheme of sp3_icp_accum).  No floating-point atomics: the same bits on
+ *   every run.  A non-finite P, W or d propagates; nothing is masked.
+ * sp3_align_loss_grad: ONE launch over all (image, 16 x 16 block) plus the finishing launch; a lane owns a pixel, a wave an 8 x 8
+ *   tile.  Tables are given as host and device copies; every index, stride and size is checked on the host copies before anything
+ *   is launched: N in 1..4096, E in 1..65536, T = blocks of the largest image <= 65536, f != 0, image indices, sides, the CSR.
+ *   ws: sp3_align_loss_grad_ws_bytes(N, E, wmax, hmax) bytes, 8-byte aligned.
+ * sp3_align_moments: for B triples (src, dst, w) of [n_b, 3] / [n_b] fp32 the 17 fp64 sums of a weighted similarity registration,
+ *   out fp64 [B, 17]: 0 sum w;  1..3 sum w p;  4..6 sum w q;  7..15 sum w p q^T (3 r + c: p_r q_c);  16 sum w |p|^2 (p = src, q = dst;
+ *   every product in fp64, (w p_r) first).  Same reduction scheme, one slab of min(ceil(n_b / 256), 1024) rows per triple.
+ *   B in 1..65535, n_b in 1..2^31 / 3.  ws: sp3_align_moments_ws_bytes(B, max n_b). */
+typedef struct sp3_align_image {
+  const float* depth;          /* device fp32 [h, row_stride] */
+  float* grad_depth;           /* device fp32 [h, row_stride]; nullable */
+  int64_t row_stride;
+  int32_t w, h;
+  float f, cx, cy;
+  float c2w[12];
+} sp3_align_image;
+typedef struct sp3_align_edge {
+  const float* pts[2];         /* device fp32 [h, row_stride[s], 3] of image img[s] */
+  const float* weight[2];      /* device fp32 [h, row_stride[s]] */
+  int64_t row_stride[2];
+  int32_t img[2];              /* (i_e, j_e) */
+  float M[12];
+  float a[3];
+} sp3_align_edge;
+typedef struct sp3_align_triple {
+  const float* src;            /* device fp32 [n, 3] */
+  const float* dst;            /* device fp32 [n, 3] */
+  const float* w;              /* device fp32 [n] */
+  int64_t n;
+} sp3_align_triple;
+int64_t sp3_align_loss_grad_ws_bytes(int N, int E, int wmax, int hmax);
+int sp3_align_loss_grad(const sp3_align_image* imgs_host, const sp3_align_image* imgs_dev, int N, const sp3_align_edge* edges_host,
+                        const sp3_align_edge* edges_dev, int E, const int* item_first_host, const int* item_edge_host,
+                        const int* item_side_host, const int* item_first_dev, const int* item_edge_dev, const int* item_side_dev,
+                        void* ws, double* img_sums, double* edge_sums, double* loss3, void* stream);
+int64_t sp3_align_moments_ws_bytes(int B, int64_t nmax);
+int sp3_align_moments(const sp3_align_triple* tr_host, const sp3_align_triple* tr_dev, int B, void* ws, double* out, void* stream);
+
 /* small utilities */
 /* n (1..8) contiguous device-to-device copies in one launch; every copy 16-byte aligned and a multiple of 16 bytes.
  * (The sequence loop's per-frame bookkeeping -- torch .clone() / slice assignments around spann3r/model.py:523-531.) */

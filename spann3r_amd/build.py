@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libspann3r_hip.so")
-SOURCES = ["error.cpp", "weight_stream.cpp", "gemm.hip", "gemm_sm.hip", "norm_rope.hip", "attention.hip", "memory.hip", "dpt.hip", "conv.hip", "preproc.hip", "loss.hip", "train.hip", "train2.hip", "postproc.hip", "eval.hip", "render.hip", "mesh.hip", "views.hip", "fusion.hip", "raycast.hip", "bricks.hip", "brick_mesh.hip", "mesh_components.hip", "mesh_simplify.hip", "mesh_sample.hip", "mesh_distance.hip", "mesh_ray.hip", "mesh_bvh.hip", "mesh_visibility.hip", "mesh_topology.hip", "mesh_boundary.hip", "multiview.hip"]
+SOURCES = ["error.cpp", "weight_stream.cpp", "gemm.hip", "gemm_sm.hip", "norm_rope.hip", "attention.hip", "memory.hip", "dpt.hip", "conv.hip", "preproc.hip", "loss.hip", "train.hip", "train2.hip", "postproc.hip", "eval.hip", "render.hip", "mesh.hip", "views.hip", "fusion.hip", "raycast.hip", "bricks.hip", "brick_mesh.hip", "mesh_components.hip", "mesh_simplify.hip", "mesh_sample.hip", "mesh_distance.hip", "mesh_ray.hip", "mesh_bvh.hip", "mesh_visibility.hip", "mesh_topology.hip", "mesh_boundary.hip", "multiview.hip", "align.hip"]
 
 
 STAMP = LIB + ".srchash"

@@ -137,6 +137,23 @@ class MultiviewOut(C.Structure):
     _fields_ = [("counts", C.c_void_p), ("conf_out", C.c_void_p), ("max_bad_conf", C.c_float)]
 
 
+class AlignImage(C.Structure):
+    """sp3_align_image (include/spann3r_hip.h)"""
+    _fields_ = [("depth", C.c_void_p), ("grad_depth", C.c_void_p), ("row_stride", C.c_int64), ("w", C.c_int32), ("h", C.c_int32),
+                ("f", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("c2w", C.c_float * 12)]
+
+
+class AlignEdge(C.Structure):
+    """sp3_align_edge (include/spann3r_hip.h)"""
+    _fields_ = [("pts", C.c_void_p * 2), ("weight", C.c_void_p * 2), ("row_stride", C.c_int64 * 2), ("img", C.c_int32 * 2),
+                ("M", C.c_float * 12), ("a", C.c_float * 3)]
+
+
+class AlignTriple(C.Structure):
+    """sp3_align_triple (include/spann3r_hip.h)"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("w", C.c_void_p), ("n", C.c_int64)]
+
+
 class MeshRayView(C.Structure):
     """sp3_mesh_ray_view (include/spann3r_hip.h)"""
     _fields_ = [("depth", C.c_void_p), ("face", C.c_void_p), ("bary", C.c_void_p), ("row_stride", C.c_int64), ("w", C.c_int32), ("h", C.c_int32),
@@ -381,6 +398,10 @@ _PROTOS = {
                                 C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "sp3_multiview_counts": [C.POINTER(TsdfFrame), C.c_void_p, C.c_int, C.c_float, C.POINTER(MultiviewOut), C.c_void_p, C.c_void_p],
     "sp3_multiview_clean": [C.POINTER(TsdfFrame), C.c_void_p, C.c_int, C.c_float, C.POINTER(MultiviewOut), C.c_void_p, C.c_void_p],
+    "sp3_align_loss_grad": [C.POINTER(AlignImage), C.c_void_p, C.c_int, C.POINTER(AlignEdge), C.c_void_p, C.c_int, C.POINTER(C.c_int32),
+                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                            C.c_void_p, C.c_void_p],
+    "sp3_align_moments": [C.POINTER(AlignTriple), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "sp3_weight_stream_set": [C.c_int],
     "sp3_tsdf_brick_extract": [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -393,7 +414,8 @@ EXPORTS = sorted(list(_PROTOS) + ["sp3_last_error", "sp3_version", "sp3_weight_s
                                   "sp3_mesh_cluster_ws_bytes", "sp3_mesh_cluster_faces_ws_bytes", "sp3_mesh_face_frames_ws_bytes",
                                   "sp3_mesh_vertex_normals_ws_bytes", "sp3_mesh_dist_query_ws_bytes", "sp3_mesh_ray_ws_bytes",
                                   "sp3_mesh_edge_table_ws_bytes", "sp3_mesh_boundary_elements_ws_bytes", "sp3_mesh_boundary_rounds",
-                                  "sp3_mesh_boundary_rank_ws_bytes", "sp3_mesh_boundary_loops_ws_bytes", "sp3_mesh_fill_count_ws_bytes"])
+                                  "sp3_mesh_boundary_rank_ws_bytes", "sp3_mesh_boundary_loops_ws_bytes", "sp3_mesh_fill_count_ws_bytes",
+                                  "sp3_align_loss_grad_ws_bytes", "sp3_align_moments_ws_bytes"])
 
 
 def load():
@@ -437,6 +459,10 @@ def load():
         getattr(lib, name).argtypes = [C.c_int64, C.c_int]
     lib.sp3_mesh_edge_table_ws_bytes.restype = C.c_int64
     lib.sp3_mesh_edge_table_ws_bytes.argtypes = [C.c_int64, C.c_int64]
+    lib.sp3_align_loss_grad_ws_bytes.restype = C.c_int64
+    lib.sp3_align_loss_grad_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.sp3_align_moments_ws_bytes.restype = C.c_int64
+    lib.sp3_align_moments_ws_bytes.argtypes = [C.c_int, C.c_int64]
     lib.sp3_mesh_boundary_rounds.restype = C.c_int
     lib.sp3_mesh_boundary_rounds.argtypes = [C.c_int64]
     for name, argtypes in _PROTOS.items():
