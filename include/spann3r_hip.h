@@ -313,6 +313,11 @@ int sp3_attention_packed(const void* qp, int q_cols, int q_col0, int npad_q, con
                          const void* vtp, void* out, int64_t ldo, int out_bf16, int out_packed,
                          int B, int heads, int Nq, int Nk, float scale, int o_group, int o_group_rows, void* stream);
 
+/* Host only, launches nothing: the query blocks of 16 rows that one workgroup of sp3_attention_packed(B, heads, Nq) takes (1 or 2; 0 for
+ * a shape the launch would refuse).  A workgroup reads its head's whole K and V^T once for all its blocks; the grid is
+ * ceil(Nq / (16 QB)) x heads x B workgroups.  A query block's result does not depend on the count that computed it, bit for bit. */
+int sp3_attention_packed_qb(int B, int heads, int Nq);
+
 /* sp3_attention_packed with the QUERY PROJECTION inside the launch (round 6): a decoder layer's cross-attention
  * (croco/models/blocks.py:149-169) reads q = RoPE2D(projq(norm2(x))) of its own side; instead of a 196 x 768 x 768 GEMM launch in front
  * of the attention launch, every attention workgroup (16 query rows x one head) computes its [16 x 64] q tile from the fragment-order

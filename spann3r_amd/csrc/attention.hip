@@ -868,6 +868,17 @@ void launch_packed(const void* qp, int q_cols, int q_col0, int npad_q, const voi
                      G.xcd_map, qa);
 }
 
+// Query blocks of 16 rows per workgroup of sp3_attention_packed.  A workgroup reads its head's whole K and V^T whatever it does with them, so
+// QB blocks divide that traffic by QB -- which pays only where the traffic is what the launch waits for: from 512 query rows on, two
+// blocks (profiles/r05_attn_long_variants.txt).  Below that it is not.  The whole-sequence encoder's launch (10 images x 16 heads x 196
+// rows, 2080 workgroups of one block) was measured at 2 and 4 blocks, 1120 and 640 workgroups with a half and a quarter of the operand
+// reads: 10.1 -> 11.0 and 12.4 us; from 1 to 20 images one block is the fastest, at 40 the three are within 3 %
+// (profiles/encoder_attention_last_step.txt: the launch time follows the workgroups' own instruction streams, not their operand bytes).
+int attn_packed_qb(int B, int heads, int Nq) {
+  (void)B; (void)heads;
+  return Nq >= 512 ? 2 : 1;
+}
+
 }  // namespace
 
 extern "C" int sp3_attention_ex(const void* q, int64_t sq, int64_t ldq, const void* k, int64_t sk, int64_t ldk, const void* vt,
@@ -907,12 +918,15 @@ extern "C" int sp3_attention_packed(const void* qp, int q_cols, int q_col0, int 
   SP3_CHECK(q_cols % 64 == 0 && k_cols % 64 == 0 && q_col0 % 64 == 0 && k_col0 % 64 == 0, "sp3_attention_packed: column geometry");
   SP3_CHECK(out_packed || ldo % 4 == 0, "sp3_attention_packed: ldo");
   SP3_CHECK(o_group == 0 || (o_group > 0 && B % o_group == 0 && o_group_rows >= o_group * Nq), "sp3_attention_packed: output grouping");
-  // two query blocks per workgroup once the grid still fills the chip that way (profiles/r05_attn_long_variants.txt)
-  const auto launch = Nq >= 512 ? launch_packed<2, 3> : launch_packed<1, 4>;
+  const auto launch = attn_packed_qb(B, heads, Nq) == 2 ? launch_packed<2, 3> : launch_packed<1, 4>;
   launch(qp, q_cols, q_col0, npad_q, kp, k_cols, k_col0, npad_k, vtp, out, ldo, out_bf16, out_packed, B, heads, Nq, Nk, scale, o_group,
          o_group_rows, QProjArgs{}, stream);
   SP3_LAUNCH_CHECK("sp3_attention_packed");
   return 0;
+}
+
+extern "C" int sp3_attention_packed_qb(int B, int heads, int Nq) {
+  return B > 0 && heads > 0 && Nq > 0 ? attn_packed_qb(B, heads, Nq) : 0;
 }
 
 extern "C" int sp3_attention_packed_qproj(const sp3_attn_qproj_desc* dp, void* stream) {

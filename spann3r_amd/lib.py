@@ -207,6 +207,7 @@ _PROTOS = {
     "sp3_attention_packed": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                              C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
                              C.c_void_p],
+    "sp3_attention_packed_qb": [C.c_int, C.c_int, C.c_int],      # host only; returns the query blocks per workgroup, not a status
     "sp3_attention_packed_qproj": [C.POINTER(AttnQProjDesc), C.c_void_p],
     "sp3_softmax_thresh": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float,
                            C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p],

@@ -844,8 +844,9 @@ class _SequenceRunner:
         ops.copy_multi(self.pair_copies(i))
 
     # ---- the kernel sequences (spann3r/model.py:485-531) ----------------------------------------------------
-    def _part1(self, first, has_next, scores_to_host, stream=False):
+    def _part1(self, first, has_next, scores_to_host, stream=False, last=False):
         """Everything up to the similarity scores: (memory read) + decoder + key MLPs + check_sim's cosine scores.
+        last (see run): neither key has a reader -- no key MLPs, no scores.
         The two decoder sides run on two streams (or as grouped launches); a third stream encodes the NEXT frame in
         the frame-by-frame mode (each frame is encoded exactly once, spann3r/model.py:293-295).
         stream (a streaming session's step, spann3r_amd/stream.py): the frame in img_next is THIS step's view 2 -- it only just
@@ -887,25 +888,28 @@ class _SequenceRunner:
         if eng.packed_attn and self.model.grouped_decoder:
             # both decoder sides and both key MLPs as grouped launches on the main stream: no per-layer fork/join
             dec1, dec2 = eng.decoder_grouped(f1, self.feat2, B, self.nh, self.nw, f1p=f1p, f2p=p2 if f1p is not None else None)
-            self.k2_aux = eng.encode_feat_keys_grouped(self.feat1, self.feat2, dec1[-1], dec2[-1], B * P, self.k1, self.k2,
-                                                       feat1p=p1, feat2p=p2, aux=self.own_aux)
+            if not last:
+                self.k2_aux = eng.encode_feat_keys_grouped(self.feat1, self.feat2, dec1[-1], dec2[-1], B * P, self.k1, self.k2,
+                                                           feat1p=p1, feat2p=p2, aux=self.own_aux)
         else:
             dec1, dec2 = eng.decoder(f1, self.feat2, B, self.nh, self.nw, self.nh, self.nw, streams=st)   # joined on return
-            st[2].wait_stream(main)
-            with torch.cuda.stream(st[2]):
-                self.k2_aux = eng.encode_feat_key(self.feat2, dec2[-1], B * P, 2, self.k2, aux=self.own_aux or True)
-            eng.encode_feat_key(self.feat1, dec1[-1], B * P, 1, self.k1)
-            main.wait_stream(st[2])
-        if not self.training and mem.sim_needed():
+            if not last:
+                st[2].wait_stream(main)
+                with torch.cuda.stream(st[2]):
+                    self.k2_aux = eng.encode_feat_key(self.feat2, dec2[-1], B * P, 2, self.k2, aux=self.own_aux or True)
+                eng.encode_feat_key(self.feat1, dec1[-1], B * P, 1, self.k1)
+                main.wait_stream(st[2])
+        if not last and not self.training and mem.sim_needed():
             mem.sim_scores(self.k1, to_host=scores_to_host and mem.state is not None)
         if has_next:
             main.wait_stream(st[3])
         self.dec = (dec1, dec2)
         self.dec2_hooks = [dec2[h] for h in self.model.cfg.hooks[1:]]
 
-    def _part2(self):
+    def _part2(self, last=False):
         """DPT head(s) + value encoder + staged memory write (spann3r/model.py:505-521).  Nothing in here feeds the
-        similarity gate, so the host reads the scores of _part1 while this part runs."""
+        similarity gate, so the host reads the scores of _part1 while this part runs.
+        last (see run): the head(s) only -- the value and the bank row it would be written to have no reader."""
         eng, mem, B = self.eng, self.mem, self.B
         dec1, dec2 = self.dec
         main = torch.cuda.current_stream()
@@ -917,24 +921,32 @@ class _SequenceRunner:
                 pts2, conf2, _ = eng.dpt_head(dec2, B, self.hh, self.hw, 2)
         pts1, conf1, _ = eng.dpt_head(dec1, B, self.hh, self.hw, 1)
         # portrait results are handed on axis-swapped (landscape_only wrapper); the value encoder sees that view
-        if eng.cfg.use_feat:                    # spann3r/model.py:312-314: the value comes from dec1[-1], not from the pointmap
+        if last:
+            pass
+        elif eng.cfg.use_feat:                  # spann3r/model.py:312-314: the value comes from dec1[-1], not from the pointmap
             eng.encode_cur_value_feat(dec1[-1], self.v, self.k1,
                                       pos32=eng.positions(B, self.nh, self.nw)[1] if eng.cfg.mem_pos_enc else None)
         else:
             eng.encode_cur_value(pts1.swapaxes(1, 2) if self.swap else pts1, self.v, self.k1)   # v = cur_v + feat_k1
-        mem.stage_write(self.k1, self.v)
+        if not last:
+            mem.stage_write(self.k1, self.v)
         if not self.defer2:
             main.wait_stream(st[2])
         self.out = (pts1, conf1, pts2, conf2)
 
-    def run(self, first, has_next, use_graphs, post_copies=(), stream=False):
+    def run(self, first, has_next, use_graphs, post_copies=(), stream=False, last=False):
         """One step: ONE function -- _part1, the hand-off of the similarity scores to the host, _part2 -- captured and replayed
         as one hipGraph, or called (use_graphs False, a profiler, or a sequence whose per-length steps launch eagerly).  The host
         polls the pinned score buffer and takes the memory decision while the second half (head, value encoder) still runs -> the
         next step's launches are queued before the GPU runs dry.  The reference syncs at the same point of the data flow (:114).
         post_copies: (src, dst) pairs issued with the step's own result copies in ONE launch after the step
         (decoder hooks -> sequence slots, the next pair of encoder features): six eager launches per frame became one
-        stream: a streaming session's step (see _part1); part of the graph key, so such steps never share a graph with forward's"""
+        stream: a streaming session's step (see _part1); part of the graph key, so such steps never share a graph with forward's
+        last: the last step of a sequence whose memory nobody will see (forward without return_memory).  What such a step would leave
+        for a next one has no reader -- both keys (k1: the gate and the bank row; k2: the next read's query), the similarity scores,
+        the value, the staged bank row, the column sums its read owes to mem_attn -- so a step kind of its own (part of the graph key)
+        launches none of it, the host neither arms nor polls the scores, and the memory stays as the step before left it (one frame
+        short of the reference's, which computes all of this and throws it away).  The outputs are the full step's."""
         mem = self.mem
         has_next = has_next and not self.batched                # nothing to prefetch: the sequence is already encoded
         gk = mem.graph_key()
@@ -943,19 +955,21 @@ class _SequenceRunner:
         per_length = 0 if gk[0] in ("s", "p") else 1 if (stream or mem.state is not None) else self._out_steps
         if not use_graphs and ops._prof is not None:
             ops._prof.step_begin()
-        need_sim = not self.training and mem.sim_needed()
+        need_sim = not last and not self.training and mem.sim_needed()
         if need_sim:
             mem.arm_score_poll()
 
         def whole():
-            self._part1(first, has_next, need_sim, stream)
+            self._part1(first, has_next, need_sim, stream, last)
             if need_sim and mem.state is None:              # (device-resident bank state: cos_mean stored into the pinned buffer itself)
                 mem.copy_scores_to_host()
-            self._part2()
-        key = ("whole", first, need_sim) + gk + (has_next, self.batched, self.defer2, self.model.grouped_decoder, self.model.packed_features,
-                                                 stream)
+            self._part2(last)
+        key = ("whole", first, need_sim, last) + gk + (has_next, self.batched, self.defer2, self.model.grouped_decoder,
+                                                       self.model.packed_features, stream)
         self.graphs.run(key, whole, use_graphs and ops._prof is None, per_length)
-        if not first:
+        if last:
+            mem._pending_attn = None            # (an eagerly launched read noted its column sums: nobody will ask for them)
+        elif not first:
             mem.note_deferred_read()            # (a replayed graph ran no Python)
         pts1, conf1, pts2, conf2 = self.out
         srcs = (pts1, conf1) + (() if pts2 is None else (pts2, conf2))
@@ -970,7 +984,9 @@ class _SequenceRunner:
             res1 = {k: v.swapaxes(1, 2) for k, v in res1.items()}
             res2 = {k: v.swapaxes(1, 2) for k, v in res2.items()}
         # memory policy (:518-521): the frame was staged inside the step; commit or drop it here
-        if self.training:
+        if last:
+            pass
+        elif self.training:
             mem.commit_staged()
         else:
             mem.finish_staged(mem.sim_verdict() if need_sim else False)
@@ -1409,7 +1425,7 @@ class Spann3R(nn.Module):
                 # after this step's kernels: the next step's pair of encoder features, side 2's hook outputs to their slots
                 nxt = run.pair_copies(i + 1) if (run.batched and i + 1 < n - 1) else []
                 return nxt + (run.dec2_copies(i) if run.defer2 else [])
-            res1, res2 = run.run(i == 0, has_next, self.use_graphs, post)
+            res1, res2 = run.run(i == 0, has_next, self.use_graphs, post, False, i == n - 2 and not return_memory)
             if not run.defer2:
                 res2["pts3d_in_other_view"] = res2.pop("pts3d")                  # :523
             if preds is None:

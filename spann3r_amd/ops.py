@@ -739,6 +739,11 @@ def attention_packed(qp, q_cols, q_col0, npad_q, kp, k_cols, k_col0, npad_k, vtp
     return out
 
 
+def attention_packed_qb(B, heads, Nq):
+    """query blocks of 16 rows per workgroup that attention_packed takes at this shape (the library's rule; launches nothing)"""
+    return int(L.load().sp3_attention_packed_qb(B, heads, Nq))
+
+
 def attention_takes_qproj(Nq, D):
     """whether a cross-attention of Nq query rows at width D takes its q projection inside the launch (attention_packed_qproj) instead
     of a projection GEMM in front of attention_packed: the shapes sp3_attention_packed_qproj accepts, on the lean path only"""
